@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — denoising steps/sec of the reverse-diffusion sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -80,6 +80,8 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=5, help="steps of the CPU baseline's timed sample (~5.5 s each at B=8)")
     ap.add_argument("--cpu-warmup", type=int, default=1)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (default 0: picked by a one-step probe of 16 / 64)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed call of rank 0 "
+                    "returned for its last step as DIR/<name>.npy (float32, at most 64 MB; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -207,6 +209,8 @@ def main():
     sd.update(synth.synthetic_state_dict(cfg, seed=0))
     model.load_state_dict(sd, strict=True)
     model = model.to(dev)
+    if not 1 <= args.steps <= int(model.num_timesteps):
+        raise SystemExit(f"bench.py: --steps {args.steps}: a timed call runs 1 ... {int(model.num_timesteps)} steps of the reverse chain")
     # the job's chain length is known up front (the reference's script always samples num_steps): the warm-up calls size the cached
     # trajectory buffers for it, whatever --warmup / --steps are, instead of leaving a new chain entry + graph capture to the timed call
     model.traj_capacity_hint = min(int(args.steps), int(model.num_timesteps))
@@ -250,13 +254,16 @@ def main():
         mine = ddist.units_of_rank(units, args.config, 0, 1)
         states = [prepare(u) for u in mine]
         secs = [[], []]
+        last = None
         for p_ in (0, 1):
             for u, st_ in zip(mine, states):
                 torch.cuda.synchronize(dev)
                 t1 = time.perf_counter()
-                sample(st_, args.steps, u.noise_seed)
+                last = sample(st_, args.steps, u.noise_seed)
                 torch.cuda.synchronize(dev)
                 secs[p_].append(time.perf_counter() - t1)
+        if args.dump_outputs:
+            dump_outputs(last, args.dump_outputs)
         lib = hip_lib.load()
         import ctypes as _ct
         buf = _ct.create_string_buffer(1024)
@@ -280,6 +287,8 @@ def main():
         assert torch.isfinite(out["pos"]).all()
         assert len(out["pos_traj"]) == args.steps
     elapsed = job["elapsed"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     if rank == 0:
         lib = hip_lib.load()
@@ -362,6 +371,37 @@ def main():
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+TRAJ_KEYS = ("pos_traj", "v_traj", "bond_traj", "v0_traj", "vt_traj", "bt_traj")
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: what the last timed call returned for its last step, as DIR/<name>.npy in float32 -- `pos` / `v` / `bond`
+    as returned and `<key>_last` for the last frame of each of the six trajectories.  Every input of the job is seeded (pocket,
+    initial state, Philox key), so the same arguments write the same inputs' results from run to run and two builds can be compared
+    array by array.  Should the arrays exceed DUMP_LIMIT_BYTES, each keeps a fixed, seeded sample of its rows (the same rows in
+    every run of the same shapes)."""
+    import numpy as np
+    if out is None:
+        print("bench.py: --dump-outputs: this rank ran no unit, nothing written", file=sys.stderr, flush=True)
+        return
+    arrays = {k: out[k] for k in ("pos", "v", "bond")}
+    for k in TRAJ_KEYS:
+        if len(out.get(k) or ()) > 0:
+            arrays[k + "_last"] = out[k][-1]
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            # (seeded by the row count: the atom arrays keep the same atoms, the bond arrays the same bonds)
+            rows = np.sort(np.random.default_rng(a.shape[0]).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print(f"bench.py: --dump-outputs: {len(arrays)} arrays written to {directory}", file=sys.stderr, flush=True)
 
 
 def measure_step_rooflines(torch, model, hip_lib, lib, state, cfg, B, NP, NL, K, dev, config, workload):

@@ -383,9 +383,14 @@ def test_rccl_single_rank_control_plane():
 
 
 def test_bench_eight_ranks_oversubscribed():
-    """The shape of the driver's `--gpus 8` run on this box's one GPU: 8 ranks spawned by bench.py
-    itself over gloo, 16 pockets of configs[3] assigned longest-first, gather of the per-unit records, imbalance, CPU
-    affinity per rank.  The per-unit checksums equal those of the 1-rank job."""
+    """The shape of the driver's `--gpus 8` run: 8 ranks spawned by bench.py itself over gloo, 16 pockets
+    of configs[3] assigned longest-first, gather of the per-unit records, imbalance, CPU affinity per rank.  The per-unit
+    checksums equal those of the 1-rank job.  Needs 8 devices: the launcher (torch.distributed.run initialises HIP to count
+    devices), this process and 8 ranks would be 10 processes holding one GPU, more than a shared GPU host admits at once --
+    on fewer devices test_bench_three_ranks_oversubscribed runs the same checks."""
+    n_dev = torch.cuda.device_count()
+    if n_dev < 8:
+        pytest.skip(f"needs 8 GPUs, found {n_dev} (8 ranks on one GPU: 10 processes holding it, more than a shared host admits)")
     common = ["--config", "3", "--pockets", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-rooflines"]
     eight, _ = _bench_line(["--gpus", "8", "--backend", "gloo", "--oversubscribe"] + common, _bench_env())
     one, _ = _bench_line(["--gpus", "1"] + common, _bench_env())
@@ -402,6 +407,28 @@ def test_bench_eight_ranks_oversubscribed():
     strip = lambda rs: [(r["unit"], r["checksum"]) for r in rs]
     assert strip(one["per_unit"]) == strip(eight["per_unit"]) and len(eight["per_unit"]) == 16
     assert one["scaling"] == eight["scaling"] == "strong"
+
+
+def test_bench_three_ranks_oversubscribed():
+    """test_bench_eight_ranks_oversubscribed on this box's one GPU: 3 ranks (with this process and the launcher, 5 processes
+    hold the GPU) over gloo, the same checks; 16 pockets over 3 ranks also leaves the LPT table with unequal unit counts."""
+    n = 3
+    common = ["--config", "3", "--pockets", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-rooflines"]
+    many, _ = _bench_line(["--gpus", str(n), "--backend", "gloo", "--oversubscribe"] + common, _bench_env())
+    one, _ = _bench_line(["--gpus", "1"] + common, _bench_env())
+    _keep_evidence(f"bench_{n}ranks_oversubscribed.json", many)
+    from decompdiff_amd import dist as ddist
+    units, _ = ddist.plan_job(3, n, n_pockets=16)
+    assert many["ranks"] == n and len(many["per_rank"]) == n and many["n_gpus"] == many["distinct_devices"] == min(n, torch.cuda.device_count())
+    assert [r["units"] for r in many["per_rank"]] == ddist.assign_lpt(units, n)
+    assert many["config"]["control_plane"] == "gloo" and many["config"]["imbalance_max_over_mean_busy"] >= 1.0
+    assert all(isinstance(r["cpu_affinity"], dict) for r in many["per_rank"])
+    bound = [r["cpu_affinity"] for r in many["per_rank"] if r["cpu_affinity"].get("bound")]
+    if len(bound) == n and len({a["numa_cpus"] for a in bound}) == 1 and bound[0]["numa_cpus"] >= n:
+        assert len({a["cpus"] for a in bound}) == n                            # ranks sharing a NUMA node: disjoint slices
+    strip = lambda rs: [(r["unit"], r["checksum"]) for r in rs]
+    assert strip(one["per_unit"]) == strip(many["per_unit"]) and len(many["per_unit"]) == 16
+    assert one["scaling"] == many["scaling"] == "strong"
 
 
 def test_ligand_atom_mask_matches_reference_behaviour():
@@ -562,6 +589,47 @@ def test_bench_json_line_contract():
     assert o["bound"] == "hbm" and o["unit"] == "GB/s" and 0.3 < o["frac"] < 1.0
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and "steps" in c["sample"]
+
+
+def test_bench_dump_outputs_are_the_timed_calls_result(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed call's result for its last step as float32 .npy files (pos / v / bond and the
+    last frame of every trajectory), identical from run to run with the same arguments (another warm-up does not change the
+    timed call's inputs), consistent with the line's per-unit checksum, within the 64 MB budget.  The timed call ran --steps steps:
+    the same unit (configs[1] unit 0, prepared as bench.py prepares it) sampled here for 4 steps gives the dumped result, for
+    3 or 5 steps it does not."""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "4", "--no-cpu-baseline", "--no-rooflines", "--no-steady"]
+    runs = []
+    for warmup in ("1", "3"):
+        d = tmp_path / f"w{warmup}"
+        line, _ = _bench_line(common + ["--warmup", warmup, "--dump-outputs", str(d)], _bench_env(), timeout=900)
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and len(line["per_unit"]) == 1
+        runs.append((line, {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}))
+    (line, a), (_, b) = runs
+    names = {"pos", "v", "bond"} | {k + "_last" for k in ("pos_traj", "v_traj", "bond_traj", "v0_traj", "vt_traj", "bt_traj")}
+    assert set(a) == set(b) == names
+    B, NL = line["config"]["batch_per_unit"], 30
+    assert a["pos"].shape == (B * NL, 3) and a["v"].shape == (B * NL,) and a["bond"].shape == (B * NL * (NL - 1),)
+    assert a["bt_traj_last"].shape == (B * NL * (NL - 1), 5)
+    assert all(x.dtype == np.float32 for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    for k in names:
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["v"], a["v_traj_last"]) and np.array_equal(a["bond"], a["bond_traj_last"])
+    cs = line["per_unit"][0]["checksum"]
+    assert int(a["v"].sum()) == cs["v"] and int(a["bond"].sum()) == cs["bond"]
+    assert abs(float(a["pos"].astype(np.float64).sum()) - cs["pos"]) < 1e-6 * max(1.0, abs(cs["pos"]))
+    from decompdiff_amd import dist as ddist
+    u = ddist.plan_job(1, 1)[0][0]
+    pocket = synth.make_pocket(u.pocket_seed, u.num_protein, u.arm_atoms, u.scaffold_atoms, num_full_protein=0)
+    torch.manual_seed(u.init_seed)
+    b = synth.build_sampling_batch(pocket, u.n_samples, per_sample_std_scale=[1.0] * u.n_samples)
+    m = model(0)
+    for steps in (4, 3, 5):
+        r = _sample_hip(m, b, steps, None, None, seed=u.noise_seed)
+        assert len(r["pos_traj"]) == steps
+        same = (maxabs(r["pos"], torch.from_numpy(a["pos"])) < 1e-5 and np.array_equal(r["v"].cpu().numpy(), a["v"])
+                and np.array_equal(r["bond"].cpu().numpy(), a["bond"]))
+        assert same == (steps == 4), steps
 
 
 def test_static_input_memo_is_invalidated_by_in_place_changes():
