@@ -197,7 +197,6 @@ DD_OPT g_head_rows_first = 0;              // dd_debug_set_option(29, v): see th
 DD_OPT g_heads_early = 1;                  // dd_debug_set_option(28, v): heads' first Linear in the last layer's projection launch
 DD_OPT g_q_in_pos = 1;                     // dd_debug_set_option(9, v): coordinate query MLPs' second layer inside attn_pos
 extern int g_pos_waves;                     // dd_attention2.hip: waves per workgroup of the coordinate launch
-extern int g_pos_quad;                      // dd_attention2.hip: four waves per segment in the coordinate launch (dd_debug_set_option(33, v))
 DD_OPT g_p2_in_pos = 0;                    // dd_debug_set_option(30, v): the projections of the new h ({P2, PL2}; in the last layer the
                                                // heads' first Linear too) run in the leading / trailing workgroups of the coordinate
                                                // launch instead of a launch of their own on the critical chain (round 5: bit-identical,
@@ -1663,7 +1662,6 @@ extern "C" int dd_debug_set_option(int key, int value) {
   if (key == 31) { dd::g_pos_g_mode = value & 3; return DD_OK; }
   if (key == 28) { dd::g_heads_early = value ? 1 : 0; return DD_OK; }
   if (key == 32) { dd::g_lin_in_node = value < 0 ? -1 : (value ? 1 : 0); return DD_OK; }
-  if (key == 33) { dd::g_pos_quad = value ? 1 : 0; return DD_OK; }
   if (key == 29) { dd::g_head_rows_first = value ? 1 : 0; return DD_OK; }
   if (key == 7) { dd::g_step_fused = value ? 1 : 0; return DD_OK; }
   if (key == 5) { if (value != 2 && value != 4 && value != 8) return DD_ERR_BAD_ARG; dd::g_pos_waves = value; return DD_OK; }

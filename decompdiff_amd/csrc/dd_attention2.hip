@@ -25,9 +25,6 @@
 #include "dd_kernels.hpp"
 #include "dd_gemm_tile.hpp"
 
-#ifndef DD_KNN_CONST_ADD
-#define DD_KNN_CONST_ADD 1
-#endif
 // Round 6 (EXPERIMENTS.md R6-1): the VALU stream of a segment cut by a quarter.  Each switch builds the round-5 form when 0
 // (tools/build_variant.sh); DD_LN_FOLD also selects the weight form the library expects (dd_weights_form(), packing.py).
 #ifndef DD_LN_FOLD
@@ -36,41 +33,13 @@
 #ifndef DD_FAST_ANGLE
 #define DD_FAST_ANGLE 1    // angle codes without library atan2f / IEEE sqrt / IEEE division
 #endif
-#ifndef DD_PEEL_FOLD
-#define DD_PEEL_FOLD 0     // first step of the query fold as products instead of zero-initialised accumulators (measured: +1 %, R6-1)
-#endif
-#ifndef DD_PEEL_Z
-#define DD_PEEL_Z 0        // the same for the aggregation chains (measured: +1.8 %, 48 more registers, R6-1)
-#endif
-#ifndef DD_COOP
-#define DD_COOP 0          // persistent bond-layer workgroups: query fold and epilogue split by head over the 8 waves of a trip (bl_coop_body);
-                           // measured equal to the per-wave fold / epilogue (EXPERIMENTS.md R6-2): built with -DDD_COOP=1 for the A/B only
-#endif
-#ifndef DD_COOP_WK_RELOAD
-#define DD_COOP_WK_RELOAD 0   // bl_coop_body: the wave's 16 W2k rows re-read (L2) with every trip's prologue instead of held in 32 registers
-#endif
-#ifndef DD_COOP_RC
-#define DD_COOP_RC 0          // bl_coop_body: the segment's own row (Rk) requested with the next trip's prologue instead of at its first tile
-#endif
-#ifndef DD_NE_COOP_EPI
-#define DD_NE_COOP_EPI 1   // node_layer_with_edge blocks: no W2v image -- the epilogue as one MFMA chain per wave (W2v rows from L2, Z~ through LDS)
-#endif
-#ifndef DD_NE_PERSIST
-#define DD_NE_PERSIST 0    // node_layer_with_edge as persistent workgroups (ne_persist_body) beside the persistent bond-layer ones: bit-identical,
-                           // measured 10 % SLOWER (EXPERIMENTS.md R6-8); compiled with -DDD_NE_PERSIST=1 for the A/B only
-#endif
 #ifndef DD_TRIP_SYNC
 #define DD_TRIP_SYNC 6     // persistent bond-layer workgroups: a workgroup barrier every n-th trip (1 <= n <= 7).  Round 2 kept the waves in
                            // lock-step (free-running waves measured 6 % slower then); round 6: n = 3 ... 6 -1.7 % at B = 8, -3.5 % at C-large, bit-identical (R6-7)
 #endif
+static_assert(DD_TRIP_SYNC >= 1 && DD_TRIP_SYNC <= 7, "DD_TRIP_SYNC: the eight trip slots of the persistent workgroups allow 1 ... 7");
 #ifndef DD_NODE_TRACE
 #define DD_NODE_TRACE 0    // measurement variant (tools/build_variant.sh trace -DDD_NODE_TRACE=1): per-workgroup clocks of the fused node launch
-#endif
-#ifndef DD_GAUSS_CACHE
-#define DD_GAUSS_CACHE 1   // node_layer_with_edge: the tile's Gaussian features kept from the k pass for the v pass
-#endif
-#ifndef DD_UNCOND_FETCH
-#define DD_UNCOND_FETCH 1  // next tile's rows requested unconditionally (clipped members): no register copies at the tile joins
 #endif
 
 namespace dd {
@@ -111,22 +80,6 @@ __device__ __forceinline__ void stage_w2k_permuted(float* WB, const float* __res
     }
   }
 }
-template <int NT, int N4>
-__device__ __forceinline__ void stage_plain(float* dst, const float* __restrict__ src) {
-  constexpr int PER = (N4 + NT - 1) / NT;
-  float4 tmp[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int i = threadIdx.x + k * NT;
-    if (N4 % NT == 0 || i < N4) tmp[k] = reinterpret_cast<const float4*>(src)[i];
-  }
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int i = threadIdx.x + k * NT;
-    if (N4 % NT == 0 || i < N4) reinterpret_cast<float4*>(dst)[i] = tmp[k];
-  }
-}
-
 __device__ __forceinline__ void add_row(float (&P)[32], const float* __restrict__ row, int cg) {
 #pragma unroll
   for (int nt = 0; nt < 8; ++nt) {
@@ -373,18 +326,14 @@ __host__ __device__ inline int ne_blocks_per_sample(int NP, int NL, int NW) { re
 // workgroups), and its two halves only meet at the very end: wave 0 of a pair runs the query MLP, the fold, the k pass and
 // the softmax, wave 1 meanwhile the v pass (activations and the 16 per-head values of every member); the attention
 // weights cross through LDS behind one workgroup barrier and wave 1 forms the coordinate update.
-// PAIR = 2 (QUAD, round 6): four waves per segment -- the two 16-member tiles of a kNN segment (odd / even tiles of a longer bond
-// segment) go to different waves on both sides; the softmax's max and sum and the two halves of the coordinate update cross through
-// LDS (3 more workgroup barriers).  With NW = 2 segments per workgroup the launch has 240 workgroups instead of 120.
-template <int MODE, int MAXT, int NW, bool PERSIST = false, bool RAG = false, int PAIR = 0, bool STAMPS = true, typename ARGS = AttnArgs>
+template <int MODE, int MAXT, int NW, bool PERSIST = false, bool RAG = false, bool PAIR = false, bool STAMPS = true, typename ARGS = AttnArgs>
 __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float* smem) {
   constexpr bool KNN = (MODE == M_NE || MODE == M_PE);
   constexpr bool POS = (MODE == M_PE || MODE == M_PB);
   constexpr bool TRIP = (MODE == M_BL);
   constexpr bool BOND = (MODE == M_NB || MODE == M_PB);
   static_assert(!PAIR || (POS && !PERSIST), "wave pairs: coordinate modes");
-  constexpr bool QUAD = PAIR == 2;
-  constexpr int NT = (QUAD ? 4 : (PAIR ? 2 : 1)) * NW * 64;
+  constexpr int NT = (PAIR ? 2 : 1) * NW * 64;
   using L = Lds<MODE>;
   constexpr int LNP = L::LNP, WAO = L::WAO;
   constexpr bool RES = L::RES;
@@ -394,9 +343,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   // (pairs: waves p and p + NW -- one k-side and one v-side wave on every SIMD, which want different units at a time)
   const int wave = PAIR ? ((threadIdx.x >> 6) % NW) : (threadIdx.x >> 6), lane0 = threadIdx.x & 63;
   const int role = PAIR ? ((threadIdx.x >> 6) / NW) : 0;  // 0: query / k pass / softmax, 1: v pass / coordinate update
-  const bool kside = !PAIR || (QUAD ? role < 2 : role == 0), vside = !PAIR || (QUAD ? role >= 2 : role == 1);   // (QUAD: roles 0, 1 / 2, 3)
-  const int tsel = role & 1;                              // QUAD: this wave's tiles are t = tsel, tsel + 2, ...
-  auto mine = [&](int t) { return !QUAD || (t & 1) == tsel; };
+  const bool kside = !PAIR || role == 0, vside = !PAIR || role == 1;
 
   const int N = a.NP + a.NL, NLm1 = a.NL - 1, Eb = a.NL * NLm1;
   // Padded heterogeneous batch (a.nl_real != NULL): sample b's real atoms are the first np_real[b] / nl_real[b] rows of
@@ -571,7 +518,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   } else if (POS && a.W2q != nullptr && kside) {
     // coordinate modes: the query MLP's second layer runs here (q = W2q . relu(LN(hidden)) + b2q, one 128x128
     // mat-vec per segment) instead of as a 16-tile GEMM launch on the critical chain.  Lane l owns outputs 2l, 2l+1.
-    float* sc = smem + L::TOTAL + (QUAD ? wave + NW * tsel : wave) * 256;   // (QUAD: both k waves of a segment form the query, each in its own scratch)
+    float* sc = smem + L::TOTAL + wave * 256;
     if (active) {
       float2 hv = *reinterpret_cast<const float2*>(a.qhid + drow * a.ld_qhid + 2 * lane);
       ln_relu2(hv.x, hv.y, a.lnq[2 * lane], a.lnq[2 * lane + 1], a.lnq[128 + 2 * lane], a.lnq[128 + 2 * lane + 1]);
@@ -630,7 +577,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   const float* rc_row = TRIP ? a.Rk + (long)seg * 128 : a.kd + drow * a.ld_kd;
   if (active && kside) {
     if (!REREAD) load_row(Rc, rc_row, cg);
-    fetch_k_rows(QUAD ? tsel : 0);
+    fetch_k_rows(0);
     if (TRIP) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) { tri_i[c] = xl[3 * si + c]; tri_j[c] = xl[3 * sj + c]; }
@@ -649,34 +596,16 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
 
   // ---- Q~ as the MFMA B operand: lane (h = mm, cg) holds Q~[h][c(kk, cg)] ----------------------------------
   float Qb[32];
-#if !DD_PEEL_FOLD
 #pragma unroll
   for (int k = 0; k < 32; ++k) Qb[k] = 0.f;
-#endif
   if (active && kside) {
     // a real loop (8 LDS reads in flight per trip): fully unrolled, the scheduler hoists all 64 reads = 256 registers.
     // The 8 query values rotate through r0 so that no dynamic register indexing is needed.
     float r0 = q0.x, r1 = q0.y, r2 = q0.z, r3 = q0.w, r4 = q1.x, r5 = q1.y, r6 = q1.z, r7 = q1.w;
-#if DD_PEEL_FOLD
-    {                                                    // d = 0 peeled: products instead of 32 zeroing moves + 32 FMAs
-      const float* wr = WB + mm * WPITCH + 4 * cg;
-#pragma unroll
-      for (int nt = 0; nt < 8; ++nt) {
-        const float4 w = *reinterpret_cast<const float4*>(wr + 16 * nt);
-        Qb[4 * nt] = r0 * w.x; Qb[4 * nt + 1] = r0 * w.y; Qb[4 * nt + 2] = r0 * w.z; Qb[4 * nt + 3] = r0 * w.w;
-      }
-      r0 = r1; r1 = r2; r2 = r3; r3 = r4; r4 = r5; r5 = r6; r6 = r7;
-    }
-#pragma nounroll
-    for (int d = 1; d < 8; ++d) {
-      const float qv = r0;
-      r0 = r1; r1 = r2; r2 = r3; r3 = r4; r4 = r5; r5 = r6; r6 = qv;
-#else
 #pragma nounroll
     for (int d = 0; d < 8; ++d) {                        // (unrolled by 2: fewer spills, but 2 % slower end to end)
       const float qv = r0;
       r0 = r1; r1 = r2; r2 = r3; r3 = r4; r4 = r5; r5 = r6; r6 = r7; r7 = qv;
-#endif
       const float* wr = WB + (d * 16 + mm) * WPITCH + 4 * cg;
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) {
@@ -709,20 +638,19 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   DD_STAMP(3);
 
   // first-layer table part of tile t (features of member 16t + mm), either orientation
-  // (DD_GAUSS_CACHE, node mode: the Gaussians of a tile are formed in the k pass and kept for the v pass -- 5 registers per tile
+  // (GCACHE, node mode: the Gaussians of a tile are formed in the k pass and kept for the v pass -- 5 registers per tile
   //  instead of 5 more expf per tile)
-  constexpr bool GCACHE = DD_GAUSS_CACHE && KNN && !POS;
+  constexpr bool GCACHE = KNN && !POS;
   float Fg[GCACHE ? MAXT : 1][5];
   auto table_part = [&](int t, int pass, f32x4 (&acc)[8], auto tr) {
     constexpr bool TR = decltype(tr)::value;
     if (KNN) {
       // Gaussian / type tables: F = 20 Gaussians + the per-type constant (24 rows = 6 k-steps).  A tile whose members
       // mix ligand and protein sources runs once per table with the other members' features zeroed.
-      // DD_KNN_CONST_ADD: the sixth k-step only adds table row 20 (feature 1, rows 21-23 are zero rows) -- fma(1, w, acc) is
-      // round(acc + w), and the steps of the OTHER table add exact zeros to a member, so the row of the member's own table added
-      // on the VALU after the Gaussian steps gives the same bits: 8 (16 in a mixed tile) MFMAs less per tile pass.
-      constexpr int KS = DD_KNN_CONST_ADD ? 5 : 6;
-      float F[6];
+      // The sixth k-step only adds table row 20 (feature 1, rows 21-23 are zero rows) -- fma(1, w, acc) is round(acc + w), and
+      // the steps of the OTHER table add exact zeros to a member, so the row of the member's own table added on the VALU after
+      // the five Gaussian steps gives the same bits: 8 (16 in a mixed tile) MFMAs less per tile pass.
+      float F[5];
       if (GCACHE) {
         if (pass == 0) {
 #pragma unroll
@@ -734,7 +662,6 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
 #pragma unroll
         for (int s = 0; s < 5; ++s) F[s] = gauss_feat(dm[t], 4 * s + cg);
       }
-      F[5] = cg == 0 ? 1.0f : 0.0f;
       const bool hi = jm[t] < a.NP;
       const float* tab = smem + L::TAB + pass * 2 * TABP + cg * 128 + mm * 4;   // [lo, hi] tables of this pass
 #pragma unroll
@@ -742,22 +669,20 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
         const bool want = half ? hi : !hi;
         if (__builtin_amdgcn_ballot_w64(want) != 0ull) {
 #pragma unroll
-          for (int s = 0; s < KS; ++s) mfma_table_step<TR>(acc, tab + half * TABP + s * 512, want ? F[s] : 0.0f);
+          for (int s = 0; s < 5; ++s) mfma_table_step<TR>(acc, tab + half * TABP + s * 512, want ? F[s] : 0.0f);
         }
       }
-      if (DD_KNN_CONST_ADD) {
-        // row 20 in the operand layout: channel 16 nt + i sits at (nt / 4) * 64 + i * 4 + nt % 4
-        const float* row20 = smem + L::TAB + pass * 2 * TABP + 20 * 128;
+      // row 20 in the operand layout: channel 16 nt + i sits at (nt / 4) * 64 + i * 4 + nt % 4
+      const float* row20 = smem + L::TAB + pass * 2 * TABP + 20 * 128;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          // TR: acc[nt][r] = member 4cg + r, channel 16 nt + mm;  else: member mm, channel 16 nt + 4cg + r
-          const bool hi_r = TR ? (jT[t][r] < a.NP) : hi;
-          const float* p = row20 + (hi_r ? TABP : 0) + (TR ? mm : 4 * cg + r) * 4;
-          const float4 c0 = *reinterpret_cast<const float4*>(p);
-          const float4 c1 = *reinterpret_cast<const float4*>(p + 64);
-          acc[0][r] += c0.x; acc[1][r] += c0.y; acc[2][r] += c0.z; acc[3][r] += c0.w;
-          acc[4][r] += c1.x; acc[5][r] += c1.y; acc[6][r] += c1.z; acc[7][r] += c1.w;
-        }
+      for (int r = 0; r < 4; ++r) {
+        // TR: acc[nt][r] = member 4cg + r, channel 16 nt + mm;  else: member mm, channel 16 nt + 4cg + r
+        const bool hi_r = TR ? (jT[t][r] < a.NP) : hi;
+        const float* p = row20 + (hi_r ? TABP : 0) + (TR ? mm : 4 * cg + r) * 4;
+        const float4 c0 = *reinterpret_cast<const float4*>(p);
+        const float4 c1 = *reinterpret_cast<const float4*>(p + 64);
+        acc[0][r] += c0.x; acc[1][r] += c0.y; acc[2][r] += c0.z; acc[3][r] += c0.w;
+        acc[4][r] += c1.x; acc[5][r] += c1.y; acc[6][r] += c1.z; acc[7][r] += c1.w;
       }
     } else if (TRIP) {
       const float* tb = smem + WAO + pass * 12 * 128 + cg * 128 + mm * 4;
@@ -789,9 +714,8 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
           if (BOND) P[k] += Pf2[k];
         }
       }
-      if (QUAD) { if (t + 2 < MAXT) fetch_k_rows(t + 2); }
-      else if (t + 1 < MAXT && (DD_UNCOND_FETCH || t + 1 < T)) fetch_k_rows(t + 1);   // next tile's rows fly during this tile's arithmetic
-                                                              // (unconditional: members are clipped, a tile beyond T re-reads row M - 1)
+      if (t + 1 < MAXT) fetch_k_rows(t + 1);              // next tile's rows fly during this tile's arithmetic (unconditional: members
+                                                          // are clipped, a tile beyond T re-reads row M - 1 -- no register copies at the tile joins)
     } else if (KNN) {
       load_row(P, tab_d + drow * ld_d, cg);
       add_row(P, tab_s + (src_base + jm[t]) * ld_s, cg);
@@ -865,7 +789,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
         if (BOND) v += Tr2[4 * nt + r];
         Tz[4 * nt + r] = v;
       }
-    if (t + 1 < MAXT && (DD_UNCOND_FETCH || t + 1 < T)) fetch_T(t + 1);       // next tile's rows fly during this tile's arithmetic
+    if (t + 1 < MAXT) fetch_T(t + 1);                    // next tile's rows fly during this tile's arithmetic
     if (KNN || TRIP) {
       f32x4 acc[8];
 #pragma unroll
@@ -880,7 +804,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   // ---- kNN node mode: the W2k image is dead once every wave has folded its query; W2v takes its place now.  The
   //      second barrier follows at once (the waves are still aligned here; one in front of the epilogue would make
   //      every wave wait for the slowest); the Gaussian tables of both passes are resident.
-  constexpr bool NECO = DD_NE_COOP_EPI && MODE == M_NE && !PERSIST && NW == 8;   // cooperative epilogue, no W2v image (see below)
+  constexpr bool NECO = MODE == M_NE && !PERSIST && NW == 8;   // cooperative epilogue, no W2v image (see below)
   if (KNN && !POS) {
     __syncthreads();                                   // (NECO: every wave has folded its query -- the image's place becomes the exchange buffer)
     if (!NECO) {
@@ -896,7 +820,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   if (active && kside) {
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) {
-      if (t < T && mine(t)) {
+      if (t < T) {
         float P[32];
         build_pre(t, 0, P);
         S[t] = mfma_rows(P, Qb);
@@ -910,7 +834,6 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
     }
     DD_STAMP(5);
     if (!POS) fetch_T(0);                              // v-pass rows of tile 0 arrive during the softmax
-    if constexpr (!QUAD) {
     // segment softmax per head: max-shift, exp, / sum  (scatter_softmax), then * e_w
     float mx = -INFINITY;
 #pragma unroll
@@ -945,53 +868,9 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
         ssum += aw;
       }
     ssum = quad_sum(ssum);
-    }
   } else {
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) S[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  // QUAD: the two k-side waves of a segment hold the scores of different tiles -- the per-head max and sum cross through LDS
-  float* const exq = smem + L::TOTAL + 2 * NW * 256 + NW * MAXT * 256;   // [NW][2][16] max, [NW][2][16] sum, [NW][2][4] dx partials
-  if constexpr (QUAD) {
-    const bool ks = active && kside;
-    float mx = -INFINITY;
-    if (ks) {
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, S[t][r]);
-      mx = quad_max(mx);
-      if (cg == 0) exq[(wave * 2 + tsel) * 16 + mm] = mx;
-    }
-    __syncthreads();
-    float sum = 0.f;
-    if (ks) {
-      mx = fmaxf(exq[(wave * 2) * 16 + mm], exq[(wave * 2 + 1) * 16 + mm]);
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = (16 * t + 4 * cg + r < M && mine(t)) ? expf(S[t][r] - mx) : 0.f;
-          S[t][r] = e;
-          sum += e;
-        }
-      sum = quad_sum(sum);
-      if (cg == 0) exq[NW * 32 + (wave * 2 + tsel) * 16 + mm] = sum;
-    }
-    __syncthreads();
-    if (ks) {
-      sum = exq[NW * 32 + (wave * 2) * 16 + mm] + exq[NW * 32 + (wave * 2 + 1) * 16 + mm];   // (the same order in both waves)
-      const float rsum = 1.0f / sum;
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = 16 * t + 4 * cg + r;
-          float w = 1.0f;
-          if (KNN) w = ewm[t][r];
-          S[t][r] = (m < M && mine(t)) ? (S[t][r] * rsum) * w : 0.f;
-        }
-    }
   }
   DD_STAMP(6);
   DD_STAMP(7);
@@ -999,7 +878,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   // ---- pass 2 -----------------------------------------------------------------------------------------------
   if (POS) {
     // wave pairs: the weights go from the k side to the v side through LDS, [tile][r][lane] per pair, behind one barrier
-    float* xw = smem + L::TOTAL + (QUAD ? 2 : 1) * NW * 256 + wave * (MAXT * 4 * 64);
+    float* xw = smem + L::TOTAL + NW * 256 + wave * (MAXT * 4 * 64);
     f32x4 Vt[MAXT];                                    // V[r] = v16[member 16t+4cg+r][head mm] - bias
     if (active && vside) {
       float Wv[32];
@@ -1010,7 +889,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
       }
 #pragma unroll
       for (int t = 0; t < MAXT; ++t) {
-        if (t < T && mine(t)) {
+        if (t < T) {
           float P[32];
           build_pre(t, 1, P);
           Vt[t] = mfma_rows(P, Wv);
@@ -1021,20 +900,16 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
       if (active && kside) {
 #pragma unroll
         for (int t = 0; t < MAXT; ++t)
-          if (mine(t)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) xw[(t * 4 + r) * 64 + lane] = S[t][r];
-          }
+          for (int r = 0; r < 4; ++r) xw[(t * 4 + r) * 64 + lane] = S[t][r];
       }
       __syncthreads();
-      if (!QUAD && role == 0) { DD_STAMP(10); return; }
+      if (role == 0) { DD_STAMP(10); return; }
       if (active && vside) {
 #pragma unroll
         for (int t = 0; t < MAXT; ++t)
-          if (mine(t)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) S[t][r] = xw[(t * 4 + r) * 64 + lane];
-          }
+          for (int r = 0; r < 4; ++r) S[t][r] = xw[(t * 4 + r) * 64 + lane];
       }
     }
     float dx = 0.f, dy = 0.f, dz = 0.f;
@@ -1042,7 +917,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
       const float bv = a.b2v16[mm];
 #pragma unroll
       for (int t = 0; t < MAXT; ++t) {
-        if (t < T && mine(t)) {
+        if (t < T) {
           const f32x4 V = Vt[t];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -1063,15 +938,8 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
       dx = wave_sum(dx) * (1.0f / 16.0f);
       dy = wave_sum(dy) * (1.0f / 16.0f);
       dz = wave_sum(dz) * (1.0f / 16.0f);
-      if (QUAD && lane < 3) exq[NW * 64 + (wave * 2 + tsel) * 4 + lane] = lane == 0 ? dx : (lane == 1 ? dy : dz);
     }
-    if (QUAD) __syncthreads();                         // (the two halves of the update; every wave of the workgroup arrives here)
-    if (active && vside && (!QUAD || tsel == 0)) {
-      if (QUAD) {                                      // even tiles + odd tiles, in this order
-        dx = exq[NW * 64 + (wave * 2) * 4 + 0] + exq[NW * 64 + (wave * 2 + 1) * 4 + 0];
-        dy = exq[NW * 64 + (wave * 2) * 4 + 1] + exq[NW * 64 + (wave * 2 + 1) * 4 + 1];
-        dz = exq[NW * 64 + (wave * 2) * 4 + 2] + exq[NW * 64 + (wave * 2 + 1) * 4 + 2];
-      }
+    if (active && vside) {
       if (lane < 3) {
         const float v = lane == 0 ? dx : (lane == 1 ? dy : dz);
         if (MODE == M_PE || a.x_next == nullptr) {
@@ -1090,37 +958,6 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   // member-major layout (row = channel 16nt + mm, k = member 16t + 4cg + ks), B = alpha*w of the same member as
   // produced by pass 1 (S[t][ks]) -- no transposes, no LDS
   f32x4 Z[8];
-#if DD_PEEL_Z
-  if (active && T > 0) {                                 // the first k-step of tile 0 starts the chains from an inline zero
-    {
-      float Tz[32];
-      finish_T(0, Tz);
-      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int nt = 0; nt < 8; ++nt) Z[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Tz[4 * nt], S[0][0], zero4, 0, 0, 0);
-#pragma unroll
-      for (int ks = 1; ks < 4; ++ks)
-#pragma unroll
-        for (int nt = 0; nt < 8; ++nt)
-          Z[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Tz[4 * nt + ks], S[0][ks], Z[nt], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 1; t < MAXT; ++t) {
-      if (t < T) {
-        float Tz[32];
-        finish_T(t, Tz);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt)
-            Z[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Tz[4 * nt + ks], S[t][ks], Z[nt], 0, 0, 0);
-      }
-    }
-  } else {                                               // (idle wave, or a bond pair without a third atom: NL = 2)
-#pragma unroll
-    for (int nt = 0; nt < 8; ++nt) Z[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-#else
 #pragma unroll
   for (int nt = 0; nt < 8; ++nt) Z[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (active) {
@@ -1137,7 +974,6 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
       }
     }
   }
-#endif
   DD_STAMP(8);
 
   // ---- epilogue: out[o] = W2v[o,:] . Z~[head(o),:] + b2v[o] * sum_m alpha*w ----------------------------------
@@ -1190,7 +1026,7 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
   }
   float* const lin_rows = smem + L::TOTAL + 16;          // [NW][WPITCH]: the attention outputs of the block's NW segments
   if constexpr (NECO) {
-    // Cooperative epilogue of a node block (as bl_coop_body's): every wave leaves its Z~ [16 heads][128] in the exchange buffer that
+    // Cooperative epilogue of a node block: every wave leaves its Z~ [16 heads][128] in the exchange buffer that
     // took the W2k image's place; wave w then forms out[s][16 w .. 16 w + 15] for the block's 8 segments as ONE 16 x 16 x 128 MFMA
     // chain -- rows i = 2 s + h' (the two heads 2w, 2w + 1 of segment s), columns = the 16 outputs of those heads, the two diagonal
     // 8-column blocks are the results -- with its 16 rows of W2v as the B operand straight from L2 (requested before the barrier).
@@ -1316,731 +1152,6 @@ __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float
 #undef DD_STAMP
 }
 
-// ---- persistent bond-layer workgroups with a COOPERATIVE query fold and epilogue (round 6, EXPERIMENTS.md R6-2) ------------------
-// In attn2_body every wave folds its own query (Q~ = q . blockdiag(W2k): each of the 16 K weights used once per segment) and runs
-// its own epilogue (W2v . Z~: the same), streaming the whole 64 KB W2k / W2v image through the LDS port shared by 8 in-phase waves:
-// 1 MiB of LDS reads per trip of 8 segments, ~8 k cycles at the port's 128 B/clk for ~3 k cycles of arithmetic.  Here the 8 waves
-// of a trip split both by HEAD instead: wave w owns heads 2w, 2w + 1 of all 8 segments.
-//   * fold: the 16 W2k rows of its heads live in 32 registers for the workgroup's lifetime (no W2k image in LDS at all); the 8
-//     queries of the trip are published in LDS (4 KB, broadcast reads); the 8 x 2 x 128 products go to an exchange buffer that
-//     takes the W2k image's place, and every wave reads the Q~ of ITS segment back in the MFMA B-operand layout (8 x 16 bytes).
-//   * epilogue: every wave writes its Z~ (16 heads x 128 channels) to the same buffer; wave w forms out[s][16w .. 16w + 15] for the 8
-//     segments as ONE 16 x 16 x 128 MFMA chain (rows = (segment, head of the pair), columns = the 16 outputs of its two heads;
-//     the two diagonal 8-column blocks are the results), W2v as the B operand from a natural-order LDS image (8 KB per wave).
-//   LDS traffic per trip: 64 (queries, broadcast) + 64 + 64 + 64 + 64 + 64 KB instead of 1 MiB.
-//   * the NEXT trip's prologue (segment indices, query, gather rows of its first k-pass tile, triplet geometry) is issued in front
-//     of the epilogue, so those loads fly during the epilogue, the trip barrier and the next fold.
-// Exchange buffer addressing: (s, h, c) -> s * XSTR + h * WPITCH + c with XSTR = 16 * WPITCH + 16: writers (lane = head, fixed
-// segment), the Q~ readers (the same) and the epilogue's A-operand readers (lane i = 2 * segment-in-pair... row i = 2s + h') all
-// hit 16-byte bank slots 2 * (lane & 15) + (lane >> 4) (mod 16), the conflict-free pattern of the weight images (see WPITCH).
-struct CoopLds {
-  static constexpr int XSTR = 16 * WPITCH + 16;
-  static constexpr int XB = 0;                          // exchange buffer [8 segments][16 heads][WPITCH] (+ 16 floats of skew per segment)
-  static constexpr int WV = 8 * XSTR;                   // W2v image, natural row order, pitch WPITCH
-  static constexpr int LNP = WV + WB_FLOATS;            // [4][128] LayerNorm parameters (k: gamma, beta; v: gamma, beta)
-  static constexpr int WAO = LNP + 512;                 // [2][12][128] angle tables (MFMA operand layout)
-  static constexpr int QS = WAO + 2 * 12 * 128;         // [8][128] queries of the trip
-  static constexpr int SS = QS + 8 * 128;               // [8][16] sum of the attention weights per (segment, head)
-  static constexpr int SG = SS + 8 * 16;                // ints: [8] dense segment ids of the trip, [8..10] trip indices (current, next)
-  static constexpr int TOTAL = SG + 16;
-};
-
-template <int MAXT, bool RAG, bool STAMPS, typename ARGS>
-__device__ __forceinline__ void bl_coop_body(const ARGS& a, float* smem) {
-  constexpr int NW = 8, NT = NW * 64;
-  using C = CoopLds;
-  constexpr int XSTR = C::XSTR;
-  const int wave = threadIdx.x >> 6, lane0 = threadIdx.x & 63;
-  const int NLm1 = a.NL - 1, Eb = a.NL * NLm1;
-  const int nseg = RAG ? a.bl_prefix[a.B] : a.B * Eb;
-  float* const XB = smem + C::XB;
-  float* const WV = smem + C::WV;
-  float* const QS = smem + C::QS;
-  float* const SS = smem + C::SS;
-  int* const sg = reinterpret_cast<int*>(smem + C::SG);
-  int* const sb = sg + 8;
-  long long* const dbg0 = STAMPS ? a.dbg_clock : nullptr;
-  long long* dbg = nullptr;
-#define DD_STAMP(i) do { if (STAMPS && dbg && threadIdx.x == 0) dbg[i] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-
-  // ---- once per workgroup: W2v image (natural order), LayerNorm parameters, angle tables; this wave's W2k rows in registers
-  {
-    constexpr int PER = 4096 / NT;
-    float4 tmp[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) tmp[k] = reinterpret_cast<const float4*>(a.W2v)[threadIdx.x + k * NT];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const int i = threadIdx.x + k * NT;
-      *reinterpret_cast<float4*>(&WV[(i >> 5) * WPITCH + (i & 31) * 4]) = tmp[k];
-    }
-    if (threadIdx.x < 64) {
-      reinterpret_cast<float4*>(smem + C::LNP)[threadIdx.x] = reinterpret_cast<const float4*>(a.lnk)[threadIdx.x];
-      reinterpret_cast<float4*>(smem + C::LNP + 256)[threadIdx.x] = reinterpret_cast<const float4*>(a.lnv)[threadIdx.x];
-    }
-    for (int i = threadIdx.x; i < 12 * 32; i += NT) {
-      reinterpret_cast<float4*>(smem + C::WAO)[i] = reinterpret_cast<const float4*>(a.Wakp)[i];
-      reinterpret_cast<float4*>(smem + C::WAO + 12 * 128)[i] = reinterpret_cast<const float4*>(a.Wavp)[i];
-    }
-  }
-  float Wk[32];                                          // W2k[16 wave + r][2 lane + {0, 1}]  (rows 8 h + d of heads 2 wave, 2 wave + 1)
-  auto load_wk = [&](int lane) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float2 w = *reinterpret_cast<const float2*>(a.W2k + (16 * wave + r) * 128 + 2 * lane);
-#if DD_LN_FOLD
-      Wk[2 * r] = w.x; Wk[2 * r + 1] = w.y;
-#else
-      Wk[2 * r] = w.x * 0.35355339059327373f; Wk[2 * r + 1] = w.y * 0.35355339059327373f;
-#endif
-    }
-  };
-  load_wk(lane0);
-  // (loop-invariant, and loaded HERE: a global load inside the epilogue would queue behind the next trip's gathers)
-  const float ep_bias = a.b2v[(2 * wave + ((lane0 & 15) >> 3)) * 8 + (lane0 & 7)];
-  if (threadIdx.x == 0) sb[0] = atomicAdd(a.work_counter, 1);
-  __syncthreads();
-
-  auto trip_range = [&](int tr, int& base, int& cnt) {
-    if (tr < a.trip_full) { base = tr * NW; cnt = NW; }
-    else { base = a.trip_full * NW + (tr - a.trip_full) * a.trip_q; cnt = a.trip_q; }
-    cnt = nseg - base < cnt ? nseg - base : cnt;         // <= 0: no work left
-  };
-  auto bl_dense_seg = [&](int r) -> int {                // compact index of a real segment -> id in the dense (padded) enumeration
-    if (!RAG) return r;
-    int bb = 0;
-    while (a.bl_prefix[bb + 1] <= r) ++bb;
-    const int nm1 = a.nl_real[bb] - 1, e = r - a.bl_prefix[bb];
-    return bb * Eb + (e / nm1) * NLm1 + (e % nm1);
-  };
-
-  // ---- state of the NEXT trip's segment, filled one trip ahead (fetch) --------------------------------------------------------
-  int segN = 0, bN = 0, siN = 0, sjN = 0, MN = 0;
-  bool actN = false;
-  float2 q2 = make_float2(0.f, 0.f);
-  float Pf[32];
-#if DD_COOP_RC
-  float Rc[32];
-#pragma unroll
-  for (int k = 0; k < 32; ++k) Rc[k] = 0.f;
-#endif
-  float tri_i[3] = {0.f, 0.f, 0.f}, tri_j[3] = {0.f, 0.f, 0.f}, tri_k[MAXT][3];
-#pragma unroll
-  for (int k = 0; k < 32; ++k) Pf[k] = 0.f;
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t) tri_k[t][0] = tri_k[t][1] = tri_k[t][2] = 0.f;
-  auto third_atom = [](int mc, int si, int sj) { const int lo = si < sj ? si : sj, hi = si < sj ? sj : si; int k = mc; if (k >= lo) ++k; if (k >= hi) ++k; return k; };
-  auto fetch = [&](int tr, int lane) {
-    int base, cnt;
-    trip_range(tr, base, cnt);
-    actN = wave < cnt;
-    if (!actN) return;
-    const int mm = lane & 15, cg = lane >> 4;
-    segN = bl_dense_seg(base + wave);
-    bN = segN / Eb;
-    const int e = segN % Eb;
-    siN = e / NLm1;
-    const int jp = e % NLm1;
-    sjN = jp + (jp >= siN ? 1 : 0);
-    MN = RAG ? a.nl_real[bN] - 2 : a.NL - 2;
-    q2 = *reinterpret_cast<const float2*>(a.q + (long)segN * 128 + 2 * lane);
-    {                                                    // k-pass rows of tile 0: bond (k -> j) of member mm
-      const int mc = mm < MN ? mm : (MN > 0 ? MN - 1 : 0);
-      const int k = third_atom(mc, siN, sjN);
-      load_row(Pf, a.ke + ((long)bN * Eb + sjN * NLm1 + (k - (k > sjN ? 1 : 0))) * a.ld_ke, cg);
-    }
-#if DD_COOP_RC
-    load_row(Rc, a.Rk + (long)segN * 128, cg);
-#endif
-    const float* xl = a.x + ((long)bN * (a.NP + a.NL) + a.NP) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { tri_i[c] = xl[3 * siN + c]; tri_j[c] = xl[3 * sjN + c]; }
-#pragma unroll
-    for (int t = 0; t < MAXT; ++t) {
-      const int m = 16 * t + mm;
-      const int k = third_atom(m < MN ? m : MN - 1, siN, sjN);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) tri_k[t][c] = xl[3 * k + c];
-    }
-  };
-  fetch(__builtin_amdgcn_readfirstlane(sb[0]), lane0);
-
-  for (int it = 0;; ++it) {
-    // (the lane id is laundered per iteration: loop-invariant per-lane address arithmetic stays inside the iteration)
-    int lane = lane0;
-    asm volatile("" : "+v"(lane) :: "memory");
-    const int mm = lane & 15, cg = lane >> 4;
-
-    // ---- 1. publish this wave's query and segment id; barrier A (also: the previous trip's epilogue reads of XB are done)
-    if (actN) *reinterpret_cast<float2*>(QS + wave * 128 + 2 * lane) = q2;
-    if (lane == 0) sg[wave] = segN;
-    __syncthreads();
-    int base, cnt;
-    trip_range(__builtin_amdgcn_readfirstlane(sb[it & 1]), base, cnt);
-    if (cnt <= 0) break;
-    if (threadIdx.x == 0) sb[(it + 1) & 1] = atomicAdd(a.work_counter, 1);
-    if (STAMPS && dbg0) dbg = dbg0 + (long)__builtin_amdgcn_readfirstlane(sb[it & 1]) * 16;
-    DD_STAMP(0);
-
-    const int seg = segN, b = bN, si = siN, sj = sjN;
-    const bool active = actN;
-    const int M = MN, T = (M + 15) >> 4;
-
-    // old values of the rows this wave will update in the epilogue (out[s][8 (2 wave + h) + j] for s = 2 (lane >> 4) + {0, 1}):
-    // requested now, ahead of every gather of the trip (loads return in order)
-    const int eh = mm >> 3, ej = mm & 7;                 // epilogue: column = output 8 eh + ej of head 2 wave + eh
-    float old0 = 0.f, old1 = 0.f;
-    float* dst0 = nullptr;
-    float* dst1 = nullptr;
-    {
-      const int s0 = 2 * cg, s1 = 2 * cg + 1;
-      if (s0 < cnt) { dst0 = a.out + (long)sg[s0] * 128 + (2 * wave + eh) * 8 + ej; old0 = *dst0; }
-      if (s1 < cnt) { dst1 = a.out + (long)sg[s1] * 128 + (2 * wave + eh) * 8 + ej; old1 = *dst1; }
-    }
-
-    // ---- 2. cooperative fold: Q~[s][h][2 lane + {0, 1}] for h = 2 wave, 2 wave + 1 and the 8 segments of the trip
-#pragma unroll 2
-    for (int s = 0; s < 8; ++s) {
-      float qv[16];
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4) {
-        const float4 v = *reinterpret_cast<const float4*>(QS + s * 128 + 16 * wave + 4 * k4);    // (wave-uniform address: broadcast)
-        qv[4 * k4] = v.x; qv[4 * k4 + 1] = v.y; qv[4 * k4 + 2] = v.z; qv[4 * k4 + 3] = v.w;
-      }
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        float a0 = qv[8 * hh] * Wk[16 * hh], a1 = qv[8 * hh] * Wk[16 * hh + 1];
-#pragma unroll
-        for (int d = 1; d < 8; ++d) {
-          a0 = fmaf(qv[8 * hh + d], Wk[16 * hh + 2 * d], a0);
-          a1 = fmaf(qv[8 * hh + d], Wk[16 * hh + 2 * d + 1], a1);
-        }
-        *reinterpret_cast<float2*>(XB + s * XSTR + (2 * wave + hh) * WPITCH + 2 * lane) = make_float2(a0, a1);
-      }
-    }
-    DD_STAMP(1);
-    __syncthreads();                                     // barrier C
-    DD_STAMP(2);
-    // ---- 3. Q~ of this wave's segment as the MFMA B operand: lane (h = mm, cg) holds Q~[h][16 nt + 4 cg + r]
-    float Qb[32];
-#pragma unroll
-    for (int nt = 0; nt < 8; ++nt) {
-      const float4 v = *reinterpret_cast<const float4*>(XB + wave * XSTR + mm * WPITCH + 16 * nt + 4 * cg);
-      Qb[4 * nt] = v.x; Qb[4 * nt + 1] = v.y; Qb[4 * nt + 2] = v.z; Qb[4 * nt + 3] = v.w;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();                                     // barrier D: XB is free for the epilogue's exchange
-    DD_STAMP(3);
-
-    // ---- 4. the segment itself: angle codes, k pass, softmax, v pass (as attn2_body<M_BL>) -----------------------------------
-    const long erow_j = (long)b * Eb + (long)sj * NLm1;   // first bond row of destination j in the dst-major tables
-    auto kj_row = [&](int m) {                           // row of bond (k -> j) for member m (clipped)
-      const int k = third_atom(m < M ? m : M - 1, si, sj);
-      return erow_j + (k - (k > sj ? 1 : 0));
-    };
-    float cod[MAXT][3];
-    f32x4 S[MAXT];
-    float ssum = 0.f;
-    f32x4 Z[8];
-#pragma unroll
-    for (int nt = 0; nt < 8; ++nt) Z[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (active) {
-      const float ax = tri_j[0] - tri_i[0], ay = tri_j[1] - tri_i[1], az = tri_j[2] - tri_i[2];
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        const float bx = tri_k[t][0] - tri_i[0], by = tri_k[t][1] - tri_i[1], bz = tri_k[t][2] - tri_i[2];
-        const float dot = ax * bx + ay * by + az * bz;
-        const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-        angle_codes(cx * cx + cy * cy + cz * cz, dot, cg, cod[t]);
-      }
-      DD_STAMP(4);
-      const float* rk_row = a.Rk + (long)seg * 128;
-      // k pass: lane (mm, cg) = member 16 t + mm, channels 16 nt + 4 cg + r
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        if (t < T) {
-          float P[32];
-#if DD_COOP_RC
-#pragma unroll
-          for (int k = 0; k < 32; ++k) P[k] = Pf[k] + Rc[k];
-#else
-#pragma unroll
-          for (int k = 0; k < 32; ++k) P[k] = Pf[k];
-          add_row(P, rk_row, cg);
-#endif
-          if (t + 1 < MAXT) load_row(Pf, a.ke + kj_row(16 * (t + 1) + mm) * a.ld_ke, cg);   // next tile's rows (clipped members)
-          if (STAMPS && dbg && t == 0) { asm volatile("" : "+v"(P[0]), "+v"(P[31])); DD_STAMP(13); }      // segment row arrived
-          f32x4 acc[8];
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) acc[nt] = f32x4{P[4 * nt], P[4 * nt + 1], P[4 * nt + 2], P[4 * nt + 3]};
-          const float* tb = smem + C::WAO + cg * 128 + mm * 4;
-#pragma unroll
-          for (int s3 = 0; s3 < 3; ++s3) mfma_table_step<false>(acc, tb + s3 * 512, cod[t][s3]);
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) { P[4 * nt] = acc[nt][0]; P[4 * nt + 1] = acc[nt][1]; P[4 * nt + 2] = acc[nt][2]; P[4 * nt + 3] = acc[nt][3]; }
-          ln_relu32(P, smem + C::LNP, cg);
-          if (STAMPS && dbg && t == 0) { asm volatile("" : "+v"(P[0]), "+v"(P[31])); DD_STAMP(14); }      // table part + LayerNorm done
-          S[t] = mfma_rows(P, Qb);
-          if (STAMPS && dbg && t == 0) { asm volatile("" : "+v"(S[t])); DD_STAMP(15); }                     // scores of tile 0 done
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (16 * t + 4 * cg + r >= M) S[t][r] = -INFINITY;
-        } else {
-          S[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        }
-      }
-      DD_STAMP(5);
-      // v-pass rows (member-major layout: lane (mm, cg) holds members 16 t + 4 cg + r, channels 16 nt + mm), one tile ahead
-      float Tc[8], Tr[32];
-      auto fetch_T = [&](int t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float* rs = a.ve + kj_row(16 * t + 4 * cg + r) * a.ld_ve + mm;
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) Tr[4 * nt + r] = rs[16 * nt];
-        }
-      };
-      {
-        const float* rc = a.Rv + (long)seg * 128 + mm;
-#pragma unroll
-        for (int nt = 0; nt < 8; ++nt) Tc[nt] = rc[16 * nt];
-      }
-      fetch_T(0);
-      // segment softmax per head (scatter_softmax): max-shift, exp, one reciprocal per head
-      float mx = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, S[t][r]);
-      mx = quad_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = (16 * t + 4 * cg + r < M) ? expf(S[t][r] - mx) : 0.f;
-          S[t][r] = e;
-          sum += e;
-        }
-      sum = quad_sum(sum);
-#if defined(DD_EXACT_MATH) && DD_EXACT_MATH
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { S[t][r] = (16 * t + 4 * cg + r < M) ? S[t][r] / sum : 0.f; ssum += S[t][r]; }
-#else
-      const float rsum = 1.0f / sum;
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { S[t][r] = (16 * t + 4 * cg + r < M) ? S[t][r] * rsum : 0.f; ssum += S[t][r]; }
-#endif
-      ssum = quad_sum(ssum);
-      DD_STAMP(6);
-      // v pass + aggregation  Z[nt][r] = Z~[head mm][channel 16 nt + 4 cg + r]
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        if (t < T) {
-          float Tz[32];
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int nt = 0; nt < 8; ++nt) Tz[4 * nt + r] = Tc[nt] + Tr[4 * nt + r];
-          if (t + 1 < MAXT) fetch_T(t + 1);
-          f32x4 acc[8];
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) acc[nt] = f32x4{Tz[4 * nt], Tz[4 * nt + 1], Tz[4 * nt + 2], Tz[4 * nt + 3]};
-          const float* tb = smem + C::WAO + 12 * 128 + cg * 128 + mm * 4;
-#pragma unroll
-          for (int s3 = 0; s3 < 3; ++s3) mfma_table_step<true>(acc, tb + s3 * 512, cod[t][s3]);
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) { Tz[4 * nt] = acc[nt][0]; Tz[4 * nt + 1] = acc[nt][1]; Tz[4 * nt + 2] = acc[nt][2]; Tz[4 * nt + 3] = acc[nt][3]; }
-          ln_relu_T(Tz, smem + C::LNP + 256, mm);
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int nt = 0; nt < 8; ++nt)
-              Z[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Tz[4 * nt + ks], S[t][ks], Z[nt], 0, 0, 0);
-        }
-      }
-    }
-    DD_STAMP(7);
-
-    // ---- 5. the next trip's prologue: its loads fly during the epilogue, barrier A and the next fold ---------------------------
-    fetch(__builtin_amdgcn_readfirstlane(sb[(it + 1) & 1]), lane);
-#if DD_COOP_WK_RELOAD
-    load_wk(lane);
-#endif
-    DD_STAMP(8);
-
-    // ---- 6. cooperative epilogue ------------------------------------------------------------------------------------------------
-    if (active) {
-#pragma unroll
-      for (int nt = 0; nt < 8; ++nt)
-        *reinterpret_cast<float4*>(XB + wave * XSTR + mm * WPITCH + 16 * nt + 4 * cg) = make_float4(Z[nt][0], Z[nt][1], Z[nt][2], Z[nt][3]);
-      if (cg == 0) SS[wave * 16 + mm] = ssum;
-    }
-    DD_STAMP(9);
-    __syncthreads();                                     // barrier E
-    DD_STAMP(10);
-    {
-      // rows i = 2 s + h' (i = lane & 15), k = channel 16 nt + 4 (lane >> 4) + r4;  columns = outputs 16 wave + (lane & 15)
-      const float* ar = XB + (mm >> 1) * XSTR + (2 * wave + (mm & 1)) * WPITCH + 4 * cg;
-      const float* br = WV + (16 * wave + mm) * WPITCH + 4 * cg;
-      f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int nt = 0; nt < 8; nt += 2) {
-        const float4 a0 = *reinterpret_cast<const float4*>(ar + 16 * nt), b0 = *reinterpret_cast<const float4*>(br + 16 * nt);
-        const float4 a1 = *reinterpret_cast<const float4*>(ar + 16 * nt + 16), b1 = *reinterpret_cast<const float4*>(br + 16 * nt + 16);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0.x, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b1.x, d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0.y, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1.y, d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0.z, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1.z, d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0.w, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, d1, 0, 0, 0);
-      }
-      const f32x4 d = d0 + d1;                           // rows 4 cg + r <-> (s = 2 cg + (r >> 1), h' = r & 1); useful: h' == eh
-      DD_STAMP(11);
-      const float bias = ep_bias;
-      if (dst0) *dst0 = old0 + fmaf(bias, SS[(2 * cg) * 16 + 2 * wave + eh], eh ? d[1] : d[0]);
-      if (dst1) *dst1 = old1 + fmaf(bias, SS[(2 * cg + 1) * 16 + 2 * wave + eh], eh ? d[3] : d[2]);
-    }
-    DD_STAMP(12);
-  }
-#undef DD_STAMP
-}
-
-// ---- persistent node_layer_with_edge workgroups (round 6, EXPERIMENTS.md R6-8) ------------------------------------------------------
-// The NE blocks of attn2_body stage 112 KB of weight images for every 8 nodes (18 % of a block's time) and start and end as workgroups of
-// their own.  Here a workgroup stages ONLY the Gaussian tables of its centre kind (protein or ligand) and the LayerNorm rows, once, and
-// then pulls blocks of 8 nodes of that kind from a counter:
-//   * no W2k image: the query fold is split by head over the 8 waves (as bl_coop_body: wave w keeps the 16 W2k rows of heads 2w, 2w + 1
-//     in registers, the block's 8 queries are published in LDS, the products cross through the exchange buffer);
-//   * no W2v image: the epilogue is one MFMA chain per wave with its 16 W2v rows straight from L2 (as the NE blocks' NECO form), Z~
-//     through the same exchange buffer.  (Launches that carry lin_node, a.lin_W, keep the block form: launch_node_nw.)
-// LDS: exchange buffer 70 KB + tables 48 KB + small = 127 KB.  Same arithmetic in the same order as the block form: bit-identical.
-struct NepLds {
-  static constexpr int XSTR = 16 * WPITCH + 16;
-  static constexpr int XB = 0;
-  static constexpr int TAB = 8 * XSTR;                  // [k lo, k hi, v lo, v hi] tables of this centre kind (4 x 24 x 128)
-  static constexpr int LNP = TAB + 4 * TABP;            // [4][128]
-  static constexpr int QS = LNP + 512;                  // [8][128] queries of the block
-  static constexpr int ROWS = QS + 8 * 128;             // [8][WPITCH] attention outputs of the block (lin_node)
-  static constexpr int SS = ROWS + 8 * WPITCH;          // [8][16]
-  static constexpr int SB = SS + 128;                   // ints: block indices (current, next)
-  static constexpr int TOTAL = SB + 16;
-};
-
-template <bool RAG, typename ARGS>
-__device__ __forceinline__ void ne_persist_body(const ARGS& a, float* smem, const bool wg_protein, int32_t* counter) {
-  constexpr int NW = 8, NT = NW * 64, MAXT = 2;
-  using C = NepLds;
-  constexpr int XSTR = C::XSTR;
-  const int wave = threadIdx.x >> 6, lane0 = threadIdx.x & 63;
-  const int N = a.NP + a.NL;
-  const int nb_kind = wg_protein ? (a.NP + NW - 1) / NW : (a.NL + NW - 1) / NW;     // blocks of this kind per sample
-  const int n_blocks = a.B * nb_kind;
-  float* const XB = smem + C::XB;
-  float* const QS = smem + C::QS;
-  float* const SS = smem + C::SS;
-  int* const sb = reinterpret_cast<int*>(smem + C::SB);
-  const int M = a.K, T = (M + 15) >> 4;
-
-  // ---- once per workgroup: tables of this centre kind, LayerNorm rows; this wave's W2k rows in registers
-  {
-    const int tyl = wg_protein ? 1 : 0;                  // edge type = 2 * (source is protein) + (centre is protein)
-    constexpr int PER = (4 * 768) / NT;
-    float4 tmp[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const int i = threadIdx.x + k * NT, q = i / 768, w = i - q * 768;
-      const float* src = (q < 2 ? a.Akp : a.Avp) + (tyl + 2 * (q & 1)) * TABP;
-      tmp[k] = reinterpret_cast<const float4*>(src)[w];
-    }
-#pragma unroll
-    for (int k = 0; k < PER; ++k) reinterpret_cast<float4*>(smem + C::TAB)[threadIdx.x + k * NT] = tmp[k];
-    if (threadIdx.x < 64) {
-      reinterpret_cast<float4*>(smem + C::LNP)[threadIdx.x] = reinterpret_cast<const float4*>(a.lnk)[threadIdx.x];
-      reinterpret_cast<float4*>(smem + C::LNP + 256)[threadIdx.x] = reinterpret_cast<const float4*>(a.lnv)[threadIdx.x];
-    }
-  }
-  if (threadIdx.x == 0) sb[0] = atomicAdd(counter, 1);
-  __syncthreads();
-
-  for (int it = 0;; ++it) {
-    int lane = lane0;
-    asm volatile("" : "+v"(lane) :: "memory");
-    const int mm = lane & 15, cg = lane >> 4;
-    const int blk = __builtin_amdgcn_readfirstlane(sb[it & 1]);
-    if (blk >= n_blocks) break;
-    const int ne_b = blk / nb_kind, rb = blk % nb_kind;
-    const int node = wg_protein ? rb * NW + wave : a.NP + rb * NW + wave;
-    bool active = node < (wg_protein ? a.NP : N);
-    if (RAG && active) active = wg_protein ? node < (a.np_real ? a.np_real[ne_b] : a.NP) : node - a.NP < a.nl_real[ne_b];
-    const long seg = (long)ne_b * N + node;
-    const float* xb = a.x + (long)ne_b * N * 3;
-    const long src_base = (long)ne_b * N;
-
-    // neighbours, edge weights, distances (two dependent round trips: first), the query, the rows of the first k-pass tile
-    int jm[MAXT], jT[MAXT][4];
-    float dm[MAXT], ewm[MAXT][4];
-    float2 q2 = make_float2(0.f, 0.f);
-    float Rc[32], Pf[32];
-    if (active) {
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        const int m = 16 * t + mm;
-        jm[t] = a.nbr[seg * a.K + (m < M ? m : M - 1)];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int mr = 16 * t + 4 * cg + r;
-          ewm[t][r] = a.ew[seg * a.K + (mr < M ? mr : 0)];
-          jT[t][r] = a.nbr[seg * a.K + (mr < M ? mr : M - 1)];
-        }
-      }
-      q2 = *reinterpret_cast<const float2*>(a.q + seg * 128 + 2 * lane);
-      const float cx = xb[3 * node], cy = xb[3 * node + 1], cz = xb[3 * node + 2];
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        const float rx = cx - xb[3 * jm[t]], ry = cy - xb[3 * jm[t] + 1], rz = cz - xb[3 * jm[t] + 2];
-        dm[t] = sqrtf(rx * rx + ry * ry + rz * rz);
-      }
-      load_row(Rc, a.kd + seg * a.ld_kd, cg);
-      load_row(Pf, a.ks + (src_base + jm[0]) * a.ld_ks, cg);
-      *reinterpret_cast<float2*>(QS + wave * 128 + 2 * lane) = q2;
-    }
-    // this wave's 16 rows of W2k (heads 2 wave, 2 wave + 1), channels 2 lane, 2 lane + 1: 8 KB per wave and block from L2 (held in
-    // registers for the whole workgroup they cost the k / v passes 32 registers: 442 spilled)
-    float Wk[32];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float2 w = *reinterpret_cast<const float2*>(a.W2k + (16 * wave + r) * 128 + 2 * lane);
-#if DD_LN_FOLD
-      Wk[2 * r] = w.x; Wk[2 * r + 1] = w.y;
-#else
-      Wk[2 * r] = w.x * 0.35355339059327373f; Wk[2 * r + 1] = w.y * 0.35355339059327373f;
-#endif
-    }
-    __syncthreads();                                     // barrier 1: queries published; the previous block's exchange reads are done
-    if (threadIdx.x == 0) sb[(it + 1) & 1] = atomicAdd(counter, 1);
-
-    // ---- cooperative fold: Q~[s][h][2 lane + {0, 1}] for h = 2 wave, 2 wave + 1 and the 8 segments of the block
-#pragma unroll 2
-    for (int s = 0; s < 8; ++s) {
-      float qv[16];
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4) {
-        const float4 v = *reinterpret_cast<const float4*>(QS + s * 128 + 16 * wave + 4 * k4);
-        qv[4 * k4] = v.x; qv[4 * k4 + 1] = v.y; qv[4 * k4 + 2] = v.z; qv[4 * k4 + 3] = v.w;
-      }
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        // (the same chain as attn2_body's fold: fma(q_d, w_d, acc) from acc = 0, d ascending)
-        float a0 = fmaf(qv[8 * hh], Wk[16 * hh], 0.f), a1 = fmaf(qv[8 * hh], Wk[16 * hh + 1], 0.f);
-#pragma unroll
-        for (int d = 1; d < 8; ++d) {
-          a0 = fmaf(qv[8 * hh + d], Wk[16 * hh + 2 * d], a0);
-          a1 = fmaf(qv[8 * hh + d], Wk[16 * hh + 2 * d + 1], a1);
-        }
-        *reinterpret_cast<float2*>(XB + s * XSTR + (2 * wave + hh) * WPITCH + 2 * lane) = make_float2(a0, a1);
-      }
-    }
-    __syncthreads();                                     // barrier 2
-    float Qb[32];
-#pragma unroll
-    for (int nt = 0; nt < 8; ++nt) {
-      const float4 v = *reinterpret_cast<const float4*>(XB + wave * XSTR + mm * WPITCH + 16 * nt + 4 * cg);
-      Qb[4 * nt] = v.x; Qb[4 * nt + 1] = v.y; Qb[4 * nt + 2] = v.z; Qb[4 * nt + 3] = v.w;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();                                     // barrier 3: the exchange buffer is free for the epilogue
-
-    // first-Linear table part (type (x) Gaussian) of tile t on the matrix cores, either orientation (see attn2_body::table_part)
-    float Fg[MAXT][5];
-    auto table_part = [&](int t, int pass, f32x4 (&acc)[8], auto tr) {
-      constexpr bool TR = decltype(tr)::value;
-      if (pass == 0) {
-#pragma unroll
-        for (int s = 0; s < 5; ++s) Fg[t][s] = gauss_feat(dm[t], 4 * s + cg);
-      }
-      const bool hi = jm[t] < a.NP;
-      const float* tab = smem + C::TAB + pass * 2 * TABP + cg * 128 + mm * 4;
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const bool want = half ? hi : !hi;
-        if (__builtin_amdgcn_ballot_w64(want) != 0ull) {
-#pragma unroll
-          for (int s = 0; s < 5; ++s) mfma_table_step<TR>(acc, tab + half * TABP + s * 512, want ? Fg[t][s] : 0.0f);
-        }
-      }
-      const float* row20 = smem + C::TAB + pass * 2 * TABP + 20 * 128;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const bool hi_r = TR ? (jT[t][r] < a.NP) : hi;
-        const float* p = row20 + (hi_r ? TABP : 0) + (TR ? mm : 4 * cg + r) * 4;
-        const float4 c0 = *reinterpret_cast<const float4*>(p);
-        const float4 c1 = *reinterpret_cast<const float4*>(p + 64);
-        acc[0][r] += c0.x; acc[1][r] += c0.y; acc[2][r] += c0.z; acc[3][r] += c0.w;
-        acc[4][r] += c1.x; acc[5][r] += c1.y; acc[6][r] += c1.z; acc[7][r] += c1.w;
-      }
-    };
-
-    f32x4 S[MAXT];
-    float ssum = 0.f;
-    f32x4 Z[8];
-#pragma unroll
-    for (int nt = 0; nt < 8; ++nt) Z[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (active) {
-      // ---- k pass
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        if (t < T) {
-          float P[32];
-#pragma unroll
-          for (int k = 0; k < 32; ++k) P[k] = Rc[k] + Pf[k];
-          if (t + 1 < MAXT) load_row(Pf, a.ks + (src_base + jm[t + 1]) * a.ld_ks, cg);
-          f32x4 acc[8];
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) acc[nt] = f32x4{P[4 * nt], P[4 * nt + 1], P[4 * nt + 2], P[4 * nt + 3]};
-          table_part(t, 0, acc, std::false_type{});
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) { P[4 * nt] = acc[nt][0]; P[4 * nt + 1] = acc[nt][1]; P[4 * nt + 2] = acc[nt][2]; P[4 * nt + 3] = acc[nt][3]; }
-          ln_relu32(P, smem + C::LNP, cg);
-          S[t] = mfma_rows(P, Qb);
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (16 * t + 4 * cg + r >= M) S[t][r] = -INFINITY;
-        } else {
-          S[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        }
-      }
-      // ---- v-pass rows of tile 0 (member-major layout), then the softmax
-      float Tc[8], Tr[32];
-      auto fetch_T = [&](int t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float* rs = a.vs + (src_base + jT[t][r]) * a.ld_vs + mm;
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) Tr[4 * nt + r] = rs[16 * nt];
-        }
-      };
-      {
-        const float* rc = a.vd + seg * a.ld_vd + mm;
-#pragma unroll
-        for (int nt = 0; nt < 8; ++nt) Tc[nt] = rc[16 * nt];
-      }
-      fetch_T(0);
-      float mx = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, S[t][r]);
-      mx = quad_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = (16 * t + 4 * cg + r < M) ? expf(S[t][r] - mx) : 0.f;
-          S[t][r] = e;
-          sum += e;
-        }
-      sum = quad_sum(sum);
-      const float rsum = 1.0f / sum;
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = 16 * t + 4 * cg + r;
-#if defined(DD_EXACT_MATH) && DD_EXACT_MATH
-          const float aw = (m < M) ? (S[t][r] / sum) * ewm[t][r] : 0.f;
-#else
-          const float aw = (m < M) ? (S[t][r] * rsum) * ewm[t][r] : 0.f;
-#endif
-          S[t][r] = aw;
-          ssum += aw;
-        }
-      ssum = quad_sum(ssum);
-      // ---- v pass + aggregation
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        if (t < T) {
-          float Tz[32];
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int nt = 0; nt < 8; ++nt) Tz[4 * nt + r] = Tc[nt] + Tr[4 * nt + r];
-          if (t + 1 < MAXT) fetch_T(t + 1);
-          f32x4 acc[8];
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) acc[nt] = f32x4{Tz[4 * nt], Tz[4 * nt + 1], Tz[4 * nt + 2], Tz[4 * nt + 3]};
-          table_part(t, 1, acc, std::true_type{});
-#pragma unroll
-          for (int nt = 0; nt < 8; ++nt) { Tz[4 * nt] = acc[nt][0]; Tz[4 * nt + 1] = acc[nt][1]; Tz[4 * nt + 2] = acc[nt][2]; Tz[4 * nt + 3] = acc[nt][3]; }
-          ln_relu_T(Tz, smem + C::LNP + 256, mm);
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int nt = 0; nt < 8; ++nt)
-              Z[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Tz[4 * nt + ks], S[t][ks], Z[nt], 0, 0, 0);
-        }
-      }
-    }
-
-    // ---- cooperative epilogue (as the NE blocks' NECO form)
-    float4 Bv[8];
-    {
-      const float* bv = a.W2v + (16 * wave + mm) * 128 + 4 * cg;
-#pragma unroll
-      for (int nt = 0; nt < 8; ++nt) Bv[nt] = *reinterpret_cast<const float4*>(bv + 16 * nt);
-    }
-    const int eh = mm >> 3;
-    const float bias2 = a.b2v[16 * wave + mm];
-    if (active) {
-#pragma unroll
-      for (int nt = 0; nt < 8; ++nt)
-        *reinterpret_cast<float4*>(XB + wave * XSTR + mm * WPITCH + 16 * nt + 4 * cg) = make_float4(Z[nt][0], Z[nt][1], Z[nt][2], Z[nt][3]);
-      if (cg == 0) SS[wave * 16 + mm] = ssum;
-    }
-    __syncthreads();                                     // barrier 4
-    {
-      const float* ar = XB + (mm >> 1) * XSTR + (2 * wave + (mm & 1)) * WPITCH + 4 * cg;
-      f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int nt = 0; nt < 8; nt += 2) {
-        const float4 a0 = *reinterpret_cast<const float4*>(ar + 16 * nt), a1 = *reinterpret_cast<const float4*>(ar + 16 * nt + 16);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, Bv[nt].x, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, Bv[nt + 1].x, d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, Bv[nt].y, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, Bv[nt + 1].y, d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, Bv[nt].z, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, Bv[nt + 1].z, d1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, Bv[nt].w, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, Bv[nt + 1].w, d1, 0, 0, 0);
-      }
-      const f32x4 d = d0 + d1;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int sI = 2 * cg + u;
-        const int nd = (wg_protein ? rb * NW : a.NP + rb * NW) + sI;
-        bool ok = nd < (wg_protein ? a.NP : N);
-        if (RAG && ok) ok = wg_protein ? nd < (a.np_real ? a.np_real[ne_b] : a.NP) : nd - a.NP < a.nl_real[ne_b];
-        const float val = fmaf(bias2, SS[sI * 16 + 2 * wave + eh], eh ? d[2 * u + 1] : d[2 * u]);
-        if (ok) a.out[((long)ne_b * N + nd) * 128 + 16 * wave + mm] = val;
-      }
-    }
-  }
-}
-
-// stand-alone launch of the cooperative bond-layer workgroups (one launch per sub-layer: dd_debug_set_fusion(0), phase stamps)
-template <int MAXT, bool RAG>
-__global__ __launch_bounds__(512) void k_attn2_bl_coop(const AttnArgs a) {
-  __shared__ __attribute__((aligned(16))) float smem[CoopLds::TOTAL];
-  bl_coop_body<MAXT, RAG, true>(a, smem);
-}
-
 template <int MODE, int MAXT, int NW, bool RAG = false>
 __global__ __launch_bounds__(NW * 64) void k_attn2(const AttnArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[Lds<MODE>::TOTAL + ((MODE == M_PE || MODE == M_PB) ? NW * 256 : 0) +
@@ -2057,7 +1168,7 @@ constexpr int imax(int a, int b) { return a > b ? a : b; }
 template <int MAXT, int NW, bool RAG = false>
 __global__ __launch_bounds__(NW * 64) void k_attn2_node(const AttnArgs ne, const AttnArgs nb, const AttnArgs bl, int n_ne, int n_nb,
                                                         int persist, int n_bl_first, const int32_t* wflags, int widx, int wn, int nep) {
-  constexpr int SZ = imax(imax(imax(Lds<M_NE>::TOTAL, Lds<M_NB>::TOTAL), Lds<M_BL>::TOTAL) + 12, imax(DD_COOP && NW == 8 && MAXT == 2 ? CoopLds::TOTAL : 0, DD_NE_PERSIST && NW == 8 ? NepLds::TOTAL : 0));
+  constexpr int SZ = imax(imax(Lds<M_NE>::TOTAL, Lds<M_NB>::TOTAL), Lds<M_BL>::TOTAL) + 12;
   __shared__ __attribute__((aligned(16))) float smem[SZ];
   int blk = blockIdx.x;
   // this layer's projection / query rows come from the previous layer's tail queue on the other stream (no graph edge)
@@ -2075,7 +1186,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn2_node(const AttnArgs ne, const
     return *reinterpret_cast<KArgs*>((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
   };
   static_assert(sizeof(AttnArgs) % 8 == 0, "kernel parameter layout");
-  (void)ne; (void)nb; (void)bl;
+  (void)ne; (void)nb; (void)bl; (void)nep;             // (nep: read by no body any more, the launches pass 0)
   // n_bl_first > 0: the persistent bond-layer workgroups come first in dispatch order and keep their CUs for the whole
   // launch, the node blocks cycle through the remaining CUs -- both parts then end together (see launch_node_nw)
 #if DD_NODE_TRACE   // (measurement variant: start / end shader clock, kind and hardware id of every workgroup -> tools/node_trace.py)
@@ -2093,36 +1204,18 @@ __global__ __launch_bounds__(NW * 64) void k_attn2_node(const AttnArgs ne, const
 #endif
   if (n_bl_first > 0) {
     if (blk < n_bl_first) {
-      if constexpr (DD_COOP && NW == 8 && MAXT == 2) bl_coop_body<MAXT, RAG, false>(args(2), smem);
-      else attn2_body<M_BL, MAXT, NW, true, RAG, false, false>(args(2), blk, smem);
+      attn2_body<M_BL, MAXT, NW, true, RAG, false, false>(args(2), blk, smem);
       DD_TRACE_END(2);
       return;
     }
     blk -= n_bl_first;
-    if constexpr (DD_NE_PERSIST && NW == 8) {
-      if (nep != 0) {
-        // persistent node_layer_with_edge workgroups (nep = protein-kind count << 16 | ligand-kind count): the NB blocks come FIRST in
-        // dispatch order, the persistent workgroups their CUs cannot hold yet start when they end and pull what is left
-        const int np_p = nep >> 16, np_l = nep & 0xffff;
-        if (blk < n_nb) { attn2_body<M_NB, MAXT, NW, false, RAG, false, false>(args(1), blk, smem); DD_TRACE_END(1); return; }
-        blk -= n_nb;
-        KArgs& na = args(0);
-        if (blk < np_p) ne_persist_body<RAG>(na, smem, true, na.work_counter);
-        else if (blk < np_p + np_l) ne_persist_body<RAG>(na, smem, false, na.work_counter + 1);
-        DD_TRACE_END(0);
-        return;
-      }
-    }
     if (blk < n_ne) { attn2_body<M_NE, 2, NW, false, RAG, false, false>(args(0), blk, smem); DD_TRACE_END(0); }
     else { attn2_body<M_NB, MAXT, NW, false, RAG, false, false>(args(1), blk - n_ne, smem); DD_TRACE_END(1); }
     return;
   }
   if (blk < n_ne) attn2_body<M_NE, 2, NW, false, RAG, false, false>(args(0), blk, smem);
   else if (blk < n_ne + n_nb) attn2_body<M_NB, MAXT, NW, false, RAG, false, false>(args(1), blk - n_ne, smem);
-  else if (persist) {
-    if constexpr (DD_COOP && NW == 8 && MAXT == 2) bl_coop_body<MAXT, RAG, false>(args(2), smem);
-    else attn2_body<M_BL, MAXT, NW, true, RAG, false, false>(args(2), blk - n_ne - n_nb, smem);
-  }
+  else if (persist) attn2_body<M_BL, MAXT, NW, true, RAG, false, false>(args(2), blk - n_ne - n_nb, smem);
   else attn2_body<M_BL, MAXT, NW, false, RAG, false, false>(args(2), blk - n_ne - n_nb, smem);
 }
 // Same for the two coordinate sub-layers (both write their own delta buffer; x is updated afterwards).
@@ -2159,17 +1252,6 @@ __global__ __launch_bounds__(NW * 128) void k_attn2_pos(const AttnArgs pe, const
     }
     if (threadIdx.x == 0) *pe.work_counter = 0;
   }
-}
-
-// QUAD variant (four waves per segment, NW = 2 segments per workgroup: attn2_body's PAIR = 2)
-template <int MAXT, int NW, bool RAG = false>
-__global__ __launch_bounds__(NW * 256) void k_attn2_pos_q(const AttnArgs pe, const AttnArgs pb, int n_pe) {
-  // + two query-MLP scratch rows per segment + the weights' hand-over + the max / sum / update exchange
-  constexpr int SZ = imax(Lds<M_PE>::TOTAL, Lds<M_PB>::TOTAL) + 2 * NW * 256 + NW * MAXT * 256 + NW * 64 + NW * 8 + 16;
-  __shared__ __attribute__((aligned(16))) float smem[SZ];
-  const int blk = blockIdx.x;
-  if (blk < n_pe) attn2_body<M_PE, 2, NW, false, RAG, 2, false>(pe, blk, smem);
-  else attn2_body<M_PB, MAXT, NW, false, RAG, 2, false>(pb, blk - n_pe, smem);
 }
 
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
@@ -2239,8 +1321,6 @@ __global__ __launch_bounds__(NW * 128) void k_attn2_pos_g(const AttnArgs pe, con
 #ifdef DD_ASM_ONLY      // (hipcc -S -DDD_ASM_ONLY: only the shipped small-ligand kernels, for instruction censuses -- 20 s instead of 2 min)
 template __global__ void k_attn2_node<2, 8, false>(const AttnArgs, const AttnArgs, const AttnArgs, int, int, int, int, const int32_t*, int, int, int);
 template __global__ void k_attn2_pos<2, 4, false>(const AttnArgs, const AttnArgs, int);
-template __global__ void k_attn2_bl_coop<2, false>(const AttnArgs);
-template __global__ void k_attn2_pos_q<2, 2, false>(const AttnArgs, const AttnArgs, int);
 }  // namespace v2
 }  // namespace dd
 #else
@@ -2262,12 +1342,7 @@ namespace dd {
 
 int g_attn_waves = 8;        // waves (= segments) per workgroup of the fused node launch
 int g_attn_persist = 1;      // bond_layer workgroups of the fused launch are persistent (global batch counter)
-#ifndef DD_BL_TAIL
-#define DD_BL_TAIL 1
-#endif
-int g_bl_tail = DD_BL_TAIL;  // the last (partial) round of bond-layer trips spread evenly over the persistent workgroups
 int g_bl_first = 1;          // bond-layer workgroups first in the node launch: 0 off, 1 measured split per shape, n>1 that many
-int g_ne_persist = [] { const char* e = getenv("DD_NE_PERSIST"); return e ? (e[0] != '0') : 1; }();   // (A/B: DD_NE_PERSIST=0 keeps the block form)
 int g_node_split_trial = -1; // >= 0 while autotune_node_split is timing a candidate (0 = node blocks first)
 long long* g_node_trace = nullptr;   // DD_NODE_TRACE builds: [workgroups][16] clocks of the next fused node launches (dd_debug_set_clock_buffer(buf, 200))
 namespace {
@@ -2302,25 +1377,6 @@ int launch_attn2(int mode, const AttnArgs& a, hipStream_t st) {
     case M_PB: return small ? launch_mode<M_PB, 2, 8>(a, a.B * a.NL, st)
                             : (big ? launch_mode<M_PB, 8, 8>(a, a.B * a.NL, st) : launch_mode<M_PB, 4, 8>(a, a.B * a.NL, st));
     case M_BL:
-#if DD_COOP
-      if (a.work_counter != nullptr && small) {        // the fused launch's persistent cooperative workgroups, on their own
-                                                       // (2-tile body only: the longer bodies spill with the carried prefetch state)
-        const int n_trips = (a.B * a.NL * (a.NL - 1) + 7) / 8;
-        if (n_trips <= 0) return DD_OK;
-        const int n_wg = n_trips < 256 ? n_trips : 256;
-        AttnArgs c = a;
-        c.trip_full = 1 << 27; c.trip_q = 0;
-#define DD_LAUNCH_COOP(MAXT)                                                                                                  \
-        do {                                                                                                                  \
-          if (a.nl_real != nullptr) hipLaunchKernelGGL((k_attn2_bl_coop<MAXT, true>), dim3(n_wg), dim3(512), 0, st, c);       \
-          else hipLaunchKernelGGL((k_attn2_bl_coop<MAXT, false>), dim3(n_wg), dim3(512), 0, st, c);                           \
-        } while (0)
-        DD_LAUNCH_COOP(2);
-#undef DD_LAUNCH_COOP
-        DD_CHECK_LAUNCH();
-        return DD_OK;
-      }
-#endif
       return small ? launch_mode<M_BL, 2, 8>(a, a.B * a.NL * (a.NL - 1), st)
                    : (big ? launch_mode<M_BL, 8, 8>(a, a.B * a.NL * (a.NL - 1), st)
                           : launch_mode<M_BL, 4, 8>(a, a.B * a.NL * (a.NL - 1), st));
@@ -2342,7 +1398,7 @@ static int launch_node_nw(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs
   AttnArgs blt = bl;                                   // + the trip plan of the persistent workgroups (set_trips below)
   blt.trip_full = 1 << 27; blt.trip_q = 0;
   auto set_trips = [&](int n_wg) {
-    if (!g_bl_tail || ne.nl_real != nullptr || n_wg <= 0) return;      // (padded batches: the segment count lives on the device)
+    if (ne.nl_real != nullptr || n_wg <= 0) return;    // (padded batches: the segment count lives on the device)
     const int nseg = ne.B * ne.NL * (ne.NL - 1);
     const int full = nseg / (NW * n_wg) * n_wg, rem = nseg - full * NW;
     blt.trip_full = full;
@@ -2368,23 +1424,12 @@ static int launch_node_nw(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs
       if (want > 0) {
         n_bl = want < 16 ? 16 : (want > n_cu - 16 ? n_cu - 16 : want);
         set_trips(n_bl);
-        // persistent node_layer_with_edge workgroups on the other CUs, split by centre kind in proportion to the blocks of each kind
-        int nep = 0, n_grid = n_ne + n_nb + n_bl;
-        if (DD_NE_PERSIST && NW == 8 && g_ne_persist && ne.work_counter != nullptr && ne.lin_W == nullptr) {
-          const int nbp = ne.B * ((ne.NP + NW - 1) / NW), nbl = ne.B * ((ne.NL + NW - 1) / NW), n_rest = n_cu - n_bl;
-          int np_l = nbl > 0 ? (int)((long)n_rest * nbl / (nbp + nbl > 0 ? nbp + nbl : 1) + 0.5) : 0;
-          if (nbl > 0 && np_l < 1) np_l = 1;
-          if (np_l > nbl) np_l = nbl;
-          int np_p = n_rest - np_l;
-          if (np_p > nbp) np_p = nbp;
-          if (np_p > 0 || np_l > 0) { nep = (np_p << 16) | np_l; n_grid = n_bl + n_nb + np_p + np_l; }
-        }
         if (ne.nl_real != nullptr)
-          hipLaunchKernelGGL((k_attn2_node<MAXT, NW, true>), dim3(n_grid), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb,
-                             persist, n_bl, wf, ne.wait_idx, wfn, nep);
+          hipLaunchKernelGGL((k_attn2_node<MAXT, NW, true>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb,
+                             persist, n_bl, wf, ne.wait_idx, wfn, 0);
         else
-          hipLaunchKernelGGL((k_attn2_node<MAXT, NW>), dim3(n_grid), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist,
-                             n_bl, wf, ne.wait_idx, wfn, nep);
+          hipLaunchKernelGGL((k_attn2_node<MAXT, NW>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist,
+                             n_bl, wf, ne.wait_idx, wfn, 0);
         DD_CHECK_LAUNCH();
         return DD_OK;
       }
@@ -2476,28 +1521,8 @@ int launch_attn2_pos_g(const AttnArgs& pe_in, const AttnArgs& pb_in, const GemmA
 }
 
 int g_pos_waves = 4;         // waves per workgroup of the fused coordinate launch: 2, 4 or 8
-#ifndef DD_POS_QUAD
-#define DD_POS_QUAD 0       // measured SLOWER (EXPERIMENTS.md R6-5): 240 workgroups of 130 KB LDS leave no CU for the side stream's GEMMs
-#endif
-int g_pos_quad = DD_POS_QUAD;   // four waves per segment, two segments per workgroup (k_attn2_pos_q); no in-launch x update in this form
-static int launch_pos_quad(const AttnArgs& pe, const AttnArgs& pb, hipStream_t st) {
-  using namespace v2;
-  constexpr int NW = 2;
-  const int n = (pe.B * pe.NL + NW - 1) / NW;
-  const dim3 grid(2 * n), block(NW * 256);
-  if (pe.nl_real != nullptr) {
-    if (pe.NL > 65) hipLaunchKernelGGL((k_attn2_pos_q<8, NW, true>), grid, block, 0, st, pe, pb, n);
-    else if (pe.NL > 33) hipLaunchKernelGGL((k_attn2_pos_q<4, NW, true>), grid, block, 0, st, pe, pb, n);
-    else hipLaunchKernelGGL((k_attn2_pos_q<2, NW, true>), grid, block, 0, st, pe, pb, n);
-  } else if (pe.NL > 65) hipLaunchKernelGGL((k_attn2_pos_q<8, NW>), grid, block, 0, st, pe, pb, n);
-  else if (pe.NL > 33) hipLaunchKernelGGL((k_attn2_pos_q<4, NW>), grid, block, 0, st, pe, pb, n);
-  else hipLaunchKernelGGL((k_attn2_pos_q<2, NW>), grid, block, 0, st, pe, pb, n);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
-}
 int launch_attn2_pos(const AttnArgs& pe, const AttnArgs& pb, hipStream_t st) {
   if (pe.NL > 129) return DD_ERR_UNSUPPORTED_SHAPE;
-  if (g_pos_quad && pe.work_counter == nullptr) return launch_pos_quad(pe, pb, st);
   if (pe.NL > 65 && g_pos_waves > 4) return launch_pos_nw<4>(pe, pb, st);
   if (g_pos_waves == 2) return launch_pos_nw<2>(pe, pb, st);
   if (g_pos_waves == 4) return launch_pos_nw<4>(pe, pb, st);

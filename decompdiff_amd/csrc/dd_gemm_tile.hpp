@@ -7,12 +7,6 @@
 
 namespace dd {
 
-#ifndef DD_GEMM_EARLY_BIAS
-#define DD_GEMM_EARLY_BIAS 1  // the bias (one float4 per thread) requested ahead of the MFMAs: -0.4 % (B = 8), -1.0 % (B = 1), 0 (B = 16); R6-5
-#endif
-#ifndef DD_GEMM_EARLY_HALF
-#define DD_GEMM_EARLY_HALF 0  // both K halves + the bias requested before the first barrier: measured 1.8 % SLOWER at B = 8 (120 instead of
-#endif                        // 104 registers per thread, EXPERIMENTS.md R6-5)
 constexpr int GT = 64;        // tile rows / cols
 constexpr int GP = 130;       // LDS row pitch (floats)
 
@@ -170,13 +164,12 @@ __device__ __forceinline__ void gemm_tile_ksplit(const GemmArgs& a, const int bx
   long long* dbg = (STAMPS && a.dbg) ? a.dbg + ((long)by * gridDim.x + bx) * 8 : nullptr;
 #define GSTAMP(i) do { if (dbg && threadIdx.x == 0) dbg[i] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
   GSTAMP(0);
-#if DD_GEMM_EARLY_HALF || DD_GEMM_EARLY_BIAS
-  // the epilogue's bias values, requested now (they used to be a dependent global load behind the output's LDS round trip)
+  // the epilogue's bias values, requested now (they used to be a dependent global load behind the output's LDS round trip):
+  // -0.4 % step time at B = 8, -1.0 % at B = 1 (EXPERIMENTS.md R6-5)
   const int bias_gc = col0 + (tid & 15) * 4;
   const bool bias_ok = a.bias != nullptr && bias_gc + 3 < a.ncols;
   float4 bias_pre = make_float4(0.f, 0.f, 0.f, 0.f);
   if (bias_ok) bias_pre = *reinterpret_cast<const float4*>(a.bias + bias_gc);
-#endif
   if (a.ln != nullptr) {
     // LayerNorm+ReLU prologue (MLP hidden activation): both K-halves of the rows are fetched first; a row's 128 channels
     // sit in one 16-lane DPP row (4 + 4 channels per lane), so mean / variance are 4-step row reductions
@@ -217,26 +210,11 @@ __device__ __forceinline__ void gemm_tile_ksplit(const GemmArgs& a, const int bx
     for (int k = 0; k < 4; ++k) xv[k] = x1[k];
     fetch_w(1, wv);
   } else {
-#if DD_GEMM_EARLY_HALF
-    // both K halves are requested before the first barrier (round 6): the second half's rows used to be requested behind the first
-    // half's LDS commit and barrier, ~0.6 us of their latency exposed after the first half's 32 MFMAs in the single-tile launches
-    // on the layer's critical chain; 16 more registers per thread, the 33 KB LDS image is unchanged
-    float4 x1[4], w1[4];
-    fetch(0);
-    fetch_x(1, x1);
-    fetch_w(1, w1);
-    commit();
-    __syncthreads();
-    GSTAMP(1);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { xv[k] = x1[k]; wv[k] = w1[k]; }
-#else
     fetch(0);
     commit();
     __syncthreads();
     GSTAMP(1);
     fetch(1);
-#endif
   }
 #pragma unroll
   for (int kk = 0; kk < 16; ++kk) {
@@ -263,11 +241,7 @@ __device__ __forceinline__ void gemm_tile_ksplit(const GemmArgs& a, const int bx
   asm volatile("" : "+v"(acc));
   GSTAMP(4);
   __syncthreads();                                     // operands dead: the tile buffer becomes the output stage
-#if DD_GEMM_EARLY_HALF || DD_GEMM_EARLY_BIAS
   gemm_epilogue<SC1>(a, smh, acc, row0, col0, bias_ok, bias_pre);
-#else
-  gemm_epilogue<SC1>(a, smh, acc, row0, col0);
-#endif
   if (dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); GSTAMP(5); }
 #undef GSTAMP
 }

@@ -477,7 +477,7 @@ def test_runtime_options_agree(debug_options):
     defaults = {1: 1, 3: 1, 5: 4, 7: 1, 8: 4, 9: 1, 11: 0, 12: 1, 14: 0, 16: 1, 17: 1, 18: 1, 19: 1, 20: 1, 21: 1}
     ref = {k: v.clone() for k, v in _forward_hip(model(0), b).items()}
     try:
-        for key in (4, 6, 10, 15):                               # removed kernel variants: their keys are rejected
+        for key in (4, 6, 10, 15, 33):                           # removed kernel variants: their keys are rejected
             assert lib.dd_debug_set_option(key, 1) != 0
         for key, val in ((1, 0), (3, 0), (5, 8), (5, 2), (8, 1), (8, 2), (8, 3), (9, 0), (11, 1), (12, 0), (14, 1), (16, 0), (17, 0), (18, 0), (18, 96), (19, 0), (8, 0), (21, 0)):
             assert lib.dd_debug_set_option(key, val) == 0
