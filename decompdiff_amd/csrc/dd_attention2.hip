@@ -326,7 +326,10 @@ __host__ __device__ inline int ne_blocks_per_sample(int NP, int NL, int NW) { re
 // workgroups), and its two halves only meet at the very end: wave 0 of a pair runs the query MLP, the fold, the k pass and
 // the softmax, wave 1 meanwhile the v pass (activations and the 16 per-head values of every member); the attention
 // weights cross through LDS behind one workgroup barrier and wave 1 forms the coordinate update.
-template <int MODE, int MAXT, int NW, bool PERSIST = false, bool RAG = false, bool PAIR = false, bool STAMPS = true, typename ARGS = AttnArgs>
+// (WIDE: set by the launches built for kNN segments of more than 2 tiles, so that they instantiate bodies of their own and leave
+// the code of the K <= 32 launches exactly as it is)
+template <int MODE, int MAXT, int NW, bool PERSIST = false, bool RAG = false, bool PAIR = false, bool STAMPS = true, bool WIDE = false,
+          typename ARGS = AttnArgs>
 __device__ __forceinline__ void attn2_body(const ARGS& a, const int block, float* smem) {
   constexpr bool KNN = (MODE == M_NE || MODE == M_PE);
   constexpr bool POS = (MODE == M_PE || MODE == M_PB);
@@ -1165,7 +1168,9 @@ constexpr int imax(int a, int b) { return a > b ? a : b; }
 // (long, one batch of NW segments each) come first, then the few NB ones; the BL workgroups are persistent and pull
 // single segments from a global counter, so they fill whatever the coarse NE schedule leaves idle and all finish
 // within one segment of each other.
-template <int MAXT, int NW, bool RAG = false>
+// KT: tiles of a kNN segment -- 2 for K <= 32 (the shipped graph), 4 for K <= 64 (DD_KNN_MAX); the bond-graph and triplet
+// bodies do not depend on K.
+template <int MAXT, int NW, bool RAG = false, int KT = 2>
 __global__ __launch_bounds__(NW * 64) void k_attn2_node(const AttnArgs ne, const AttnArgs nb, const AttnArgs bl, int n_ne, int n_nb,
                                                         int persist, int n_bl_first, const int32_t* wflags, int widx, int wn, int nep) {
   constexpr int SZ = imax(imax(Lds<M_NE>::TOTAL, Lds<M_NB>::TOTAL), Lds<M_BL>::TOTAL) + 12;
@@ -1204,32 +1209,33 @@ __global__ __launch_bounds__(NW * 64) void k_attn2_node(const AttnArgs ne, const
 #endif
   if (n_bl_first > 0) {
     if (blk < n_bl_first) {
-      attn2_body<M_BL, MAXT, NW, true, RAG, false, false>(args(2), blk, smem);
+      attn2_body<M_BL, MAXT, NW, true, RAG, false, false, (KT > 2)>(args(2), blk, smem);
       DD_TRACE_END(2);
       return;
     }
     blk -= n_bl_first;
-    if (blk < n_ne) { attn2_body<M_NE, 2, NW, false, RAG, false, false>(args(0), blk, smem); DD_TRACE_END(0); }
-    else { attn2_body<M_NB, MAXT, NW, false, RAG, false, false>(args(1), blk - n_ne, smem); DD_TRACE_END(1); }
+    if (blk < n_ne) { attn2_body<M_NE, KT, NW, false, RAG, false, false, (KT > 2)>(args(0), blk, smem); DD_TRACE_END(0); }
+    else { attn2_body<M_NB, MAXT, NW, false, RAG, false, false, (KT > 2)>(args(1), blk - n_ne, smem); DD_TRACE_END(1); }
     return;
   }
-  if (blk < n_ne) attn2_body<M_NE, 2, NW, false, RAG, false, false>(args(0), blk, smem);
-  else if (blk < n_ne + n_nb) attn2_body<M_NB, MAXT, NW, false, RAG, false, false>(args(1), blk - n_ne, smem);
-  else if (persist) attn2_body<M_BL, MAXT, NW, true, RAG, false, false>(args(2), blk - n_ne - n_nb, smem);
-  else attn2_body<M_BL, MAXT, NW, false, RAG, false, false>(args(2), blk - n_ne - n_nb, smem);
+  if (blk < n_ne) attn2_body<M_NE, KT, NW, false, RAG, false, false, (KT > 2)>(args(0), blk, smem);
+  else if (blk < n_ne + n_nb) attn2_body<M_NB, MAXT, NW, false, RAG, false, false, (KT > 2)>(args(1), blk - n_ne, smem);
+  else if (persist) attn2_body<M_BL, MAXT, NW, true, RAG, false, false, (KT > 2)>(args(2), blk - n_ne - n_nb, smem);
+  else attn2_body<M_BL, MAXT, NW, false, RAG, false, false, (KT > 2)>(args(2), blk - n_ne - n_nb, smem);
 }
 // Same for the two coordinate sub-layers (both write their own delta buffer; x is updated afterwards).
 // (NW segments = 2 NW waves per workgroup: attn2_body's PAIR)
-template <int MAXT, int NW, bool RAG = false>
+// (KT: tiles of a kNN segment, as in k_attn2_node)
+template <int MAXT, int NW, bool RAG = false, int KT = 2>
 __global__ __launch_bounds__(NW * 128) void k_attn2_pos(const AttnArgs pe, const AttnArgs pb, int n_pe) {
   // + per-segment scratch of the in-kernel query MLP + the attention weights handed from the k wave to the v wave
-  constexpr int SZ = imax(Lds<M_PE>::TOTAL, Lds<M_PB>::TOTAL) + NW * 256 + NW * MAXT * 256;
+  constexpr int SZ = imax(Lds<M_PE>::TOTAL, Lds<M_PB>::TOTAL) + NW * 256 + NW * imax(MAXT, KT) * 256;
   __shared__ __attribute__((aligned(16))) float smem[SZ];
   const int blk = blockIdx.x;
   // projections of the new h / h_bond from the layer-tail queue on the other stream (no graph edge): poll, one acquire
   dd_wait_flags(pe.wait_flags, pe.wait_idx, pe.wait_n, -1, 0, DD_FLAG_ERR, 400);
-  if (blk < n_pe) attn2_body<M_PE, 2, NW, false, RAG, true, false>(pe, blk, smem);
-  else attn2_body<M_PB, MAXT, NW, false, RAG, true, false>(pb, blk - n_pe, smem);
+  if (blk < n_pe) attn2_body<M_PE, KT, NW, false, RAG, true, false, (KT > 2)>(pe, blk, smem);
+  else attn2_body<M_PB, MAXT, NW, false, RAG, true, false, (KT > 2)>(pb, blk - n_pe, smem);
   // x update (x += (dx_edge + dx_bond) on the ligand rows, uni_transformer_edge.py:285) by the workgroup that finishes
   // last: ~120 workgroups, so the ticket costs nothing and a launch on the critical chain is saved
   if (pe.work_counter == nullptr) return;
@@ -1368,10 +1374,13 @@ int launch_attn2(int mode, const AttnArgs& a, hipStream_t st) {
   const int N = a.NP + a.NL;
   const bool small = a.NL <= 33;                     // NL-1 <= 32 members -> 2 tiles
   const bool big = a.NL > 65;                        // up to 128 ligand atoms: 8 tiles (register spills accepted: rare sizes)
-  if (a.NL > 129) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (a.NL > 129 || a.K > DD_KNN_MAX) return DD_ERR_UNSUPPORTED_SHAPE;
   switch (mode) {
-    case M_NE: return launch_mode<M_NE, 2, 8>(a, a.B * v2::ne_blocks_per_sample(a.NP, a.NL, 8) * 8, st);   // (blocks * NW)
-    case M_PE: return launch_mode<M_PE, 2, 8>(a, a.B * a.NL, st);
+    case M_NE: {
+      const int nseg = a.B * v2::ne_blocks_per_sample(a.NP, a.NL, 8) * 8;                                // (blocks * NW)
+      return a.K <= 32 ? launch_mode<M_NE, 2, 8>(a, nseg, st) : launch_mode<M_NE, 4, 8>(a, nseg, st);
+    }
+    case M_PE: return a.K <= 32 ? launch_mode<M_PE, 2, 8>(a, a.B * a.NL, st) : launch_mode<M_PE, 4, 8>(a, a.B * a.NL, st);
     case M_NB: return small ? launch_mode<M_NB, 2, 8>(a, a.B * a.NL, st)
                             : (big ? launch_mode<M_NB, 8, 8>(a, a.B * a.NL, st) : launch_mode<M_NB, 4, 8>(a, a.B * a.NL, st));
     case M_PB: return small ? launch_mode<M_PB, 2, 8>(a, a.B * a.NL, st)
@@ -1386,7 +1395,7 @@ int launch_attn2(int mode, const AttnArgs& a, hipStream_t st) {
 
 // Fused launches (ligands with <= 33 atoms).  Returns DD_ERR_UNSUPPORTED_SHAPE for larger ligands; the caller then
 // falls back to one launch per sub-layer.
-template <int NW, int MAXT>
+template <int NW, int MAXT, int KT>
 static int launch_node_nw(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs& bl, hipStream_t st) {
   using namespace v2;
   const int N = ne.NP + ne.NL;
@@ -1425,10 +1434,10 @@ static int launch_node_nw(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs
         n_bl = want < 16 ? 16 : (want > n_cu - 16 ? n_cu - 16 : want);
         set_trips(n_bl);
         if (ne.nl_real != nullptr)
-          hipLaunchKernelGGL((k_attn2_node<MAXT, NW, true>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb,
+          hipLaunchKernelGGL((k_attn2_node<MAXT, NW, true, KT>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb,
                              persist, n_bl, wf, ne.wait_idx, wfn, 0);
         else
-          hipLaunchKernelGGL((k_attn2_node<MAXT, NW>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist,
+          hipLaunchKernelGGL((k_attn2_node<MAXT, NW, false, KT>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist,
                              n_bl, wf, ne.wait_idx, wfn, 0);
         DD_CHECK_LAUNCH();
         return DD_OK;
@@ -1437,27 +1446,31 @@ static int launch_node_nw(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs
   }
   if (persist) set_trips(n_bl);
   if (ne.nl_real != nullptr)
-    hipLaunchKernelGGL((k_attn2_node<MAXT, NW, true>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist, 0, wf, ne.wait_idx, wfn, 0);
+    hipLaunchKernelGGL((k_attn2_node<MAXT, NW, true, KT>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist, 0, wf, ne.wait_idx, wfn, 0);
   else
-    hipLaunchKernelGGL((k_attn2_node<MAXT, NW>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist, 0, wf, ne.wait_idx, wfn, 0);
+    hipLaunchKernelGGL((k_attn2_node<MAXT, NW, false, KT>), dim3(n_ne + n_nb + n_bl), dim3(NW * 64), 0, st, ne, nb, blt, n_ne, n_nb, persist, 0, wf, ne.wait_idx, wfn, 0);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
-int launch_attn2_node(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs& bl, hipStream_t st) {
-  if (ne.NL > 129) return DD_ERR_UNSUPPORTED_SHAPE;
-  if (ne.NL > 65) return launch_node_nw<8, 8>(ne, nb, bl, st);    // 65 .. 128 members per segment: 8 tiles (spills: rare sizes)
-  if (ne.NL > 49) return launch_node_nw<8, 4>(ne, nb, bl, st);    // up to 64 members per segment: 4 tiles
-  if (ne.NL > 33) return launch_node_nw<8, 3>(ne, nb, bl, st);    // up to 48 members: 3 tiles (fewer live registers than 4)
-  return launch_node_nw<8, 2>(ne, nb, bl, st);             // (12- and 16-wave workgroups were tried: register spills)
+template <int KT>
+static int launch_node_kt(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs& bl, hipStream_t st) {
+  if (ne.NL > 65) return launch_node_nw<8, 8, KT>(ne, nb, bl, st);    // 65 .. 128 members per segment: 8 tiles (spills: rare sizes)
+  if (ne.NL > 49) return launch_node_nw<8, 4, KT>(ne, nb, bl, st);    // up to 64 members per segment: 4 tiles
+  if (ne.NL > 33) return launch_node_nw<8, 3, KT>(ne, nb, bl, st);    // up to 48 members: 3 tiles (fewer live registers than 4)
+  return launch_node_nw<8, 2, KT>(ne, nb, bl, st);             // (12- and 16-wave workgroups were tried: register spills)
 }
-template <int NW>
+int launch_attn2_node(const AttnArgs& ne, const AttnArgs& nb, const AttnArgs& bl, hipStream_t st) {
+  if (ne.NL > 129 || ne.K > DD_KNN_MAX) return DD_ERR_UNSUPPORTED_SHAPE;
+  return ne.K <= 32 ? launch_node_kt<2>(ne, nb, bl, st) : launch_node_kt<4>(ne, nb, bl, st);   // kNN segments of 2 / 4 tiles
+}
+template <int NW, int KT>
 static int launch_pos_nw(const AttnArgs& pe, const AttnArgs& pb, hipStream_t st) {
   using namespace v2;
   const int n = (pe.B * pe.NL + NW - 1) / NW;
   if (pe.NL > 65) {                                    // 8 tiles: the weights' hand-over buffer fits the LDS for NW <= 4 only
     if constexpr (NW <= 4) {
-      if (pe.nl_real != nullptr) hipLaunchKernelGGL((k_attn2_pos<8, NW, true>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
-      else hipLaunchKernelGGL((k_attn2_pos<8, NW>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+      if (pe.nl_real != nullptr) hipLaunchKernelGGL((k_attn2_pos<8, NW, true, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+      else hipLaunchKernelGGL((k_attn2_pos<8, NW, false, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
       DD_CHECK_LAUNCH();
       return DD_OK;
     } else {
@@ -1465,12 +1478,12 @@ static int launch_pos_nw(const AttnArgs& pe, const AttnArgs& pb, hipStream_t st)
     }
   }
   if (pe.nl_real != nullptr) {
-    if (pe.NL > 49) hipLaunchKernelGGL((k_attn2_pos<4, NW, true>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
-    else if (pe.NL > 33) hipLaunchKernelGGL((k_attn2_pos<3, NW, true>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
-    else hipLaunchKernelGGL((k_attn2_pos<2, NW, true>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
-  } else if (pe.NL > 49) hipLaunchKernelGGL((k_attn2_pos<4, NW>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
-  else if (pe.NL > 33) hipLaunchKernelGGL((k_attn2_pos<3, NW>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
-  else hipLaunchKernelGGL((k_attn2_pos<2, NW>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+    if (pe.NL > 49) hipLaunchKernelGGL((k_attn2_pos<4, NW, true, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+    else if (pe.NL > 33) hipLaunchKernelGGL((k_attn2_pos<3, NW, true, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+    else hipLaunchKernelGGL((k_attn2_pos<2, NW, true, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+  } else if (pe.NL > 49) hipLaunchKernelGGL((k_attn2_pos<4, NW, false, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+  else if (pe.NL > 33) hipLaunchKernelGGL((k_attn2_pos<3, NW, false, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
+  else hipLaunchKernelGGL((k_attn2_pos<2, NW, false, KT>), dim3(2 * n), dim3(NW * 128), 0, st, pe, pb, n);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
@@ -1486,7 +1499,7 @@ int launch_attn2_pos_g(const AttnArgs& pe_in, const AttnArgs& pb_in, const GemmA
 #else
   using namespace v2;
   if (njobs <= 0 || njobs > 4 || n_lead <= 0 || n_lead > njobs || counter == nullptr) return DD_ERR_BAD_ARG;
-  if (pe_in.NL > 65 || pe_in.work_counter != nullptr) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (pe_in.NL > 65 || pe_in.K > 32 || pe_in.work_counter != nullptr) return DD_ERR_UNSUPPORTED_SHAPE;   // (2-tile kNN segments only)
   for (int i = 0; i < njobs; ++i)
     if (jobs[i].ln != nullptr || (jobs[i].ldy & 3) || (jobs[i].ncols & 3) || (reinterpret_cast<size_t>(jobs[i].Y) & 15))
       return DD_ERR_UNSUPPORTED_SHAPE;                   // (the write-through epilogue is the 16-byte path)
@@ -1522,11 +1535,12 @@ int launch_attn2_pos_g(const AttnArgs& pe_in, const AttnArgs& pb_in, const GemmA
 
 int g_pos_waves = 4;         // waves per workgroup of the fused coordinate launch: 2, 4 or 8
 int launch_attn2_pos(const AttnArgs& pe, const AttnArgs& pb, hipStream_t st) {
-  if (pe.NL > 129) return DD_ERR_UNSUPPORTED_SHAPE;
-  if (pe.NL > 65 && g_pos_waves > 4) return launch_pos_nw<4>(pe, pb, st);
-  if (g_pos_waves == 2) return launch_pos_nw<2>(pe, pb, st);
-  if (g_pos_waves == 4) return launch_pos_nw<4>(pe, pb, st);
-  return launch_pos_nw<8>(pe, pb, st);
+  if (pe.NL > 129 || pe.K > DD_KNN_MAX) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (pe.K > 32) return launch_pos_nw<4, 4>(pe, pb, st);   // kNN segments of up to 4 tiles: the default 4-wave workgroups only
+  if (pe.NL > 65 && g_pos_waves > 4) return launch_pos_nw<4, 2>(pe, pb, st);
+  if (g_pos_waves == 2) return launch_pos_nw<2, 2>(pe, pb, st);
+  if (g_pos_waves == 4) return launch_pos_nw<4, 2>(pe, pb, st);
+  return launch_pos_nw<8, 2>(pe, pb, st);
 }
 
 }  // namespace dd

@@ -10,7 +10,7 @@
 namespace dd {
 
 // ------------------------------------------------------------------------------------ kNN
-// One wave per centre.  Each lane owns candidates c = lane, lane+64, ... (<= 32 per lane,
+// One wave per centre, K <= 64 neighbours.  Each lane owns candidates c = lane, lane+64, ... (<= 32 per lane,
 // N <= 2048).  Key = (bits(d2) << 32) | index is monotone in (d2, index) because d2 >= 0: the K
 // smallest keys in ascending order are the neighbours in ascending (distance, index) — the same
 // total order the oracle's stable sort uses.  d2 = (dx*dx + dy*dy) + dz*dz with no FMA contraction.
@@ -362,10 +362,11 @@ struct HeadArgs {
   long atom_f4;
   int n_graph, n_embed_nodes, n_embed;
 };
-template <int CAND>
+// KW: the width of the LDS hand-off srt -- 32 for K <= 32 (the shipped graph), 64 for K <= DD_KNN_MAX
+template <int CAND, int KW>
 __global__ __launch_bounds__(256, 3) void k_head_graph(const HeadArgs a) {
   __shared__ unsigned long long sel[4][64];
-  __shared__ int32_t srt[4][32];
+  __shared__ int32_t srt[4][KW];
   __shared__ __attribute__((aligned(16))) float lw[512];
   ew_stage(lw, a.EW_b1, a.EW_ln, a.EW_w2);
   __syncthreads();                                       // (before any wave leaves)
@@ -575,13 +576,23 @@ int launch_embed_all(const float* protein_h, const float* protein_pos, const flo
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
+template <int KW>
+static void launch_head_graph(const HeadArgs& a, int N, dim3 grid, dim3 block, hipStream_t st) {
+  const int cand = (N + 63) / 64;
+  if (cand <= 2) hipLaunchKernelGGL((k_head_graph<2, KW>), grid, block, 0, st, a);
+  else if (cand <= 4) hipLaunchKernelGGL((k_head_graph<4, KW>), grid, block, 0, st, a);
+  else if (cand <= 6) hipLaunchKernelGGL((k_head_graph<6, KW>), grid, block, 0, st, a);
+  else if (cand <= 11) hipLaunchKernelGGL((k_head_graph<11, KW>), grid, block, 0, st, a);
+  else if (cand <= 16) hipLaunchKernelGGL((k_head_graph<16, KW>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_head_graph<DD_N_MAX / 64, KW>), grid, block, 0, st, a);
+}
 int launch_head_all(const float* protein_h, const float* protein_pos, const float* lig_pos, const int32_t* lig_v,
                     const float* lig_aux, const float* Wl, const float* bl, int B, int NP, int NL, int K, float* h, float* xa, float* xb,
                     const int32_t* bond, long bond_rows, const float* Wb, const float* bb, float* hb, int32_t* counters,
                     int32_t* advance, int32_t* nbr, float* ew, const float* EW_W1T, const float* EW_b1, const float* EW_ln,
                     const float* EW_w2, const float* EW_b2, const int32_t* np_real, const int32_t* nl_real, const float* l0_tables,
                     float* l0_P, float* PL, float* l0_qn, float* qlnb, float* PB, float* qb, hipStream_t st, int parts, int nv) {
-  if (K > 32 || (parts & 3) == 0 || (l0_tables != nullptr && nv != DD_NUM_V)) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (K > DD_KNN_MAX || (parts & 3) == 0 || (l0_tables != nullptr && nv != DD_NUM_V)) return DD_ERR_UNSUPPORTED_SHAPE;
   const int N = NP + NL;
   HeadArgs a;
   a.B = B; a.NP = NP; a.NL = NL; a.K = K;
@@ -603,13 +614,8 @@ int launch_head_all(const float* protein_h, const float* protein_pos, const floa
   if (parts & 2) hipLaunchKernelGGL(k_head_rows, dim3((unsigned)(a.n_embed + n_l0)), block, 0, st, a);   // parts: 2 = embedding + layer-0 rows
   if (parts & 1) {                                                                                        //        1 = graph
     const dim3 grid((unsigned)a.n_graph);
-    const int cand = (N + 63) / 64;
-    if (cand <= 2) hipLaunchKernelGGL(k_head_graph<2>, grid, block, 0, st, a);
-    else if (cand <= 4) hipLaunchKernelGGL(k_head_graph<4>, grid, block, 0, st, a);
-    else if (cand <= 6) hipLaunchKernelGGL(k_head_graph<6>, grid, block, 0, st, a);
-    else if (cand <= 11) hipLaunchKernelGGL(k_head_graph<11>, grid, block, 0, st, a);
-    else if (cand <= 16) hipLaunchKernelGGL(k_head_graph<16>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_head_graph<DD_N_MAX / 64>, grid, block, 0, st, a);
+    if (K <= 32) launch_head_graph<32>(a, N, grid, block, st);
+    else launch_head_graph<64>(a, N, grid, block, st);
   }
   DD_CHECK_LAUNCH();
   return DD_OK;

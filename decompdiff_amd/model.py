@@ -180,7 +180,7 @@ class DecompScorePosNet3D(nn.Module):
         need(num_classes in (8, 13, 23), "num_classes in {8, 13, 23} (ligand_atom_mode basic / add_aromatic / full)")
         need(pdim == 29 and ldim == num_classes + 2, "protein feature dim 29, ligand feature dim num_classes + 2")
         need(not getattr(config, "sync_twoup", False), "sync_twoup=False")
-        need(config.knn <= 32, "knn<=32")
+        need(1 <= config.knn <= 64, "1<=knn<=64")
 
     # ------------------------------------------------------------------------------------------
     def _device(self):

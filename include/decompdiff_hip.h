@@ -30,7 +30,7 @@ extern "C" {
 #define DD_HIDDEN 128
 #define DD_HEADS 16
 #define DD_NGAUSS 20
-#define DD_KNN_MAX 32
+#define DD_KNN_MAX 64    /* neighbours per centre (kNN segments of up to 2 / 4 tiles of 16 members: K <= 32 / K <= 64) */
 #define DD_NL_MAX 128     /* ligand atoms per sample supported by the fused kernels (tile counts 2 / 3 / 4 / 8 of 16 members) */
 #define DD_N_MAX 2048     /* atoms per sample supported by the kNN kernel (candidates per lane: 2 / 4 / 6 / 11 / 16 / 32) */
 #define DD_NUM_V 8        /* atom classes of ligand_atom_mode 'basic' (scripts/sample_diffusion_decomp.py:540); dd_sampler.num_v
