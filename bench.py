@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — denoising steps/sec of the reverse-diffusion sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -20,7 +20,10 @@ noise, all six trajectories recorded and streamed to the host inside the timed r
 `sample_diffusion` returns).  Every unit is warmed up first (W steps: kernels, the one-off per-shape measurement of the
 node-launch CU split, graph capture).  `value` = (units x K) / max-over-ranks seconds.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  With `--full`
+the line also carries (measured after the timed region, rank 0; each can be left out with its --no-* option)
+  steady_ms_per_step, per_call_overhead_ms
+                    configs 1/2: one long call of the same unit, ms per step once the fixed cost of a call is amortised;
   roofline          the dominant kernel of a step, the fused node-attention launch dd::v2::k_attn2_node (NE + NB + BL
                     sub-layers, 6 launches per step): mean launch duration measured live with HIP events on the launch
                     stream (dd_profile_step, launches serialised), against the fp32 MFMA peak with the FLOPs the matrix
@@ -72,9 +75,12 @@ def parse():
     ap.add_argument("--allow-gloo-fallback", action="store_true", help="(the default since round 4; kept for old command lines)")
     ap.add_argument("--plan-only", action="store_true", help="print the job plan for --gpus N (units per rank, planned cost and imbalance, "
                     "device and CPU slice per rank) as one JSON line and exit; needs no GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-rooflines", action="store_true")
-    ap.add_argument("--no-steady", action="store_true", help="skip the long call behind the timed region (steady_ms_per_step, per_call_overhead_ms)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure what the headline figure does not need: "
+                    "the steady-state long call, the step and op-level rooflines and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-rooflines", action="store_true", help="--full without the rooflines")
+    ap.add_argument("--no-steady", action="store_true", help="--full without the long call behind the timed region (steady_ms_per_step, "
+                    "per_call_overhead_ms)")
     ap.add_argument("--cold", action="store_true", help="config 3: no warm-up -- every pocket timed from first touch (per-shape launch "
                     "measurement or split-cache lookup, graph capture, then the steps): cold_seconds_per_unit / per_shape_setup_ms")
     ap.add_argument("--cpu-steps", type=int, default=5, help="steps of the CPU baseline's timed sample (~5.5 s each at B=8)")
@@ -301,7 +307,7 @@ def main():
         # unit after the timed region -- ms per step once the fixed cost of a call (set-up, trajectory drain, checksum, two syncs) is
         # amortised -- and what that fixed cost is for the timed call
         steady = None
-        if args.config in (1, 2) and not args.no_steady:
+        if args.full and args.config in (1, 2) and not args.no_steady:
             st0 = prepare(u0)
             n_long = min(max(200, 10 * args.steps), int(model.num_timesteps))
             # (the long call twice: a process's FIRST call of a new length captures its graph and first-touches the pages of the result
@@ -317,12 +323,12 @@ def main():
                       # (only meaningful when the long call is much longer than the timed one, and not when the long call's larger
                       #  trajectory drains make its steps the slower ones: a negative difference is no overhead)
                       "per_call_overhead_ms": round(over, 3) if n_long >= 4 * args.steps and over >= 0 else None}
-        if not args.no_rooflines:
+        if args.full and not args.no_rooflines:
             roofline, roofline_gemm = measure_step_rooflines(torch, model, hip_lib, lib, prepare(u0), cfg, B, NP, NL, K, dev,
                                                              args.config, args.workload)
             op_roofline = measure_op_level_roofline(torch, hip_lib, lib, dev)
         cpu = None
-        if not args.no_cpu_baseline:                       # (rank 0 only, after the timed region and its closing barrier)
+        if args.full and not args.no_cpu_baseline:         # (rank 0 only, after the timed region and its closing barrier)
             cpu = cpu_baseline(torch, synth, cfg, cpu_batches[u0.uid], DRIFT if u0.drift else None, B, args.cpu_steps, args.cpu_warmup,
                                args.cpu_threads)
         wl = {1: "configs[1]: single pocket ref_prior",

@@ -564,11 +564,11 @@ def test_same_shape_sub_batches_equal_the_whole_batch():
 
 
 def test_bench_json_line_contract():
-    """The driver's contract for bench.py: ONE JSON line from rank 0 with the metric of BASELINE.json, the whole-job value,
+    """The driver's contract for bench.py --full: ONE JSON line from rank 0 with the metric of BASELINE.json, the whole-job value,
     and the roofline / cpu_baseline objects."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--cpu-steps", "1",
-                        "--cpu-warmup", "1", "--cpu-threads", "16"], capture_output=True, text=True, env=env, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full",
+                        "--cpu-steps", "1", "--cpu-warmup", "1", "--cpu-threads", "16"], capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -589,6 +589,21 @@ def test_bench_json_line_contract():
     assert o["bound"] == "hbm" and o["unit"] == "GB/s" and 0.3 < o["frac"] < 1.0
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and "steps" in c["sample"]
+    assert d["steady_ms_per_step"] > 0 and d["steady_steps"] >= 200
+
+
+def test_plain_bench_line_measures_only_the_headline():
+    """bench.py without --full: the same headline keys as the --full line, and none of the measurements behind the timed
+    region (steady-state call, rooflines, CPU baseline) -- their keys are null."""
+    d, _ = _bench_line(["--gpus", "1", "--steps", "6", "--warmup", "2"], _bench_env(), timeout=900)
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] in base["metric"] and d["unit"] == "denoising steps/s" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["dtype"] == "f32"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    for k in ("steady_ms_per_step", "per_call_overhead_ms", "steady_steps", "roofline", "roofline_gemm", "roofline_op_level",
+              "cpu_baseline"):
+        assert d[k] is None, k
+    assert "speedup_vs_cpu_baseline" not in d["config"]
 
 
 def test_bench_dump_outputs_are_the_timed_calls_result(tmp_path):

@@ -21,7 +21,7 @@ done
 cd $GRAFT_REPO_ROOT
 for d in $O/pmc_*; do [ -d "$d" ] || continue; f=$(find $d -name "*.db" | head -1); [ -n "$f" ] && python tools/rocpd_pmc.py "$f" 6 > $d.md; done
 find $O -name "*.db" -delete; find $O -type d -empty -delete
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err
 grep -h k_attn2_node $O/pmc_*.md | cut -c1-160
 python -c "
 import json

@@ -8,16 +8,16 @@ sha256sum decompdiff_amd/csrc/dd_attention2.hip | cut -c1-16 > $O/kernel_source_
 python -X faulthandler -m pytest tests -m gpu -q --durations=5 > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee $O/pytest.rc
 grep -E "passed|failed|FAILED|ERROR" $O/pytest.log | tail -5
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err
-for i in 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-rooflines > $O/bench_driver_style_$i.json 2>> $O/bench.err; done
-python bench.py --steps 1000 --warmup 20 --no-cpu-baseline > $O/bench_cfg1_1000.json 2>> $O/bench.err
-python bench.py --config 2 --steps 1000 --warmup 20 --no-cpu-baseline > $O/bench_cfg2_drift.json 2>> $O/bench.err
-python bench.py --config 1 --batch 16 --steps 500 --warmup 20 --no-cpu-baseline > $O/bench_cfg1_b16.json 2>> $O/bench.err
-python bench.py --config 1 --batch 1 --steps 1000 --warmup 20 --no-cpu-baseline --no-rooflines > $O/bench_cfg1_b1.json 2>> $O/bench.err
-python bench.py --config 3 --steps 100 --warmup 3 --no-cpu-baseline > $O/bench_cfg3_100pockets.json 2>> $O/bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err
+for i in 2 3; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-rooflines > $O/bench_driver_style_$i.json 2>> $O/bench.err; done
+python bench.py --full --steps 1000 --warmup 20 --no-cpu-baseline > $O/bench_cfg1_1000.json 2>> $O/bench.err
+python bench.py --full --config 2 --steps 1000 --warmup 20 --no-cpu-baseline > $O/bench_cfg2_drift.json 2>> $O/bench.err
+python bench.py --full --config 1 --batch 16 --steps 500 --warmup 20 --no-cpu-baseline > $O/bench_cfg1_b16.json 2>> $O/bench.err
+python bench.py --full --config 1 --batch 1 --steps 1000 --warmup 20 --no-cpu-baseline --no-rooflines > $O/bench_cfg1_b1.json 2>> $O/bench.err
+python bench.py --full --config 3 --steps 100 --warmup 3 --no-cpu-baseline > $O/bench_cfg3_100pockets.json 2>> $O/bench.err
 rm -rf /tmp/nscache; DD_NODE_SPLIT_CACHE_DIR=/tmp/nscache python bench.py --config 3 --steps 1000 --cold --no-cpu-baseline --no-rooflines > $O/bench_cfg3_cold_cachecold.json 2>> $O/bench.err
 DD_NODE_SPLIT_CACHE_DIR=/tmp/nscache python bench.py --config 3 --steps 1000 --cold --no-cpu-baseline --no-rooflines > $O/bench_cfg3_cold_cachewarm.json 2>> $O/bench.err
-python bench.py --config 4 --steps 200 --warmup 10 --no-cpu-baseline > $O/bench_cfg4_large.json 2>> $O/bench.err
+python bench.py --full --config 4 --steps 200 --warmup 10 --no-cpu-baseline > $O/bench_cfg4_large.json 2>> $O/bench.err
 for b in 8 1; do for p in 0 1; do echo "## DD_SIDE_PRIO=$p B=$b"; DD_SIDE_PRIO=$p python tools/two_lengths.py 200 400 $b 2>&1 | grep steps | sed 's/ steps: /:/; s/ ms\/step//' | tr '\n' ';'; echo; done; done > $O/two_lengths.txt; cat $O/two_lengths.txt
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/prof_small -- python $GRAFT_REPO_ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-rooflines --no-steady > $GRAFT_REPO_ROOT/$O/prof_small.log 2>&1

@@ -3,8 +3,8 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/$1; mkdir -p $O
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err
-python bench.py --steps 1000 --warmup 20 --no-cpu-baseline --no-rooflines > $O/bench_cfg1_1000.json 2>> $O/bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench.err
+python bench.py --full --steps 1000 --warmup 20 --no-cpu-baseline --no-rooflines > $O/bench_cfg1_1000.json 2>> $O/bench.err
 python tools/phase_clocks.py > $O/phase_clocks.txt 2>&1
 cd /tmp
 rocprofv3 --kernel-trace --stats -d /tmp/prof_small -- python $GRAFT_REPO_ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-rooflines > $GRAFT_REPO_ROOT/$O/prof_small.log 2>&1
