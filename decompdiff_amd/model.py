@@ -211,9 +211,38 @@ class DecompScorePosNet3D(nn.Module):
         self.__dict__["_param_list"] = None                 # (.to() may replace the parameter tensors)
         return r
 
+    def position_step_table(self, model_mean_type=None):
+        """The [3][T] fp32 table the step kernels read as ``dd_sampler.tab_pos``: for each t, the coefficients of the network's
+        coordinate output and of x_t in the posterior mean, then posterior_logvar.  C0: posterior_mean_c0_coef and
+        posterior_mean_ct_coef as they are.  'noise': the eps -> x0 map of the reference (_predict_x0_from_eps,
+        decompdiff.py:353-356) folded into them -- with eps = pred - x_t the mean c0 * x0 + ct * x_t is
+        (-c0 * sqrt_recipm1) * pred + (ct + c0 * (sqrt_recip + sqrt_recipm1)) * x_t, the two rows composed in float64 from
+        this module's schedule tables and rounded once."""
+        mode = self.model_mean_type if model_mean_type is None else model_mean_type
+        c0, ct = self.posterior_mean_c0_coef.detach(), self.posterior_mean_ct_coef.detach()
+        if mode == "noise":
+            c0d, ctd = c0.double(), ct.double()
+            sr = self.sqrt_recip_alphas_cumprod.detach().double()
+            srm1 = self.sqrt_recipm1_alphas_cumprod.detach().double()
+            c0, ct = -c0d * srm1, ctd + c0d * (sr + srm1)
+        elif mode != "C0":
+            raise ValueError(mode)
+        return torch.stack([c0.float(), ct.float(), self.posterior_logvar.detach().float()]).contiguous()
+
+    def _predict_x0_from_eps(self, xt, eps, t, batch):
+        """x0 from a predicted noise (decompdiff.py:353-356); t [num_graphs], batch [n] on the device of the tables."""
+        return self.sqrt_recip_alphas_cumprod[t][batch].unsqueeze(-1) * xt - \
+            self.sqrt_recipm1_alphas_cumprod[t][batch].unsqueeze(-1) * eps
+
+    def q_pos_posterior(self, x0, xt, t, batch):
+        """Mean of q(x_{t-1} | x_t, x_0) (decompdiff.py:358-362)."""
+        return self.posterior_mean_c0_coef[t][batch].unsqueeze(-1) * x0 + \
+            self.posterior_mean_ct_coef[t][batch].unsqueeze(-1) * xt
+
     def _packed_weights(self):
         dev = self._device()
-        key = str(dev)
+        # (the mean type selects the tab_pos rows: changing model.model_mean_type repacks)
+        key = (str(dev), self.model_mean_type)
         # in-place parameter updates (optimizer.step on a loss of the caller's own, an EMA copy, param.data.copy_) bump the
         # tensors' version counters: the packed copy is rebuilt when their sum moves (the tensor list is kept: walking the
         # module tree costs 0.4 ms per call, the 600 attribute reads 0.05; DD_CHECK_PARAM_VERSIONS=0 turns the check off)
@@ -227,8 +256,8 @@ class DecompScorePosNet3D(nn.Module):
                 self._evict_chain_cache(0)                                  # cached chains point into the old arena
             sd = {k: v for k, v in self.state_dict().items()}
             arena, offsets, _ = packing.pack_model(sd, self.config, kernel_form=hip_lib.weights_form() == 1)
-            tab_pos = torch.stack([self.posterior_mean_c0_coef, self.posterior_mean_ct_coef,
-                                   self.posterior_logvar]).detach().float().contiguous()
+            # (an unknown mean type never reaches a step kernel: sample_diffusion refuses it; forward does not read the rows)
+            tab_pos = self.position_step_table("noise" if self.model_mean_type == "noise" else "C0")
             tv = self.atom_type_trans
             tb = self.bond_type_trans
             # [4][T] schedule rows followed by the [K] class log-prior (uniform unless prior_*_types were given)
@@ -918,9 +947,7 @@ class DecompScorePosNet3D(nn.Module):
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
-        if self.model_mean_type != "C0":
-            if self.model_mean_type == "noise":
-                raise NotImplementedError("model_mean_type='noise' is not the shipped configuration")
+        if self.model_mean_type not in ("C0", "noise"):          # ('noise': folded into tab_pos, position_step_table)
             raise ValueError(self.model_mean_type)
         if num_steps is None:
             num_steps = self.num_timesteps

@@ -793,6 +793,16 @@ PREP_TENSORS = ("time_step", "pos_noise", "u_v", "u_b", "protein_pos", "protein_
                 "ligand_fc_bond_type", "batch_ligand_bond")
 
 
+def _pos_pred_target(model, pred_pos, x_t, x_0, pos_noise):
+    """(prediction, target) of the position loss (decompdiff.py:522-530): C0 regresses the coordinates x0, 'noise' the drawn
+    (unscaled) position noise through pred - x_t."""
+    if model.model_mean_type == "C0":
+        return pred_pos, x_0
+    if model.model_mean_type == "noise":
+        return pred_pos - x_t, pos_noise
+    raise ValueError(model.model_mean_type)
+
+
 def objective(model, prep: Dict, network_fn=None) -> Dict:
     """Device side of get_diffusion_loss (decompdiff.py:455-550) on a prepared batch: forward diffusion of the state, the
     score network, the three losses.  No device -> host round trip when the batch is dense (one size for all samples) and
@@ -844,7 +854,8 @@ def objective(model, prep: Dict, network_fn=None) -> Dict:
                    tb.posterior(log_b0, log_bt, time_step, batch_ligand_bond), time_step, batch_ligand_bond, B, plan_b)
     if model.loss_pos_type != "mse":
         raise ValueError(model.loss_pos_type)
-    loss_pos = FN_mean((((pred_pos - x_0) ** 2) / (stds ** 2)).sum(-1), plan_l, B).mean()
+    pred, target = _pos_pred_target(model, pred_pos, x_t, x_0, prep["pos_noise"])
+    loss_pos = FN_mean((((pred - target) ** 2) / (stds ** 2)).sum(-1), plan_l, B).mean()
     return {"losses": {"pos": loss_pos, "v": kl_v.mean(), "bond": kl_b.mean()},
             "x0": x_0, "pred_ligand_pos": pred_pos, "pred_ligand_v": pred_v, "pred_pos_noise": pred_pos - x_t,
             "ligand_v_recon": F.softmax(pred_v, dim=-1), "ligand_b_recon": F.softmax(preds["pred_bond"], dim=-1),
@@ -949,7 +960,8 @@ def objective_padded(model, pp: Dict) -> Dict:
                   pp["w_b"], plan_b, pp["cnt_b"])
     if model.loss_pos_type != "mse":
         raise ValueError(model.loss_pos_type)
-    loss_pos = sample_mean((((pred_pos - x_0) ** 2) / (stds ** 2)).sum(-1), pp["w_l"], plan_l, pp["cnt_l"]).mean()
+    pred, target = _pos_pred_target(model, pred_pos, x_t, x_0, pp["pos_noise"])
+    loss_pos = sample_mean((((pred - target) ** 2) / (stds ** 2)).sum(-1), pp["w_l"], plan_l, pp["cnt_l"]).mean()
     return {"losses": {"pos": loss_pos, "v": kl_v.mean(), "bond": kl_b.mean()}, "pred_ligand_pos": pred_pos, "pred_ligand_v": pred_v,
             "pred_bond": preds["pred_bond"], "x0": x_0, "time_step": time_step}
 
@@ -1043,7 +1055,7 @@ class GraphedTrainStep:
         if os.environ.get("DD_TRAIN_GRAPH", "1") == "0":
             return self._eager(prep)
         if dense:
-            key = (tuple(n_p), tuple(n_l), int(prior_centers.shape[0]), str(dev))
+            key = (tuple(n_p), tuple(n_l), int(prior_centers.shape[0]), str(dev), model.model_mean_type)
             data, names, fn = prep, PREP_TENSORS, objective
         else:
             # samples of different sizes: the padded layout of their shape bucket (sizes rounded up to `bucket`) -- all batches
@@ -1051,7 +1063,7 @@ class GraphedTrainStep:
             data = pad_prepared(model, prep, self.bucket)
             if data is None:
                 return self._eager(prep)
-            key = ("padded", data["B"], data["NPm"], data["NLm"], str(dev))
+            key = ("padded", data["B"], data["NPm"], data["NLm"], str(dev), model.model_mean_type)
             names, fn = PAD_TENSORS, objective_padded
         ent = self._graphs.get(key)
         if ent is not None and ent["lrs"] != self._float_lrs():   # a float lr changed since the capture: it is baked into the graph

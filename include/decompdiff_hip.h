@@ -80,7 +80,10 @@ typedef struct dd_sampler {
   /* model */
   const float* weights;            /* packed arena */
   const int64_t* slot_off;         /* HOST: offsets (floats) [num_layers*DD_NUM_LAYER_SLOTS + DD_NUM_GLOBAL_SLOTS] */
-  const float* tab_pos;            /* [3][T]: posterior_mean_c0_coef, posterior_mean_ct_coef, posterior_logvar */
+  const float* tab_pos;            /* [3][T]: coefficient of the network's coordinate output, coefficient of x_t, posterior_logvar.
+                                      C0: posterior_mean_c0_coef, posterior_mean_ct_coef.  model_mean_type 'noise': the eps -> x0
+                                      map folded in, -c0 * sqrt_recipm1_alphas_cumprod and ct + c0 * (sqrt_recip_alphas_cumprod +
+                                      sqrt_recipm1_alphas_cumprod) (DecompScorePosNet3D.position_step_table) */
   const float* tab_v;              /* [4][T]: log_alphas_v, log_one_minus_alphas_v, log_alphas_cumprod_v, log_one_minus_alphas_cumprod_v (atoms),
                                       followed by [8] log prior_probs (DiscreteTransition.prior_probs, transitions.py:114-120; uniform = -log 8) */
   const float* tab_b;              /* [4][T] + [5]: same for bonds */
@@ -270,7 +273,8 @@ int dd_forward(const dd_sampler* s, void* stream);
 
 /* One reverse transition from network outputs the host computed itself (decompdiff.py:601-689 without the forward):
  * log_softmax + q_v_posterior + log_sample_categorical for atoms and bonds (logits_v [B*NL,8], logits_b [B*Eb,5]),
- * C0 posterior mean from x0 [B*NL,3] (centred), drift, noise; updates s->lig_pos / lig_v / lig_bond, writes the
+ * posterior mean from x0 [B*NL,3] (centred; the network's coordinate output -- for a noise-mode model s->tab_pos holds
+ * the folded rows, see dd_sampler.tab_pos), drift, noise; updates s->lig_pos / lig_v / lig_bond, writes the
  * trajectories at the current step index and advances s->step_counter -- exactly what a step of dd_sample_steps does
  * after its forward (bit-identical when fed dd_forward's pred_*). */
 int dd_reverse_step(const dd_sampler* s, const float* logits_v, const float* logits_b, const float* x0, void* stream);
