@@ -247,6 +247,88 @@ struct StepFold {
   const float* xprev = nullptr;          // out: != nullptr when the tail was deferred
 };
 
+// Distance-aware bond head ('pre_att', decompdiff.py:323-341; include/decompdiff_hip.h dd_bond_head): the hidden row of
+// ligand bond e = (src, dst) of the dst-major bond list,
+//   out[e] = W_r^T exp(coeff (d - offset)^2) + P[dst] + P[src] + b1,   d = |x_dst - x_src| of the FINAL coordinates,
+// where P = (W1_h / 2) h is one GEMM row per ligand atom (rows b * NL + i, launched in front of this one).  The final ligand
+// coordinates are x[b, NP + i] -- plus dxe + dxb when the last coordinate update is still pending (the folded step tail; the
+// same association as k_xupdate and the step kernel's x0).  One wave per bond, two hidden channels per lane; W_r, b1 and the
+// centres stay in registers for all bonds of a wave.  Bonds with an endpoint at or beyond nl_real[b] (padding atoms of a
+// padded batch) get a zero row.
+__global__ __launch_bounds__(256) void k_bond_head_pre_att(const float* __restrict__ P, const float* __restrict__ x,
+                                                           const float* __restrict__ dxe, const float* __restrict__ dxb, int NP, int NL,
+                                                           const float* __restrict__ W_r, const float* __restrict__ b1,
+                                                           const float* __restrict__ offset, float coeff,
+                                                           const int32_t* __restrict__ nl_real, long rows, float* __restrict__ out) {
+  constexpr int G = 20;
+  const int lane = threadIdx.x & 63;
+  const long nwaves = (long)gridDim.x * 4;
+  float2 wr[G];
+  float c[G];
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    wr[k] = *reinterpret_cast<const float2*>(W_r + k * 128 + 2 * lane);
+    c[k] = offset[k];
+  }
+  const float2 bb = *reinterpret_cast<const float2*>(b1 + 2 * lane);
+  const int N = NP + NL, NLm1 = NL - 1;
+  const long Eb = (long)NL * NLm1;
+  for (long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6); e < rows; e += nwaves) {
+    const int b = (int)(e / Eb);
+    const int r = (int)(e - (long)b * Eb);
+    const int t = r / NLm1, sp = r - t * NLm1;
+    const int src = sp + (sp >= t);
+    float2* o = reinterpret_cast<float2*>(out + e * 128 + 2 * lane);
+    if (nl_real != nullptr && (t >= nl_real[b] || src >= nl_real[b])) {
+      *o = make_float2(0.f, 0.f);
+      continue;
+    }
+    float xd[3], xs[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      xd[q] = x[((long)b * N + NP + t) * 3 + q];
+      xs[q] = x[((long)b * N + NP + src) * 3 + q];
+      if (dxe != nullptr) {
+        const long id = ((long)b * NL + t) * 3 + q, is = ((long)b * NL + src) * 3 + q;
+        xd[q] = xd[q] + dxe[id] + dxb[id];
+        xs[q] = xs[q] + dxe[is] + dxb[is];
+      }
+    }
+    const float dx = xd[0] - xs[0], dy = xd[1] - xs[1], dz = xd[2] - xs[2];
+    const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float2 pd = *reinterpret_cast<const float2*>(P + ((long)b * NL + t) * 128 + 2 * lane);
+    const float2 ps = *reinterpret_cast<const float2*>(P + ((long)b * NL + src) * 128 + 2 * lane);
+    float2 acc = make_float2(bb.x + (pd.x + ps.x), bb.y + (pd.y + ps.y));
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const float u = d - c[k];
+      const float g = expf(coeff * (u * u));
+      acc.x = fmaf(wr[k].x, g, acc.x);
+      acc.y = fmaf(wr[k].y, g, acc.y);
+    }
+    *o = acc;
+  }
+}
+
+static bool is_pre_att(const dd_bond_head* bh) { return bh != nullptr && bh->kind == DD_BOND_HEAD_PRE_ATT; }
+
+static int check_bond_head(const dd_bond_head* bh) {
+  if (bh == nullptr || bh->kind == DD_BOND_HEAD_LIN) return DD_OK;
+  if (bh->kind != DD_BOND_HEAD_PRE_ATT || bh->num_r != 20 || !bh->W_p || !bh->W_r || !bh->b1 || !bh->offset) return DD_ERR_BAD_ARG;
+  return DD_OK;
+}
+
+// hidden rows of the pre_att head into w.qb from P (w.P) and the final coordinates (see k_bond_head_pre_att)
+static int launch_bond_head_pre_att(const dd_sampler* s, const Workspace& w, const dd_bond_head* bh, const float* x, const float* dxe,
+                                    const float* dxb, int NP, hipStream_t st) {
+  const long rows = (long)s->B * s->NL * (s->NL - 1);
+  const long blocks = (rows + 15) / 16;                 // (four bonds per wave)
+  hipLaunchKernelGGL(k_bond_head_pre_att, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, w.P, x, dxe, dxb, NP,
+                     s->NL, bh->W_r, bh->b1, bh->offset, bh->coeff, s->nl_real, rows, w.qb);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
 // First-Linear projections of layer `ll` from h / h_bond (one launch) and the query MLPs' second layer (one launch):
 // the forward's own launches, also run by dd_layer0_tables on its 16-atom problem.
 // (anb != NULL: the previous layer's W_lin . A_nb is still pending on the ligand rows of h -- lin_node inside the node launch)
@@ -490,8 +572,9 @@ static int forward_tail(const dd_sampler* s, hipStream_t st, StepFold* fold, boo
 
 #endif
 
-static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nullptr) {
+static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nullptr, const dd_bond_head* bh = nullptr) {
   DD_TRY(check_shapes(s));
+  const bool pre_att = is_pre_att(bh);
   const int B = s->B, NP = s->NP, NL = s->NL, K = s->K, N = NP + NL;
   const long Eb = (long)NL * (NL - 1);
   Workspace w = carve(s->workspace, B, NP, NL, K);
@@ -507,7 +590,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   const bool fused = g_fuse && NL <= g_fused_max_nl && g_dbg_clock == nullptr;
   const bool overlap = fused && g_overlap && g_prof == nullptr && s->num_layers <= 8;
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
-  if (fused && g_sched >= 5 && s->num_layers <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
+  if (fused && !pre_att && g_sched >= 5 && s->num_layers <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
       g_xup_in_asm && !g_xup_in_pos)
     return forward_tail(s, st, fold, overlap);
 #endif
@@ -743,6 +826,8 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     GemmArgs p2x[6];                                     // (lin_in_node: + the coordinate sub-layer's bond projections, which rode with lin_node)
     if (g_heads_early && g_lin_with_pb2 && l + 1 == s->num_layers) {
       p2j[2] = gemm_args(w.hb, nE, 0, 128, nE, GW(DD_G_BH_W1), GW(DD_G_BH_b1), nullptr, w.qb, nE, 0, 128, 128, 0);
+      if (pre_att)                                       // (pre_att: P = W_p h of the ligand rows; w.P is free after the node launch)
+        p2j[2] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, bh->W_p, nullptr, nullptr, w.P, B * NL, 0, 128, 128, 0);
       p2j[3] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, GW(DD_G_VH_W1), GW(DD_G_VH_b1), nullptr, w.qn, B * NL, 0, 128, 128, 0);
       p2n = 4;
       heads_done = true;
@@ -752,7 +837,12 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       p2x[p2xn++] = p2j[0]; add_anb(p2x[0], true);
       p2x[p2xn++] = p2j[1]; add_anb(p2x[1], false);
       p2x[p2xn++] = gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0);
-      if (p2n == 4) { p2x[p2xn++] = p2j[2]; p2x[p2xn] = p2j[3]; add_anb(p2x[p2xn], false); ++p2xn; }
+      if (p2n == 4) {
+        p2x[p2xn] = p2j[2];
+        if (pre_att) add_anb(p2x[p2xn], false);
+        ++p2xn;
+        p2x[p2xn] = p2j[3]; add_anb(p2x[p2xn], false); ++p2xn;
+      }
       if (proj_main && l + 1 < s->num_layers) {           // the next layer's node projections (the side stream is the longer branch otherwise)
         p2x[p2xn] = gemm_args(hcur, B * N, 0, 128, B * N, LW(l + 1, DD_W_n1), LW(l + 1, DD_b_n1), nullptr, w.P, B * N, 0, 640, 640, 0);
         add_anb(p2x[p2xn], true); ++p2xn;
@@ -923,8 +1013,11 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     GemmArgs j[2] = {
         gemm_args(w.hb, (int)(B * Eb), 0, 128, (int)(B * Eb), GW(DD_G_BH_W1), GW(DD_G_BH_b1), nullptr, w.qb, (int)(B * Eb), 0, 128, 128, 0),
         gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, GW(DD_G_VH_W1), GW(DD_G_VH_b1), nullptr, w.qn, B * NL, 0, 128, 128, 0)};
+    if (pre_att)
+      j[0] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, bh->W_p, nullptr, nullptr, w.P, B * NL, 0, 128, 128, 0);
     if (fused && lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early) {   // (lin_in_node: the last layer's W_lin . A_nb is pending)
       j[1].X2 = ((s->num_layers - 1) & 1) ? w.A : w.Anb; j[1].x2_N = NL; j[1].x2_NP = 0;
+      if (pre_att) { j[0].X2 = j[1].X2; j[0].x2_N = NL; j[0].x2_NP = 0; }
     }
     DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(j, 2, st));   // (v-head hidden -> qn: ql may still be read by the overlapped pos sub-layer)
   }
@@ -939,11 +1032,15 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   }
   // x0-hat = ligand rows of the final x
   if (!s->pred_pos) return DD_ERR_BAD_ARG;
+  // pre_att: the bond head's hidden rows need the final coordinates -- the last launch of the forward, right in front of the
+  // step kernel (or dd_forward's logits) that reads them; P was formed with the heads' first Linear above
   if (xup_prev != nullptr) {                             // folded tail: the step kernel applies the update and extracts
+    if (pre_att) DD_TRYP(DD_PROF_GEMM, launch_bond_head_pre_att(s, w, bh, xup_prev, w.dxe, w.dxb, NP, st));
     fold->xprev = xup_prev;
     return DD_OK;
   }
   DD_TRYP(DD_PROF_MISC, launch_extract_ligand(xcur, B, NP, NL, s->pred_pos, st));
+  if (pre_att) DD_TRYP(DD_PROF_GEMM, launch_bond_head_pre_att(s, w, bh, s->pred_pos, nullptr, nullptr, 0, st));
   return DD_OK;
 }
 
@@ -1176,9 +1273,13 @@ extern "C" int dd_workspace_view(const dd_sampler* s, dd_ws_view* out) {
   return DD_OK;
 }
 
-extern "C" int dd_forward(const dd_sampler* s, void* stream) {
+extern "C" int dd_forward(const dd_sampler* s, void* stream) { return dd_forward_ex(s, nullptr, stream); }
+
+extern "C" int dd_forward_ex(const dd_sampler* s, const dd_bond_head* bh, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = dd::forward_impl(s, st);
+  int rc = dd::check_bond_head(bh);
+  if (rc != DD_OK) return rc;
+  rc = dd::forward_impl(s, st, nullptr, bh);
   if (rc != DD_OK) return rc;
   if (!s->pred_pos || !s->pred_v || !s->pred_bond) return DD_ERR_BAD_ARG;
   dd::Workspace w = dd::carve(s->workspace, s->B, s->NP, s->NL, s->K);
@@ -1371,10 +1472,10 @@ extern "C" int dd_debug_node_split_cache_path(char* out, int cap) {
   return DD_OK;
 }
 
-static int one_step(const dd_sampler* s, hipStream_t st) {
+static int one_step(const dd_sampler* s, hipStream_t st, const dd_bond_head* bh = nullptr) {
   dd::StepFold fold;
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
-  int rc = dd::forward_impl(s, st, &fold);
+  int rc = dd::forward_impl(s, st, &fold, bh);
   if (rc != DD_OK) return rc;
   return dd::heads_and_step(s, st, &fold);
 }
@@ -1388,19 +1489,27 @@ extern "C" int dd_reverse_step(const dd_sampler* s, const float* logits_v, const
   return dd::reverse_step_from_logits(s, logits_v, logits_b, x0, (hipStream_t)stream);
 }
 
-extern "C" int dd_sample_steps(const dd_sampler* s, int n_steps, void* stream) {
+extern "C" int dd_sample_steps(const dd_sampler* s, int n_steps, void* stream) { return dd_sample_steps_ex(s, nullptr, n_steps, stream); }
+
+extern "C" int dd_sample_steps_ex(const dd_sampler* s, const dd_bond_head* bh, int n_steps, void* stream) {
+  if (dd::check_bond_head(bh) != DD_OK) return DD_ERR_BAD_ARG;
   if (!s || n_steps < 0 || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
       !s->pred_pos)
     return DD_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_steps; ++i) {
-    int rc = one_step(s, st);
+    int rc = one_step(s, st, bh);
     if (rc != DD_OK) return rc;
   }
   return DD_OK;
 }
 
 extern "C" int dd_sample_steps_graph(const dd_sampler* s, int n_steps, void* stream) {
+  return dd_sample_steps_graph_ex(s, nullptr, n_steps, stream);
+}
+
+extern "C" int dd_sample_steps_graph_ex(const dd_sampler* s, const dd_bond_head* bh, int n_steps, void* stream) {
+  if (dd::check_bond_head(bh) != DD_OK) return DD_ERR_BAD_ARG;
   if (!s || n_steps < 0 || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
       !s->pred_pos)
     return DD_ERR_BAD_ARG;
@@ -1418,7 +1527,7 @@ extern "C" int dd_sample_steps_graph(const dd_sampler* s, int n_steps, void* str
     (void)hipGetLastError();                     // do not leave a sticky error behind for the caller
     return DD_ERR_HIP;
   }
-  rc = one_step(s, st);
+  rc = one_step(s, st, bh);
   hipError_t e = hipStreamEndCapture(st, &graph);
   capture_lock.unlock();
   if (rc != DD_OK || e != hipSuccess || !graph) {
@@ -1445,6 +1554,11 @@ extern "C" int dd_sample_steps_graph(const dd_sampler* s, int n_steps, void* str
 namespace { struct StepGraph { unsigned magic = 0x44444753u; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; }; }
 
 extern "C" int dd_graph_create(const dd_sampler* s, int steps_per_graph, void* stream, void** graph_out) {
+  return dd_graph_create_ex(s, nullptr, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_graph_create_ex(const dd_sampler* s, const dd_bond_head* bh, int steps_per_graph, void* stream, void** graph_out) {
+  if (dd::check_bond_head(bh) != DD_OK) return DD_ERR_BAD_ARG;
   if (!s || !graph_out || steps_per_graph < 1 || steps_per_graph > 64 || !s->step_counter || !s->tab_pos || !s->tab_v ||
       !s->tab_b || !s->atom_std || !s->offset || !s->pred_pos)
     return DD_ERR_BAD_ARG;
@@ -1461,7 +1575,7 @@ extern "C" int dd_graph_create(const dd_sampler* s, int steps_per_graph, void* s
     delete g;
     return DD_ERR_HIP;
   }
-  for (int i = 0; i < steps_per_graph && rc == DD_OK; ++i) rc = one_step(s, st);
+  for (int i = 0; i < steps_per_graph && rc == DD_OK; ++i) rc = one_step(s, st, bh);
   hipError_t e = hipStreamEndCapture(st, &g->graph);
   capture_lock.unlock();
   if (rc == DD_OK && (e != hipSuccess || !g->graph)) rc = DD_ERR_HIP;
@@ -1495,8 +1609,14 @@ extern "C" int dd_graph_destroy(void* graph) {
 }
 
 extern "C" int dd_sample_steps_graph_multi(const dd_sampler* const* ss, int n, int n_steps, void* const* streams) {
+  return dd_sample_steps_graph_multi_ex(ss, nullptr, n, n_steps, streams);
+}
+
+extern "C" int dd_sample_steps_graph_multi_ex(const dd_sampler* const* ss, const dd_bond_head* const* bhs, int n, int n_steps,
+                                              void* const* streams) {
   if (!ss || !streams || n <= 0 || n > 64 || n_steps < 0) return DD_ERR_BAD_ARG;
   for (int i = 0; i < n; ++i) {
+    if (bhs && dd::check_bond_head(bhs[i]) != DD_OK) return DD_ERR_BAD_ARG;
     const dd_sampler* s = ss[i];
     if (!s || !streams[i] || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
         !s->pred_pos)
@@ -1518,7 +1638,7 @@ extern "C" int dd_sample_steps_graph_multi(const dd_sampler* const* ss, int n, i
     if (rc != DD_OK) break;
     std::lock_guard<std::mutex> capture_lock(dd::g_capture_mutex);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { rc = DD_ERR_HIP; break; }
-    int rs = one_step(ss[i], st);
+    int rs = one_step(ss[i], st, bhs ? bhs[i] : nullptr);
     hipError_t e = hipStreamEndCapture(st, &graph[i]);
     if (rs != DD_OK || e != hipSuccess || !graph[i]) { rc = rs != DD_OK ? rs : DD_ERR_HIP; break; }
     if (hipGraphInstantiate(&exec[i], graph[i], nullptr, nullptr, 0) != hipSuccess) rc = DD_ERR_HIP;

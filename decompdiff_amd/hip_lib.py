@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "dd_attn_aggregate_node", "dd_attn_aggregate_triplet", "dd_attn_aggregate_pos", "dd_reverse_step",
     "dd_segment_reduce", "dd_segment_softmax", "dd_sampler_reset",
     "dd_layer0_tables", "dd_layer0_prepare",
+    "dd_forward_ex", "dd_sample_steps_ex", "dd_sample_steps_graph_ex", "dd_graph_create_ex", "dd_sample_steps_graph_multi_ex",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -61,6 +62,15 @@ class DDSampler(ctypes.Structure):
         ("l0_tables", c_void_p), ("l0_P", c_void_p), ("l0_qn", c_void_p),
         ("num_v", c_int32), ("drift_repul", c_int32), ("repul_max_d", c_float), ("repul_scale", c_int32),
     ]
+
+
+BOND_HEAD_LIN, BOND_HEAD_PRE_ATT = 0, 1             # dd_bond_head.kind
+
+
+class DDBondHead(ctypes.Structure):
+    """struct dd_bond_head (include/decompdiff_hip.h): the bond head handed to the *_ex entry points (NULL = lin)."""
+    _fields_ = [("kind", c_int32), ("num_r", c_int32), ("W_p", c_void_p), ("W_r", c_void_p), ("b1", c_void_p),
+                ("offset", c_void_p), ("coeff", c_float), ("reserved", c_int32)]
 
 
 L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128      # DD_L0_TABLE_FLOATS
@@ -133,6 +143,11 @@ def load():
         "dd_graph_launch": [c_void_p, c_int, c_void_p],
         "dd_graph_destroy": [c_void_p],
         "dd_sample_steps_graph_multi": [POINTER(S), c_int, c_int, POINTER(c_void_p)],
+        "dd_forward_ex": [S, POINTER(DDBondHead), c_void_p],
+        "dd_sample_steps_ex": [S, POINTER(DDBondHead), c_int, c_void_p],
+        "dd_sample_steps_graph_ex": [S, POINTER(DDBondHead), c_int, c_void_p],
+        "dd_graph_create_ex": [S, POINTER(DDBondHead), c_int, c_void_p, POINTER(c_void_p)],
+        "dd_sample_steps_graph_multi_ex": [POINTER(S), POINTER(POINTER(DDBondHead)), c_int, c_int, POINTER(c_void_p)],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],

@@ -45,6 +45,8 @@ def _attach(root: nn.Module, dotted: str, tensor: torch.Tensor, kind: str):
         mod.register_buffer(parts[-1], tensor)
 
 
+BOND_NET_TYPES = ("lin", "pre_att")     # bond head on the last h_bond / on the final distances and atom features
+
 GAUSS_OFFSETS = [0, 1, 1.25, 1.5, 1.75, 2, 2.25, 2.5, 2.75, 3, 3.5, 4, 4.5, 5, 5.5, 6, 7, 8, 9, 10]
 
 
@@ -165,8 +167,8 @@ class DecompScorePosNet3D(nn.Module):
         need(config.model_type == "uni_o2_bond", "model_type=uni_o2_bond")
         need(config.hidden_dim == 128 and config.n_heads == 16, "hidden_dim=128, n_heads=16")
         need(config.cutoff_mode == "knn", "cutoff_mode=knn")
-        need(getattr(config, "bond_diffusion", False) and getattr(config, "bond_net_type", "mlp") == "lin",
-             "bond_diffusion with bond_net_type=lin")
+        need(getattr(config, "bond_diffusion", False) and getattr(config, "bond_net_type", "mlp") in BOND_NET_TYPES,
+             "bond_diffusion with bond_net_type in {lin, pre_att}")
         need(not getattr(config, "add_prior_node", False), "add_prior_node=False")
         need(config.time_emb_dim == 0, "time_emb_dim=0")
         need(config.node_indicator, "node_indicator=True")
@@ -268,9 +270,34 @@ class DecompScorePosNet3D(nn.Module):
             self._packed = dict(arena=arena.to(dev), offsets=offsets.numpy().astype(np.int64).copy(),
                                 tab_pos=tab_pos.to(dev), tab_v=tab_v.to(dev), tab_b=tab_b.to(dev),
                                 tab_score=self.pos_score_coef.detach().float().contiguous().to(dev))
+            self._packed["bond_head"] = self._bond_head_descriptor(sd, self._packed)
             self._packed_key = key
         return self._packed
 
+
+    def _bond_head_descriptor(self, sd, pw):
+        """The dd_bond_head of the *_ex entry points: None for the lin head (the arena's BH_W1 / BH_b1 slots, the entry points'
+        default); for 'pre_att' the factorised head of packing.bond_head_pre_att -- W_p = W1[:, 20:] / 2 sits in the BH_W1 slot
+        (pack_global), b1 in BH_b1, W_r^T and the Gaussian centres in a small device buffer kept in the packed dict."""
+        if self.bond_net_type != "pre_att":
+            return None
+        form = packing.bond_head_pre_att(sd, self.config)
+        arena = pw["arena"]
+        buf = torch.cat([form["W_r"].reshape(-1), form["offset"].reshape(-1)]).contiguous().to(arena.device)
+        pw["bond_head_buf"] = buf
+        g = self._global_offsets(pw)
+        bh = hip_lib.DDBondHead()
+        bh.kind, bh.num_r = hip_lib.BOND_HEAD_PRE_ATT, int(form["W_r"].shape[0])
+        bh.W_p, bh.b1 = arena.data_ptr() + 4 * g["BH_W1"], arena.data_ptr() + 4 * g["BH_b1"]
+        bh.W_r, bh.offset = buf.data_ptr(), buf.data_ptr() + 4 * form["W_r"].numel()
+        bh.coeff = float(form["coeff"])
+        return bh
+
+    def _bond_head(self, pw=None):
+        """ctypes pointer to this model's dd_bond_head, None for the lin head (NULL: the lin entry points' behaviour)."""
+        pw = self._packed if pw is None else pw
+        bh = pw.get("bond_head") if pw else None
+        return None if bh is None else ctypes.pointer(bh)
 
     def _layer0_tables(self, pw, dev):
         """dd_sampler.l0_tables for this weight set (built once): the first layer's projection / query rows of the 16
@@ -692,7 +719,7 @@ class DecompScorePosNet3D(nn.Module):
             hint = int(getattr(self, "traj_capacity_hint", 0) or 0)
             cap = max(32, 1 << (max(int(n_steps), hint) - 1).bit_length())   # trajectory capacity: 5 and 20 steps share buffers
         key = (str(dev), B, NP, NL, K, NF, cap if keep_traj else 0, bool(keep_traj), decomp_index is not None, arena.data_ptr(),
-               masks is not None, int(cache_slot))     # cache_slot: chains of ONE call that share a shape need separate buffers
+               masks is not None, int(cache_slot), self.bond_net_type)     # cache_slot: chains of ONE call that share a shape need separate buffers
         cache = DecompScorePosNet3D._chain_cache
         ent = cache.pop(key, None) if cacheable else None
         if ent is None:
@@ -876,7 +903,7 @@ class DecompScorePosNet3D(nn.Module):
             dummy3 = torch.ones(B * NL, 3, device=dev)
             s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, dummy3,
                                             torch.zeros(B, 3, device=dev), None, None, 0)
-            hip_lib.check(hip_lib.load().dd_forward(ctypes.byref(s), hip_lib.stream_ptr(dev)), "dd_forward")
+            hip_lib.check(hip_lib.load().dd_forward_ex(ctypes.byref(s), self._bond_head(pw), hip_lib.stream_ptr(dev)), "dd_forward")
             _check_queue(s, dev)
             preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3),
                      "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes)}
@@ -1065,7 +1092,8 @@ class DecompScorePosNet3D(nn.Module):
                         if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                             self._drop_cached_graphs()
                         graph = ctypes.c_void_p()
-                        hip_lib.check(lib.dd_graph_create(ctypes.byref(c["s"]), 1, side.cuda_stream, ctypes.byref(graph)), "dd_graph_create")
+                        hip_lib.check(lib.dd_graph_create_ex(ctypes.byref(c["s"]), self._bond_head(), 1, side.cuda_stream,
+                                                             ctypes.byref(graph)), "dd_graph_create")
                         ent["graph"], ent["graph_sig"] = graph, gsig
                         DecompScorePosNet3D._graph_counter += 1
                         ent["graph_id"] = DecompScorePosNet3D._graph_counter
@@ -1079,7 +1107,8 @@ class DecompScorePosNet3D(nn.Module):
             else:
                 with torch.cuda.stream(side):
                     for c in chains:
-                        hip_lib.check(lib.dd_sample_steps(ctypes.byref(c["s"]), int(num_steps), hip_lib.stream_ptr(dev)), "dd_sample_steps")
+                        hip_lib.check(lib.dd_sample_steps_ex(ctypes.byref(c["s"]), self._bond_head(), int(num_steps),
+                                                             hip_lib.stream_ptr(dev)), "dd_sample_steps")
             cur.wait_stream(side)
             return
         if len(chains) > 64:                            # dd_sample_steps_graph_multi takes at most 64 chains
@@ -1095,7 +1124,9 @@ class DecompScorePosNet3D(nn.Module):
         # (the C entry point captures one graph per chain and destroys them at the end: no other graph may be alive across
         #  that, see _parked_graphs -- cached entries re-capture theirs on next use)
         self._drop_cached_graphs()
-        hip_lib.check(lib.dd_sample_steps_graph_multi(ss, n, int(num_steps), sts), "dd_sample_steps_graph_multi")
+        bh = self._bond_head()
+        bhs = None if bh is None else (ctypes.POINTER(hip_lib.DDBondHead) * n)(*([bh] * n))
+        hip_lib.check(lib.dd_sample_steps_graph_multi_ex(ss, bhs, n, int(num_steps), sts), "dd_sample_steps_graph_multi")
         for st in pool:
             cur.wait_stream(st)
 
@@ -1138,7 +1169,8 @@ class DecompScorePosNet3D(nn.Module):
             if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                 self._drop_cached_graphs()                 # (all live graphs, newest first; cached entries re-capture on next use)
             graph = ctypes.c_void_p()
-            hip_lib.check(lib.dd_graph_create(ctypes.byref(s), spg, side.cuda_stream, ctypes.byref(graph)), "dd_graph_create")
+            hip_lib.check(lib.dd_graph_create_ex(ctypes.byref(s), self._bond_head(), spg, side.cuda_stream, ctypes.byref(graph)),
+                          "dd_graph_create")
             ent["graph"], ent["graph_sig"] = graph, gsig
             DecompScorePosNet3D._graph_counter += 1
             ent["graph_id"] = DecompScorePosNet3D._graph_counter

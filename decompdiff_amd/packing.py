@@ -275,9 +275,30 @@ def pack_global(sd, cfg) -> "OrderedDict[str, torch.Tensor]":
     out["VH_W1"], out["VH_b1"] = sd["v_inference.0.weight"], sd["v_inference.0.bias"]
     out["VH_W2"], out["VH_b2"] = sd["v_inference.2.weight"], sd["v_inference.2.bias"]
     out["BH_W1"], out["BH_b1"] = sd["bond_inference.0.weight"], sd["bond_inference.0.bias"]
+    if getattr(cfg, "bond_net_type", "lin") == "pre_att":
+        out["BH_W1"] = bond_head_pre_att(sd, cfg)["W_p"]     # (same [128, 128] slot: the per-atom projection P = W_p h)
     out["BH_W2"], out["BH_b2"] = sd["bond_inference.2.weight"], sd["bond_inference.2.bias"]
     assert list(out.keys()) == GLOBAL_SLOTS
     return out
+
+
+def bond_head_pre_att(sd, cfg) -> Dict[str, object]:
+    """The 'pre_att' bond head (decompdiff.py:199-211, 323-341) in the factorised form the kernels use.  The reference computes,
+    for ligand bond (src, dst) with d = |x_dst - x_src| of the final coordinates and h the final node features,
+        W1 [r(d); (h_dst + h_src) / 2] + b1,   r_k(d) = exp(coeff (d - offset_k)^2)   (GaussianSmearing(0, 5, 20, fix_offset=False)),
+    which is exactly  W_r^T r(d) + P[dst] + P[src] + b1  with  P = W_p h,  W_p = W1[:, 20:] / 2,  W_r = W1[:, :20]^T:
+    one 128 x 128 GEMM row per ligand atom instead of one 148-wide row per bond.  `offset` is the model's
+    distance_expansion.offset buffer (linspace(0, 5, num_r_gaussian) if the state dict lacks it); coeff is formed as the
+    reference forms it (a Python float from the fp32 offsets)."""
+    W1 = sd["bond_inference.0.weight"].detach().cpu()
+    G = int(cfg.num_r_gaussian)
+    if tuple(W1.shape) != (H, G + H):
+        raise ValueError(f"bond_inference.0.weight of a pre_att head is [{H}, {G + H}], got {list(W1.shape)}")
+    off = sd.get("distance_expansion.offset")
+    off = torch.linspace(0.0, 5.0, G) if off is None else off.detach().cpu().float()
+    coeff = -0.5 / (off[1] - off[0]).item() ** 2
+    return {"W_p": (W1[:, G:] * 0.5).contiguous(), "W_r": W1[:, :G].t().contiguous(),
+            "b1": sd["bond_inference.0.bias"].detach().cpu().contiguous(), "offset": off.contiguous(), "coeff": coeff}
 
 
 def pack_model(sd: Dict[str, torch.Tensor], cfg, kernel_form: bool = False):

@@ -338,7 +338,9 @@ def learnable_param_shapes(config, protein_atom_feature_dim=29, ligand_atom_feat
     linear("v_inference.0", H, H)
     linear("v_inference.2", num_classes, H)
     if getattr(config, "bond_diffusion", False):
-        linear("bond_inference.0", H, H)
+        # 'pre_att' (decompdiff.py:199-211): [distance_expansion(|x_dst - x_src|) (num_r_gaussian), (h_dst + h_src) / 2 (H)]
+        pre_att = getattr(config, "bond_net_type", "lin") == "pre_att"
+        linear("bond_inference.0", H, (config.num_r_gaussian if pre_att else 0) + H)
         linear("bond_inference.2", nb, H)
     return shapes
 

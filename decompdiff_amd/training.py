@@ -668,10 +668,31 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         h, h_bond = new_h, new_h_bond
     softplus = lambda t: F.softplus(t) - math.log(2.0)                              # ShiftedSoftplus (common.py:66-72)
     final_h = h.index_select(0, lig_rows)
+    if getattr(model, "bond_net_type", "lin") == "pre_att":
+        bond_hidden = _bond_hidden_pre_att(P, model, x, h, p_bdst, S["p_bsrc"], bond_src)
+    else:
+        bond_hidden = P.lin("bond_inference.0", h_bond)
     out = {"pred_ligand_pos": x.index_select(0, lig_rows),
            "pred_ligand_v": P.lin("v_inference.2", softplus(P.lin("v_inference.0", final_h))),
-           "pred_bond": P.lin("bond_inference.2", softplus(P.lin("bond_inference.0", h_bond)))}
+           "pred_bond": P.lin("bond_inference.2", softplus(bond_hidden))}
     return out
+
+
+def _bond_hidden_pre_att(P, model, x, h, p_bdst, p_bsrc, bond_src):
+    """First Linear of the 'pre_att' bond head (decompdiff.py:323-341) on the final x / h, in the factorised form of the kernels
+    (packing.bond_head_pre_att): W1 [r(d); (h_dst + h_src) / 2] + b1 = W_r^T r(d) + (W1_h h)[dst] / 2 + (W1_h h)[src] / 2 + b1.
+    The gradient reaches bond_inference.0, h, and through the distance every parameter upstream of the final coordinates.
+    (Padded batches: bonds with a padding endpoint lie ~1e3 A apart, r(d) is exactly 0 there, and network_padded drops their
+    rows, so they contribute neither to a result nor to a gradient.)"""
+    W = P.w("bond_inference.0")
+    G = W.size(1) - H
+    off = model.distance_expansion.offset
+    grid = torch.linspace(0.0, 5.0, G)                                  # (GaussianSmearing(0, 5, G, fix_offset=False): the buffer's
+    coeff = -0.5 / (grid[1] - grid[0]).item() ** 2                      #  values; coeff from host values -- no device sync)
+    d = (gather(x, p_bdst) - x.index_select(0, bond_src)).norm(dim=-1)
+    r = torch.exp(coeff * (d.reshape(-1, 1) - off.to(d.dtype)) ** 2)
+    Ph = linear128(h, W[:, G:])
+    return linear_feat(r, W[:, :G]) + 0.5 * (gather(Ph, p_bdst) + gather(Ph, p_bsrc)) + P.b("bond_inference.0")
 
 
 # --------------------------------------------------------------------------------------------------------------------

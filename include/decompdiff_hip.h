@@ -303,6 +303,38 @@ int dd_graph_destroy(void* graph);
 int dd_sample_steps_graph_multi(const dd_sampler* const* s /*HOST [n]*/, int n, int n_steps,
                                 void* const* streams /*HOST [n]*/);
 
+/* Bond head of the model (decompdiff.py:199-211, 323-341).  The entry points without the _ex suffix run the 'lin' head
+ * (bond_inference on the last layer's h_bond, slots DD_G_BH_W1 / DD_G_BH_b1); they equal the _ex variants with bh = NULL.
+ * 'pre_att' reads the final coordinates and atom features: for ligand bond e = (src, dst),
+ *   hidden[e] = W_r^T r(d) + P[dst] + P[src] + b1,  d = |x_dst - x_src| of the network's output coordinates,
+ *   r_k(d) = exp(coeff * (d - offset[k])^2) (k < 20),  P = W_p h of the final h (ligand rows),
+ * where W_p = W1[:, 20:148] / 2 and W_r = W1[:, 0:20]^T of the reference's bond_inference.0 (W1 [128, 148], bias b1); the
+ * second Linear stays in the slots DD_G_BH_W2 / DD_G_BH_b2.  All pointers are DEVICE pointers and must stay valid while a
+ * graph captured with the descriptor is alive. */
+#define DD_BOND_HEAD_LIN 0
+#define DD_BOND_HEAD_PRE_ATT 1
+typedef struct dd_bond_head {
+  int32_t kind;            /* DD_BOND_HEAD_LIN or DD_BOND_HEAD_PRE_ATT */
+  int32_t num_r;           /* Gaussians of the distance expansion: 20 */
+  const float* W_p;        /* [128, 128] (out, in): the feature half of W1, halved */
+  const float* W_r;        /* [20, 128]: the distance columns of W1, transposed */
+  const float* b1;         /* [128] */
+  const float* offset;     /* [20] centres of the distance expansion */
+  float coeff;             /* its exponent factor, -0.5 / (offset[1] - offset[0])^2 */
+  int32_t reserved;
+} dd_bond_head;
+
+/* dd_forward / dd_sample_steps / dd_sample_steps_graph / dd_graph_create / dd_sample_steps_graph_multi with a bond head
+ * (NULL or kind DD_BOND_HEAD_LIN: exactly the functions above).  bh of the multi variant: HOST array of n descriptors
+ * (entries may be NULL), or NULL for all lin. */
+int dd_forward_ex(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, void* stream);
+int dd_sample_steps_ex(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, int n_steps, void* stream);
+int dd_sample_steps_graph_ex(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, int n_steps, void* stream);
+int dd_graph_create_ex(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, int steps_per_graph, void* stream,
+                       void** graph_out /*HOST*/);
+int dd_sample_steps_graph_multi_ex(const dd_sampler* const* s /*HOST [n]*/, const dd_bond_head* const* bh /*HOST [n]*/, int n,
+                                   int n_steps, void* const* streams /*HOST [n]*/);
+
 /* Drift guidance gradients at x_t (utils/guidance_funcs.py:24-78), analytic. grad [B,NL,3]. */
 int dd_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                     float* grad, int accumulate, void* stream);
