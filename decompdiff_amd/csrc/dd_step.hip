@@ -88,7 +88,9 @@ __global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
   float se = 0.f;
 #pragma unroll
   for (int c = 0; c < NC; ++c) se += expf(logit[c] - mx);
-  const float lse = mx + logf(se);
+  // (x - max) - log(sum), as torch's log_softmax: x - (max + log(sum)) rounds the sum at the size of the logits, which costs the
+  //  leading class half an ulp of max (1.2e-4 at logits of a few thousand) and carries into the posterior
+  const float lsum = logf(se);
   const int tm1 = t - 1 < 0 ? 0 : t - 1;
   const float la_t = a.tab[t], l1ma_t = a.tab[a.T + t];
   const float lca = a.tab[2 * a.T + tm1], l1mca = a.tab[3 * a.T + tm1];
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const float log_prior = log_prior_tab[c];
-    const float lv0 = logit[c] - lse;
+    const float lv0 = (logit[c] - mx) - lsum;
     const float lvt = (c == cur) ? 0.f : -69.07755278982137f;    // log(clamp(onehot, 1e-30))
     const float q0 = log_add_exp(lv0 + lca, l1mca + log_prior);  // q(v_{t-1} | v0)
     const float q1 = log_add_exp(lvt + la_t, l1ma_t + log_prior); // q(v_t | v_{t-1})
@@ -426,13 +428,13 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
   float se = 0.f;
 #pragma unroll
   for (int k = 0; k < NC; ++k) se += lane_bcast(e, k);
-  const float lse = mx + logf(se);
+  const float lsum = logf(se);                            // (log_softmax as (x - max) - log(sum): see k_step_rows)
   const int tm1 = t - 1 < 0 ? 0 : t - 1;
   const float la_t = a.tab[t], l1ma_t = a.tab[a.T + t];
   const float lca = a.tab[2 * a.T + tm1], l1mca = a.tab[3 * a.T + tm1];
   const float log_prior = a.tab[4 * a.T + c];            // log prior of this lane's class (uniform: -log NC)
   const int cur = a.state[row];
-  const float lv0 = mine - lse;
+  const float lv0 = (mine - mx) - lsum;
   const float lvt = (c == cur) ? 0.f : -69.07755278982137f;      // log(clamp(onehot, 1e-30))
   const float q0 = log_add_exp(lv0 + lca, l1mca + log_prior);    // q(v_{t-1} | v0)
   const float q1 = log_add_exp(lvt + la_t, l1ma_t + log_prior);  // q(v_t | v_{t-1})

@@ -51,9 +51,9 @@ __global__ __launch_bounds__(256) void k_ln_relu_fwd(const float* __restrict__ x
 #pragma unroll
       for (int c = 0; c < 8; ++c) v[c] = 0.f;
     }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s += v[c];
+    // pairwise, like the DPP steps after it: the sum of 128 equal values is then exact at every level, so a constant row has
+    // v - mean == 0 exactly and y = relu(beta) (a running sum rounds at 3c, 5c, ...: one ulp of the mean times rstd = 316)
+    const float s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
     const float mean = row16_sum(s) * (1.0f / 128.0f);
     float q = 0.f;
 #pragma unroll

@@ -43,7 +43,8 @@ def angular_encoding(angle):
 
 
 def linear(sd, name, x):
-    return F.linear(x, sd[name + ".weight"], sd[name + ".bias"])
+    w = sd[name + ".weight"]
+    return F.linear(x.to(w.dtype), w, sd[name + ".bias"])                # (a no-op in fp32; the float64 mode of forward())
 
 
 def mlp(sd, name, x):
@@ -62,17 +63,21 @@ def outer_product_feat(edge_type, dist_feat):
     return (edge_type.unsqueeze(-1) * dist_feat.unsqueeze(1)).reshape(edge_type.size(0), -1)
 
 
-def attention_weights(q_dst, k, seg, n_seg, n_heads):
+def attention_weights(q_dst, k, seg, n_seg, n_heads, stats=None):
     """alpha = scatter_softmax((q*k/sqrt(d)).sum(-1), seg)
-    (uni_transformer_edge.py:64, 160, 205)."""
+    (uni_transformer_edge.py:64, 160, 205).  ``stats``: a list that receives (largest |score|, mean over the segments and heads
+    of the largest attention weight) of this call -- how selective the softmaxes of a weight set are."""
     d = k.size(-1) // n_heads
     kk = k.view(-1, n_heads, d)
     qq = q_dst.view(-1, n_heads, d)
-    alpha = ops.scatter_softmax((qq * kk / math.sqrt(d)).sum(-1), seg, dim=0, dim_size=n_seg)
+    score = (qq * kk / math.sqrt(d)).sum(-1)
+    alpha = ops.scatter_softmax(score, seg, dim=0, dim_size=n_seg)
+    if stats is not None and score.numel():
+        stats.append((float(score.abs().max()), float(ops.scatter_max(alpha, seg, 0, n_seg)[seg.unique()].mean())))
     return alpha
 
 
-def node_update(sd, name, h, edge_feat, edge_index, e_w, n_heads):
+def node_update(sd, name, h, edge_feat, edge_index, e_w, n_heads, stats=None):
     """NodeUpdateLayer.forward with out_fc=False (uni_transformer_edge.py:42-74)."""
     N = h.size(0)
     src, dst = edge_index
@@ -82,13 +87,13 @@ def node_update(sd, name, h, edge_feat, edge_index, e_w, n_heads):
     if e_w is not None:
         v = v * e_w.view(-1, 1)
     q = mlp(sd, name + ".hq_func", h)
-    alpha = attention_weights(q[dst], k, dst, N, n_heads)
+    alpha = attention_weights(q[dst], k, dst, N, n_heads, stats)
     d = v.size(-1) // n_heads
     m = alpha.unsqueeze(-1) * v.view(-1, n_heads, d)
     return ops.scatter_sum(m, dst, dim=0, dim_size=N).view(N, -1)
 
 
-def pos_update(sd, name, h, rel_x, edge_feat, edge_index, e_w, n_heads):
+def pos_update(sd, name, h, rel_x, edge_feat, edge_index, e_w, n_heads, stats=None):
     """PosUpdateLayer.forward (uni_transformer_edge.py:188-210)."""
     N = h.size(0)
     src, dst = edge_index
@@ -99,12 +104,12 @@ def pos_update(sd, name, h, rel_x, edge_feat, edge_index, e_w, n_heads):
         v = v * e_w.view(-1, 1)
     v = v.unsqueeze(-1) * rel_x.unsqueeze(1)                             # [E, heads, 3]
     q = mlp(sd, name + ".xq_func", h)
-    alpha = attention_weights(q[dst], k, dst, N, n_heads)
+    alpha = attention_weights(q[dst], k, dst, N, n_heads, stats)
     m = alpha.unsqueeze(-1) * v
     return ops.scatter_sum(m, dst, dim=0, dim_size=N).mean(1)
 
 
-def bond_update(sd, name, h, h_bond, pos, bond_index, n_heads):
+def bond_update(sd, name, h, h_bond, pos, bond_index, n_heads, stats=None):
     """BondUpdateLayer.forward with include_h_node=True (uni_transformer_edge.py:125-167)."""
     E = h_bond.size(0)
     i, j, idx_i, idx_j, idx_k, idx_kj, idx_ji = ops.bond_triplets(bond_index, h.size(0))
@@ -121,7 +126,7 @@ def bond_update(sd, name, h, h_bond, pos, bond_index, n_heads):
     k = mlp(sd, name + ".hk_func", kv)
     v = mlp(sd, name + ".hv_func", kv)
     q = mlp(sd, name + ".hq_func", qin)
-    alpha = attention_weights(q, k, idx_ji, E, n_heads)
+    alpha = attention_weights(q, k, idx_ji, E, n_heads, stats)
     d = v.size(-1) // n_heads
     m = alpha.unsqueeze(-1) * v.view(-1, n_heads, d)
     return ops.scatter_sum(m, idx_ji, dim=0, dim_size=E).view(E, -1)
@@ -140,22 +145,22 @@ def edge_types(edge_index, mask_ligand):
 
 
 def attention_layer(sd, name, h, x, edge_type, edge_index, h_bond, bond_index, mask_ligand_atom, e_w, n_heads,
-                    trace=None):
+                    trace=None, stats=None):
     """AttentionLayerO2TwoUpdateNodeGeneral.forward (uni_transformer_edge.py:259-287)."""
     src, dst = edge_index
     rel_x = x[dst] - x[src]
     dist = torch.norm(rel_x, p=2, dim=-1, keepdim=True)
     dist_feat = outer_product_feat(edge_type.to(x.dtype), gaussian_smearing(dist))
     edge_feat = torch.cat([dist_feat, edge_type.to(x.dtype)], -1)
-    a_edge = node_update(sd, name + ".node_layer_with_edge", h, edge_feat, edge_index, e_w, n_heads)
-    a_bond = node_update(sd, name + ".node_layer_with_bond", h, h_bond, bond_index, None, n_heads)
-    d_bond = bond_update(sd, name + ".bond_layer", h, h_bond, x, bond_index, n_heads)
+    a_edge = node_update(sd, name + ".node_layer_with_edge", h, edge_feat, edge_index, e_w, n_heads, stats)
+    a_bond = node_update(sd, name + ".node_layer_with_bond", h, h_bond, bond_index, None, n_heads, stats)
+    d_bond = bond_update(sd, name + ".bond_layer", h, h_bond, x, bond_index, n_heads, stats)
     new_h_bond = h_bond + d_bond
     new_h = h + linear(sd, name + ".lin_node", a_edge + a_bond)
-    dx_edge = pos_update(sd, name + ".pos_layer_with_edge", new_h, rel_x, edge_feat, edge_index, e_w, n_heads)
+    dx_edge = pos_update(sd, name + ".pos_layer_with_edge", new_h, rel_x, edge_feat, edge_index, e_w, n_heads, stats)
     b_src, b_dst = bond_index
     rel_bx = x[b_dst] - x[b_src]
-    dx_bond = pos_update(sd, name + ".pos_layer_with_bond", new_h, rel_bx, new_h_bond, bond_index, None, n_heads)
+    dx_bond = pos_update(sd, name + ".pos_layer_with_bond", new_h, rel_bx, new_h_bond, bond_index, None, n_heads, stats)
     new_x = x + (dx_edge + dx_bond) * mask_ligand_atom[:, None]
     if trace is not None:
         trace.append(dict(a_edge=a_edge, a_bond=a_bond, d_bond=d_bond, h=new_h, h_bond=new_h_bond,
@@ -163,10 +168,12 @@ def attention_layer(sd, name, h, x, edge_type, edge_index, h_bond, bond_index, m
     return new_h, new_h_bond, new_x
 
 
-def refine_net(sd, cfg, h, x, bond_index, h_bond, mask_ligand, mask_ligand_atom, batch, trace=None):
+def refine_net(sd, cfg, h, x, bond_index, h_bond, mask_ligand, mask_ligand_atom, batch, trace=None, stats=None):
     """UniTransformerO2TwoUpdateGeneralBond.forward, cutoff_mode='knn' (uni_transformer_edge.py:394-443)."""
     for _ in range(cfg.num_blocks):
-        edge_index = ops.knn_graph(x, k=cfg.knn, batch=batch)
+        # the graph is a discrete input: a float64 run selects its neighbours from the fp32 coordinates with the fp32 distance
+        # formula, as the fp32 run (and dd_knn) do -- forward() checks that the coordinates are fp32 values
+        edge_index = ops.knn_graph(x if x.dtype == torch.float32 else x.float(), k=cfg.knn, batch=batch)
         etype = edge_types(edge_index, mask_ligand)
         src, dst = edge_index
         dist = torch.norm(x[dst] - x[src], p=2, dim=-1, keepdim=True)
@@ -175,7 +182,7 @@ def refine_net(sd, cfg, h, x, bond_index, h_bond, mask_ligand, mask_ligand_atom,
             trace.append(dict(edge_index=edge_index, e_w=e_w))
         for l in range(cfg.num_layers):
             h, h_bond, x = attention_layer(sd, f"refine_net.base_block.{l}", h, x, etype, edge_index, h_bond,
-                                           bond_index, mask_ligand_atom, e_w, cfg.n_heads, trace)
+                                           bond_index, mask_ligand_atom, e_w, cfg.n_heads, trace, stats)
     return dict(x=x, h=h, h_bond=h_bond)
 
 
@@ -201,12 +208,22 @@ def compose_context(h_protein, h_ligand, pos_protein, pos_ligand, batch_protein,
 
 def forward(sd, cfg, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, init_ligand_v_aux,
             batch_ligand, ligand_fc_bond_index, init_ligand_fc_bond_type, ligand_atom_mask=None,
-            num_classes=8, trace=None):
+            num_classes=8, trace=None, dtype=None, stats=None):
     """DecompScorePosNet3D.forward for the shipped config (models/decompdiff.py:213-351).
 
     ``time_step``, the ``*_group_idx`` and ``prior_*`` arguments of the reference are unused
     on this path (time_emb_dim=0, add_prior_node=False) and are therefore not taken.
+
+    ``dtype=torch.float64`` evaluates the same code in double precision on the same fp32 weights and inputs (the yardstick
+    that says how far fp32 itself is from the truth on an input); the kNN graph is still the fp32 one.  With the default
+    nothing is cast and the fp32 arithmetic is untouched.
     """
+    if dtype is not None and dtype != torch.float32:
+        assert protein_pos.dtype == init_ligand_pos.dtype == torch.float32 and cfg.num_blocks == 1, \
+            "the float64 mode takes fp32 inputs and builds one kNN graph, from them"
+        sd = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+        protein_pos, init_ligand_pos = protein_pos.to(dtype), init_ligand_pos.to(dtype)
+        protein_v, init_ligand_v_aux = protein_v.to(dtype), init_ligand_v_aux.to(dtype)
     lig_feat = torch.cat([F.one_hot(init_ligand_v, num_classes).float(), init_ligand_v_aux], -1)
     h_protein = linear(sd, "protein_atom_emb", protein_v)
     h_ligand = linear(sd, "ligand_atom_emb", lig_feat)
@@ -217,7 +234,7 @@ def forward(sd, cfg, protein_pos, protein_v, batch_protein, init_ligand_pos, ini
         h_protein, h_ligand, protein_pos, init_ligand_pos, batch_protein, batch_ligand, ligand_atom_mask)
     bond_index = l_idx[ligand_fc_bond_index]
     h_bond = linear(sd, "ligand_bond_emb", F.one_hot(init_ligand_fc_bond_type, cfg.num_bond_classes).float())
-    out = refine_net(sd, cfg, h_all, pos_all, bond_index, h_bond, mask_ligand, mask_ligand_atom, batch_all, trace)
+    out = refine_net(sd, cfg, h_all, pos_all, bond_index, h_bond, mask_ligand, mask_ligand_atom, batch_all, trace, stats)
     final_h = out["h"][mask_ligand_atom]
     v_logits = linear(sd, "v_inference.2", shifted_softplus(linear(sd, "v_inference.0", final_h)))
     preds = dict(pred_ligand_pos=out["x"][mask_ligand_atom], pred_ligand_v=v_logits)

@@ -81,8 +81,11 @@ def test_knn_rejects_unsupported_shapes():
 
 
 @pytest.mark.parametrize("rows,ncols,ln,acc", [(330, 640, False, False), (61, 128, True, False), (870, 256, False, True),
-                                               (1, 64, True, True)])
+                                               (1, 64, True, True), (61, 128, "mixed", False), (870, 256, "mixed", True),
+                                               (1, 64, "mixed", True)])
 def test_gemm128(rows, ncols, ln, acc):
+    """ln == "mixed": the fused LayerNorm with 40 gamma channels negated and 5 exactly zero, and the first quarter of the rows
+    (at least one) exactly constant over the 128 input columns (variance 0: the output is relu(beta) W^T + bias)."""
     lib = hip_lib.load()
     g = torch.Generator().manual_seed(rows + ncols)
     ldx, ldy = 256, ncols + 64
@@ -91,6 +94,13 @@ def test_gemm128(rows, ncols, ln, acc):
     bias = torch.randn(ncols, generator=g)
     lnp = torch.stack([1 + 0.1 * torch.randn(128, generator=g), 0.1 * torch.randn(128, generator=g)])
     Y0 = torch.randn(rows, ldy, generator=g)
+    if ln == "mixed":
+        perm = torch.randperm(128, generator=g)
+        lnp[0, perm[:40]] *= -1.0
+        lnp[0, perm[40:45]] = 0.0
+        n_const = max(1, rows // 4)
+        X[:n_const, 64:192] = X[:n_const, 64:65]
+        assert int((lnp[0] < 0).sum()) == 40 and int((lnp[0] == 0).sum()) == 5
     xin = X[:, 64:192].double()
     if ln:
         xin = torch.relu(torch.nn.functional.layer_norm(xin, (128,), lnp[0].double(), lnp[1].double(), 1e-5))

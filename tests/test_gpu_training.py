@@ -336,34 +336,49 @@ def test_gemm128_tn_bias_matches_torch():
 
 def test_fused_layernorm_relu_matches_torch():
     """training.ln_relu (dd_ln_relu_forward / _backward): y, dx, dgamma, dbeta against torch autograd in float64, row counts from
-    one row to more rows than the backward has partial-sum slabs."""
+    one row to more rows than the backward has partial-sum slabs.  Every row count runs twice: as drawn, and with 40 gamma
+    channels negated, 5 exactly zero and a leading block of exactly constant rows (variance 0: rstd = 1 / sqrt(eps), y = relu(beta))."""
     from decompdiff_amd import training
     torch.manual_seed(4)
+    perm = torch.randperm(128, generator=torch.Generator().manual_seed(40)).to(dev())
     for rows in (1, 3, 130, 4099, 97440):
-        x = torch.randn(rows, 128, device=dev()) * 1.7 + 0.3
-        g = torch.randn(128, device=dev()) * 0.5 + 1.0
+        x0 = torch.randn(rows, 128, device=dev()) * 1.7 + 0.3
+        g0 = torch.randn(128, device=dev()) * 0.5 + 1.0
         b = torch.randn(128, device=dev()) * 0.3
         dy = torch.randn(rows, 128, device=dev())
-        xs, gs, bs = (t.clone().requires_grad_(True) for t in (x, g, b))
-        y = training.ln_relu(xs, gs, bs)
-        y.backward(dy)
-        xd, gd, bd = x.double(), g.double(), b.double()
-        yd = torch.relu(torch.nn.functional.layer_norm(xd, (128,), gd, bd, 1e-5))
-        assert float((y.double() - yd).abs().max()) < 1e-5
-        # the backward in float64 WITH THE KERNEL'S OWN ReLU mask (y > 0): a pre-activation within rounding of 0 may take either
-        # side in fp32, and one such element moves a whole row's dx -- the mask is part of the forward result, not of the test
-        mask = (y > 0).double()
-        mean = xd.mean(1, keepdim=True)
-        rstd = 1.0 / torch.sqrt(xd.var(1, unbiased=False, keepdim=True) + 1e-5)
-        xhat = (xd - mean) * rstd
-        dz = dy.double() * mask
-        dxhat = dz * gd
-        want_dx = rstd * (dxhat - dxhat.mean(1, keepdim=True) - xhat * (dxhat * xhat).mean(1, keepdim=True))
-        assert float((xs.grad.double() - want_dx).abs().max()) < 2e-5 * max(1.0, float(want_dx.abs().max())), rows
-        for a, w in ((gs.grad, (dz * xhat).sum(0)), (bs.grad, dz.sum(0))):
-            assert float((a.double() - w).abs().max()) < 1e-4 * max(1.0, float(w.abs().max())), rows
-        y2 = training.ln_relu(xs, gs, bs)
-        assert torch.equal(y, y2)                              # run to run bit-identical (no atomics)
+        for mixed in (False, True):
+            x, g = x0.clone(), g0.clone()
+            if mixed:
+                g[perm[:40]] = -g[perm[:40]].abs()
+                g[perm[40:45]] = 0.0
+                n_const = max(1, rows // 4)
+                x[:n_const] = x[:n_const, :1]
+                assert int((g < 0).sum()) >= 40 and int((g == 0).sum()) == 5 and float(x[:n_const].var(1, unbiased=False).max()) == 0.0
+            xs, gs, bs = (t.clone().requires_grad_(True) for t in (x, g, b))
+            y = training.ln_relu(xs, gs, bs)
+            y.backward(dy)
+            xd, gd, bd = x.double(), g.double(), b.double()
+            yd = torch.relu(torch.nn.functional.layer_norm(xd, (128,), gd, bd, 1e-5))
+            assert float((y.double() - yd).abs().max()) < 1e-5, (rows, mixed)
+            # the backward in float64 WITH THE KERNEL'S OWN ReLU mask (y > 0): a pre-activation within rounding of 0 may take either
+            # side in fp32, and one such element moves a whole row's dx -- the mask is part of the forward result, not of the test
+            mask = (y > 0).double()
+            mean = xd.mean(1, keepdim=True)
+            rstd = 1.0 / torch.sqrt(xd.var(1, unbiased=False, keepdim=True) + 1e-5)
+            xhat = (xd - mean) * rstd
+            dz = dy.double() * mask
+            dxhat = dz * gd
+            want_dx = rstd * (dxhat - dxhat.mean(1, keepdim=True) - xhat * (dxhat * xhat).mean(1, keepdim=True))
+            # (the constant rows, rstd = 316, and the ordinary rows each against their own largest dx: the same relative bound)
+            n_const = max(1, rows // 4) if mixed else 0
+            for blk in (slice(0, n_const), slice(n_const, rows)):
+                if blk.stop > blk.start:
+                    err = float((xs.grad[blk].double() - want_dx[blk]).abs().max())
+                    assert err < 2e-5 * max(1.0, float(want_dx[blk].abs().max())), (rows, mixed, blk)
+            for a, w in ((gs.grad, (dz * xhat).sum(0)), (bs.grad, dz.sum(0))):
+                assert float((a.double() - w).abs().max()) < 1e-4 * max(1.0, float(w.abs().max())), (rows, mixed)
+            y2 = training.ln_relu(xs, gs, bs)
+            assert torch.equal(y, y2)                              # run to run bit-identical (no atomics)
 
 
 def _grads_agree(ga, gb, g=None):
