@@ -1,5 +1,6 @@
 // Graph construction and light per-node / per-edge kernels:
 //   k_knn            torch_cluster.knn via torch_geometric.nn.knn_graph (uni_transformer_edge.py:353)
+//   k_knn_csr        the same call on a flat batch of different samples (op level: functional.knn_graph)
 //   k_edge_weights   e_w = sigmoid(MLP_{20->128->1}(G(dist)))           (uni_transformer_edge.py:422-427)
 //   k_embed_*        atom / bond embeddings + context composition        (decompdiff.py:219-256,279,296-297)
 //   k_bl_assemble3   per-bond-edge partial sums of the bond_layer first Linear (packing.py docstring)
@@ -110,6 +111,104 @@ __global__ __launch_bounds__(256) void k_knn(const float* __restrict__ x, int B,
   const float* xb = x + (long)b * N * 3;
   const PosView pv{xb, xb + 3 * (long)NP, NP};
   knn_wave<CAND>(pv, i, N, K, nbr + (long)centre * K, masked, npb, nlb, sel[threadIdx.x >> 6], nullptr);
+}
+
+// ------------------------------------------------------------------- kNN over a flat, ragged batch
+// torch_geometric.nn.knn_graph on a PyG Batch of DIFFERENT complexes: x is one flat [n,3] tensor, sample b owns rows
+// ptr[b] .. ptr[b+1]-1 (any count, 0 and 1 included) and its centres get k_b = min(K, n_b - 1) neighbours (loop: the centre is a
+// candidate too, k_b = min(K, n_b)).  One wave per centre row, the same key and the same total order as knn_wave -- a dense batch
+// gives the lists of k_knn -- but the candidates are STREAMED: chunks of 64 * CAND rows (<= 2048), and the k_b best keys so far
+// ride along in registers as one more candidate per lane (lane j: the j-th smallest, so ties among them are in index order,
+// and they come before the chunk's candidates in the tie order because their indices are lower).  Every chunk is then the
+// selection of knn_wave over CAND + 1 candidates per lane; the result is exact for every n_b.  The first chunk holds at least
+// k_b real candidates (64 * CAND - 1 >= 64 when the sample is longer than a chunk), so from then on k_b real keys are carried.
+// The wave writes its k_b edges as global int64 rows into the compact [2,E] edge_index (row 0 neighbour, row 1 centre) at
+// out_off[b] + i * k_b.  ptr / out_off are read defensively: rows or edges outside [0,n) / [0,E) are never touched.
+template <int CAND>
+__global__ __launch_bounds__(256) void k_knn_csr(const float* __restrict__ x, const int32_t* __restrict__ ptr, int B, int n, int K,
+                                                 int loop, const int64_t* __restrict__ out_off, long E,
+                                                 int64_t* __restrict__ edge_index) {
+  __shared__ unsigned long long sel_all[4][64], srt_all[4][64];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: the sample search is scalar)
+  unsigned long long* sel = sel_all[w];
+  unsigned long long* srt = srt_all[w];
+  const int r = blockIdx.x * 4 + w;                        // centre: global row
+  if (r >= n) return;
+  int lo = 0, hi = B - 1;                                  // the sample with ptr[b] <= r < ptr[b+1] (empty samples are skipped)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (ptr[mid + 1] <= r) lo = mid + 1; else hi = mid;
+  }
+  const int s0 = ptr[lo], s1 = min(ptr[lo + 1], n);
+  const int nb = s1 - s0, i = r - s0;
+  if (s0 < 0 || i < 0 || i >= nb) return;
+  const int kb = min(K, loop ? nb : nb - 1);
+  if (kb <= 0) return;
+  const long pos = (long)out_off[lo] + (long)i * kb;
+  if (pos < 0 || pos + kb > E) return;
+  const float* xs = x + 3 * (long)s0;
+  const float cx = xs[3 * i], cy = xs[3 * i + 1], cz = xs[3 * i + 2];
+  unsigned chi = ~0u, clo = ~0u;                           // carried key of this lane (none yet)
+  for (int c0 = 0; c0 < nb; c0 += 64 * CAND) {
+    unsigned khi[CAND], klo[CAND];
+#pragma unroll
+    for (int t = 0; t < CAND; ++t) {
+      const int c = c0 + lane + 64 * t;
+      khi[t] = ~0u; klo[t] = ~0u;
+      if (c < nb && (loop || c != i)) {
+        float dx = __fsub_rn(cx, xs[3 * (long)c]), dy = __fsub_rn(cy, xs[3 * (long)c + 1]), dz = __fsub_rn(cz, xs[3 * (long)c + 2]);
+        float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+        khi[t] = __float_as_uint(d2); klo[t] = (unsigned)c;
+      }
+    }
+    // (1) radix select of the k_b-th smallest distance among carried + chunk keys
+    unsigned prefix = 0;
+    int need = kb;
+    for (int bit = 31; bit >= 0; --bit) {
+      int n0 = __builtin_popcountll(__builtin_amdgcn_ballot_w64((chi >> bit) == (prefix >> bit)));
+#pragma unroll
+      for (int t = 0; t < CAND; ++t)
+        n0 += __builtin_popcountll(__builtin_amdgcn_ballot_w64((khi[t] >> bit) == (prefix >> bit)));
+      if (n0 < need) { need -= n0; prefix |= 1u << bit; }
+    }
+    // (2) keys below it, and of those at it the `need` lowest indices: carried keys first, then (t, lane) order
+    int base = 0, ties = 0;
+    auto place = [&](unsigned h, unsigned l) {
+      const bool eq = h == prefix;
+      const unsigned long long meq = __builtin_amdgcn_ballot_w64(eq);
+      const int tie_rank = ties + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(meq >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)meq, 0u));
+      const bool take = h < prefix || (eq && tie_rank < need);
+      const unsigned long long mtk = __builtin_amdgcn_ballot_w64(take);
+      const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mtk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mtk, 0u));
+      if (take && slot < 64) sel[slot] = ((unsigned long long)h << 32) | l;
+      base += __builtin_popcountll(mtk);
+      ties += __builtin_popcountll(meq);
+    };
+    place(chi, clo);
+#pragma unroll
+    for (int t = 0; t < CAND; ++t) place(khi[t], klo[t]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's LDS writes before its reads below (one wave owns the slices)
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // (3) rank the k_b selected keys: lane j carries the j-th smallest into the next chunk
+    if (lane < kb) {
+      const unsigned long long mine = sel[lane];
+      int rank = 0;
+      for (int j = 0; j < kb; ++j) rank += sel[j] < mine ? 1 : 0;
+      srt[rank] = mine;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const unsigned long long s = lane < kb ? srt[lane] : ~0ull;
+    chi = (unsigned)(s >> 32); clo = (unsigned)(s & 0xffffffffull);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // ... and these reads before the next chunk's writes
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (lane < kb) {
+    edge_index[pos + lane] = (int64_t)s0 + (int64_t)clo;
+    edge_index[E + pos + lane] = (int64_t)r;
+  }
 }
 
 // ------------------------------------------------------------------------------ edge weights
@@ -656,6 +755,28 @@ extern "C" int dd_knn_masked(const float* x, int B, int NP, int NL, int K, const
   const int N = NP + NL;
   if (!x || !nbr || !nl_real || B <= 0 || NP < 0 || NL <= 0 || K <= 0 || K > DD_KNN_MAX || K > N - 1 || N > DD_N_MAX) return DD_ERR_BAD_ARG;
   return dd::launch_knn(x, B, N, K, nbr, (hipStream_t)stream, NP, np_real, nl_real);
+}
+
+// ... for a flat PyG batch of different samples (k_knn_csr).  n_max (the largest sample) only picks the chunk size: the
+// candidates are streamed, so every value gives the same result.
+extern "C" int dd_knn_csr(const float* x, const int32_t* ptr, int B, int n, int n_max, int K, int loop, const int64_t* out_off,
+                          int64_t E, int64_t* edge_index, void* stream) {
+  if (!ptr || !out_off || B <= 0 || n < 0 || E < 0 || K <= 0 || (loop != 0 && loop != 1)) return DD_ERR_BAD_ARG;
+  if (K > DD_KNN_MAX) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (n == 0 || E == 0) return DD_OK;
+  if (!x || !edge_index) return DD_ERR_BAD_ARG;
+  const dim3 grid((unsigned)(((long)n + 3) / 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const int cand = (n_max + 63) / 64;
+#define DD_KNN_CSR(C) hipLaunchKernelGGL(dd::k_knn_csr<C>, grid, block, 0, st, x, ptr, B, n, K, loop, out_off, (long)E, edge_index)
+  if (cand <= 2) DD_KNN_CSR(2);
+  else if (cand <= 4) DD_KNN_CSR(4);
+  else if (cand <= 8) DD_KNN_CSR(8);
+  else if (cand <= 16) DD_KNN_CSR(16);
+  else DD_KNN_CSR(DD_N_MAX / 64);
+#undef DD_KNN_CSR
+  DD_CHECK_LAUNCH();
+  return DD_OK;
 }
 
 extern "C" int dd_edge_weights(const float* x, const int32_t* nbr, int B, int N, int K, const float* W1T,

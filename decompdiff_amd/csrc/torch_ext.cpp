@@ -30,6 +30,21 @@ at::Tensor knn(const at::Tensor& x, int64_t k) {
   return nbr;
 }
 
+// torch_geometric.nn.knn_graph on a flat batch of different samples: x [n,3], ptr [B+1] int32 sample offsets, out_off [B+1] int64
+// edge offsets (E = out_off[B], n_max = the largest sample: host values the caller has already) -> edge_index [2,E] int64
+at::Tensor knn_csr(const at::Tensor& x, const at::Tensor& ptr, const at::Tensor& out_off, int64_t E, int64_t n_max, int64_t k, bool loop) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.size(1) == 3, "knn_csr: x must be a [n,3] tensor on a HIP device");
+  TORCH_CHECK(ptr.is_cuda() && ptr.scalar_type() == at::kInt && ptr.is_contiguous() && ptr.numel() >= 2, "knn_csr: int32 ptr [B+1] on HIP");
+  TORCH_CHECK(out_off.is_cuda() && out_off.scalar_type() == at::kLong && out_off.is_contiguous() && out_off.numel() == ptr.numel(),
+              "knn_csr: int64 out_off [B+1] on HIP");
+  TORCH_CHECK(E >= 0, "knn_csr: E < 0");
+  const at::Tensor xc = f32c(x);
+  at::Tensor edge_index = at::empty({2, E}, x.options().dtype(at::kLong));
+  check(dd_knn_csr(fptr(xc), ptr.data_ptr<int32_t>(), (int)(ptr.numel() - 1), (int)x.size(0), (int)n_max, (int)k, loop ? 1 : 0,
+                   out_off.data_ptr<int64_t>(), E, edge_index.data_ptr<int64_t>(), cur_stream(x)), "dd_knn_csr");
+  return edge_index;
+}
+
 // scatter_sum / mean / min / max over dim 0 of [E,F] rows grouped by destination (CSR seg_ptr [n+1] int32); op 0..3
 std::tuple<at::Tensor, at::Tensor> segment_reduce(const at::Tensor& src, const at::Tensor& seg_ptr, int64_t op) {
   TORCH_CHECK(src.is_cuda() && src.dim() == 2 && seg_ptr.is_cuda() && seg_ptr.scalar_type() == at::kInt, "segment_reduce: [E,F] fp32 + int32 seg_ptr on HIP");
@@ -83,6 +98,7 @@ at::Tensor attn_aggregate_pos(const at::Tensor& q, const at::Tensor& k, const at
 
 TORCH_LIBRARY(decompdiff_hip, m) {
   m.def("knn(Tensor x, int k) -> Tensor");
+  m.def("knn_csr(Tensor x, Tensor ptr, Tensor out_off, int E, int n_max, int k, bool loop) -> Tensor");
   m.def("segment_reduce(Tensor src, Tensor seg_ptr, int op) -> (Tensor, Tensor)");
   m.def("segment_softmax(Tensor src, Tensor seg_ptr) -> Tensor");
   m.def("attn_aggregate_node(Tensor q, bool q_per_edge, Tensor k, Tensor v, Tensor? e_w, Tensor seg_ptr) -> Tensor");
@@ -92,6 +108,7 @@ TORCH_LIBRARY(decompdiff_hip, m) {
 
 TORCH_LIBRARY_IMPL(decompdiff_hip, CUDA, m) {     // (the CUDA dispatch key is the HIP device on a ROCm build)
   m.impl("knn", &knn);
+  m.impl("knn_csr", &knn_csr);
   m.impl("segment_reduce", &segment_reduce);
   m.impl("segment_softmax", &segment_softmax);
   m.impl("attn_aggregate_node", &attn_aggregate_node);

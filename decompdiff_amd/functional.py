@@ -49,23 +49,35 @@ def knn_graph(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
               flow: str = "source_to_target") -> torch.Tensor:
     """``edge_index [2,E]`` (row 0 = neighbour / source, row 1 = centre / target), grouped by centre in ascending
     order, neighbours by ascending distance, self loops excluded, candidates restricted to the same ``batch`` id — the
-    order torch_cluster returns.  Samples must be contiguous and of equal size (PyG ``Batch`` of one pocket); a sample
-    with fewer than ``k`` other atoms contributes all of them."""
-    if flow != "source_to_target" or loop:
-        raise NotImplementedError("knn_graph: flow='source_to_target', loop=False (the reference's call)")
+    order torch_cluster returns.  ``batch`` must be sorted (torch_cluster requires that too); the samples may have any
+    sizes and ids may be missing -- a PyG ``Batch`` of different complexes (``dd_knn_csr``); equal counts of at most 2048
+    atoms take the dense kernel (``dd_knn``), with the same result.  A sample with fewer than ``k`` other atoms
+    contributes all of them.  ``loop=True`` makes the centre a candidate of its own list;
+    ``flow='target_to_source'`` swaps the two rows, as torch_geometric does."""
+    if flow not in ("source_to_target", "target_to_source"):
+        raise ValueError(f"knn_graph: flow '{flow}'")
     hip_lib.require_gpu(x, "x")
-    n = x.size(0)
+    if x.dim() != 2 or x.size(1) != 3:
+        raise ValueError("knn_graph: x must be [n,3]")
+    n, k, dev = x.size(0), int(k), x.device
+    swap = (lambda e: e.flip(0)) if flow == "target_to_source" else (lambda e: e)
+    if n == 0 or k <= 0:
+        return torch.empty(2, 0, dtype=torch.long, device=dev)
+    dense = not loop
     if batch is None:
         B, N = 1, n
     else:
+        if batch.dim() != 1 or batch.numel() != n:
+            raise ValueError("knn_graph: batch must have one entry per row of x")
         B = int(batch.max().item()) + 1
         N = n // B
-        if n % B or not torch.equal(batch, torch.arange(B, device=x.device).repeat_interleave(N)):
-            raise NotImplementedError("knn_graph: batch must be sorted with equal counts per sample")
-    kk = min(int(k), N - 1)
-    if kk <= 0:
-        return torch.empty(2, 0, dtype=torch.long, device=x.device)
+        dense = dense and n % B == 0 and torch.equal(batch, torch.arange(B, device=dev).repeat_interleave(N))
     xc = x.detach().to(torch.float32).contiguous()
+    if not dense or N > 2048:
+        return swap(_knn_graph_csr(xc, k, batch, B, loop))
+    kk = min(k, N - 1)
+    if kk <= 0:
+        return torch.empty(2, 0, dtype=torch.long, device=dev)
     ext = torch_ext()
     if ext is not None:
         nbr = ext.knn(xc.view(B, N, 3), kk)
@@ -75,7 +87,34 @@ def knn_graph(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
     base = (torch.arange(B, device=x.device) * N).view(B, 1, 1)
     src = (nbr.long() + base).reshape(-1)
     dst = torch.arange(n, device=x.device).repeat_interleave(kk)
-    return torch.stack([src, dst], 0)
+    return swap(torch.stack([src, dst], 0))
+
+
+def _knn_graph_csr(xc: torch.Tensor, k: int, batch: Optional[torch.Tensor], B: int, loop: bool) -> torch.Tensor:
+    """``edge_index`` of a flat batch with any count per sample (dd_knn_csr): sample offsets and the edge prefix sums are
+    made here (one device -> host copy for E and the largest sample), the kernel writes global int64 rows."""
+    n, dev = xc.size(0), xc.device
+    if batch is None:
+        counts = torch.tensor([n], device=dev)
+    else:
+        if batch.numel() > 1 and bool((batch[1:] < batch[:-1]).any().item()):
+            raise NotImplementedError("knn_graph: batch must be sorted (non-decreasing), as torch_cluster requires")
+        counts = torch.bincount(batch, minlength=B)
+    if k > 64:
+        raise NotImplementedError("knn_graph: k <= 64 (DD_KNN_MAX)")
+    kb = (counts - (0 if loop else 1)).clamp(min=0, max=k)
+    ptr = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    ptr[1:] = counts.cumsum(0)
+    out_off = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    out_off[1:] = (counts * kb).cumsum(0)
+    E, n_max = torch.stack([out_off[-1], counts.max()]).tolist()
+    ext = torch_ext()
+    if ext is not None:
+        return ext.knn_csr(xc, ptr, out_off, E, n_max, k, bool(loop))
+    edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
+    hip_lib.check(hip_lib.load().dd_knn_csr(hip_lib.ptr(xc), hip_lib.ptr(ptr), B, n, n_max, k, int(bool(loop)), hip_lib.ptr(out_off), E,
+                                            hip_lib.ptr(edge_index), hip_lib.stream_ptr(dev)), "dd_knn_csr")
+    return edge_index
 
 
 def _seg_ptr(index: torch.Tensor, dim_size: int) -> torch.Tensor:

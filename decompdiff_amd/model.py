@@ -366,34 +366,28 @@ class DecompScorePosNet3D(nn.Module):
         return self._sample_ragged(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
                                    use_graph, start_step=start_step)
 
-    def _sample_padded(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, start_step, n_p, n_l):
-        """Heterogeneous batch as one padded dense batch: every sample's atoms are the first rows of its [NPmax] / [NLmax]
-        blocks, the kernels read the real counts from dd_sampler.np_real / nl_real (padding atoms are no kNN candidates,
-        own no softmax segment and are no members of one) and the results are gathered back into the caller's flat order.
-        Exact: a sample's chain does not depend on its batch, with the one batch-wide quantity of the reference -- the
-        armsca loss is averaged over the whole batch (guidance_funcs.py:78) -- unchanged because the batch is whole."""
-        _check_ligand_atom_mask(ligand_atom_mask, kw["batch_ligand"].numel())
-        dev = kw["protein_pos"].device
-        hip_lib.require_gpu(kw["protein_pos"], "protein_pos")
-        hip_lib.require_gpu(kw["init_ligand_pos"], "init_ligand_pos")
-        bp, bl, bpr = kw["batch_protein"], kw["batch_ligand"], kw["batch_prior"]
-        for name, t in (("batch_protein", bp), ("batch_ligand", bl), ("batch_prior", bpr)):
+    def _padded_inputs(self, protein_pos, protein_v, bp, ligand_pos, ligand_v, aux, bl, fc_index, bond_type, batch_ligand_bond,
+                       n_p, n_l, center_pos_mode):
+        """A validated heterogeneous flat batch (n_p / n_l: atoms per sample) as the padded dense layout of dd_sampler.np_real /
+        nl_real / bl_prefix: every sample's atoms are the first rows of its [NPmax] / [NLmax] blocks, its bonds the dst-major
+        rows of its [NLmax (NLmax - 1)] block; padding rows are zeros.  Shared by the padded sampler and the ragged forward.
+        Returns the dense dict `d` of _make_sampler (positions centred by `center_pos_mode`), the per-sample offset, the
+        masks and the row maps flat row -> padded row (rows_* on the host, d_* on the device)."""
+        dev = protein_pos.device
+        hip_lib.require_gpu(protein_pos, "protein_pos")
+        hip_lib.require_gpu(ligand_pos, "init_ligand_pos")
+        for name, t in (("batch_protein", bp), ("batch_ligand", bl)):
             if t.numel() > 1 and bool((t[1:] < t[:-1]).any().item()):
                 raise NotImplementedError(f"{name} must be sorted (PyG Batch order)")
         B = len(n_p)
         NP, NL = max(n_p), max(n_l)
         Eb = NL * (NL - 1)
         n_b = [n * (n - 1) for n in n_l]
-        if kw["ligand_fc_bond_index"] is None or kw["init_ligand_fc_bond_type"] is None:
+        if fc_index is None or bond_type is None:
             raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
         cnt = lambda t: torch.bincount(t.cpu(), minlength=B).tolist()
-        if kw["init_ligand_fc_bond_type"].numel() != sum(n_b) or \
-                (kw["batch_ligand_bond"] is not None and cnt(kw["batch_ligand_bond"]) != n_b):
+        if bond_type.numel() != sum(n_b) or (batch_ligand_bond is not None and cnt(batch_ligand_bond) != n_b):
             raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
-        has_full = kw["full_protein_pos"] is not None and kw["full_batch_protein"] is not None
-        n_f = cnt(kw["full_batch_protein"]) if has_full else [0] * B
-        NF = max(n_f) if has_full else 0
         ar = torch.arange
         # flat (caller) row -> padded row
         rows_p = torch.cat([b * NP + ar(n_p[b]) for b in range(B)])
@@ -408,33 +402,63 @@ class DecompScorePosNet3D(nn.Module):
             exp_fc.append(torch.stack([src, dst], 0) + o_l[b])
             rows_b.append(b * Eb + dst * (NL - 1) + sp)
         exp_fc, rows_b = torch.cat(exp_fc, 1), torch.cat(rows_b)
-        if kw["ligand_fc_bond_index"].shape != exp_fc.shape or not torch.equal(kw["ligand_fc_bond_index"].cpu(), exp_fc):
+        if fc_index.shape != exp_fc.shape or not torch.equal(fc_index.cpu(), exp_fc):
             raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
         d_p, d_l, d_b = rows_p.to(dev), rows_l.to(dev), rows_b.to(dev)
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
-        protein_v, ligand_v, aux = kw["protein_v"], kw["init_ligand_v"], kw["ligand_v_aux"]
         if protein_v.dim() != 2 or protein_v.shape[1] != 29 or aux.dim() != 2 or aux.shape[1] != 2:
             raise ValueError("protein_v must be [n,29] and ligand_v_aux [n,2]")
         assert int(ligand_v.min()) >= 0 and int(ligand_v.max()) < self.num_classes, f"Error: {int(ligand_v.max())} >= {self.num_classes}"
-        bt = kw["init_ligand_fc_bond_type"]
+        bt = bond_type
         assert int(bt.min()) >= 0 and int(bt.max()) < self.num_bond_classes, f"Error: {int(bt.max())} >= {self.num_bond_classes}"
         # center_pos (decompdiff.py:20-32): per-sample mean of the REAL protein atoms, fp32 in row order (as the dense path)
         if center_pos_mode == "protein":
-            tot = torch.zeros(B, 3).index_add_(0, bp.cpu(), kw["protein_pos"].detach().float().cpu())
+            tot = torch.zeros(B, 3).index_add_(0, bp.cpu(), protein_pos.detach().float().cpu())
             offset = (tot / torch.tensor(n_p, dtype=torch.float32).clamp(min=1).view(B, 1)).to(dev)
         elif center_pos_mode == "none":
             offset = torch.zeros(B, 3, device=dev)
         else:
             raise NotImplementedError(center_pos_mode)
         zeros = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
-        ppos = zeros(B * NP, 3).index_copy_(0, d_p, f32(kw["protein_pos"]) - offset[bp.to(dev)])
-        lpos = zeros(B * NL, 3).index_copy_(0, d_l, f32(kw["init_ligand_pos"]) - offset[bl.to(dev)])
+        ppos = zeros(B * NP, 3).index_copy_(0, d_p, f32(protein_pos) - offset[bp.to(dev)])
+        lpos = zeros(B * NL, 3).index_copy_(0, d_l, f32(ligand_pos) - offset[bl.to(dev)])
         d = dict(B=B, NP=NP, NL=NL, protein_pos=ppos.view(B, NP, 3), ligand_pos=lpos.view(B, NL, 3),
                  protein_pos_centered=ppos.view(B, NP, 3), ligand_pos_centered=lpos.view(B, NL, 3),
                  protein_v=zeros(B * NP, 29).index_copy_(0, d_p, f32(protein_v)).view(B, NP, 29),
                  ligand_v=zeros(B * NL, dtype=torch.int32).index_copy_(0, d_l, ligand_v.to(device=dev, dtype=torch.int32)),
                  ligand_aux=zeros(B * NL, 2).index_copy_(0, d_l, f32(aux)).view(B, NL, 2),
                  bond=zeros(B * Eb, dtype=torch.int32).index_copy_(0, d_b, bt.to(device=dev, dtype=torch.int32)))
+        prefix = np.concatenate([[0], np.cumsum(n_b)]).astype(np.int32)
+        masks = {"np_real": torch.tensor(n_p, dtype=torch.int32), "nl_real": torch.tensor(n_l, dtype=torch.int32),
+                 "bl_prefix": torch.from_numpy(prefix)}
+        return dict(d=d, offset=offset, masks=masks, n_b=n_b, rows_l=rows_l, rows_b=rows_b, d_l=d_l, d_b=d_b)
+
+    def _sample_padded(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
+                       use_graph, start_step, n_p, n_l):
+        """Heterogeneous batch as one padded dense batch: every sample's atoms are the first rows of its [NPmax] / [NLmax]
+        blocks, the kernels read the real counts from dd_sampler.np_real / nl_real (padding atoms are no kNN candidates,
+        own no softmax segment and are no members of one) and the results are gathered back into the caller's flat order.
+        Exact: a sample's chain does not depend on its batch, with the one batch-wide quantity of the reference -- the
+        armsca loss is averaged over the whole batch (guidance_funcs.py:78) -- unchanged because the batch is whole."""
+        _check_ligand_atom_mask(ligand_atom_mask, kw["batch_ligand"].numel())
+        bpr = kw["batch_prior"]
+        if bpr.numel() > 1 and bool((bpr[1:] < bpr[:-1]).any().item()):
+            raise NotImplementedError("batch_prior must be sorted (PyG Batch order)")
+        pad = self._padded_inputs(kw["protein_pos"], kw["protein_v"], kw["batch_protein"], kw["init_ligand_pos"], kw["init_ligand_v"],
+                                  kw["ligand_v_aux"], kw["batch_ligand"], kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"],
+                                  kw["batch_ligand_bond"], n_p, n_l, center_pos_mode)
+        d, offset, masks, n_b = pad["d"], pad["offset"], pad["masks"], pad["n_b"]
+        rows_l, rows_b, d_l, d_b = pad["rows_l"], pad["rows_b"], pad["d_l"], pad["d_b"]
+        B, NP, NL = d["B"], d["NP"], d["NL"]
+        Eb = NL * (NL - 1)
+        dev = d["protein_pos"].device
+        ar = torch.arange
+        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
+        zeros = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
+        cnt = lambda t: torch.bincount(t.cpu(), minlength=B).tolist()
+        has_full = kw["full_protein_pos"] is not None and kw["full_batch_protein"] is not None
+        n_f = cnt(kw["full_batch_protein"]) if has_full else [0] * B
+        NF = max(n_f) if has_full else 0
         atom_std = zeros(B * NL, 3).index_copy_(0, d_l, f32(kw["prior_stds"])[kw["ligand_decomp_batch"].to(dev)])
         decomp = None
         if kw["ligand_decomp_index"] is not None:                          # -2: neither arm nor scaffold (padding)
@@ -457,9 +481,6 @@ class DecompScorePosNet3D(nn.Module):
                 "u_v": torch.full((num_steps, B * NL, self.num_classes), 0.5, device=dev).index_copy_(1, d_l, f32(noise["u_v"])),
                 "u_b": torch.full((num_steps, B * Eb, 5), 0.5, device=dev).index_copy_(1, d_b, f32(noise["u_b"])),
                 "eps": zeros(num_steps, B * NL, 3).index_copy_(1, d_l, f32(noise["eps"]))}
-        prefix = np.concatenate([[0], np.cumsum(n_b)]).astype(np.int32)
-        masks = {"np_real": torch.tensor(n_p, dtype=torch.int32), "nl_real": torch.tensor(n_l, dtype=torch.int32),
-                 "bl_prefix": torch.from_numpy(prefix)}
         if num_steps + start_step > self.num_timesteps or start_step < 0:
             raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
         pw = self._packed_weights()
@@ -882,6 +903,72 @@ class DecompScorePosNet3D(nn.Module):
         return {k: int(pw["offsets"][n + i]) for i, k in enumerate(packing.GLOBAL_SLOTS)}
 
     # ------------------------------------------------------------------------------------------
+    def _forward_heterogeneous(self, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, ligand_v_aux, batch_ligand,
+                               ligand_fc_bond_index, ligand_bond_type, ligand_atom_mask):
+        """forward() on samples with different atom counts (the same two ways as `_sample_heterogeneous`): one padded
+        dd_forward_ex with per-sample real counts, or one dense forward per group of equal sizes."""
+        hip_lib.require_gpu(protein_pos, "protein_pos")
+        hip_lib.require_gpu(ligand_pos, "init_ligand_pos")
+        _check_ligand_atom_mask(ligand_atom_mask, batch_ligand.numel())
+        if ligand_fc_bond_index is None or ligand_bond_type is None:
+            raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
+        dev = protein_pos.device
+        for name, t in (("batch_protein", batch_protein), ("batch_ligand", batch_ligand)):
+            if t.numel() > 1 and bool((t[1:] < t[:-1]).any().item()):
+                raise NotImplementedError(f"{name} must be sorted (PyG Batch order)")
+        B = int(batch_protein.max().item()) + 1
+        n_p = torch.bincount(batch_protein, minlength=B).tolist()
+        n_l = torch.bincount(batch_ligand, minlength=B).tolist()
+        if len(n_l) != B or min(n_p) < 1 or min(n_l) < 2:
+            raise NotImplementedError("every sample needs protein atoms and at least 2 ligand atoms")
+        if max(n_l) > 128:
+            raise NotImplementedError(f"ligand size {max(n_l)} outside the supported range [2, 128]")
+        if max(a + b for a, b in zip(n_p, n_l)) > 2048:
+            raise NotImplementedError("more than 2048 atoms per sample")
+        fits = min(a + b for a, b in zip(n_p, n_l)) - 1 >= int(self.config.knn) and max(n_p) + max(n_l) <= 2048
+        if os.environ.get("DD_RAGGED_MODE", "padded") != "groups" and fits:
+            pad = self._padded_inputs(protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, ligand_v_aux, batch_ligand,
+                                      ligand_fc_bond_index, ligand_bond_type, None, n_p, n_l, "none")
+            d, d_l, d_b = pad["d"], pad["d_l"], pad["d_b"]
+            NL = d["NL"]
+            pw = self._packed_weights()
+            s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, torch.ones(B * NL, 3, device=dev),
+                                            torch.zeros(B, 3, device=dev), None, None, 0, masks=pad["masks"])
+            hip_lib.check(hip_lib.load().dd_forward_ex(ctypes.byref(s), self._bond_head(pw), hip_lib.stream_ptr(dev)), "dd_forward")
+            _check_queue(s, dev)
+            preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3).index_select(0, d_l),
+                     "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes).index_select(0, d_l)}
+            if self.bond_diffusion:
+                preds["pred_bond"] = bufs["pred_bond"].index_select(0, d_b)
+            self._last = (s, bufs)
+            return preds
+        # one dense forward per group of equal (protein, ligand) sizes, rows put back in the caller's order
+        o_p, o_l = [0] + list(np.cumsum(n_p)), [0] + list(np.cumsum(n_l))
+        n_b = [n * (n - 1) for n in n_l]
+        o_b = [0] + list(np.cumsum(n_b))
+        if ligand_bond_type.numel() != o_b[-1] or ligand_fc_bond_index.shape != (2, o_b[-1]):
+            raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
+        groups: Dict[tuple, list] = {}
+        for b in range(B):
+            groups.setdefault((n_p[b], n_l[b]), []).append(b)
+        out = {"pred_ligand_pos": torch.empty(o_l[-1], 3, device=dev), "pred_ligand_v": torch.empty(o_l[-1], self.num_classes, device=dev)}
+        if self.bond_diffusion:
+            out["pred_bond"] = torch.empty(o_b[-1], 5, device=dev)
+        rng = lambda o, c, ids: torch.cat([torch.arange(o[b], o[b] + c[b]) for b in ids]).to(dev)
+        for (np_, nl_), ids in groups.items():
+            G = len(ids)
+            r_p, r_l, r_b = rng(o_p, n_p, ids), rng(o_l, n_l, ids), rng(o_b, n_b, ids)
+            ar = lambda n: torch.arange(G, device=dev).repeat_interleave(n)
+            old0 = torch.tensor([o_l[b] for b in ids], device=dev).repeat_interleave(nl_ * (nl_ - 1))
+            new0 = (torch.arange(G, device=dev) * nl_).repeat_interleave(nl_ * (nl_ - 1))
+            fc = ligand_fc_bond_index.to(dev)[:, r_b] - old0[None, :] + new0[None, :]       # (validated by the dense call)
+            r = self.forward(protein_pos[r_p], protein_v[r_p], ar(np_), None, ligand_pos[r_l], ligand_v[r_l], ligand_v_aux[r_l],
+                             ar(nl_), None, None, None, None, None, fc, ligand_bond_type[r_b])
+            out["pred_ligand_pos"][r_l], out["pred_ligand_v"][r_l] = r["pred_ligand_pos"], r["pred_ligand_v"]
+            if self.bond_diffusion:
+                out["pred_bond"][r_b] = r["pred_bond"]
+        return out
+
     def forward(self, protein_pos, protein_v, batch_protein, protein_group_idx,
                 init_ligand_pos, init_ligand_v, init_ligand_v_aux, batch_ligand, ligand_group_idx,
                 prior_centers, prior_stds, batch_prior, prior_group_idx,
@@ -889,10 +976,22 @@ class DecompScorePosNet3D(nn.Module):
                 ligand_atom_mask=None, time_step=None, return_all=False):
         """Score network once (reference: models/decompdiff.py:213-351).  ``time_step``, the group
         indices and the prior tensors are accepted for signature compatibility; the shipped
-        configuration never reads them (time_emb_dim=0, add_prior_node=False)."""
+        configuration never reads them (time_emb_dim=0, add_prior_node=False).
+
+        A batch whose samples differ in size (a PyG ``Batch`` of different complexes, sorted batch vectors, per-sample
+        dst-major fully connected bond lists) is accepted: it runs as ONE launch sequence over the batch padded to its
+        largest pocket / ligand with the real counts in ``dd_sampler.np_real / nl_real / bl_prefix`` (the layer-0 tables,
+        which need a dense batch, are off for that call), or -- ``DD_RAGGED_MODE=groups``, or a sample with fewer than
+        ``knn + 1`` atoms -- as one dense call per group of equal sizes.  Either way the predictions cover the real atoms
+        and bonds only, in the flat order of the inputs.  ``ligand_atom_mask``: None or an all-True mask, as in
+        :meth:`sample_diffusion`."""
         if return_all:
             raise NotImplementedError("return_all (per-block intermediates) is a training-time option")
         with torch.no_grad():
+            if self._is_ragged(batch_protein, batch_ligand):
+                return self._forward_heterogeneous(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
+                                                   init_ligand_v_aux, batch_ligand, ligand_fc_bond_index,
+                                                   init_ligand_fc_bond_type, ligand_atom_mask)
             d = self._dense_inputs(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
                                    init_ligand_v_aux, batch_ligand, ligand_fc_bond_index, init_ligand_fc_bond_type,
                                    ligand_atom_mask)

@@ -194,6 +194,18 @@ int dd_knn(const float* x /*[B,N,3]*/, int B, int N, int K, int32_t* nbr /*[B,N,
  * padding centre is zeros.  Every sample needs at least K + 1 real atoms.  (Round 5: the padded training network.) */
 int dd_knn_masked(const float* x /*[B,NP+NL,3]*/, int B, int NP, int NL, int K, const int32_t* np_real, const int32_t* nl_real,
                   int32_t* nbr /*[B,NP+NL,K]*/, void* stream);
+/* torch_geometric.nn.knn_graph(x, k, batch, loop) on a flat PyG batch of DIFFERENT samples (the reference's loader collates
+ * different complexes, utils/data.py:389-446): sample b owns rows ptr[b] .. ptr[b+1]-1 of x (ptr[0] = 0, non-decreasing,
+ * ptr[B] = n; any count per sample, 0, 1 and more than DD_N_MAX included).  Its centres get k_b = min(K, n_b - 1) neighbours
+ * (loop = 1: the centre is a candidate itself, k_b = min(K, n_b)), in the order of dd_knn -- a dense batch gives dd_knn's lists.
+ * out_off[b] = sum over b' < b of n_b' * k_b' and E = out_off[B] (host prefix sums; device pointers like ptr).  The kernel writes
+ * GLOBAL row ids as int64 into the compact edge_index [2,E]: row 0 the neighbour, row 1 the centre; edges grouped by centre in
+ * ascending row order.  One wave per centre streams the sample's rows in chunks of at most DD_N_MAX and carries the k_b best keys
+ * between chunks: exact for every size.  n_max = the largest n_b (picks the chunk size only; any value gives the same result).
+ * Rows outside [0,n) and edges outside [0,E) are never touched, whatever ptr / out_off hold.  K <= DD_KNN_MAX.
+ * (New entry point, ABI unchanged.) */
+int dd_knn_csr(const float* x /*[n,3]*/, const int32_t* ptr /*[B+1]*/, int B, int n, int n_max, int K, int loop,
+               const int64_t* out_off /*[B+1]*/, int64_t E, int64_t* edge_index /*[2,E]*/, void* stream);
 
 /* e_w = sigmoid(MLP(GaussianSmearing(dist)))  (uni_transformer_edge.py:422-427). */
 int dd_edge_weights(const float* x, const int32_t* nbr, int B, int N, int K, const float* W1T /*[20,128]*/,
