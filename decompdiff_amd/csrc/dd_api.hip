@@ -572,9 +572,23 @@ static int forward_tail(const dd_sampler* s, hipStream_t st, StepFold* fold, boo
 
 #endif
 
-static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nullptr, const dd_bond_head* bh = nullptr) {
+// Node output MLPs (x2h_out_fc; include/decompdiff_hip.h dd_node_out): NULL = a model without them
+static int check_node_out(const dd_node_out* no, const dd_sampler* s) {
+  if (no == nullptr) return DD_OK;
+  if (!s || no->num_layers != s->num_layers || no->num_layers < 1 || no->num_layers > 64) return DD_ERR_BAD_ARG;
+  for (int l = 0; l < no->num_layers; ++l)
+    if (!no->layer[l] || (reinterpret_cast<size_t>(no->layer[l]) & 15) != 0) return DD_ERR_BAD_ARG;
+  return DD_OK;
+}
+
+static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nullptr, const dd_bond_head* bh = nullptr,
+                        const dd_node_out* no = nullptr) {
   DD_TRY(check_shapes(s));
+  DD_TRY(check_node_out(no, s));
   const bool pre_att = is_pre_att(bh);
+  // x2h_out_fc: k_node_out_fc (node output MLPs + lin_node, one launch) takes the place of the lin_node GEMM job; the node
+  // launch's in-kernel lin_node has no node-output stage, so lin_in_node is off for such a model
+  const bool out_fc = no != nullptr;
   const int B = s->B, NP = s->NP, NL = s->NL, K = s->K, N = NP + NL;
   const long Eb = (long)NL * (NL - 1);
   Workspace w = carve(s->workspace, B, NP, NL, K);
@@ -590,10 +604,12 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   const bool fused = g_fuse && NL <= g_fused_max_nl && g_dbg_clock == nullptr;
   const bool overlap = fused && g_overlap && g_prof == nullptr && s->num_layers <= 8;
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
+  if (out_fc && (g_sched >= 5 || g_side_lin)) return DD_ERR_UNSUPPORTED_SHAPE;   // (measurement schedules without the node-output stage)
   if (fused && !pre_att && g_sched >= 5 && s->num_layers <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
       g_xup_in_asm && !g_xup_in_pos)
     return forward_tail(s, st, fold, overlap);
 #endif
+  if (out_fc && !fused) return DD_ERR_UNSUPPORTED_SHAPE;   // (the one-launch-per-sub-layer loop has no node-output stage)
   if (overlap) DD_TRY(ensure_side_stream());
 
   // layer-0 tables: the first layer's projection and query rows are gathered (ligand atoms: 16 combinations of class and
@@ -674,7 +690,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     // lin_node inside the node launch (g_lin_in_node): the NE blocks update h in place, the NB blocks leave W_lin . A_nb of this
     // layer in anb_cur (ping-pong between w.Anb and w.A, which no longer holds the attention output); every consumer of the new h
     // adds it to the ligand rows (GemmArgs::X2) and the next layer's NE blocks fold it into h
-    const bool lin_in_node = lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early;
+    const bool lin_in_node = !out_fc && lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early;
     float* const anb_cur = (l & 1) ? w.A : w.Anb;
     const float* const anb_prev = (lin_in_node && l > 0) ? ((l & 1) ? w.Anb : w.A) : nullptr;
     auto add_anb = [&](GemmArgs& g, bool all_nodes) {     // X rows of g: all nodes of the batch / the ligand rows only
@@ -788,7 +804,11 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     const bool side_lin = g_side_lin && ahead_split && ahead_b2 && l + 1 < s->num_layers;
     float* const hold = hcur;
     GemmArgs lin_dup;
-    if (!lin_in_node) {
+    if (out_fc) {
+      // the jobs that ride with the lin_node GEMM (PB2, next layer's PB) ride with the projections behind this launch instead
+      NodeOutArgs na{w.A, w.Anb, hcur, hcur, no->layer[l], B, NP, NL};
+      DD_TRYP(DD_PROF_GEMM, launch_node_out_fc(na, st));
+    } else if (!lin_in_node) {
       GemmArgs g = gemm_args(w.A, B * N, 0, 128, B * N, LW(l, DD_W_lin), LW(l, DD_b_lin), nullptr, hcur, B * N, 0, 128, 128, 1);
       g.X2 = w.Anb; g.x2_N = N; g.x2_NP = NP;
       if (side_lin) {
@@ -854,7 +874,18 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     // workgroups wait for the first two, the heads' tiles trail behind them
     bool p2_in_pos = g_p2_in_pos && g_lin_with_pb2 && g_q_in_pos && !g_xup_in_pos && g_pos_waves == 4 && NL <= 65 && l < 64 &&
                      !(overlap && !ahead);
-    if (lin_in_node) {
+    if (out_fc) {
+      // {P2, PL2} of the new h, the coordinate sub-layer's bond projections, the heads' first Linear (last layer) or the next
+      // layer's bond projections where they would have shared the lin_node launch: one launch, at most five jobs
+      p2_in_pos = false;
+      p2x[p2xn++] = p2j[0];
+      p2x[p2xn++] = p2j[1];
+      p2x[p2xn++] = gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0);
+      if (p2n == 4) { p2x[p2xn++] = p2j[2]; p2x[p2xn++] = p2j[3]; }
+      if (pb_early && g_lin_with_pb2 && l + 1 < s->num_layers)
+        p2x[p2xn++] = gemm_args(w.hb, nE, 0, 128, nE, LW(l + 1, DD_W_b1), LW(l + 1, DD_b_b1), nullptr, w.PB, nE, 0, 640, 640, 0);
+      DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(p2x, p2xn, st));
+    } else if (lin_in_node) {
       p2_in_pos = false;
       DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(p2x, p2xn, st));
       if (proj_main && l + 1 < s->num_layers && hipEventRecord(g_ev_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // P, PL of the next layer
@@ -1015,7 +1046,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
         gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, GW(DD_G_VH_W1), GW(DD_G_VH_b1), nullptr, w.qn, B * NL, 0, 128, 128, 0)};
     if (pre_att)
       j[0] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, bh->W_p, nullptr, nullptr, w.P, B * NL, 0, 128, 128, 0);
-    if (fused && lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early) {   // (lin_in_node: the last layer's W_lin . A_nb is pending)
+    if (fused && !out_fc && lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early) {   // (lin_in_node: the last layer's W_lin . A_nb is pending)
       j[1].X2 = ((s->num_layers - 1) & 1) ? w.A : w.Anb; j[1].x2_N = NL; j[1].x2_NP = 0;
       if (pre_att) { j[0].X2 = j[1].X2; j[0].x2_N = NL; j[0].x2_NP = 0; }
     }
@@ -1275,11 +1306,13 @@ extern "C" int dd_workspace_view(const dd_sampler* s, dd_ws_view* out) {
 
 extern "C" int dd_forward(const dd_sampler* s, void* stream) { return dd_forward_ex(s, nullptr, stream); }
 
-extern "C" int dd_forward_ex(const dd_sampler* s, const dd_bond_head* bh, void* stream) {
+extern "C" int dd_forward_ex(const dd_sampler* s, const dd_bond_head* bh, void* stream) { return dd_forward_ex2(s, bh, nullptr, stream); }
+
+extern "C" int dd_forward_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   int rc = dd::check_bond_head(bh);
   if (rc != DD_OK) return rc;
-  rc = dd::forward_impl(s, st, nullptr, bh);
+  rc = dd::forward_impl(s, st, nullptr, bh, no);
   if (rc != DD_OK) return rc;
   if (!s->pred_pos || !s->pred_v || !s->pred_bond) return DD_ERR_BAD_ARG;
   dd::Workspace w = dd::carve(s->workspace, s->B, s->NP, s->NL, s->K);
@@ -1472,10 +1505,10 @@ extern "C" int dd_debug_node_split_cache_path(char* out, int cap) {
   return DD_OK;
 }
 
-static int one_step(const dd_sampler* s, hipStream_t st, const dd_bond_head* bh = nullptr) {
+static int one_step(const dd_sampler* s, hipStream_t st, const dd_bond_head* bh = nullptr, const dd_node_out* no = nullptr) {
   dd::StepFold fold;
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
-  int rc = dd::forward_impl(s, st, &fold, bh);
+  int rc = dd::forward_impl(s, st, &fold, bh, no);
   if (rc != DD_OK) return rc;
   return dd::heads_and_step(s, st, &fold);
 }
@@ -1492,13 +1525,17 @@ extern "C" int dd_reverse_step(const dd_sampler* s, const float* logits_v, const
 extern "C" int dd_sample_steps(const dd_sampler* s, int n_steps, void* stream) { return dd_sample_steps_ex(s, nullptr, n_steps, stream); }
 
 extern "C" int dd_sample_steps_ex(const dd_sampler* s, const dd_bond_head* bh, int n_steps, void* stream) {
-  if (dd::check_bond_head(bh) != DD_OK) return DD_ERR_BAD_ARG;
+  return dd_sample_steps_ex2(s, bh, nullptr, n_steps, stream);
+}
+
+extern "C" int dd_sample_steps_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int n_steps, void* stream) {
+  if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
   if (!s || n_steps < 0 || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
       !s->pred_pos)
     return DD_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_steps; ++i) {
-    int rc = one_step(s, st, bh);
+    int rc = one_step(s, st, bh, no);
     if (rc != DD_OK) return rc;
   }
   return DD_OK;
@@ -1509,7 +1546,11 @@ extern "C" int dd_sample_steps_graph(const dd_sampler* s, int n_steps, void* str
 }
 
 extern "C" int dd_sample_steps_graph_ex(const dd_sampler* s, const dd_bond_head* bh, int n_steps, void* stream) {
-  if (dd::check_bond_head(bh) != DD_OK) return DD_ERR_BAD_ARG;
+  return dd_sample_steps_graph_ex2(s, bh, nullptr, n_steps, stream);
+}
+
+extern "C" int dd_sample_steps_graph_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int n_steps, void* stream) {
+  if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
   if (!s || n_steps < 0 || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
       !s->pred_pos)
     return DD_ERR_BAD_ARG;
@@ -1527,7 +1568,7 @@ extern "C" int dd_sample_steps_graph_ex(const dd_sampler* s, const dd_bond_head*
     (void)hipGetLastError();                     // do not leave a sticky error behind for the caller
     return DD_ERR_HIP;
   }
-  rc = one_step(s, st, bh);
+  rc = one_step(s, st, bh, no);
   hipError_t e = hipStreamEndCapture(st, &graph);
   capture_lock.unlock();
   if (rc != DD_OK || e != hipSuccess || !graph) {
@@ -1558,7 +1599,12 @@ extern "C" int dd_graph_create(const dd_sampler* s, int steps_per_graph, void* s
 }
 
 extern "C" int dd_graph_create_ex(const dd_sampler* s, const dd_bond_head* bh, int steps_per_graph, void* stream, void** graph_out) {
-  if (dd::check_bond_head(bh) != DD_OK) return DD_ERR_BAD_ARG;
+  return dd_graph_create_ex2(s, bh, nullptr, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_graph_create_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int steps_per_graph, void* stream,
+                                   void** graph_out) {
+  if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
   if (!s || !graph_out || steps_per_graph < 1 || steps_per_graph > 64 || !s->step_counter || !s->tab_pos || !s->tab_v ||
       !s->tab_b || !s->atom_std || !s->offset || !s->pred_pos)
     return DD_ERR_BAD_ARG;
@@ -1575,7 +1621,7 @@ extern "C" int dd_graph_create_ex(const dd_sampler* s, const dd_bond_head* bh, i
     delete g;
     return DD_ERR_HIP;
   }
-  for (int i = 0; i < steps_per_graph && rc == DD_OK; ++i) rc = one_step(s, st, bh);
+  for (int i = 0; i < steps_per_graph && rc == DD_OK; ++i) rc = one_step(s, st, bh, no);
   hipError_t e = hipStreamEndCapture(st, &g->graph);
   capture_lock.unlock();
   if (rc == DD_OK && (e != hipSuccess || !g->graph)) rc = DD_ERR_HIP;
@@ -1614,9 +1660,15 @@ extern "C" int dd_sample_steps_graph_multi(const dd_sampler* const* ss, int n, i
 
 extern "C" int dd_sample_steps_graph_multi_ex(const dd_sampler* const* ss, const dd_bond_head* const* bhs, int n, int n_steps,
                                               void* const* streams) {
+  return dd_sample_steps_graph_multi_ex2(ss, bhs, nullptr, n, n_steps, streams);
+}
+
+extern "C" int dd_sample_steps_graph_multi_ex2(const dd_sampler* const* ss, const dd_bond_head* const* bhs, const dd_node_out* const* nos,
+                                               int n, int n_steps, void* const* streams) {
   if (!ss || !streams || n <= 0 || n > 64 || n_steps < 0) return DD_ERR_BAD_ARG;
   for (int i = 0; i < n; ++i) {
     if (bhs && dd::check_bond_head(bhs[i]) != DD_OK) return DD_ERR_BAD_ARG;
+    if (nos && dd::check_node_out(nos[i], ss[i]) != DD_OK) return DD_ERR_BAD_ARG;
     const dd_sampler* s = ss[i];
     if (!s || !streams[i] || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
         !s->pred_pos)
@@ -1638,7 +1690,7 @@ extern "C" int dd_sample_steps_graph_multi_ex(const dd_sampler* const* ss, const
     if (rc != DD_OK) break;
     std::lock_guard<std::mutex> capture_lock(dd::g_capture_mutex);
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { rc = DD_ERR_HIP; break; }
-    int rs = one_step(ss[i], st, bhs ? bhs[i] : nullptr);
+    int rs = one_step(ss[i], st, bhs ? bhs[i] : nullptr, nos ? nos[i] : nullptr);
     hipError_t e = hipStreamEndCapture(st, &graph[i]);
     if (rs != DD_OK || e != hipSuccess || !graph[i]) { rc = rs != DD_OK ? rs : DD_ERR_HIP; break; }
     if (hipGraphInstantiate(&exec[i], graph[i], nullptr, nullptr, 0) != hipSuccess) rc = DD_ERR_HIP;

@@ -67,6 +67,10 @@ int launch_gemm_tail(TailArgs& ta, hipStream_t st);
 int launch_gemm128(const GemmArgs& a, hipStream_t st);
 // up to 6 independent projections in one launch (small ones ride along with the big ones)
 int launch_gemm128_batch(const GemmArgs* jobs, int njobs, hipStream_t st);
+// node output MLPs + lin_node of a layer (x2h_out_fc; dd_node_out.hip): out = h + W2_e' z_e + W2_b' z_b + c0 over all B (NP + NL)
+// rows; Ab holds the ligand rows only ([B, NL, 128]); blk: the layer's weight block (DD_NO_* offsets); out may be h
+struct NodeOutArgs { const float* Ae; const float* Ab; const float* h; float* out; const float* blk; int B, NP, NL; };
+int launch_node_out_fc(const NodeOutArgs& a, hipStream_t st);
 
 int launch_embed_all(const float* protein_h, const float* protein_pos, const float* lig_pos, const int32_t* lig_v,
                      const float* lig_aux, const float* Wl, const float* bl, int B, int NP, int NL, float* h, float* xa, float* xb,

@@ -29,6 +29,8 @@ EXPORTED_SYMBOLS = [
     "dd_segment_reduce", "dd_segment_softmax", "dd_sampler_reset",
     "dd_layer0_tables", "dd_layer0_prepare",
     "dd_forward_ex", "dd_sample_steps_ex", "dd_sample_steps_graph_ex", "dd_graph_create_ex", "dd_sample_steps_graph_multi_ex",
+    "dd_node_out_fc",
+    "dd_forward_ex2", "dd_sample_steps_ex2", "dd_sample_steps_graph_ex2", "dd_graph_create_ex2", "dd_sample_steps_graph_multi_ex2",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -71,6 +73,12 @@ class DDBondHead(ctypes.Structure):
     """struct dd_bond_head (include/decompdiff_hip.h): the bond head handed to the *_ex entry points (NULL = lin)."""
     _fields_ = [("kind", c_int32), ("num_r", c_int32), ("W_p", c_void_p), ("W_r", c_void_p), ("b1", c_void_p),
                 ("offset", c_void_p), ("coeff", c_float), ("reserved", c_int32)]
+
+
+class DDNodeOut(ctypes.Structure):
+    """struct dd_node_out (include/decompdiff_hip.h): the node output MLPs of an x2h_out_fc model, handed to the *_ex2 entry
+    points (NULL = a model without them); layer[l]: device block of packing.node_out_block."""
+    _fields_ = [("num_layers", c_int32), ("reserved", c_int32), ("layer", c_void_p * 64)]
 
 
 L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128      # DD_L0_TABLE_FLOATS
@@ -149,6 +157,13 @@ def load():
         "dd_sample_steps_graph_ex": [S, POINTER(DDBondHead), c_int, c_void_p],
         "dd_graph_create_ex": [S, POINTER(DDBondHead), c_int, c_void_p, POINTER(c_void_p)],
         "dd_sample_steps_graph_multi_ex": [POINTER(S), POINTER(POINTER(DDBondHead)), c_int, c_int, POINTER(c_void_p)],
+        "dd_node_out_fc": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+        "dd_forward_ex2": [S, POINTER(DDBondHead), POINTER(DDNodeOut), c_void_p],
+        "dd_sample_steps_ex2": [S, POINTER(DDBondHead), POINTER(DDNodeOut), c_int, c_void_p],
+        "dd_sample_steps_graph_ex2": [S, POINTER(DDBondHead), POINTER(DDNodeOut), c_int, c_void_p],
+        "dd_graph_create_ex2": [S, POINTER(DDBondHead), POINTER(DDNodeOut), c_int, c_void_p, POINTER(c_void_p)],
+        "dd_sample_steps_graph_multi_ex2": [POINTER(S), POINTER(POINTER(DDBondHead)), POINTER(POINTER(DDNodeOut)), c_int, c_int,
+                                            POINTER(c_void_p)],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],

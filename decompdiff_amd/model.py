@@ -103,6 +103,7 @@ class DecompScorePosNet3D(nn.Module):
         self.add_prior_node = getattr(config, "add_prior_node", False)
         self.bond_diffusion = getattr(config, "bond_diffusion", False)
         self.bond_net_type = getattr(config, "bond_net_type", "mlp")
+        self.x2h_out_fc = bool(getattr(config, "x2h_out_fc", False))
         self.sample_time_method = getattr(config, "sample_time_method", "symmetric")
         self.loss_pos_type = getattr(config, "loss_pos_type", "mse")
         self.refine_net_type = config.model_type
@@ -129,8 +130,13 @@ class DecompScorePosNet3D(nn.Module):
         gen = torch.Generator().manual_seed(0)
         shapes = learnable_param_shapes(config, protein_atom_feature_dim=protein_atom_feature_dim,
                                         ligand_atom_feature_dim=ligand_atom_feature_dim, num_classes=num_classes)
+        gen_out = torch.Generator().manual_seed(1)          # (node_output MLPs, x2h_out_fc: drawn apart, behind the others)
         for k, shp in shapes.items():
-            if len(shp) == 2:
+            if ".node_output." in k and len(shp) == 2:
+                t = (torch.rand(shp, generator=gen_out) * 2 - 1) * (1.0 / np.sqrt(shp[1]))
+            elif ".node_output." in k and ".net.1." not in k:
+                t = (torch.rand(shp, generator=gen_out) * 2 - 1) * 0.05
+            elif len(shp) == 2:
                 bound = 1.0 / np.sqrt(shp[1])
                 t = (torch.rand(shp, generator=gen) * 2 - 1) * bound
             elif k.endswith(".net.1.weight"):
@@ -175,7 +181,7 @@ class DecompScorePosNet3D(nn.Module):
         need(config.num_blocks == 1, "num_blocks=1")
         need(config.edge_feat_dim == 4 and config.num_r_gaussian == 20, "edge_feat_dim=4, num_r_gaussian=20")
         need(getattr(config, "h_node_in_bond_net", False), "h_node_in_bond_net=True")
-        need(not config.x2h_out_fc and config.norm and config.act_fn == "relu", "x2h_out_fc=False, norm, relu")
+        need(config.x2h_out_fc in (False, True) and config.norm and config.act_fn == "relu", "x2h_out_fc in {False, True}, norm, relu")
         need(getattr(config, "num_bond_classes", 1) == 5, "num_bond_classes=5")
         # ligand_atom_mode basic / add_aromatic / full: 8 / 13 / 23 atom classes (utils/transforms.py:15-64,138-151;
         # scripts/sample_diffusion_decomp.py:538-540: feature dim = classes + the 2 arm / scaffold indicators)
@@ -271,6 +277,7 @@ class DecompScorePosNet3D(nn.Module):
                                 tab_pos=tab_pos.to(dev), tab_v=tab_v.to(dev), tab_b=tab_b.to(dev),
                                 tab_score=self.pos_score_coef.detach().float().contiguous().to(dev))
             self._packed["bond_head"] = self._bond_head_descriptor(sd, self._packed)
+            self._packed["node_out"] = self._node_out_descriptor(sd, self._packed)
             self._packed_key = key
         return self._packed
 
@@ -298,6 +305,26 @@ class DecompScorePosNet3D(nn.Module):
         pw = self._packed if pw is None else pw
         bh = pw.get("bond_head") if pw else None
         return None if bh is None else ctypes.pointer(bh)
+
+    def _node_out_descriptor(self, sd, pw):
+        """The dd_node_out of the *_ex2 entry points: None without x2h_out_fc; else the per-layer blocks of
+        packing.node_out_fc in one device buffer kept in the packed dict (the descriptor points into it)."""
+        if not self.x2h_out_fc:
+            return None
+        form = packing.node_out_fc({k: v.detach().float().cpu() for k, v in sd.items()}, self.config)
+        buf = torch.stack([packing.node_out_block(f) for f in form]).contiguous().to(pw["arena"].device)
+        pw["node_out_buf"] = buf
+        no = hip_lib.DDNodeOut()
+        no.num_layers = len(form)
+        for l in range(len(form)):
+            no.layer[l] = buf.data_ptr() + 4 * l * packing.NODE_OUT_BLOCK_FLOATS
+        return no
+
+    def _node_out(self, pw=None):
+        """ctypes pointer to this model's dd_node_out, None without x2h_out_fc (NULL: the behaviour of the _ex entry points)."""
+        pw = self._packed if pw is None else pw
+        no = pw.get("node_out") if pw else None
+        return None if no is None else ctypes.pointer(no)
 
     def _layer0_tables(self, pw, dev):
         """dd_sampler.l0_tables for this weight set (built once): the first layer's projection / query rows of the 16
@@ -740,7 +767,7 @@ class DecompScorePosNet3D(nn.Module):
             hint = int(getattr(self, "traj_capacity_hint", 0) or 0)
             cap = max(32, 1 << (max(int(n_steps), hint) - 1).bit_length())   # trajectory capacity: 5 and 20 steps share buffers
         key = (str(dev), B, NP, NL, K, NF, cap if keep_traj else 0, bool(keep_traj), decomp_index is not None, arena.data_ptr(),
-               masks is not None, int(cache_slot), self.bond_net_type)     # cache_slot: chains of ONE call that share a shape need separate buffers
+               masks is not None, int(cache_slot), self.bond_net_type, self.x2h_out_fc)     # cache_slot: chains of ONE call that share a shape need separate buffers
         cache = DecompScorePosNet3D._chain_cache
         ent = cache.pop(key, None) if cacheable else None
         if ent is None:
@@ -934,7 +961,7 @@ class DecompScorePosNet3D(nn.Module):
             pw = self._packed_weights()
             s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, torch.ones(B * NL, 3, device=dev),
                                             torch.zeros(B, 3, device=dev), None, None, 0, masks=pad["masks"])
-            hip_lib.check(hip_lib.load().dd_forward_ex(ctypes.byref(s), self._bond_head(pw), hip_lib.stream_ptr(dev)), "dd_forward")
+            hip_lib.check(hip_lib.load().dd_forward_ex2(ctypes.byref(s), self._bond_head(pw), self._node_out(pw), hip_lib.stream_ptr(dev)), "dd_forward")
             _check_queue(s, dev)
             preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3).index_select(0, d_l),
                      "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes).index_select(0, d_l)}
@@ -1002,7 +1029,7 @@ class DecompScorePosNet3D(nn.Module):
             dummy3 = torch.ones(B * NL, 3, device=dev)
             s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, dummy3,
                                             torch.zeros(B, 3, device=dev), None, None, 0)
-            hip_lib.check(hip_lib.load().dd_forward_ex(ctypes.byref(s), self._bond_head(pw), hip_lib.stream_ptr(dev)), "dd_forward")
+            hip_lib.check(hip_lib.load().dd_forward_ex2(ctypes.byref(s), self._bond_head(pw), self._node_out(pw), hip_lib.stream_ptr(dev)), "dd_forward")
             _check_queue(s, dev)
             preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3),
                      "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes)}
@@ -1191,7 +1218,7 @@ class DecompScorePosNet3D(nn.Module):
                         if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                             self._drop_cached_graphs()
                         graph = ctypes.c_void_p()
-                        hip_lib.check(lib.dd_graph_create_ex(ctypes.byref(c["s"]), self._bond_head(), 1, side.cuda_stream,
+                        hip_lib.check(lib.dd_graph_create_ex2(ctypes.byref(c["s"]), self._bond_head(), self._node_out(), 1, side.cuda_stream,
                                                              ctypes.byref(graph)), "dd_graph_create")
                         ent["graph"], ent["graph_sig"] = graph, gsig
                         DecompScorePosNet3D._graph_counter += 1
@@ -1206,7 +1233,7 @@ class DecompScorePosNet3D(nn.Module):
             else:
                 with torch.cuda.stream(side):
                     for c in chains:
-                        hip_lib.check(lib.dd_sample_steps_ex(ctypes.byref(c["s"]), self._bond_head(), int(num_steps),
+                        hip_lib.check(lib.dd_sample_steps_ex2(ctypes.byref(c["s"]), self._bond_head(), self._node_out(), int(num_steps),
                                                              hip_lib.stream_ptr(dev)), "dd_sample_steps")
             cur.wait_stream(side)
             return
@@ -1225,7 +1252,9 @@ class DecompScorePosNet3D(nn.Module):
         self._drop_cached_graphs()
         bh = self._bond_head()
         bhs = None if bh is None else (ctypes.POINTER(hip_lib.DDBondHead) * n)(*([bh] * n))
-        hip_lib.check(lib.dd_sample_steps_graph_multi_ex(ss, bhs, n, int(num_steps), sts), "dd_sample_steps_graph_multi")
+        no = self._node_out()
+        nos = None if no is None else (ctypes.POINTER(hip_lib.DDNodeOut) * n)(*([no] * n))
+        hip_lib.check(lib.dd_sample_steps_graph_multi_ex2(ss, bhs, nos, n, int(num_steps), sts), "dd_sample_steps_graph_multi")
         for st in pool:
             cur.wait_stream(st)
 
@@ -1268,7 +1297,7 @@ class DecompScorePosNet3D(nn.Module):
             if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                 self._drop_cached_graphs()                 # (all live graphs, newest first; cached entries re-capture on next use)
             graph = ctypes.c_void_p()
-            hip_lib.check(lib.dd_graph_create_ex(ctypes.byref(s), self._bond_head(), spg, side.cuda_stream, ctypes.byref(graph)),
+            hip_lib.check(lib.dd_graph_create_ex2(ctypes.byref(s), self._bond_head(), self._node_out(), spg, side.cuda_stream, ctypes.byref(graph)),
                           "dd_graph_create")
             ent["graph"], ent["graph_sig"] = graph, gsig
             DecompScorePosNet3D._graph_counter += 1

@@ -301,6 +301,50 @@ def bond_head_pre_att(sd, cfg) -> Dict[str, object]:
             "b1": sd["bond_inference.0.bias"].detach().cpu().contiguous(), "offset": off.contiguous(), "coeff": coeff}
 
 
+# float offsets of a layer's node-output block (include/decompdiff_hip.h: DD_NO_*)
+NODE_OUT_FIELDS = (("W1_e", 0), ("W1_b", 32768), ("W2_e", 65536), ("W2_b", 81920), ("b1_e", 98304), ("b1_b", 98432),
+                   ("ln_e", 98560), ("ln_b", 98816), ("c0", 99072))
+NODE_OUT_BLOCK_FLOATS = 99200
+
+
+def node_out_fc(sd, cfg):
+    """The node output MLPs (x2h_out_fc: True; uni_transformer_edge.py:39-40, 70-71) and lin_node (:277) of every layer in the
+    form k_node_out_fc consumes.  The reference computes, with A_e / A_b the aggregates of node_layer_with_edge / _with_bond
+    (A_b = 0 on protein rows) and MLP_m = node_output of the two layers,
+        h_new = h + W_lin (MLP_e([A_e ; h]) + MLP_b([A_b ; h])) + b_lin,   MLP_m(u) = W2_m relu(LN_m(W1_m u + b1_m)) + b2_m.
+    lin_node is linear in the two second Linears, so per layer
+        z_m = relu(LN_m(W1_m [A_m ; h] + b1_m)),   h_new = h + W2_e' z_e + W2_b' z_b + c0,
+        W2_m' = W_lin W2_m,   c0 = W_lin (b2_e + b2_b) + b_lin      (composed in float64, rounded once).
+    Returns a list of per-layer dicts of fp32 tensors: W1_e, W1_b [128, 256], b1_e, b1_b [128], ln_e, ln_b [2, 128] (gamma ; beta),
+    W2_e, W2_b [128, 128] (composed), c0 [128]."""
+    out = []
+    for l in range(cfg.num_layers):
+        p = f"refine_net.base_block.{l}"
+        f = lambda k: sd[k].detach().cpu()
+        Wl, bl = f(f"{p}.lin_node.weight").double(), f(f"{p}.lin_node.bias").double()
+        d = {}
+        b2 = torch.zeros(H, dtype=torch.float64)
+        for m, name in (("e", "node_layer_with_edge"), ("b", "node_layer_with_bond")):
+            W1, b1, ln, W2, b2m = _mlp({k: f(k) for k in sd if k.startswith(f"{p}.{name}.node_output.")}, f"{p}.{name}.node_output")
+            if tuple(W1.shape) != (H, 2 * H):
+                raise ValueError(f"{p}.{name}.node_output.net.0.weight is [{H}, {2 * H}], got {list(W1.shape)}")
+            d["W1_" + m], d["b1_" + m], d["ln_" + m] = W1.float().contiguous(), b1.float().contiguous(), ln.float().contiguous()
+            d["W2_" + m] = (Wl @ W2.double()).float().contiguous()
+            b2 = b2 + b2m.double()
+        d["c0"] = (Wl @ b2 + bl).float().contiguous()
+        out.append(d)
+    return out
+
+
+def node_out_block(form_layer) -> torch.Tensor:
+    """One layer of node_out_fc as the flat device block of dd_node_out (DD_NO_* offsets)."""
+    blk = torch.zeros(NODE_OUT_BLOCK_FLOATS)
+    for name, off in NODE_OUT_FIELDS:
+        t = form_layer[name].reshape(-1)
+        blk[off:off + t.numel()] = t
+    return blk
+
+
 def pack_model(sd: Dict[str, torch.Tensor], cfg, kernel_form: bool = False):
     """Return (arena fp32 [n], offsets int64 [n_layers*len(LAYER_SLOTS)+len(GLOBAL_SLOTS)], named views).
     kernel_form: the attention MLPs in the form the kernels consume (kernel_form_layer) instead of the canonical,

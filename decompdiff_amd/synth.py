@@ -342,6 +342,13 @@ def learnable_param_shapes(config, protein_atom_feature_dim=29, ligand_atom_feat
         pre_att = getattr(config, "bond_net_type", "lin") == "pre_att"
         linear("bond_inference.0", H, (config.num_r_gaussian if pre_att else 0) + H)
         linear("bond_inference.2", nb, H)
+    if getattr(config, "x2h_out_fc", False):
+        # node_output = MLP(2H -> H) on cat([aggregate, h]) at the end of both NodeUpdateLayers (uni_transformer_edge.py:39-40).
+        # Listed behind every other tensor: the model's initialiser draws them from a generator of their own, so the values of
+        # the shared tensors do not depend on the switch.
+        for l in range(config.num_layers):
+            for f in ("node_layer_with_edge", "node_layer_with_bond"):
+                mlp(f"refine_net.base_block.{l}.{f}.node_output", 2 * H, H)
     return shapes
 
 

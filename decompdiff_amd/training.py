@@ -588,6 +588,7 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
     e_w = torch.sigmoid(P.mlp("refine_net.edge_pred_layer", _gauss(d0)))
     NLm1, Ebs = NL - 1, NL * (NL - 1)
     mask_l = is_lig.float().unsqueeze(-1)
+    out_fc = bool(getattr(cfg, "x2h_out_fc", False))
     for l in range(int(cfg.num_layers)):
         p = f"refine_net.base_block.{l}"
         rel = gather(x, p_dst) - x.index_select(0, src)
@@ -653,6 +654,14 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         else:
             d_hb = torch.zeros_like(h_bond)
         new_h_bond = h_bond + d_hb
+        if out_fc:
+            # x2h_out_fc: node_output = MLP(cat([aggregate, h])) at the end of both NodeUpdateLayers (:39-40, 70-71), the first
+            # Linear split over the two halves of the concatenation (a_bond is zero on protein rows, its MLP output is not)
+            def node_output(name, agg):
+                nm = f"{p}.{name}.node_output"
+                W = P.w(nm + ".net.0")
+                return P.mlp_tail(nm, linear128(agg, W[:, 0:H]) + linear128(h, W[:, H:2 * H]) + P.b(nm + ".net.0"))
+            a_edge, a_bond = node_output("node_layer_with_edge", a_edge), node_output("node_layer_with_bond", a_bond)
         new_h = h + P.lin(f"{p}.lin_node", a_edge + a_bond)
         # pos_layer_with_edge / pos_layer_with_bond (PosUpdateLayer, :188-210), with the NEW h / h_bond
         k_pe, v_pe = node_layer_edge("pos_layer_with_edge", new_h, NH)

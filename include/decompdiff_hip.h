@@ -347,6 +347,46 @@ int dd_graph_create_ex(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, int
 int dd_sample_steps_graph_multi_ex(const dd_sampler* const* s /*HOST [n]*/, const dd_bond_head* const* bh /*HOST [n]*/, int n,
                                    int n_steps, void* const* streams /*HOST [n]*/);
 
+/* Node output MLPs (x2h_out_fc: True; uni_transformer_edge.py:39-40, 70-71).  Each NodeUpdateLayer of a layer then ends in
+ * node_output = MLP(256 -> 128, LayerNorm, ReLU, 128 -> 128) on cat([aggregate, h]), and the layer's node update is
+ *   z_e = relu(LN_e(W1_e [A_e ; h] + b1_e)),  z_b = relu(LN_b(W1_b [A_b ; h] + b1_b))   (A_b = 0 on protein rows),
+ *   h_new = h + W2_e' z_e + W2_b' z_b + c0,   W2_m' = W_lin W2_m,  c0 = W_lin (b2_e + b2_b) + b_lin   (composed on the host).
+ * A layer's weights are one DEVICE block of DD_NO_BLOCK_FLOATS floats (16-byte aligned) at the offsets below; W1_* are
+ * [128, 256] (out, in) as in the checkpoint, W2_*' [128, 128] (out, in), ln_* [2, 128] gamma ; beta.  The entry points without a
+ * dd_node_out run the model without these MLPs (h_new = h + W_lin (A_e + A_b) + b_lin from the slots DD_W_lin / DD_b_lin). */
+#define DD_NO_W1E 0
+#define DD_NO_W1B 32768
+#define DD_NO_W2E 65536
+#define DD_NO_W2B 81920
+#define DD_NO_B1E 98304
+#define DD_NO_B1B 98432
+#define DD_NO_LNE 98560
+#define DD_NO_LNB 98816
+#define DD_NO_C0 99072
+#define DD_NO_BLOCK_FLOATS 99200
+typedef struct dd_node_out {
+  int32_t num_layers;      /* = dd_sampler.num_layers */
+  int32_t reserved;
+  const float* layer[64];  /* DEVICE block of each layer; must stay valid while a graph captured with the descriptor is alive */
+} dd_node_out;
+
+/* The kernel alone: h_out[B (NP + NL), 128] = the node update above from A_e [B (NP + NL), 128], A_b [B NL, 128] (ligand rows
+ * only), h [B (NP + NL), 128] and one layer block `weights`; h_out may be h.  np_real / nl_real (padded batches, may be NULL):
+ * padding rows are computed like real ones, as the lin_node GEMM does -- finite inputs give finite rows nobody reads. */
+int dd_node_out_fc(const float* A_e, const float* A_b, const float* h, int B, int NP, int NL, const float* weights,
+                   const int32_t* np_real, const int32_t* nl_real, float* h_out, void* stream);
+
+/* The _ex entry points with both descriptors (no NULL: exactly the _ex functions, which call these).  no of the multi variant:
+ * HOST array of n descriptors (entries may be NULL), or NULL. */
+int dd_forward_ex2(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, const dd_node_out* no /*HOST*/, void* stream);
+int dd_sample_steps_ex2(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, const dd_node_out* no /*HOST*/, int n_steps, void* stream);
+int dd_sample_steps_graph_ex2(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, const dd_node_out* no /*HOST*/, int n_steps,
+                              void* stream);
+int dd_graph_create_ex2(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, const dd_node_out* no /*HOST*/, int steps_per_graph,
+                        void* stream, void** graph_out /*HOST*/);
+int dd_sample_steps_graph_multi_ex2(const dd_sampler* const* s /*HOST [n]*/, const dd_bond_head* const* bh /*HOST [n]*/,
+                                    const dd_node_out* const* no /*HOST [n]*/, int n, int n_steps, void* const* streams /*HOST [n]*/);
+
 /* Drift guidance gradients at x_t (utils/guidance_funcs.py:24-78), analytic. grad [B,NL,3]. */
 int dd_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                     float* grad, int accumulate, void* stream);
