@@ -17,6 +17,7 @@ from typing import Optional
 import torch
 
 from . import hip_lib
+from .batch_layout import N_MAX
 
 # ------------------------------------------------------------------------------------------------------------------
 # The compiled torch extension (csrc/torch_ext.cpp -> lib/decompdiff_torch_ext.so: TORCH_LIBRARY(decompdiff_hip, ...),
@@ -73,7 +74,7 @@ def knn_graph(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
         N = n // B
         dense = dense and n % B == 0 and torch.equal(batch, torch.arange(B, device=dev).repeat_interleave(N))
     xc = x.detach().to(torch.float32).contiguous()
-    if not dense or N > 2048:
+    if not dense or N > N_MAX:
         return swap(_knn_graph_csr(xc, k, batch, B, loop))
     kk = min(k, N - 1)
     if kk <= 0:

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import hip_lib, packing, schedules
+from . import batch_layout as BL, hip_lib, packing, schedules
 from .synth import learnable_param_shapes
 
 H = 128
@@ -362,75 +362,53 @@ class DecompScorePosNet3D(nn.Module):
     # ------------------------------------------------------------------------------------------
     # Ragged batches (samples with different atom counts).  Every sample's chain is independent of the
     # rest of its batch (all graph ops of the reference are segmented by `batch`; tests/test_gpu_parity.py checks that
-    # the kernels keep this bit for bit), so a ragged batch is run as one dense launch sequence per group of samples
-    # with equal (protein, ligand, prior, full-protein) sizes and the results are scattered back into batch order.
+    # the kernels keep this bit for bit), so a ragged batch runs padded to its largest sample or as one dense launch
+    # sequence per group of equal sizes.  Counts, validation, row maps and groups come from `batch_layout`.
     @staticmethod
     def _is_ragged(batch_protein, batch_ligand) -> bool:
         if batch_protein.numel() == 0 or batch_ligand.numel() == 0:
             return False
-        B = int(batch_protein.max().item()) + 1
-        cp = torch.bincount(batch_protein, minlength=B)
-        cl = torch.bincount(batch_ligand, minlength=B)
-        return bool((cp != cp[0]).any().item() or (cl != cl[0]).any().item())
+        n_p = BL.sample_counts(batch_protein)
+        return not BL.BatchLayout(n_p, BL.sample_counts(batch_ligand, len(n_p))).is_dense
+
+    @staticmethod
+    def _sampling_layout(kw):
+        """The validated layout of sample_diffusion's arguments.  (A sample without pocket atoms is left to the dense path.)"""
+        if kw["ligand_fc_bond_index"] is None or kw["init_ligand_fc_bond_type"] is None:
+            raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
+        has_full = kw["full_protein_pos"] is not None and kw["full_batch_protein"] is not None
+        return BL.BatchLayout.from_batch(kw["batch_protein"], kw["batch_ligand"], kw["batch_prior"],
+                                         kw["full_batch_protein"] if has_full else None, kw["batch_ligand_bond"],
+                                         kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"].numel(), need_protein=False)
 
     def _sample_heterogeneous(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
                               use_graph, start_step=0):
         """Samples with different atom counts in one batch (PyG collate, utils/data.py:389-446).  Default: ONE launch
         sequence over the batch padded to its largest pocket / ligand with per-sample real counts (`_sample_padded`).
-        Fallbacks to equal-size groups (`_sample_ragged`): DD_RAGGED_MODE=groups, or a sample with fewer than knn + 1
-        atoms (its kNN lists would be shorter than the others')."""
-        mode = os.environ.get("DD_RAGGED_MODE", "padded")
-        if mode != "groups":
-            bp, bl = kw["batch_protein"], kw["batch_ligand"]
-            B = int(bp.max().item()) + 1
-            n_p = torch.bincount(bp, minlength=B).cpu()
-            n_l = torch.bincount(bl, minlength=B).cpu()
-            fits = int((n_p + n_l).min()) - 1 >= int(self.config.knn) and int(n_l.min()) >= 2 and int(n_l.max()) <= 128 \
-                and int(n_p.max()) + int(n_l.max()) <= 2048
-            if fits:
+        Fallbacks to equal-size groups (`_sample_ragged`): DD_RAGGED_MODE=groups, or `batch_layout.fits_padded` says no."""
+        layout = None
+        if os.environ.get("DD_RAGGED_MODE", "padded") != "groups":
+            layout = self._sampling_layout(kw)
+            if BL.fits_padded(layout, self.config.knn):
                 return self._sample_padded(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed,
-                                           keep_traj, use_graph, start_step, n_p.tolist(), n_l.tolist())
+                                           keep_traj, use_graph, start_step, layout.n_p, layout.n_l)
         return self._sample_ragged(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                                   use_graph, start_step=start_step)
+                                   use_graph, start_step=start_step, layout=layout)
 
     def _padded_inputs(self, protein_pos, protein_v, bp, ligand_pos, ligand_v, aux, bl, fc_index, bond_type, batch_ligand_bond,
                        n_p, n_l, center_pos_mode):
-        """A validated heterogeneous flat batch (n_p / n_l: atoms per sample) as the padded dense layout of dd_sampler.np_real /
-        nl_real / bl_prefix: every sample's atoms are the first rows of its [NPmax] / [NLmax] blocks, its bonds the dst-major
-        rows of its [NLmax (NLmax - 1)] block; padding rows are zeros.  Shared by the padded sampler and the ragged forward.
-        Returns the dense dict `d` of _make_sampler (positions centred by `center_pos_mode`), the per-sample offset, the
-        masks and the row maps flat row -> padded row (rows_* on the host, d_* on the device)."""
+        """A heterogeneous flat batch validated by `BatchLayout.from_batch` (n_p / n_l: its atoms per sample) as the padded dense
+        layout of dd_sampler.np_real / nl_real / bl_prefix (`BatchLayout.padded_rows`); padding rows are zeros.  Shared by the
+        padded sampler and the ragged forward.  Returns the dense dict `d` of _make_sampler (positions centred by
+        `center_pos_mode`), the per-sample offset, the masks and the row maps flat row -> padded row (rows_* on the host, d_* on
+        the device)."""
         dev = protein_pos.device
         hip_lib.require_gpu(protein_pos, "protein_pos")
         hip_lib.require_gpu(ligand_pos, "init_ligand_pos")
-        for name, t in (("batch_protein", bp), ("batch_ligand", bl)):
-            if t.numel() > 1 and bool((t[1:] < t[:-1]).any().item()):
-                raise NotImplementedError(f"{name} must be sorted (PyG Batch order)")
-        B = len(n_p)
-        NP, NL = max(n_p), max(n_l)
+        layout = BL.BatchLayout(n_p, n_l)
+        B, NP, NL, n_b = layout.B, max(n_p), max(n_l), layout.n_b
         Eb = NL * (NL - 1)
-        n_b = [n * (n - 1) for n in n_l]
-        if fc_index is None or bond_type is None:
-            raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
-        cnt = lambda t: torch.bincount(t.cpu(), minlength=B).tolist()
-        if bond_type.numel() != sum(n_b) or (batch_ligand_bond is not None and cnt(batch_ligand_bond) != n_b):
-            raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
-        ar = torch.arange
-        # flat (caller) row -> padded row
-        rows_p = torch.cat([b * NP + ar(n_p[b]) for b in range(B)])
-        rows_l = torch.cat([b * NL + ar(n_l[b]) for b in range(B)])
-        o_l = [0] + list(np.cumsum(n_l))
-        exp_fc, rows_b = [], []
-        for b in range(B):
-            n = n_l[b]
-            dst = ar(n).repeat_interleave(n - 1)
-            sp = ar(n - 1).repeat(n)
-            src = sp + (sp >= dst).long()
-            exp_fc.append(torch.stack([src, dst], 0) + o_l[b])
-            rows_b.append(b * Eb + dst * (NL - 1) + sp)
-        exp_fc, rows_b = torch.cat(exp_fc, 1), torch.cat(rows_b)
-        if fc_index.shape != exp_fc.shape or not torch.equal(fc_index.cpu(), exp_fc):
-            raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
+        rows_p, rows_l, rows_b = layout.padded_rows()
         d_p, d_l, d_b = rows_p.to(dev), rows_l.to(dev), rows_b.to(dev)
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
         if protein_v.dim() != 2 or protein_v.shape[1] != 29 or aux.dim() != 2 or aux.shape[1] != 2:
@@ -468,24 +446,17 @@ class DecompScorePosNet3D(nn.Module):
         Exact: a sample's chain does not depend on its batch, with the one batch-wide quantity of the reference -- the
         armsca loss is averaged over the whole batch (guidance_funcs.py:78) -- unchanged because the batch is whole."""
         _check_ligand_atom_mask(ligand_atom_mask, kw["batch_ligand"].numel())
-        bpr = kw["batch_prior"]
-        if bpr.numel() > 1 and bool((bpr[1:] < bpr[:-1]).any().item()):
-            raise NotImplementedError("batch_prior must be sorted (PyG Batch order)")
         pad = self._padded_inputs(kw["protein_pos"], kw["protein_v"], kw["batch_protein"], kw["init_ligand_pos"], kw["init_ligand_v"],
                                   kw["ligand_v_aux"], kw["batch_ligand"], kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"],
                                   kw["batch_ligand_bond"], n_p, n_l, center_pos_mode)
         d, offset, masks, n_b = pad["d"], pad["offset"], pad["masks"], pad["n_b"]
         rows_l, rows_b, d_l, d_b = pad["rows_l"], pad["rows_b"], pad["d_l"], pad["d_b"]
-        B, NP, NL = d["B"], d["NP"], d["NL"]
+        B, NL = d["B"], d["NL"]
         Eb = NL * (NL - 1)
         dev = d["protein_pos"].device
-        ar = torch.arange
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
         zeros = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
-        cnt = lambda t: torch.bincount(t.cpu(), minlength=B).tolist()
         has_full = kw["full_protein_pos"] is not None and kw["full_batch_protein"] is not None
-        n_f = cnt(kw["full_batch_protein"]) if has_full else [0] * B
-        NF = max(n_f) if has_full else 0
         atom_std = zeros(B * NL, 3).index_copy_(0, d_l, f32(kw["prior_stds"])[kw["ligand_decomp_batch"].to(dev)])
         decomp = None
         if kw["ligand_decomp_index"] is not None:                          # -2: neither arm nor scaffold (padding)
@@ -495,7 +466,9 @@ class DecompScorePosNet3D(nn.Module):
         if energy_drift_opt is not None and any(dr["type"] == "clash" for dr in energy_drift_opt):
             if not has_full:
                 raise ValueError("clash drift needs full_protein_pos / full_batch_protein")
-            rows_f = torch.cat([b * NF + ar(n_f[b]) for b in range(B)]).to(dev)
+            n_f = BL.sample_counts(kw["full_batch_protein"], B)
+            NF = max(n_f)
+            rows_f = BL.block_rows(n_f, NF).to(dev)
             # padding far away: exp(-|p - y|^2 / sigma) underflows to exactly 0, so it adds nothing to any sum
             fpp = torch.full((B * NF, 3), 1.0e6, device=dev).index_copy_(0, rows_f, f32(kw["full_protein_pos"])).view(B, NF, 3)
         pad_noise = None
@@ -520,75 +493,37 @@ class DecompScorePosNet3D(nn.Module):
         return out
 
     def _sample_ragged(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, concurrent=None, start_step=0, split=1):
-        """One dense chain per group of samples of equal size.  ``split`` > 1 additionally cuts every group into that many
-        sub-batches (measurement aid, tools/split_bench.py: two concurrent half-batches were measured slower than one
-        chain)."""
+                       use_graph, concurrent=None, start_step=0, split=1, layout=None):
+        """One dense chain per group of samples of equal size (`BatchLayout.size_groups`).  ``split`` > 1 additionally cuts
+        every group into that many sub-batches (measurement aid, tools/split_bench.py: two concurrent half-batches were
+        measured slower than one chain).  ``layout``: what `_sampling_layout(kw)` gave the caller."""
         _check_ligand_atom_mask(ligand_atom_mask, kw["batch_ligand"].numel())
         dev = kw["protein_pos"].device
-        bp, bl, bpr = kw["batch_protein"], kw["batch_ligand"], kw["batch_prior"]
-        for name, t in (("batch_protein", bp), ("batch_ligand", bl), ("batch_prior", bpr)):
-            if t.numel() > 1 and bool((t[1:] < t[:-1]).any().item()):
-                raise NotImplementedError(f"{name} must be sorted (PyG Batch order)")
-        B = int(bp.max().item()) + 1
-        cnt = lambda t: torch.bincount(t.cpu(), minlength=B).tolist()
-        n_p, n_l, n_pr = cnt(bp), cnt(bl), cnt(bpr)
-        n_b = [n * (n - 1) for n in n_l]
-        if kw["ligand_fc_bond_index"] is None or kw["init_ligand_fc_bond_type"] is None:
-            raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
-        if kw["init_ligand_fc_bond_type"].numel() != sum(n_b):
-            raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
-        if kw["batch_ligand_bond"] is not None and cnt(kw["batch_ligand_bond"]) != n_b:
-            raise NotImplementedError("batch_ligand_bond does not match the fully connected bond graph")
-        has_full = kw["full_protein_pos"] is not None and kw["full_batch_protein"] is not None
-        n_f = cnt(kw["full_batch_protein"]) if has_full else [0] * B
-        off = lambda c: [0] + list(np.cumsum(c))
-        o_p, o_l, o_pr, o_b, o_f = off(n_p), off(n_l), off(n_pr), off(n_b), off(n_f)
-        groups: Dict[tuple, list] = {}
-        for b in range(B):
-            groups.setdefault((n_p[b], n_l[b], n_pr[b], n_f[b], (b * split) // B), []).append(b)
-        n_lig, n_bond = sum(n_l), sum(n_b)
+        layout = layout or self._sampling_layout(kw)
+        B, has_full = layout.B, max(layout.n_f) > 0
+        n_lig, n_bond = sum(layout.n_l), sum(layout.n_b)
         out = {"pos": torch.empty(n_lig, 3, device=dev), "v": torch.empty(n_lig, dtype=torch.long, device=dev),
                "bond": torch.empty(n_bond, dtype=torch.long, device=dev)}
         traj: Dict[str, Optional[torch.Tensor]] = {k: None for k in ("pos_traj", "v_traj", "bond_traj", "v0_traj", "vt_traj", "bt_traj")}
-        rng = lambda o, c, ids: torch.cat([torch.arange(o[b], o[b] + c[b]) for b in ids])
         prepared = []
-        for gi, ((np_, nl_, npr_, nf_, _part), ids) in enumerate(sorted(groups.items(), key=lambda kv: kv[1][0])):
-            G = len(ids)
-            r_p, r_l, r_pr, r_b = rng(o_p, n_p, ids), rng(o_l, n_l, ids), rng(o_pr, n_pr, ids), rng(o_b, n_b, ids)
-            d_p, d_l, d_pr, d_b = r_p.to(dev), r_l.to(dev), r_pr.to(dev), r_b.to(dev)
-            ar = lambda n: torch.arange(G, device=dev).repeat_interleave(n)
-            k_of_row_l = torch.arange(G).repeat_interleave(nl_).to(dev)          # sample slot of each ligand row
-            old_lig0 = torch.tensor([o_l[b] for b in ids], device=dev)
-            old_pr0 = torch.tensor([o_pr[b] for b in ids], device=dev)
-            sub = dict(
-                protein_pos=kw["protein_pos"][d_p], protein_v=kw["protein_v"][d_p], batch_protein=ar(np_),
-                protein_group_idx=None, init_ligand_pos=kw["init_ligand_pos"][d_l], init_ligand_v=kw["init_ligand_v"][d_l],
-                ligand_v_aux=kw["ligand_v_aux"][d_l], batch_ligand=ar(nl_), ligand_group_idx=None,
-                prior_centers=kw["prior_centers"][d_pr], prior_stds=kw["prior_stds"][d_pr],
-                prior_num_atoms=kw["prior_num_atoms"][d_pr] if kw["prior_num_atoms"] is not None else None,
-                batch_prior=ar(npr_), prior_group_idx=None,
-                ligand_decomp_batch=kw["ligand_decomp_batch"].to(dev)[d_l] - old_pr0[k_of_row_l] + k_of_row_l * npr_,
-                ligand_decomp_index=kw["ligand_decomp_index"][d_l] if kw["ligand_decomp_index"] is not None else None,
-                ligand_fc_bond_index=kw["ligand_fc_bond_index"].to(dev)[:, d_b]
-                - old_lig0.repeat_interleave(nl_ * (nl_ - 1))[None, :] + (torch.arange(G, device=dev) * nl_).repeat_interleave(nl_ * (nl_ - 1))[None, :],
-                init_ligand_fc_bond_type=kw["init_ligand_fc_bond_type"][d_b], batch_ligand_bond=ar(nl_ * (nl_ - 1)))
-            if has_full:
-                d_f = rng(o_f, n_f, ids).to(dev)
-                sub["full_protein_pos"] = kw["full_protein_pos"].to(dev)[d_f]
-                sub["full_batch_protein"] = ar(nf_)
+        for gi, g in enumerate(layout.size_groups([(b * split) // B for b in range(B)] if split > 1 else ())):
+            G, r_l, r_b = len(g.ids), g.rows_l, g.rows_b
+            d_p, d_l, d_pr, d_b = g.rows_p.to(dev), r_l.to(dev), g.rows_pr.to(dev), r_b.to(dev)
+            b_p, b_l, fc = self._expected_layout(G, g.n_p, g.n_l, dev)          # (b_l: sample slot of each ligand row)
+            old_pr0 = torch.tensor(g.first_pr, device=dev)
             sub_noise = None
             if noise is not None:
                 sub_noise = {"u_v": noise["u_v"][:, r_l], "u_b": noise["u_b"][:, r_b], "eps": noise["eps"][:, r_l]}
-            if self._is_ragged(sub["batch_protein"], sub["batch_ligand"]):
-                raise AssertionError("group is not dense")
             chain = self._prepare_chain(
-                sub["protein_pos"], sub["protein_v"], sub["batch_protein"], sub["init_ligand_pos"], sub["init_ligand_v"],
-                sub["ligand_v_aux"], sub["batch_ligand"], sub["prior_stds"], sub["ligand_decomp_batch"],
-                sub["ligand_decomp_index"], None, sub["ligand_fc_bond_index"], sub["init_ligand_fc_bond_type"], num_steps,
-                center_pos_mode, energy_drift_opt, sub.get("full_protein_pos"), sub.get("full_batch_protein"), sub_noise,
+                kw["protein_pos"][d_p], kw["protein_v"][d_p], b_p, kw["init_ligand_pos"][d_l], kw["init_ligand_v"][d_l],
+                kw["ligand_v_aux"][d_l], b_l, kw["prior_stds"][d_pr],
+                kw["ligand_decomp_batch"].to(dev)[d_l] - old_pr0[b_l] + b_l * g.n_pr,
+                kw["ligand_decomp_index"][d_l] if kw["ligand_decomp_index"] is not None else None, None, fc,
+                kw["init_ligand_fc_bond_type"][d_b], num_steps, center_pos_mode, energy_drift_opt,
+                kw["full_protein_pos"].to(dev)[g.rows_f.to(dev)] if has_full else None,
+                BL.batch_vector(G, g.n_f, dev) if has_full else None, sub_noise,
                 seed + 7919 * gi, keep_traj, B, start_step,        # (the armsca loss is averaged over the whole batch)
-                cache_slot=_part)                                  # (sub-batches of one shape: own cached buffers each)
+                cache_slot=(g.ids[0] * split) // B)                # (sub-batches of one shape: own cached buffers each)
             prepared.append((chain, d_l, d_b, r_l, r_b))
         if concurrent is None:
             # measured on MI355X (tools/ragged_bench.py, DESIGN.md): with the runtime's default 4 hardware queues the
@@ -641,10 +576,7 @@ class DecompScorePosNet3D(nn.Module):
             exp_p, exp_l, exp_fc = self._expected_layout(B, NP, NL, dev)
             if not (torch.equal(batch_protein, exp_p) and torch.equal(batch_ligand, exp_l)):
                 raise NotImplementedError("batch vectors must be sorted with equal counts per sample (PyG Batch order)")
-        if NL < 2 or NL > 128:
-            raise NotImplementedError(f"ligand size {NL} outside the supported range [2, 128]")
-        if NP + NL > 2048:
-            raise NotImplementedError("more than 2048 atoms per sample")
+        BL.check_size_limits(NP, NL)
         # the fused kernels use the closed-form fc layout of FeaturizeLigandBond('fc') (utils/transforms.py:331-337)
         if layout is None and (ligand_fc_bond_index.shape != exp_fc.shape or not torch.equal(ligand_fc_bond_index, exp_fc)):
             raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
@@ -741,12 +673,7 @@ class DecompScorePosNet3D(nn.Module):
         if key not in memo:
             if len(memo) > 16:
                 memo.clear()
-            dst = torch.arange(NL, device=dev).repeat_interleave(NL)
-            src = torch.arange(NL, device=dev).repeat(NL)
-            keep = dst != src
-            fc = torch.stack([src[keep], dst[keep]], 0)
-            memo[key] = (torch.arange(B, device=dev).repeat_interleave(NP), torch.arange(B, device=dev).repeat_interleave(NL),
-                         torch.cat([fc + b * NL for b in range(B)], 1))
+            memo[key] = BL.dense_vectors(B, NP, NL, dev)
         return memo[key]
 
     def _make_sampler(self, d, pw, n_steps, t_start, noise, keep_traj, drift, atom_std, offset, decomp_index,
@@ -940,20 +867,11 @@ class DecompScorePosNet3D(nn.Module):
         if ligand_fc_bond_index is None or ligand_bond_type is None:
             raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
         dev = protein_pos.device
-        for name, t in (("batch_protein", batch_protein), ("batch_ligand", batch_ligand)):
-            if t.numel() > 1 and bool((t[1:] < t[:-1]).any().item()):
-                raise NotImplementedError(f"{name} must be sorted (PyG Batch order)")
-        B = int(batch_protein.max().item()) + 1
-        n_p = torch.bincount(batch_protein, minlength=B).tolist()
-        n_l = torch.bincount(batch_ligand, minlength=B).tolist()
-        if len(n_l) != B or min(n_p) < 1 or min(n_l) < 2:
-            raise NotImplementedError("every sample needs protein atoms and at least 2 ligand atoms")
-        if max(n_l) > 128:
-            raise NotImplementedError(f"ligand size {max(n_l)} outside the supported range [2, 128]")
-        if max(a + b for a, b in zip(n_p, n_l)) > 2048:
-            raise NotImplementedError("more than 2048 atoms per sample")
-        fits = min(a + b for a, b in zip(n_p, n_l)) - 1 >= int(self.config.knn) and max(n_p) + max(n_l) <= 2048
-        if os.environ.get("DD_RAGGED_MODE", "padded") != "groups" and fits:
+        layout = BL.BatchLayout.from_batch(batch_protein, batch_ligand, ligand_fc_bond_index=ligand_fc_bond_index.to(dev),
+                                           n_bonds=ligand_bond_type.numel())
+        B, n_p, n_l = layout.B, layout.n_p, layout.n_l
+        BL.check_size_limits(n_p, n_l)
+        if os.environ.get("DD_RAGGED_MODE", "padded") != "groups" and BL.fits_padded(layout, self.config.knn):
             pad = self._padded_inputs(protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, ligand_v_aux, batch_ligand,
                                       ligand_fc_bond_index, ligand_bond_type, None, n_p, n_l, "none")
             d, d_l, d_b = pad["d"], pad["d_l"], pad["d_b"]
@@ -970,27 +888,14 @@ class DecompScorePosNet3D(nn.Module):
             self._last = (s, bufs)
             return preds
         # one dense forward per group of equal (protein, ligand) sizes, rows put back in the caller's order
-        o_p, o_l = [0] + list(np.cumsum(n_p)), [0] + list(np.cumsum(n_l))
-        n_b = [n * (n - 1) for n in n_l]
-        o_b = [0] + list(np.cumsum(n_b))
-        if ligand_bond_type.numel() != o_b[-1] or ligand_fc_bond_index.shape != (2, o_b[-1]):
-            raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
-        groups: Dict[tuple, list] = {}
-        for b in range(B):
-            groups.setdefault((n_p[b], n_l[b]), []).append(b)
-        out = {"pred_ligand_pos": torch.empty(o_l[-1], 3, device=dev), "pred_ligand_v": torch.empty(o_l[-1], self.num_classes, device=dev)}
+        out = {"pred_ligand_pos": torch.empty(sum(n_l), 3, device=dev), "pred_ligand_v": torch.empty(sum(n_l), self.num_classes, device=dev)}
         if self.bond_diffusion:
-            out["pred_bond"] = torch.empty(o_b[-1], 5, device=dev)
-        rng = lambda o, c, ids: torch.cat([torch.arange(o[b], o[b] + c[b]) for b in ids]).to(dev)
-        for (np_, nl_), ids in groups.items():
-            G = len(ids)
-            r_p, r_l, r_b = rng(o_p, n_p, ids), rng(o_l, n_l, ids), rng(o_b, n_b, ids)
-            ar = lambda n: torch.arange(G, device=dev).repeat_interleave(n)
-            old0 = torch.tensor([o_l[b] for b in ids], device=dev).repeat_interleave(nl_ * (nl_ - 1))
-            new0 = (torch.arange(G, device=dev) * nl_).repeat_interleave(nl_ * (nl_ - 1))
-            fc = ligand_fc_bond_index.to(dev)[:, r_b] - old0[None, :] + new0[None, :]       # (validated by the dense call)
-            r = self.forward(protein_pos[r_p], protein_v[r_p], ar(np_), None, ligand_pos[r_l], ligand_v[r_l], ligand_v_aux[r_l],
-                             ar(nl_), None, None, None, None, None, fc, ligand_bond_type[r_b])
+            out["pred_bond"] = torch.empty(sum(layout.n_b), 5, device=dev)
+        for g in layout.size_groups():
+            r_p, r_l, r_b = g.rows_p.to(dev), g.rows_l.to(dev), g.rows_b.to(dev)
+            b_p, b_l, fc = self._expected_layout(len(g.ids), g.n_p, g.n_l, dev)
+            r = self.forward(protein_pos[r_p], protein_v[r_p], b_p, None, ligand_pos[r_l], ligand_v[r_l], ligand_v_aux[r_l],
+                             b_l, None, None, None, None, None, fc, ligand_bond_type[r_b])
             out["pred_ligand_pos"][r_l], out["pred_ligand_v"][r_l] = r["pred_ligand_pos"], r["pred_ligand_v"]
             if self.bond_diffusion:
                 out["pred_bond"][r_b] = r["pred_bond"]
@@ -1005,12 +910,12 @@ class DecompScorePosNet3D(nn.Module):
         indices and the prior tensors are accepted for signature compatibility; the shipped
         configuration never reads them (time_emb_dim=0, add_prior_node=False).
 
-        A batch whose samples differ in size (a PyG ``Batch`` of different complexes, sorted batch vectors, per-sample
-        dst-major fully connected bond lists) is accepted: it runs as ONE launch sequence over the batch padded to its
+        A batch whose samples differ in size (a PyG ``Batch`` of different complexes; layout validated by
+        ``batch_layout.BatchLayout.from_batch``) is accepted: it runs as ONE launch sequence over the batch padded to its
         largest pocket / ligand with the real counts in ``dd_sampler.np_real / nl_real / bl_prefix`` (the layer-0 tables,
-        which need a dense batch, are off for that call), or -- ``DD_RAGGED_MODE=groups``, or a sample with fewer than
-        ``knn + 1`` atoms -- as one dense call per group of equal sizes.  Either way the predictions cover the real atoms
-        and bonds only, in the flat order of the inputs.  ``ligand_atom_mask``: None or an all-True mask, as in
+        which need a dense batch, are off for that call), or -- ``DD_RAGGED_MODE=groups``, or ``batch_layout.fits_padded``
+        says no -- as one dense call per group of equal sizes.  Either way the predictions cover the real atoms and
+        bonds only, in the flat order of the inputs.  ``ligand_atom_mask``: None or an all-True mask, as in
         :meth:`sample_diffusion`."""
         if return_all:
             raise NotImplementedError("return_all (per-block intermediates) is a training-time option")
@@ -1053,8 +958,8 @@ class DecompScorePosNet3D(nn.Module):
         With autograd enabled the network runs through :mod:`decompdiff_amd.training` (torch dense layers + the HIP graph
         ops with analytic backward passes), so ``results['losses']`` can be back-propagated into all parameters.  Under
         ``torch.no_grad()`` (the reference's validation loop) the network output comes from the fused ``dd_forward``
-        kernels instead.  The batch layout (sorted batch vectors, dst-major fully connected bond lists) is validated
-        on every call for both paths (`training.check_batch_layout`); samples of different sizes -- the reference's
+        kernels instead.  The batch layout is validated on every call for both paths (`training.check_batch_layout`,
+        i.e. `batch_layout.BatchLayout.from_batch`); samples of different sizes -- the reference's
         training batches -- run as one dense sub-batch per distinct size (`training.network_grouped`)."""
         from . import training
         _check_ligand_atom_mask(ligand_atom_mask, batch_ligand.numel())

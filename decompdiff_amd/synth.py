@@ -25,6 +25,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from .batch_layout import fc_bond_index, fc_bond_index_batch          # (fc_bond_index: re-exported, pocket_data and the tests import it from here)
 from .config import NUM_ATOM_CLASSES
 
 
@@ -137,14 +138,6 @@ def make_pocket_tiny(seed=0, num_protein=40, arm_atoms=(2, 2), scaffold_atoms=2)
 # --------------------------------------------------------------------------------------
 # harness: batch assembly (ref_prior) with the reference's RNG draw order
 # --------------------------------------------------------------------------------------
-def fc_bond_index(n_atoms: int) -> torch.Tensor:
-    """Fully-connected directed bond list, dst-major (utils/transforms.py:331-337)."""
-    dst = torch.repeat_interleave(torch.arange(n_atoms), n_atoms)
-    src = torch.arange(n_atoms).repeat(n_atoms)
-    keep = dst != src
-    return torch.stack([src[keep], dst[keep]], 0)
-
-
 def gumbel_argmax_uniform(n_rows: int, n_classes: int) -> torch.Tensor:
     """`log_sample_categorical(zeros)` (models/transitions.py:78-84) on the global CPU RNG."""
     u = torch.rand(n_rows, n_classes)
@@ -214,7 +207,7 @@ def build_sampling_batch(pocket: Pocket, n_data: int, num_bond_classes: int = 5,
         prior_num_atoms=torch.tensor((pocket.arm_num_atoms + [pocket.scaffold_num_atoms]) * n_data),
         batch_prior=torch.repeat_interleave(torch.arange(n_data), A + 1),
         prior_group_idx=torch.cat([torch.arange(A + 1) for _ in range(n_data)]),
-        ligand_fc_bond_index=torch.cat([fc + s * NL for s in range(n_data)], 1),
+        ligand_fc_bond_index=fc_bond_index_batch([NL] * n_data),
         init_ligand_fc_bond_type=torch.cat(bond_types, 0),
         batch_ligand_bond=torch.repeat_interleave(torch.arange(n_data), n_bond),
         ligand_decomp_batch=torch.cat([decomp_mask + s * (A + 1) for s in range(n_data)]),

@@ -29,6 +29,7 @@ import torch.nn.functional as F
 
 from . import functional as FN
 from . import hip_lib
+from .batch_layout import BatchLayout, batch_vector, fc_bond_index_batch, fits_padded
 
 GAUSS_OFFSETS = [0, 1, 1.25, 1.5, 1.75, 2, 2.25, 2.5, 2.75, 3, 3.5, 4, 4.5, 5, 5.5, 6, 7, 8, 9, 10]
 H, NH = 128, 16
@@ -309,100 +310,48 @@ def _edge_mlp_pre(P, name, W_off, dst_tab, src_tab, dst, src, extra):
 
 def check_batch_layout(batch_protein, batch_ligand, ligand_fc_bond_index, batch_ligand_bond=None):
     """The layout both network paths assume, checked once per call (never silently wrong triplets / gradients): sorted
-    PyG batch vectors and, per sample, the dst-major fully connected bond list of FeaturizeLigandBond('fc')
-    (utils/transforms.py:331-337) offset by the sample's first ligand row (utils/data.py:443-444).
-    Returns (n_p, n_l) per sample as python lists."""
-    for name, t in (("batch_protein", batch_protein), ("batch_ligand", batch_ligand)):
-        if t.numel() == 0:
-            raise ValueError("empty batch")
-        if t.numel() > 1 and bool((t[1:] < t[:-1]).any().item()):
-            raise NotImplementedError(f"{name} must be sorted (PyG Batch order)")
-    B = int(batch_protein.max().item()) + 1
-    n_p = torch.bincount(batch_protein, minlength=B).tolist()
-    n_l = torch.bincount(batch_ligand, minlength=B).tolist()
-    if len(n_l) != B or min(n_p) < 1 or min(n_l) < 2:
-        raise NotImplementedError("every sample needs protein atoms and at least 2 ligand atoms")
-    dev = ligand_fc_bond_index.device
-    exp, off = [], 0
-    for n in n_l:
-        dst = torch.arange(n, device=dev).repeat_interleave(n - 1)
-        sp = torch.arange(n - 1, device=dev).repeat(n)
-        exp.append(torch.stack([sp + (sp >= dst).long(), dst], 0) + off)
-        off += n
-    exp = torch.cat(exp, 1)
-    if ligand_fc_bond_index.shape != exp.shape or not torch.equal(ligand_fc_bond_index, exp):
-        raise NotImplementedError("ligand_fc_bond_index must be the dst-major fully connected graph ('fc' mode)")
-    if batch_ligand_bond is not None:
-        want = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor([n * (n - 1) for n in n_l], device=dev))
-        if batch_ligand_bond.shape != want.shape or not torch.equal(batch_ligand_bond, want):
-            raise NotImplementedError("batch_ligand_bond does not match the fully connected bond lists")
-    return n_p, n_l
+    PyG batch vectors and, per sample, the dst-major fully connected bond list of FeaturizeLigandBond('fc') offset by the
+    sample's first ligand row (`BatchLayout.from_batch`).  Returns (n_p, n_l) per sample as python lists."""
+    lay = BatchLayout.from_batch(batch_protein, batch_ligand, batch_ligand_bond=batch_ligand_bond,
+                                 ligand_fc_bond_index=ligand_fc_bond_index)
+    return lay.n_p, lay.n_l
 
 
 def network_grouped(net, model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, ligand_v_aux, batch_ligand,
                     ligand_fc_bond_index, ligand_bond_type, sizes=None) -> Dict[str, torch.Tensor]:
     """``net`` (``network`` or the fused forward) on a batch whose samples differ in size -- what the reference's training
     batches are (batch_size 4 of different complexes, configs/training.yml:62): samples of equal (protein, ligand) size
-    form one dense sub-batch each, the outputs are put back in the caller's row order (differentiable: cat + index_select).
-    Exact because every graph op of the network is segmented by sample."""
-    n_p, n_l = sizes if sizes is not None else check_batch_layout(batch_protein, batch_ligand, ligand_fc_bond_index)
-    B, dev = len(n_p), protein_pos.device
-    if len(set(zip(n_p, n_l))) == 1:
+    form one dense sub-batch each (`BatchLayout.size_groups`), the outputs are put back in the caller's row order
+    (differentiable: cat + index_select).  Exact because every graph op of the network is segmented by sample."""
+    lay = BatchLayout(*(sizes if sizes is not None else check_batch_layout(batch_protein, batch_ligand, ligand_fc_bond_index)))
+    B, dev = lay.B, protein_pos.device
+    if lay.is_dense:
         if net is network and sizes is not None:            # (layout established by check_batch_layout: no re-check, no sync)
             return net(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, ligand_v_aux, batch_ligand,
                        ligand_fc_bond_index, ligand_bond_type, checked_B=B)
         return net(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, ligand_v_aux, batch_ligand,
                    ligand_fc_bond_index, ligand_bond_type)
     if net is network and os.environ.get("DD_TRAIN_PAD", "1") != "0":
-        out = network_padded(model, protein_pos, protein_v, ligand_pos, ligand_v, ligand_v_aux, ligand_bond_type, n_p, n_l)
+        out = network_padded(model, protein_pos, protein_v, ligand_pos, ligand_v, ligand_v_aux, ligand_bond_type, lay.n_p, lay.n_l)
         if out is not None:
             return out
-    o_p = [0] + list(torch.tensor(n_p).cumsum(0).tolist())
-    o_l = [0] + list(torch.tensor(n_l).cumsum(0).tolist())
-    n_b = [n * (n - 1) for n in n_l]
-    o_b = [0] + list(torch.tensor(n_b).cumsum(0).tolist())
-    groups: Dict = {}
-    for b in range(B):
-        groups.setdefault((n_p[b], n_l[b]), []).append(b)
     outs, rows_l, rows_b = [], [], []
-    ar = lambda a, n: torch.arange(a, a + n, device=dev)
-    for (np_, nl_), members in groups.items():
-        rp = torch.cat([ar(o_p[b], np_) for b in members])
-        rl = torch.cat([ar(o_l[b], nl_) for b in members])
-        rb = torch.cat([ar(o_b[b], nl_ * (nl_ - 1)) for b in members])
-        g = len(members)
-        _, _, fc = model._expected_layout(g, np_, nl_, dev)
-        extra = {"checked_B": g} if net is network else {}      # (batch vectors and bond list built right here: no re-check, no sync)
-        outs.append(net(model, protein_pos[rp], protein_v[rp], torch.arange(g, device=dev).repeat_interleave(np_),
-                        ligand_pos[rl], ligand_v[rl], ligand_v_aux[rl], torch.arange(g, device=dev).repeat_interleave(nl_),
+    for g in lay.size_groups():
+        rp, rl, rb = g.rows_p.to(dev), g.rows_l.to(dev), g.rows_b.to(dev)
+        b_p, b_l, fc = model._expected_layout(len(g.ids), g.n_p, g.n_l, dev)
+        extra = {"checked_B": len(g.ids)} if net is network else {}     # (batch vectors and bond list built right here: no re-check, no sync)
+        outs.append(net(model, protein_pos[rp], protein_v[rp], b_p, ligand_pos[rl], ligand_v[rl], ligand_v_aux[rl], b_l,
                         fc, ligand_bond_type[rb], **extra))
         rows_l.append(rl)
         rows_b.append(rb)
-    inv_l = torch.empty(o_l[-1], dtype=torch.long, device=dev)
-    inv_l[torch.cat(rows_l)] = torch.arange(o_l[-1], device=dev)
-    inv_b = torch.empty(o_b[-1], dtype=torch.long, device=dev)
-    inv_b[torch.cat(rows_b)] = torch.arange(o_b[-1], device=dev)
+    n_lig, n_bond = sum(lay.n_l), sum(lay.n_b)
+    inv_l = torch.empty(n_lig, dtype=torch.long, device=dev)
+    inv_l[torch.cat(rows_l)] = torch.arange(n_lig, device=dev)
+    inv_b = torch.empty(n_bond, dtype=torch.long, device=dev)
+    inv_b[torch.cat(rows_b)] = torch.arange(n_bond, device=dev)
     cat = lambda k, inv: torch.cat([o[k] for o in outs], 0).index_select(0, inv)
     return {"pred_ligand_pos": cat("pred_ligand_pos", inv_l), "pred_ligand_v": cat("pred_ligand_v", inv_l),
             "pred_bond": cat("pred_bond", inv_b)}
-
-
-def _pad_rows(n_p, n_l, NPm=None, NLm=None):
-    """Row maps of a heterogeneous batch into its padded dense layout (numpy, host): real protein / ligand rows and real bonds
-    (the caller's dst-major lists over n_l[b] atoms) -> rows of the [B*NPm] / [B*NLm] / [B*NLm(NLm-1)] padded arrays."""
-    import numpy as np
-    B = len(n_p)
-    NPm, NLm = NPm or max(n_p), NLm or max(n_l)
-    Ebm = NLm * (NLm - 1)
-    rows_p = np.concatenate([b * NPm + np.arange(n) for b, n in enumerate(n_p)])
-    rows_l = np.concatenate([b * NLm + np.arange(n) for b, n in enumerate(n_l)])
-    rb = []
-    for b, n in enumerate(n_l):
-        dst = np.repeat(np.arange(n), n - 1)
-        sp = np.tile(np.arange(n - 1), n)
-        src = sp + (sp >= dst)
-        rb.append(b * Ebm + dst * (NLm - 1) + (src - (src > dst)))
-    return rows_p, rows_l, np.concatenate(rb)
 
 
 def _far_positions(B, NPm, NLm, dev):
@@ -423,12 +372,11 @@ def network_padded(model, protein_pos, protein_v, ligand_pos, ligand_v, ligand_v
     pass instead of one per distinct size (4 x fewer launches of a host-bound step) for max-size padding waste in the NL^3
     triplet count.  Returns None if a sample has fewer than K + 1 real atoms (the per-sample kNN degree would differ)."""
     dev = protein_pos.device
-    B, NPm, NLm = len(n_p), max(n_p), max(n_l)
-    N = NPm + NLm
-    K = min(int(model.config.knn), N - 1)
-    if min(a + b for a, b in zip(n_p, n_l)) < K + 1:
+    lay = BatchLayout(n_p, n_l)
+    B, NPm, NLm = lay.B, max(n_p), max(n_l)
+    if not fits_padded(lay, model.config.knn, size_limits=False):       # (no size limits of its own: the kNN kernel refuses what it cannot do)
         return None
-    rows_p, rows_l, rows_b = (torch.from_numpy(r).to(dev) for r in _pad_rows(n_p, n_l))
+    rows_p, rows_l, rows_b = (r.to(dev) for r in lay.padded_rows())
     far_p, far_l = _far_positions(B, NPm, NLm, dev)
     pp = far_p.index_copy(0, rows_p, protein_pos.to(torch.float32))
     lp = far_l.index_copy(0, rows_l, ligand_pos.to(torch.float32))
@@ -481,11 +429,7 @@ def _structure(B, NP, NL, K, dev):
     N = NP + NL
     is_lig = torch.cat([torch.zeros(NP, dtype=torch.bool), torch.ones(NL, dtype=torch.bool)]).repeat(B).to(dev)
     lig_rows = is_lig.nonzero().squeeze(1)
-    # dst-major fully connected bond list of FeaturizeLigandBond('fc') (utils/transforms.py:331-337), per-sample offsets
-    d = torch.arange(NL, device=dev).repeat_interleave(NL - 1)
-    sp = torch.arange(NL - 1, device=dev).repeat(NL)
-    fc1 = torch.stack([sp + (sp >= d).long(), d], 0)
-    fc = torch.cat([fc1 + b * NL for b in range(B)], 1)
+    fc = fc_bond_index_batch([NL] * B, dev)
     bond_src, bond_dst = lig_rows[fc[0]], lig_rows[fc[1]]
     bsrc_loc, b_of_bond = fc[0] % NL, fc[0] // NL           # (padded batches: is the source atom of a bond real?)
     dst = torch.arange(B * N, device=dev).repeat_interleave(K)
@@ -898,15 +842,14 @@ def pad_prepared(model, prep: Dict, bucket=(32, 4)) -> Optional[Dict]:
     (1 real, 0 padding) and the real counts.  Runs outside any capture (its index maps have batch-dependent lengths); the result
     feeds `objective_padded`, whose tensors all have shapes that depend on (B, NPm, NLm) only.  None if a sample has fewer than
     K + 1 real atoms."""
-    n_p, n_l = prep["sizes"]
-    B = len(n_p)
+    lay = BatchLayout(*prep["sizes"])
+    B, n_p, n_l = lay.B, lay.n_p, lay.n_l
     up = lambda n, q: -(-n // q) * q
     NPm, NLm = up(max(n_p), int(bucket[0])), up(max(n_l), int(bucket[1]))
     dev = prep["protein_pos"].device
-    K = min(int(model.config.knn), NPm + NLm - 1)
-    if min(a + b for a, b in zip(n_p, n_l)) < K + 1:
+    if not fits_padded(lay, model.config.knn, NPm, NLm, size_limits=False):
         return None
-    rows_p, rows_l, rows_b = (torch.from_numpy(r).to(dev) for r in _pad_rows(n_p, n_l, NPm, NLm))
+    rows_p, rows_l, rows_b = (r.to(dev) for r in lay.padded_rows(NPm, NLm))
     Ebm = NLm * (NLm - 1)
     far_p, far_l = _far_positions(B, NPm, NLm, dev)
     z = lambda n, like, fill=0: torch.full((n,) + tuple(like.shape[1:]), fill, device=dev, dtype=like.dtype)
@@ -947,7 +890,7 @@ def objective_padded(model, pp: Dict) -> Dict:
     dev = pp["protein_pos"].device
     time_step = pp["time_step"]
     b_p, b_l, fc = model._expected_layout(B, NPm, NLm, dev)
-    b_b = torch.arange(B, device=dev).repeat_interleave(NLm * (NLm - 1))
+    b_b = batch_vector(B, NLm * (NLm - 1), dev)
     a = model.alphas_cumprod.index_select(0, time_step)
     a_pos = a[b_l].unsqueeze(-1)
     ligand_pos, centers, stds = pp["ligand_pos"], pp["centers"], pp["stds"]
@@ -1080,7 +1023,7 @@ class GraphedTrainStep:
                              prior_centers, prior_stds, prior_num_atoms, batch_prior, ligand_decomp_batch, ligand_fc_bond_index,
                              ligand_fc_bond_type, batch_ligand_bond, time_step=time_step)
         n_p, n_l = prep["sizes"]
-        dense = len(set(zip(n_p, n_l))) == 1
+        dense = BatchLayout(n_p, n_l).is_dense
         dev = protein_pos.device
         if os.environ.get("DD_TRAIN_GRAPH", "1") == "0":
             return self._eager(prep)
