@@ -95,8 +95,8 @@ static Profiler* g_prof = nullptr;
 
 struct ProfScope {
   hipStream_t st; int idx;
-  ProfScope(int cat, hipStream_t s) : st(s), idx(-1) {
-    if (g_prof && g_prof->n < Profiler::MAXEV) {
+  ProfScope(int cat, hipStream_t s, bool on = true) : st(s), idx(-1) {
+    if (on && g_prof && g_prof->n < Profiler::MAXEV) {
       idx = g_prof->n++;
       g_prof->cat[idx] = cat;
       (void)hipEventRecord(g_prof->start[idx], st);
@@ -133,16 +133,11 @@ struct DevCtx {
 };
 static DevCtx g_dev_ctx[16];
 static std::mutex g_capture_mutex;
-static DevCtx& dev_ctx() {
+static DevCtx& dev_ctx() {                       // (fetched once at the top of a forward)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
   return g_dev_ctx[dev];
 }
-#define g_side (dev_ctx().side)
-#define g_ev_qa_fork (dev_ctx().ev_qa_fork)
-#define g_ev_qb_fork (dev_ctx().ev_qb_fork)
-#define g_ev_fork (dev_ctx().ev_fork)
-#define g_ev_join (dev_ctx().ev_join)
 // Launch-schedule / kernel alternatives kept for A/B measurements (EXPERIMENTS.md).  They exist only in the measurement
 // build (`python -m decompdiff_amd.build --debug-options` -> lib/libdecompdiff_hip_dbg.so, -DDD_DEBUG_OPTIONS=1, selected
 // with DD_HIP_LIB); in the default library the values below are compile-time constants, the alternative paths are not
@@ -195,6 +190,11 @@ static bool lin_in_node_for(int B, int NL) {
 }
 DD_OPT g_head_rows_first = 0;              // dd_debug_set_option(29, v): see the head of forward_impl
 DD_OPT g_heads_early = 1;                  // dd_debug_set_option(28, v): heads' first Linear in the last layer's projection launch
+// Does this forward run lin_node inside the node launch?  (out_fc: the in-kernel lin_node has no node-output stage; fused: the
+// one-launch-per-sub-layer loop has no such launch.)  Asked by the layer loop, the heads at the tail and dd_workspace_view.
+static bool uses_lin_in_node(int B, int NL, bool out_fc, bool fused) {
+  return fused && !out_fc && lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early;
+}
 DD_OPT g_q_in_pos = 1;                     // dd_debug_set_option(9, v): coordinate query MLPs' second layer inside attn_pos
 extern int g_pos_waves;                     // dd_attention2.hip: waves per workgroup of the coordinate launch
 DD_OPT g_p2_in_pos = 0;                    // dd_debug_set_option(30, v): the projections of the new h ({P2, PL2}; in the last layer the
@@ -209,20 +209,20 @@ DD_OPT g_p2_in_pos = 0;                    // dd_debug_set_option(30, v): the pr
 // streams share the four queues (EXPERIMENTS.md R6-11; tools/two_lengths.py).
 static int g_side_low_priority = [] { const char* e = getenv("DD_SIDE_PRIO"); return (e && e[0] == '1') ? 1 : ((e && e[0] == '2') ? 2 : 0); }();
 static int g_overlap = 1;                     // measured in-process A/B: -3.5 % step time
-static int ensure_side_stream() {
-  if (g_side) return DD_OK;
+static int ensure_side_stream(DevCtx& dc) {
+  if (dc.side) return DD_OK;
   {
     int lo = 0, hi = 0;                                  // (DD_SIDE_PRIO=1: lowest priority -- side work fills CUs the main chain leaves idle)
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; (void)hipGetLastError(); }
-    if (hipStreamCreateWithPriority(&g_side, hipStreamNonBlocking, g_side_low_priority == 1 ? lo : (g_side_low_priority == 2 ? hi : 0)) != hipSuccess) return DD_ERR_HIP;
+    if (hipStreamCreateWithPriority(&dc.side, hipStreamNonBlocking, g_side_low_priority == 1 ? lo : (g_side_low_priority == 2 ? hi : 0)) != hipSuccess) return DD_ERR_HIP;
   }
   for (int i = 0; i < 8; ++i)
-    if (hipEventCreateWithFlags(&g_ev_qa_fork[i], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g_ev_qb_fork[i], hipEventDisableTiming) != hipSuccess)
+    if (hipEventCreateWithFlags(&dc.ev_qa_fork[i], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&dc.ev_qb_fork[i], hipEventDisableTiming) != hipSuccess)
       return DD_ERR_HIP;
   for (int i = 0; i < 9; ++i)
-    if (hipEventCreateWithFlags(&g_ev_fork[i], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g_ev_join[i], hipEventDisableTiming) != hipSuccess)
+    if (hipEventCreateWithFlags(&dc.ev_fork[i], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&dc.ev_join[i], hipEventDisableTiming) != hipSuccess)
       return DD_ERR_HIP;
   return DD_OK;
 }
@@ -329,39 +329,192 @@ static int launch_bond_head_pre_att(const dd_sampler* s, const Workspace& w, con
   return DD_OK;
 }
 
-// First-Linear projections of layer `ll` from h / h_bond (one launch) and the query MLPs' second layer (one launch):
-// the forward's own launches, also run by dd_layer0_tables on its 16-atom problem.
-// (anb != NULL: the previous layer's W_lin . A_nb is still pending on the ligand rows of h -- lin_node inside the node launch)
-static int launch_projections1(const dd_sampler* s, const Workspace& w, int ll, const float* h, float* P, hipStream_t sx,
-                               const float* anb = nullptr) {
-  const int B = s->B, NP = s->NP, NL = s->NL, N = NP + NL;
-  const int nE = B * NL * (NL - 1);
-  const long hN = (long)N * 128;
-  const float* W = s->weights;
-  auto LW = [&](int l, int slot) { return W + s->slot_off[(long)l * DD_NUM_LAYER_SLOTS + slot]; };
-  GemmArgs j[3] = {
-      gemm_args(h, B * N, 0, 128, B * N, LW(ll, DD_W_n1), LW(ll, DD_b_n1), nullptr, P, B * N, 0, 640, 640, 0),
-      gemm_args(h + (long)NP * 128, NL, hN, 128, B * NL, LW(ll, DD_W_l1), LW(ll, DD_b_l1), nullptr, w.PL, B * NL, 0, 1280, 1280, 0),
-      gemm_args(w.hb, nE, 0, 128, nE, LW(ll, DD_W_b1), LW(ll, DD_b_b1), nullptr, w.PB, nE, 0, 640, 640, 0)};
-  if (anb) {
-    j[0].X2 = anb; j[0].x2_N = N; j[0].x2_NP = NP;       // all-node rows: ligand rows n >= NP take row n - NP of their sample
-    j[1].X2 = anb; j[1].x2_N = NL; j[1].x2_NP = 0;       // ligand rows only
+// ---- forward context: where every launch's arguments are defined -----------------------------------------------------------
+// Jobs of up to six GEMMs for one launch_gemm128_batch call, appended one by one.
+struct GemmList {
+  GemmArgs j[6];
+  int n = 0;
+  void add(const GemmArgs& g) { j[n++] = g; }
+  int launch(hipStream_t st) const { return launch_gemm128_batch(j, n, st); }
+};
+
+// g with W_lin . A_nb (still pending on the ligand rows of the h it reads) added to its X rows: all nodes of the batch (ligand
+// rows n >= NP take row n - NP of their sample) or the ligand rows only.  anb == NULL: nothing is pending, g as it is.
+static GemmArgs add_anb(GemmArgs g, const float* anb, bool all_nodes, int NP, int NL) {
+  if (anb) { g.X2 = anb; g.x2_N = all_nodes ? NP + NL : NL; g.x2_NP = all_nodes ? NP : 0; }
+  return g;
+}
+
+// What the sampler, the carved workspace and the shape say about each launch of a forward: one builder per GEMM job and per
+// attention sub-layer of the network.  The schedules (forward_impl's two loops, forward_tail) only decide which jobs share a
+// launch, on which stream, in which order, and set the few fields that depend on that.
+struct Fwd {
+  const dd_sampler* s;
+  Workspace w;
+  int B, NP, NL, K, N, nE;
+  long Eb, hN;
+  explicit Fwd(const dd_sampler* s_)
+      : s(s_), w(carve(s_->workspace, s_->B, s_->NP, s_->NL, s_->K)), B(s_->B), NP(s_->NP), NL(s_->NL), K(s_->K), N(s_->NP + s_->NL),
+        nE((int)((long)s_->B * s_->NL * (s_->NL - 1))), Eb((long)s_->NL * (s_->NL - 1)), hN((long)(s_->NP + s_->NL) * 128) {}
+  const float* LW(int l, int slot) const { return s->weights + s->slot_off[(long)l * DD_NUM_LAYER_SLOTS + slot]; }
+  const float* GW(int slot) const { return LW(s->num_layers, slot); }
+  GemmArgs add_anb(const GemmArgs& g, const float* anb, bool all_nodes) const { return dd::add_anb(g, anb, all_nodes, NP, NL); }
+  float* anb_buf(int l) const { return (l & 1) ? w.A : w.Anb; }   // lin_in_node: where layer l's NB blocks leave W_lin . A_nb
+
+  // -- first Linear of the node / bond sub-layers' MLPs from h / h_bond: columns [col0, col0 + ncols) of the 640-wide n1 and b1 rows
+  //    (forward_tail forms the query-hidden block [512, 640) ahead of the rest), all 1280 of l1 (ligand rows of h)
+  GemmArgs n1(int l, const float* h, int col0 = 0, int ncols = 640) const {
+    return gemm_args(h, B * N, 0, 128, B * N, LW(l, DD_W_n1) + col0 * 128, LW(l, DD_b_n1) + col0, nullptr, w.P + col0, B * N, 0, 640, ncols, 0);
   }
-  return launch_gemm128_batch(j, 3, sx);
-}
-static int launch_queries_q1(const dd_sampler* s, const Workspace& w, int ll, const float* P, float* qn, hipStream_t sx) {
-  const int B = s->B, NP = s->NP, NL = s->NL, N = NP + NL;
-  const long Eb = (long)NL * (NL - 1);
-  const int nE = (int)(B * Eb);
-  const float* W = s->weights;
-  auto LW = [&](int l, int slot) { return W + s->slot_off[(long)l * DD_NUM_LAYER_SLOTS + slot]; };
-  GemmArgs j[3] = {
-      gemm_args(w.PB + 512, nE, 0, 640, nE, LW(ll, DD_BL_W2q), LW(ll, DD_BL_b2q), LW(ll, DD_BL_lnq), w.qb, nE, 0, 128, 128, 0),
-      gemm_args(P + 512, B * N, 0, 640, B * N, LW(ll, DD_NE_W2q), LW(ll, DD_NE_b2q), LW(ll, DD_NE_lnq), qn, B * N, 0, 128, 128, 0),
-      gemm_args(w.PL + 512, B * NL, 0, 1280, B * NL, LW(ll, DD_NB_W2q), LW(ll, DD_NB_b2q), LW(ll, DD_NB_lnq), w.qlnb, B * NL, 0, 128, 128, 0)};
-  j[0].X2 = w.PL + 1152; j[0].x2_N = NL; j[0].x2_Eb = (int)Eb; j[0].x2_NLm1 = NL - 1; j[0].x2_ld = 1280;
-  return launch_gemm128_batch(j, 3, sx);
-}
+  // (dd_layer0_prepare: the protein rows of layer 0 alone, static per chain, mapped into the [B, N] table s->l0_P)
+  GemmArgs n1_l0_protein() const {
+    return gemm_args(s->protein_h, NP, (long)NP * 128, 128, B * NP, LW(0, DD_W_n1), LW(0, DD_b_n1), nullptr, s->l0_P, NP, (long)N * 640, 640, 640, 0);
+  }
+  GemmArgs l1(int l, const float* h) const {
+    return gemm_args(h + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l1), LW(l, DD_b_l1), nullptr, w.PL, B * NL, 0, 1280, 1280, 0);
+  }
+  GemmArgs b1(int l, int col0 = 0, int ncols = 640) const {
+    return gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b1) + col0 * 128, LW(l, DD_b_b1) + col0, nullptr, w.PB + col0, nE, 0, 640, ncols, 0);
+  }
+  // -- the same for the coordinate sub-layers, from the new h / h_bond
+  GemmArgs n2(int l, const float* h) const {
+    return gemm_args(h, B * N, 0, 128, B * N, LW(l, DD_W_n2), LW(l, DD_b_n2), nullptr, w.P2, B * N, 0, 256, 256, 0);
+  }
+  GemmArgs l2(int l, const float* h) const {
+    return gemm_args(h + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l2), LW(l, DD_b_l2), nullptr, w.PL2, B * NL, 0, 1024, 1024, 0);
+  }
+  GemmArgs b2(int l) const { return gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0); }
+  // -- query MLPs, second Linear (LayerNorm + ReLU prologue).  Bond layer: the hidden row is q_hb[bond] + q_hi[destination atom],
+  //    summed while the tile stages its rows (x2_sum), or read from w.q1bl where the assemble launch left the sum
+  GemmArgs q_bl(int l, bool x2_sum) const {
+    GemmArgs g = gemm_args(x2_sum ? w.PB + 512 : w.q1bl, nE, 0, x2_sum ? 640 : 128, nE, LW(l, DD_BL_W2q), LW(l, DD_BL_b2q), LW(l, DD_BL_lnq),
+                           w.qb, nE, 0, 128, 128, 0);
+    if (x2_sum) { g.X2 = w.PL + 1152; g.x2_N = NL; g.x2_Eb = (int)Eb; g.x2_NLm1 = NL - 1; g.x2_ld = 1280; }
+    return g;
+  }
+  GemmArgs q_ne(int l) const {
+    return gemm_args(w.P + 512, B * N, 0, 640, B * N, LW(l, DD_NE_W2q), LW(l, DD_NE_b2q), LW(l, DD_NE_lnq), w.qn, B * N, 0, 128, 128, 0);
+  }
+  GemmArgs q_ne_l0_protein() const {                     // (the same rows' node queries, s->l0_P -> s->l0_qn)
+    return gemm_args(s->l0_P + 512, NP, (long)N * 640, 640, B * NP, LW(0, DD_NE_W2q), LW(0, DD_NE_b2q), LW(0, DD_NE_lnq), s->l0_qn, NP,
+                     (long)N * 128, 128, 128, 0);
+  }
+  GemmArgs q_nb(int l) const {
+    return gemm_args(w.PL + 512, B * NL, 0, 1280, B * NL, LW(l, DD_NB_W2q), LW(l, DD_NB_b2q), LW(l, DD_NB_lnq), w.qlnb, B * NL, 0, 128, 128, 0);
+  }
+  // (coordinate sub-layers: only where the coordinate launch does not evaluate them itself, see q_in_pos)
+  GemmArgs q_pe(int l) const {
+    return gemm_args(w.PL2 + 256, B * NL, 0, 1024, B * NL, LW(l, DD_PE_W2q), LW(l, DD_PE_b2q), LW(l, DD_PE_lnq), w.ql, B * NL, 0, 128, 128, 0);
+  }
+  GemmArgs q_pb(int l) const {
+    return gemm_args(w.PL2 + 896, B * NL, 0, 1024, B * NL, LW(l, DD_PB_W2q), LW(l, DD_PB_b2q), LW(l, DD_PB_lnq), w.ql2, B * NL, 0, 128, 128, 0);
+  }
+  // -- h_out = h + lin_node(A) (+ A_nb on the ligand rows, where the NB sub-layer left it in a buffer of its own)
+  GemmArgs lin(int l, float* h, const float* anb) const {
+    return add_anb(gemm_args(w.A, B * N, 0, 128, B * N, LW(l, DD_W_lin), LW(l, DD_b_lin), nullptr, h, B * N, 0, 128, 128, 1), anb, true);
+  }
+  // -- heads, first Linear (decompdiff.py:194-211): bond head on h_bond, v head on the ligand rows of h; pre_att bond head:
+  //    P = W_p h of the ligand rows (w.P is free after the node launch)
+  GemmArgs bond_head1() const { return gemm_args(w.hb, nE, 0, 128, nE, GW(DD_G_BH_W1), GW(DD_G_BH_b1), nullptr, w.qb, nE, 0, 128, 128, 0); }
+  GemmArgs v_head1(const float* h) const {   // (hidden -> qn: ql may still be read by the overlapped coordinate sub-layer)
+    return gemm_args(h + (long)NP * 128, NL, hN, 128, B * NL, GW(DD_G_VH_W1), GW(DD_G_VH_b1), nullptr, w.qn, B * NL, 0, 128, 128, 0);
+  }
+  GemmArgs pre_att_p(const dd_bond_head* bh, const float* h) const {
+    return gemm_args(h + (long)NP * 128, NL, hN, 128, B * NL, bh->W_p, nullptr, nullptr, w.P, B * NL, 0, 128, 128, 0);
+  }
+
+  // First-Linear projections of layer `l` from h / h_bond (one launch) and the query MLPs' second layer (one launch):
+  // the forward's own launches, also run by dd_layer0_tables on its 16-atom problem.
+  // (anb != NULL: the previous layer's W_lin . A_nb is still pending on the ligand rows of h -- lin_node inside the node launch)
+  int launch_projections1(int l, const float* h, hipStream_t sx, const float* anb = nullptr) const {
+    GemmList j;
+    j.add(add_anb(n1(l, h), anb, true));
+    j.add(add_anb(l1(l, h), anb, false));
+    j.add(b1(l));
+    return j.launch(sx);
+  }
+  int launch_queries(int l, bool x2_sum, hipStream_t sx) const {
+    GemmList j;
+    j.add(q_bl(l, x2_sum));
+    j.add(q_ne(l));
+    j.add(q_nb(l));
+    return j.launch(sx);
+  }
+
+  // -- attention sub-layers at layer l, positions x: what every schedule passes; the call sites add what depends on the schedule
+  AttnArgs attn_common(const float* x) const {
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.np_real = s->np_real; a.nl_real = s->nl_real;
+    a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = x;
+    return a;
+  }
+  // node_layer_with_edge (l0_here: this layer's projection / query rows came from the layer-0 tables)
+  AttnArgs attn_ne(int l, const float* x, bool l0_here) const {
+    AttnArgs ne = attn_common(x);
+    ne.nbr = w.nbr; ne.ew = w.ew;
+    const float* Pn = l0_here ? s->l0_P : w.P;
+    ne.kd = Pn; ne.ks = Pn + 128; ne.vd = Pn + 256; ne.vs = Pn + 384; ne.ld_kd = ne.ld_ks = ne.ld_vd = ne.ld_vs = 640;
+    ne.q = l0_here ? s->l0_qn : w.qn; ne.Akp = LW(l, DD_NE_Akp); ne.Avp = LW(l, DD_NE_Avp); ne.lnk = LW(l, DD_NE_lnk); ne.lnv = LW(l, DD_NE_lnv);
+    ne.W2k = LW(l, DD_NE_W2k); ne.W2v = LW(l, DD_NE_W2v); ne.b2v = LW(l, DD_NE_b2v); ne.out = w.A;
+    // persistent node_layer_with_edge workgroups of the fused launch: two block counters per layer, DD_NUM_COUNTERS holds 32 layers' worth
+    ne.work_counter = (l < 32) ? w.counters + 128 + 2 * l : nullptr;
+    return ne;
+  }
+  // node_layer_with_bond: its rows [B * NL, 128] assigned to a buffer of their own
+  AttnArgs attn_nb(int l, const float* x) const {
+    AttnArgs nb = attn_common(x);
+    nb.kd = w.PL; nb.ks = w.PL + 128; nb.vd = w.PL + 256; nb.vs = w.PL + 384; nb.ld_kd = nb.ld_ks = nb.ld_vd = nb.ld_vs = 1280;
+    nb.ke = w.PB; nb.ve = w.PB + 128; nb.ld_ke = nb.ld_ve = 640;
+    nb.q = w.qlnb; nb.lnk = LW(l, DD_NB_lnk); nb.lnv = LW(l, DD_NB_lnv);
+    nb.W2k = LW(l, DD_NB_W2k); nb.W2v = LW(l, DD_NB_W2v); nb.b2v = LW(l, DD_NB_b2v); nb.out = w.Anb; nb.out_assign = 1;
+    return nb;
+  }
+  // bond_layer (residual add into h_bond)
+  AttnArgs attn_bl(int l, const float* x) const {
+    AttnArgs bl = attn_common(x);
+    bl.bl_prefix = s->bl_prefix;
+    bl.ke = w.Ek; bl.ve = w.Ev; bl.ld_ke = bl.ld_ve = 128;
+    bl.q = w.qb; bl.Wakp = LW(l, DD_BL_Wakp); bl.Wavp = LW(l, DD_BL_Wavp);
+    bl.lnk = LW(l, DD_BL_lnk); bl.lnv = LW(l, DD_BL_lnv);
+    bl.W2k = LW(l, DD_BL_W2k); bl.W2v = LW(l, DD_BL_W2v); bl.b2v = LW(l, DD_BL_b2v); bl.out = w.hb;
+    bl.Rk = w.Rk; bl.Rv = w.Rv;
+    bl.work_counter = w.counters + l;                    // persistent workgroups; [0, 64) of the counters: check_shapes keeps num_layers <= 64
+    return bl;
+  }
+  // pos_layer_with_edge / pos_layer_with_bond
+  AttnArgs attn_pe(int l, const float* x) const {
+    AttnArgs pe = attn_common(x);
+    pe.nbr = w.nbr; pe.ew = w.ew;
+    pe.kd = w.PL2; pe.vd = w.PL2 + 128; pe.ld_kd = pe.ld_vd = 1024; pe.ks = w.P2; pe.vs = w.P2 + 128; pe.ld_ks = pe.ld_vs = 256;
+    pe.q = w.ql; pe.Akp = LW(l, DD_PE_Akp); pe.Avp = LW(l, DD_PE_Avp); pe.lnk = LW(l, DD_PE_lnk); pe.lnv = LW(l, DD_PE_lnv);
+    pe.W2k = LW(l, DD_PE_W2k); pe.W2v16 = LW(l, DD_PE_W2v); pe.b2v16 = LW(l, DD_PE_b2v); pe.out = w.dxe;
+    return pe;
+  }
+  AttnArgs attn_pb(int l, const float* x) const {
+    AttnArgs pb = attn_common(x);
+    pb.kd = w.PL2 + 384; pb.ks = w.PL2 + 512; pb.vd = w.PL2 + 640; pb.vs = w.PL2 + 768; pb.ld_kd = pb.ld_ks = pb.ld_vd = pb.ld_vs = 1024;
+    pb.ke = w.PB2; pb.ve = w.PB2 + 128; pb.ld_ke = pb.ld_ve = 256;
+    pb.q = w.ql2; pb.lnk = LW(l, DD_PB_lnk); pb.lnv = LW(l, DD_PB_lnv);
+    pb.W2k = LW(l, DD_PB_W2k); pb.W2v16 = LW(l, DD_PB_W2v); pb.b2v16 = LW(l, DD_PB_b2v); pb.out = w.dxb;
+    return pb;
+  }
+  // q_in_pos: the coordinate launch evaluates the second layer of its query MLPs itself (q_pe / q_pb are then not launched)
+  void set_q_in_pos(int l, AttnArgs& pe, AttnArgs& pb) const {
+    pe.qhid = w.PL2 + 256; pe.ld_qhid = 1024; pe.lnq = LW(l, DD_PE_lnq); pe.W2q = LW(l, DD_PE_W2qT); pe.b2q = LW(l, DD_PE_b2q);
+    pb.qhid = w.PL2 + 896; pb.ld_qhid = 1024; pb.lnq = LW(l, DD_PB_lnq); pb.W2q = LW(l, DD_PB_W2qT); pb.b2q = LW(l, DD_PB_b2q);
+  }
+
+  // head of a forward (dd_graph.hip): kNN graph + edge weights (parts & 1), embeddings / context / zeroed counters + layer-0 rows
+  // (parts & 2; l0: gathered from the tables).  advance != NULL: the launch advances the step counter too.
+  int launch_head(hipStream_t sx, int parts, bool l0, int32_t* advance) const {
+    return launch_head_all(s->protein_h, s->protein_pos, s->lig_pos, s->lig_v, s->lig_aux, GW(DD_G_W_lemb), GW(DD_G_b_lemb), B, NP, NL,
+                           K, w.h, w.xa, w.xb, s->lig_bond, (long)B * Eb, GW(DD_G_W_bemb), GW(DD_G_b_bemb), w.hb, w.counters, advance,
+                           w.nbr, w.ew, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2), GW(DD_G_EW_b2),
+                           s->np_real, s->nl_real, l0 ? s->l0_tables : nullptr, s->l0_P, w.PL, s->l0_qn, w.qlnb, w.PB, w.qb, sx, parts,
+                           num_v(s));
+  }
+};
 
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
 // ---------------------------------------------------------------------------------------------------------------------
@@ -373,44 +526,32 @@ static int launch_queries_q1(const dd_sampler* s, const Workspace& w, int ll, co
 // per forward).  Bit-identical to schedule 4, 31 instead of 51 launches per step, and SLOWER (1.41 vs 1.24 ms/step): a
 // polling consumer with a large per-CU footprint keeps the producers' workgroups off the chip.  `two_streams` false
 // (profiling): the same launches on one stream -- every wait is then satisfied when it is reached.
-static int forward_tail(const dd_sampler* s, hipStream_t st, StepFold* fold, bool two_streams) {
-  const int B = s->B, NP = s->NP, NL = s->NL, K = s->K, N = NP + NL, L = s->num_layers;
-  const long Eb = (long)NL * (NL - 1);
-  const int nE = (int)(B * Eb);
-  Workspace w = carve(s->workspace, B, NP, NL, K);
-  const float* W = s->weights;
-  const int64_t* off = s->slot_off;
-  auto LW = [&](int l, int slot) { return W + off[(long)l * DD_NUM_LAYER_SLOTS + slot]; };
-  auto GW = [&](int slot) { return W + off[(long)L * DD_NUM_LAYER_SLOTS + slot]; };
+static int forward_tail(const Fwd& f, DevCtx& dc, hipStream_t st, StepFold* fold, bool two_streams) {
+  const dd_sampler* s = f.s;
+  const Workspace& w = f.w;
+  const int B = f.B, NP = f.NP, NL = f.NL, N = f.N, nE = f.nE, L = s->num_layers;
   int32_t* flags = w.counters + DD_NUM_COUNTERS;
-  auto FL = [&](int l, int f) { return (l * DD_FLAGS_PER_LAYER + f) * DD_FLAG_STRIDE; };
-  const long hN = (long)N * 128;
-  if (two_streams) DD_TRY(ensure_side_stream());
+  auto FL = [&](int l, int fl) { return (l * DD_FLAGS_PER_LAYER + fl) * DD_FLAG_STRIDE; };
+  if (two_streams) DD_TRY(ensure_side_stream(dc));
   const bool l0 = g_l0_tables && s->l0_tables && s->l0_P && s->l0_qn && s->nl_real == nullptr;
   int32_t* advance = (fold && fold->advance) ? s->step_counter : nullptr;
 
   // ---- head of the forward: kNN graph + edge weights (side stream) beside embeddings / context / zeroed counters and
   //      flags / layer-0 rows (main stream); decompdiff.py:219-297, uni_transformer_edge.py:404-427
-  auto head = [&](hipStream_t sx, int parts) -> int {
-    return launch_head_all(s->protein_h, s->protein_pos, s->lig_pos, s->lig_v, s->lig_aux, GW(DD_G_W_lemb), GW(DD_G_b_lemb), B, NP, NL,
-                           K, w.h, w.xa, w.xb, s->lig_bond, (long)B * Eb, GW(DD_G_W_bemb), GW(DD_G_b_bemb), w.hb, w.counters, advance,
-                           w.nbr, w.ew, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2), GW(DD_G_EW_b2),
-                           s->np_real, s->nl_real, l0 ? s->l0_tables : nullptr, s->l0_P, w.PL, s->l0_qn, w.qlnb, w.PB, w.qb, sx, parts, num_v(s));
-  };
   bool head_join = false;
   if (two_streams) {
-    if (hipEventRecord(g_ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(g_side, g_ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
-    DD_TRY(head(g_side, 1));
-    if (hipEventRecord(g_ev_join[8], g_side) != hipSuccess) return DD_ERR_HIP;
+    if (hipEventRecord(dc.ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(dc.side, dc.ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
+    DD_TRY(f.launch_head(dc.side, 1, l0, advance));
+    if (hipEventRecord(dc.ev_join[8], dc.side) != hipSuccess) return DD_ERR_HIP;
     head_join = true;
-    DD_TRY(head(st, 2));
+    DD_TRY(f.launch_head(st, 2, l0, advance));
   } else {
-    DD_TRYP(DD_PROF_MISC, head(st, 2));
-    DD_TRYP(DD_PROF_MISC, head(st, 1));
+    DD_TRYP(DD_PROF_MISC, f.launch_head(st, 2, l0, advance));
+    DD_TRYP(DD_PROF_MISC, f.launch_head(st, 1, l0, advance));
   }
   if (!l0) {                                             // first layer's projections / queries as GEMMs (no tables)
-    DD_TRYP(DD_PROF_GEMM, launch_projections1(s, w, 0, w.h, w.P, st));
-    DD_TRYP(DD_PROF_GEMM, launch_queries_q1(s, w, 0, w.P, w.qn, st));
+    DD_TRYP(DD_PROF_GEMM, f.launch_projections1(0, w.h, st));
+    DD_TRYP(DD_PROF_GEMM, f.launch_queries(0, true, st));
   }
   // tile counts of the queue's jobs (targets of the counters)
   const int n_lin = gemm_tiles(B * N, 128), n_p2 = gemm_tiles(B * N, 256), n_pl2 = gemm_tiles(B * NL, 1024), n_pb2 = gemm_tiles(nE, 256);
@@ -426,42 +567,20 @@ static int forward_tail(const dd_sampler* s, hipStream_t st, StepFold* fold, boo
     // ---- assemble (bond_layer first-Linear partial sums; applies the previous layer's coordinate update)
     FlagWait fw = no_wait();
     if (l > 0) fw = FlagWait{flags, FL(l - 1, DD_FLAG_PB1R), n_pb1r, FL(l - 1, DD_FLAG_PL1), n_pl1};
-    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev, nullptr, w.Rk, w.Rv, st,
+    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, f.LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev, nullptr, w.Rk, w.Rv, st,
                                                   xup_prev, w.dxe, w.dxb, xup_prev ? xcur : nullptr, fw));
     xup_prev = nullptr;
     if (head_join) {                                     // kNN graph + edge weights: first needed by the node attention
-      if (hipStreamWaitEvent(st, g_ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
+      if (hipStreamWaitEvent(st, dc.ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
       head_join = false;
     }
     // ---- node_layer_with_edge + node_layer_with_bond + bond_layer: one launch (uni_transformer_edge.py:42-167)
     {
-      const bool l0_here = l0 && l == 0;
-      AttnArgs ne, nb, bl;
-      memset(&ne, 0, sizeof(ne)); memset(&nb, 0, sizeof(nb)); memset(&bl, 0, sizeof(bl));
-      ne.np_real = nb.np_real = bl.np_real = s->np_real; ne.nl_real = nb.nl_real = bl.nl_real = s->nl_real;
-      bl.bl_prefix = s->bl_prefix;
-      ne.B = B; ne.NP = NP; ne.NL = NL; ne.K = K; ne.x = xcur; ne.nbr = w.nbr; ne.ew = w.ew;
-      const float* Pn = l0_here ? s->l0_P : w.P;
-      ne.kd = Pn; ne.ks = Pn + 128; ne.vd = Pn + 256; ne.vs = Pn + 384; ne.ld_kd = ne.ld_ks = ne.ld_vd = ne.ld_vs = 640;
-      ne.q = l0_here ? s->l0_qn : w.qn; ne.Akp = LW(l, DD_NE_Akp); ne.Avp = LW(l, DD_NE_Avp); ne.lnk = LW(l, DD_NE_lnk); ne.lnv = LW(l, DD_NE_lnv);
-      ne.W2k = LW(l, DD_NE_W2k); ne.W2v = LW(l, DD_NE_W2v); ne.b2v = LW(l, DD_NE_b2v); ne.out = w.A;
-      ne.work_counter = (l < 32) ? w.counters + 128 + 2 * l : nullptr;   // persistent node_layer_with_edge workgroups (two block counters)
-      nb.B = B; nb.NP = NP; nb.NL = NL; nb.K = K; nb.x = xcur;
-      nb.kd = w.PL; nb.ks = w.PL + 128; nb.vd = w.PL + 256; nb.vs = w.PL + 384; nb.ld_kd = nb.ld_ks = nb.ld_vd = nb.ld_vs = 1280;
-      nb.ke = w.PB; nb.ve = w.PB + 128; nb.ld_ke = nb.ld_ve = 640;
-      nb.q = w.qlnb; nb.lnk = LW(l, DD_NB_lnk); nb.lnv = LW(l, DD_NB_lnv);
-      nb.W2k = LW(l, DD_NB_W2k); nb.W2v = LW(l, DD_NB_W2v); nb.b2v = LW(l, DD_NB_b2v); nb.out = w.Anb; nb.out_assign = 1;
-      bl.B = B; bl.NP = NP; bl.NL = NL; bl.K = K; bl.x = xcur;
-      bl.ke = w.Ek; bl.ve = w.Ev; bl.ld_ke = bl.ld_ve = 128;
-      bl.q = w.qb; bl.Wakp = LW(l, DD_BL_Wakp); bl.Wavp = LW(l, DD_BL_Wavp);
-      bl.lnk = LW(l, DD_BL_lnk); bl.lnv = LW(l, DD_BL_lnv);
-      bl.W2k = LW(l, DD_BL_W2k); bl.W2v = LW(l, DD_BL_W2v); bl.b2v = LW(l, DD_BL_b2v); bl.out = w.hb;
-      bl.Rk = w.Rk; bl.Rv = w.Rv;
-      bl.work_counter = w.counters + l;
+      AttnArgs ne = f.attn_ne(l, xcur, l0 && l == 0);
       if (l > 0) {                                       // (its other inputs -- PB, PL -- were awaited by this layer's assemble)
         ne.wait_flags = flags; ne.wait_idx = FL(l - 1, DD_FLAG_NODE); ne.wait_n = n_q + n_p1r;
       }
-      DD_TRYP(DD_PROF_ATTN_BL, launch_attn2_node(ne, nb, bl, st));
+      DD_TRYP(DD_PROF_ATTN_BL, launch_attn2_node(ne, f.attn_nb(l, xcur), f.attn_bl(l, xcur), st));
     }
     // ---- the two tile queues of the layer: `ta` (lin_node + the coordinate sub-layers' projections: what the coordinate
     //      attention needs) on the main stream, `tb` (next layer's projections / queries, or the heads) on the side stream
@@ -475,75 +594,47 @@ static int forward_tail(const dd_sampler* s, hipStream_t st, StepFold* fold, boo
       const int fLIN = FL(l, DD_FLAG_LIN), fNODE = FL(l, DD_FLAG_NODE);
       const int fPOS = -1;                               // (the coordinate launch follows `ta` in stream order)
       int n = 0;
-      GemmArgs g = gemm_args(w.A, B * N, 0, 128, B * N, LW(l, DD_W_lin), LW(l, DD_b_lin), nullptr, w.h, B * N, 0, 128, 128, 1);
-      g.X2 = w.Anb; g.x2_N = N; g.x2_NP = NP;                                           // h += lin_node(A + A_nb on ligand rows)
-      ta.job[n++] = tail_job(g, -1, 0, fLIN);
+      ta.job[n++] = tail_job(f.lin(l, w.h, w.Anb), -1, 0, fLIN);                        // h += lin_node(A + A_nb on ligand rows)
       // (independent tiles right behind lin_node: the workgroups of the first wave work instead of polling for it)
-      ta.job[n++] = tail_job(gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0),
-                             -1, 0, fPOS);
-      ta.job[n++] = tail_job(gemm_args(w.h, B * N, 0, 128, B * N, LW(l, DD_W_n2), LW(l, DD_b_n2), nullptr, w.P2, B * N, 0, 256, 256, 0),
-                             fLIN, n_lin, fPOS);
-      ta.job[n++] = tail_job(gemm_args(w.h + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l2), LW(l, DD_b_l2), nullptr, w.PL2, B * NL,
-                                       0, 1024, 1024, 0), fLIN, n_lin, fPOS);
+      ta.job[n++] = tail_job(f.b2(l), -1, 0, fPOS);
+      ta.job[n++] = tail_job(f.n2(l, w.h), fLIN, n_lin, fPOS);
+      ta.job[n++] = tail_job(f.l2(l, w.h), fLIN, n_lin, fPOS);
       ta.njobs = n;
       n = 0;
       if (l + 1 < L) {
         const int ll = l + 1;
         const int fPL1 = FL(l, DD_FLAG_PL1), fP1Q = FL(l, DD_FLAG_P1Q), fPBQ = FL(l, DD_FLAG_PBQ), fPB1R = FL(l, DD_FLAG_PB1R);
         // next layer's projections: the query-hidden column blocks first (their consumers sit at the end of the list)
-        tb.job[n++] = tail_job(gemm_args(w.hb, nE, 0, 128, nE, LW(ll, DD_W_b1) + 512 * 128, LW(ll, DD_b_b1) + 512, nullptr, w.PB + 512,
-                                         nE, 0, 640, 128, 0), -1, 0, fPBQ);
-        tb.job[n++] = tail_job(gemm_args(w.h + (long)NP * 128, NL, hN, 128, B * NL, LW(ll, DD_W_l1), LW(ll, DD_b_l1), nullptr, w.PL,
-                                         B * NL, 0, 1280, 1280, 0), fLIN, n_lin, fPL1);
-        tb.job[n++] = tail_job(gemm_args(w.h, B * N, 0, 128, B * N, LW(ll, DD_W_n1) + 512 * 128, LW(ll, DD_b_n1) + 512, nullptr,
-                                         w.P + 512, B * N, 0, 640, 128, 0), fLIN, n_lin, fP1Q);
-        tb.job[n++] = tail_job(gemm_args(w.hb, nE, 0, 128, nE, LW(ll, DD_W_b1), LW(ll, DD_b_b1), nullptr, w.PB, nE, 0, 640, 512, 0),
-                               -1, 0, fPB1R);
-        tb.job[n++] = tail_job(gemm_args(w.h, B * N, 0, 128, B * N, LW(ll, DD_W_n1), LW(ll, DD_b_n1), nullptr, w.P, B * N, 0, 640, 512, 0),
-                               fLIN, n_lin, fNODE);
+        tb.job[n++] = tail_job(f.b1(ll, 512, 128), -1, 0, fPBQ);
+        tb.job[n++] = tail_job(f.l1(ll, w.h), fLIN, n_lin, fPL1);
+        tb.job[n++] = tail_job(f.n1(ll, w.h, 512, 128), fLIN, n_lin, fP1Q);
+        tb.job[n++] = tail_job(f.b1(ll, 0, 512), -1, 0, fPB1R);
+        tb.job[n++] = tail_job(f.n1(ll, w.h, 0, 512), fLIN, n_lin, fNODE);
         // next layer's query MLPs, second Linear (LayerNorm + ReLU prologue); the bond-layer hidden row is
         // q_hb[bond] + q_hi[destination atom], summed while the tile stages its rows
-        tb.job[n++] = tail_job(gemm_args(w.P + 512, B * N, 0, 640, B * N, LW(ll, DD_NE_W2q), LW(ll, DD_NE_b2q), LW(ll, DD_NE_lnq), w.qn,
-                                         B * N, 0, 128, 128, 0), fP1Q, n_p1q, fNODE);
-        tb.job[n++] = tail_job(gemm_args(w.PL + 512, B * NL, 0, 1280, B * NL, LW(ll, DD_NB_W2q), LW(ll, DD_NB_b2q), LW(ll, DD_NB_lnq),
-                                         w.qlnb, B * NL, 0, 128, 128, 0), fPL1, n_pl1, fNODE);
-        GemmArgs qb = gemm_args(w.PB + 512, nE, 0, 640, nE, LW(ll, DD_BL_W2q), LW(ll, DD_BL_b2q), LW(ll, DD_BL_lnq), w.qb, nE, 0, 128, 128, 0);
-        qb.X2 = w.PL + 1152; qb.x2_N = NL; qb.x2_Eb = (int)Eb; qb.x2_NLm1 = NL - 1; qb.x2_ld = 1280;
-        tb.job[n++] = tail_job(qb, fPBQ, n_pbq, fNODE, fPL1, n_pl1);
+        tb.job[n++] = tail_job(f.q_ne(ll), fP1Q, n_p1q, fNODE);
+        tb.job[n++] = tail_job(f.q_nb(ll), fPL1, n_pl1, fNODE);
+        tb.job[n++] = tail_job(f.q_bl(ll, true), fPBQ, n_pbq, fNODE, fPL1, n_pl1);
       } else {
-        // heads, first Linear (decompdiff.py:194-211): bond head on h_bond, v head on the ligand rows of the new h
-        tb.job[n++] = tail_job(gemm_args(w.hb, nE, 0, 128, nE, GW(DD_G_BH_W1), GW(DD_G_BH_b1), nullptr, w.qb, nE, 0, 128, 128, 0),
-                               -1, 0, fNODE);
-        tb.job[n++] = tail_job(gemm_args(w.h + (long)NP * 128, NL, hN, 128, B * NL, GW(DD_G_VH_W1), GW(DD_G_VH_b1), nullptr, w.qn,
-                                         B * NL, 0, 128, 128, 0), fLIN, n_lin, fNODE);
+        // heads, first Linear: bond head on h_bond, v head on the ligand rows of the new h
+        tb.job[n++] = tail_job(f.bond_head1(), -1, 0, fNODE);
+        tb.job[n++] = tail_job(f.v_head1(w.h), fLIN, n_lin, fNODE);
       }
       tb.njobs = n;
     }
     // ---- pos_layer_with_edge + pos_layer_with_bond: one launch (uni_transformer_edge.py:188-210), query MLPs inside
     {
-      AttnArgs pe, pb;
-      memset(&pe, 0, sizeof(pe)); memset(&pb, 0, sizeof(pb));
-      pe.np_real = pb.np_real = s->np_real; pe.nl_real = pb.nl_real = s->nl_real;
-      pe.B = B; pe.NP = NP; pe.NL = NL; pe.K = K; pe.x = xcur; pe.nbr = w.nbr; pe.ew = w.ew;
-      pe.kd = w.PL2; pe.vd = w.PL2 + 128; pe.ld_kd = pe.ld_vd = 1024; pe.ks = w.P2; pe.vs = w.P2 + 128; pe.ld_ks = pe.ld_vs = 256;
-      pe.q = w.ql; pe.Akp = LW(l, DD_PE_Akp); pe.Avp = LW(l, DD_PE_Avp); pe.lnk = LW(l, DD_PE_lnk); pe.lnv = LW(l, DD_PE_lnv);
-      pe.W2k = LW(l, DD_PE_W2k); pe.W2v16 = LW(l, DD_PE_W2v); pe.b2v16 = LW(l, DD_PE_b2v); pe.out = w.dxe;
-      pb.B = B; pb.NP = NP; pb.NL = NL; pb.K = K; pb.x = xcur;
-      pb.kd = w.PL2 + 384; pb.ks = w.PL2 + 512; pb.vd = w.PL2 + 640; pb.vs = w.PL2 + 768; pb.ld_kd = pb.ld_ks = pb.ld_vd = pb.ld_vs = 1024;
-      pb.ke = w.PB2; pb.ve = w.PB2 + 128; pb.ld_ke = pb.ld_ve = 256;
-      pb.q = w.ql2; pb.lnk = LW(l, DD_PB_lnk); pb.lnv = LW(l, DD_PB_lnv);
-      pb.W2k = LW(l, DD_PB_W2k); pb.W2v16 = LW(l, DD_PB_W2v); pb.b2v16 = LW(l, DD_PB_b2v); pb.out = w.dxb; pb.x_next = nullptr;
-      pe.qhid = w.PL2 + 256; pe.ld_qhid = 1024; pe.lnq = LW(l, DD_PE_lnq); pe.W2q = LW(l, DD_PE_W2qT); pe.b2q = LW(l, DD_PE_b2q);
-      pb.qhid = w.PL2 + 896; pb.ld_qhid = 1024; pb.lnq = LW(l, DD_PB_lnq); pb.W2q = LW(l, DD_PB_W2qT); pb.b2q = LW(l, DD_PB_b2q);
+      AttnArgs pe = f.attn_pe(l, xcur), pb = f.attn_pb(l, xcur);
+      f.set_q_in_pos(l, pe, pb);
       if (two_streams) {
         // Recording order matters: the graph runtime keeps the FIRST-recorded successor of a node on that node's hardware
         // queue and pays the cross-queue latency (7-12 us) on the others -- `ta`, which gates the coordinate attention,
         // is recorded first; `tb` has ~50 us of slack before its first consumer (the next assemble) polls its counters.
-        if (hipEventRecord(g_ev_fork[l], st) != hipSuccess) return DD_ERR_HIP;
+        if (hipEventRecord(dc.ev_fork[l], st) != hipSuccess) return DD_ERR_HIP;
         DD_TRY(launch_gemm_tail(ta, st));
-        if (hipStreamWaitEvent(g_side, g_ev_fork[l], 0) != hipSuccess) return DD_ERR_HIP;
-        DD_TRY(launch_gemm_tail(tb, g_side));
-        if (l + 1 == L && hipEventRecord(g_ev_join[l], g_side) != hipSuccess) return DD_ERR_HIP;
+        if (hipStreamWaitEvent(dc.side, dc.ev_fork[l], 0) != hipSuccess) return DD_ERR_HIP;
+        DD_TRY(launch_gemm_tail(tb, dc.side));
+        if (l + 1 == L && hipEventRecord(dc.ev_join[l], dc.side) != hipSuccess) return DD_ERR_HIP;
         DD_TRY(launch_attn2_pos(pe, pb, st));
       } else {
         DD_TRYP(DD_PROF_GEMM, launch_gemm_tail(ta, st));
@@ -559,8 +650,8 @@ static int forward_tail(const dd_sampler* s, hipStream_t st, StepFold* fold, boo
     }
     float* t = xcur; xcur = xnext; xnext = t;
   }
-  if (head_join && hipStreamWaitEvent(st, g_ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
-  if (two_streams && hipStreamWaitEvent(st, g_ev_join[L - 1], 0) != hipSuccess) return DD_ERR_HIP;   // last queue: the heads' hidden rows
+  if (head_join && hipStreamWaitEvent(st, dc.ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
+  if (two_streams && hipStreamWaitEvent(st, dc.ev_join[L - 1], 0) != hipSuccess) return DD_ERR_HIP;   // last queue: the heads' hidden rows
   if (!s->pred_pos) return DD_ERR_BAD_ARG;
   if (xup_prev != nullptr) {                             // folded tail: the step kernel applies the update and extracts x0
     fold->xprev = xup_prev;
@@ -589,28 +680,24 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   // x2h_out_fc: k_node_out_fc (node output MLPs + lin_node, one launch) takes the place of the lin_node GEMM job; the node
   // launch's in-kernel lin_node has no node-output stage, so lin_in_node is off for such a model
   const bool out_fc = no != nullptr;
-  const int B = s->B, NP = s->NP, NL = s->NL, K = s->K, N = NP + NL;
-  const long Eb = (long)NL * (NL - 1);
-  Workspace w = carve(s->workspace, B, NP, NL, K);
-  const float* W = s->weights;
-  const int64_t* off = s->slot_off;
-  auto LW = [&](int l, int slot) { return W + off[(long)l * DD_NUM_LAYER_SLOTS + slot]; };
-  auto GW = [&](int slot) { return W + off[(long)s->num_layers * DD_NUM_LAYER_SLOTS + slot]; };
+  const Fwd f(s);
+  const Workspace& w = f.w;
+  const int B = f.B, NP = f.NP, NL = f.NL, N = f.N, L = s->num_layers;
+  DevCtx& dc = dev_ctx();                                // side stream + fork / join events of this device
 
   float* xcur = w.xa;
   float* xnext = w.xb;
   float* hcur = w.h;                                     // (ping-pong with w.h2 under the one-fork schedule only)
-  const long hN = (long)N * 128;
   const bool fused = g_fuse && NL <= g_fused_max_nl && g_dbg_clock == nullptr;
-  const bool overlap = fused && g_overlap && g_prof == nullptr && s->num_layers <= 8;
+  const bool overlap = fused && g_overlap && g_prof == nullptr && L <= 8;
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
   if (out_fc && (g_sched >= 5 || g_side_lin)) return DD_ERR_UNSUPPORTED_SHAPE;   // (measurement schedules without the node-output stage)
-  if (fused && !pre_att && g_sched >= 5 && s->num_layers <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
+  if (fused && !pre_att && g_sched >= 5 && L <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
       g_xup_in_asm && !g_xup_in_pos)
-    return forward_tail(s, st, fold, overlap);
+    return forward_tail(f, dc, st, fold, overlap);
 #endif
   if (out_fc && !fused) return DD_ERR_UNSUPPORTED_SHAPE;   // (the one-launch-per-sub-layer loop has no node-output stage)
-  if (overlap) DD_TRY(ensure_side_stream());
+  if (overlap) DD_TRY(ensure_side_stream(dc));
 
   // layer-0 tables: the first layer's projection and query rows are gathered (ligand atoms: 16 combinations of class and
   // arm flag, bonds: type x destination combination; protein rows are static per chain) instead of two GEMM launches
@@ -624,27 +711,20 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     // on the main stream beside it -- two launches instead of four.  (Measured and dropped: all four bodies in one
     // kernel, +2.5 % step time -- one register allocation for every block kind, and assemble then waits for a graph it
     // does not need; rows first and the graph forked after them, +1 %.)
-    auto head = [&](hipStream_t sx, int parts) -> int {
-      return launch_head_all(s->protein_h, s->protein_pos, s->lig_pos, s->lig_v, s->lig_aux, GW(DD_G_W_lemb), GW(DD_G_b_lemb), B, NP, NL,
-                             K, w.h, w.xa, w.xb, s->lig_bond, (long)B * Eb, GW(DD_G_W_bemb), GW(DD_G_b_bemb), w.hb, w.counters, advance,
-                             w.nbr, w.ew, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2), GW(DD_G_EW_b2),
-                             s->np_real, s->nl_real, l0 ? s->l0_tables : nullptr, s->l0_P, w.PL, s->l0_qn, w.qlnb, w.PB, w.qb, sx,
-                             parts, num_v(s));
-    };
-    if (hipEventRecord(g_ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(g_side, g_ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
+    if (hipEventRecord(dc.ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(dc.side, dc.ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
     // (option 29: the rows launch is RECORDED first -- same dependencies, the fork point is the event above -- so that the graph
     // runtime, which keeps the first-recorded successor of a node on its hardware queue, leaves the main chain's launch on the
     // previous step kernel's queue and moves the graph construction, which has slack, to the other one)
-    if (g_head_rows_first) DD_TRYP(DD_PROF_MISC, head(st, 2));
-    DD_TRYP(DD_PROF_MISC, head(g_side, 1));
-    if (hipEventRecord(g_ev_join[8], g_side) != hipSuccess) return DD_ERR_HIP;
+    if (g_head_rows_first) DD_TRYP(DD_PROF_MISC, f.launch_head(st, 2, l0, advance));
+    DD_TRYP(DD_PROF_MISC, f.launch_head(dc.side, 1, l0, advance));
+    if (hipEventRecord(dc.ev_join[8], dc.side) != hipSuccess) return DD_ERR_HIP;
     head_join = true;
-    if (!g_head_rows_first) DD_TRYP(DD_PROF_MISC, head(st, 2));
+    if (!g_head_rows_first) DD_TRYP(DD_PROF_MISC, f.launch_head(st, 2, l0, advance));
   } else {
     // embeddings + context (decompdiff.py:219-297) and the zeroed work counters: one launch
-    DD_TRYP(DD_PROF_MISC, launch_embed_all(s->protein_h, s->protein_pos, s->lig_pos, s->lig_v, s->lig_aux, GW(DD_G_W_lemb),
-                                           GW(DD_G_b_lemb), B, NP, NL, w.h, w.xa, w.xb, s->lig_bond, (long)B * Eb, GW(DD_G_W_bemb),
-                                           GW(DD_G_b_bemb), w.hb, w.counters, st, advance, num_v(s)));
+    DD_TRYP(DD_PROF_MISC, launch_embed_all(s->protein_h, s->protein_pos, s->lig_pos, s->lig_v, s->lig_aux, f.GW(DD_G_W_lemb),
+                                           f.GW(DD_G_b_lemb), B, NP, NL, w.h, w.xa, w.xb, s->lig_bond, (long)B * f.Eb, f.GW(DD_G_W_bemb),
+                                           f.GW(DD_G_b_bemb), w.hb, w.counters, st, advance, num_v(s)));
     if (l0)
       DD_TRYP(DD_PROF_MISC, launch_layer0_rows(s->l0_tables, s->lig_v, s->lig_aux, s->lig_bond, B, NP, NL, s->l0_P, w.PL, s->l0_qn,
                                                 w.qlnb, w.PB, w.qb, st));
@@ -652,19 +732,23 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     // beside the bond embedding and the first layer's projections
     hipStream_t gs = st;
     if (overlap) {
-      if (hipEventRecord(g_ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(g_side, g_ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
-      gs = g_side;
+      if (hipEventRecord(dc.ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(dc.side, dc.ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
+      gs = dc.side;
     }
-    DD_TRYP(DD_PROF_MISC, launch_knn(w.xa, B, N, K, w.nbr, gs, NP, s->np_real, s->nl_real));
-    DD_TRYP(DD_PROF_MISC, launch_edge_weights(w.xa, w.nbr, B, N, K, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2),
-                               GW(DD_G_EW_b2), w.ew, gs, NP, s->np_real, s->nl_real));
+    DD_TRYP(DD_PROF_MISC, launch_knn(w.xa, B, N, f.K, w.nbr, gs, NP, s->np_real, s->nl_real));
+    DD_TRYP(DD_PROF_MISC, launch_edge_weights(w.xa, w.nbr, B, N, f.K, f.GW(DD_G_EW_W1T), f.GW(DD_G_EW_b1), f.GW(DD_G_EW_ln), f.GW(DD_G_EW_w2),
+                               f.GW(DD_G_EW_b2), w.ew, gs, NP, s->np_real, s->nl_real));
     if (overlap) {
-      if (hipEventRecord(g_ev_join[8], g_side) != hipSuccess) return DD_ERR_HIP;
+      if (hipEventRecord(dc.ev_join[8], dc.side) != hipSuccess) return DD_ERR_HIP;
       head_join = true;
     }
   }
   int pending_join = -1;
   bool heads_done = false;
+  // lin_node inside the node launch (g_lin_in_node): the NE blocks update h in place, the NB blocks leave W_lin . A_nb of layer l
+  // in anb_buf(l) (ping-pong between w.Anb and w.A, which no longer holds the attention output); every consumer of the new h
+  // adds it to the ligand rows (GemmArgs::X2, Fwd::add_anb) and the next layer's NE blocks fold it into h
+  const bool lin_in_node = uses_lin_in_node(B, NL, out_fc, fused);
   // (schedule 0) the coordinate launch of layer l is *recorded* after the next layer's projection / query GEMMs: the graph
   // runtime keeps the first-recorded successor of a node on the same hardware queue, and the branch that pays the
   // 10-12 us of cross-queue fork + join latency must be the short one (coordinates), not the GEMM chain
@@ -673,53 +757,43 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   auto flush_pos = [&]() -> int {
     if (!dpos.armed) return DD_OK;
     dpos.armed = false;
-    if (hipStreamWaitEvent(g_side, g_ev_fork[dpos.layer], 0) != hipSuccess) return DD_ERR_HIP;
-    int rc = launch_attn2_pos(dpos.pe, dpos.pb, g_side);
-    if (rc == DD_OK && !dpos.xup) rc = launch_xupdate(dpos.xcur, w.dxe, w.dxb, B, NP, NL, dpos.xnext, g_side);
+    if (hipStreamWaitEvent(dc.side, dc.ev_fork[dpos.layer], 0) != hipSuccess) return DD_ERR_HIP;
+    int rc = launch_attn2_pos(dpos.pe, dpos.pb, dc.side);
+    if (rc == DD_OK && !dpos.xup) rc = launch_xupdate(dpos.xcur, w.dxe, w.dxb, B, NP, NL, dpos.xnext, dc.side);
     if (rc != DD_OK) return rc;
-    if (hipEventRecord(g_ev_join[dpos.layer], g_side) != hipSuccess) return DD_ERR_HIP;
+    if (hipEventRecord(dc.ev_join[dpos.layer], dc.side) != hipSuccess) return DD_ERR_HIP;
     pending_join = dpos.layer;
     return DD_OK;
   };
   const float* xup_prev = nullptr;                       // != nullptr: x of the previous layer, its update still pending
-  for (int l = 0; l < s->num_layers && fused; ++l) {
-    const int nE = (int)(B * Eb);
+  for (int l = 0; l < L && fused; ++l) {
+    const bool last = l + 1 == L;
     // ---- projections of the old h / h_bond: one launch (the q blocks are the last columns: skipped when fused above).
     //      With the projection-ahead schedule this launch was already issued on the side stream right after the
     //      previous layer's lin_node (it needs h and h_bond only) and is joined before its first consumer.
-    // lin_node inside the node launch (g_lin_in_node): the NE blocks update h in place, the NB blocks leave W_lin . A_nb of this
-    // layer in anb_cur (ping-pong between w.Anb and w.A, which no longer holds the attention output); every consumer of the new h
-    // adds it to the ligand rows (GemmArgs::X2) and the next layer's NE blocks fold it into h
-    const bool lin_in_node = !out_fc && lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early;
-    float* const anb_cur = (l & 1) ? w.A : w.Anb;
-    const float* const anb_prev = (lin_in_node && l > 0) ? ((l & 1) ? w.Anb : w.A) : nullptr;
-    auto add_anb = [&](GemmArgs& g, bool all_nodes) {     // X rows of g: all nodes of the batch / the ligand rows only
-      g.X2 = anb_cur; g.x2_N = all_nodes ? N : NL; g.x2_NP = all_nodes ? NP : 0;
-    };
-    // (called for THIS layer at its head -- the previous layer's W_lin . A_nb is pending -- or for the NEXT one behind the node launch)
-    auto launch_batch1 = [&](int ll, hipStream_t sx) -> int {
-      return launch_projections1(s, w, ll, hcur, w.P, sx, ll == l ? anb_prev : (lin_in_node ? anb_cur : nullptr));
-    };
+    // (W_lin . A_nb pending on the ligand rows of h: the previous layer's at the head of this layer, this layer's behind the node launch)
+    const float* const anb_prev = (lin_in_node && l > 0) ? f.anb_buf(l - 1) : nullptr;
+    const float* const anb_new = lin_in_node ? f.anb_buf(l) : nullptr;
+    // (called for THIS layer at its head or for the NEXT one behind the node launch)
+    auto launch_batch1 = [&](int ll, hipStream_t sx) -> int { return f.launch_projections1(ll, hcur, sx, ll == l ? anb_prev : anb_new); };
     // (schedule 2) the same projections in two launches: the bond part only needs h_bond, final once the node
-    // attention is done; the node parts need h (lin_node)
+    // attention is done; the node parts (called for the NEXT layer) need h (lin_node)
     // (hsrc: the h the node parts read; lin_dup: the lin_node job that forms it first, one-fork schedule)
     auto launch_batch1_part = [&](int ll, int part, hipStream_t sx, const float* hsrc, const GemmArgs* lin_dup) -> int {
+      GemmList j;
       if (part == 0) {
-        GemmArgs j[2] = {gemm_args(w.hb, nE, 0, 128, nE, LW(ll, DD_W_b1), LW(ll, DD_b_b1), nullptr, w.PB, nE, 0, 640, 640, 0),
-                         gemm_args(w.hb, nE, 0, 128, nE, LW(ll, DD_W_b1), LW(ll, DD_b_b1), nullptr, w.PB, nE, 0, 640, 640, 0)};
-        if (lin_dup) { j[1] = j[0]; j[0] = *lin_dup; }     // (the small job first: its consumers are the next launch)
-        return launch_gemm128_batch(j, lin_dup ? 2 : 1, sx);
+        if (lin_dup) j.add(*lin_dup);                      // (the small job first: its consumers are the next launch)
+        j.add(f.b1(ll));
+      } else {
+        j.add(f.add_anb(f.n1(ll, hsrc), anb_new, true));
+        j.add(f.add_anb(f.l1(ll, hsrc), anb_new, false));
       }
-      GemmArgs j[2] = {
-          gemm_args(hsrc, B * N, 0, 128, B * N, LW(ll, DD_W_n1), LW(ll, DD_b_n1), nullptr, w.P, B * N, 0, 640, 640, 0),
-          gemm_args(hsrc + (long)NP * 128, NL, hN, 128, B * NL, LW(ll, DD_W_l1), LW(ll, DD_b_l1), nullptr, w.PL, B * NL, 0, 1280, 1280, 0)};
-      if (lin_in_node) { add_anb(j[0], true); add_anb(j[1], false); }   // (called for the NEXT layer: this layer's W_lin . A_nb is pending)
-      return launch_gemm128_batch(j, 2, sx);
+      return j.launch(sx);
     };
     const bool ahead = overlap && g_sched >= 1;
     const bool ahead_split = overlap && g_sched >= 2;
     const bool ahead_b2 = overlap && g_sched >= 3 && g_q1_in_gemm && g_gemm_ksplit_on();
-    const bool two_joins = ahead_b2 && g_sched >= 4;     // g_ev_qb_fork[l]: layer l's projections done (side stream)
+    const bool two_joins = ahead_b2 && g_sched >= 4;     // ev_qb_fork[l]: layer l's projections done (side stream)
     const bool proj_main = lin_in_node && g_lin_proj_main && two_joins && ahead_split;   // next layer's node projections in the main launch
     const bool pb_early = g_pb_early && g_lin_with_pb2 && !ahead && !lin_in_node;   // next layer's bond projections ride with lin_node
     const bool l0_here = l0 && l == 0;                  // this layer's projection / query rows came from the tables
@@ -729,79 +803,51 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     //      q_hb[bond] + q_hi[dst atom], summed while the GEMM stages its rows, so this launch depends on the projections
     //      only and runs before the coordinates of the previous layer are joined.
     const bool q1_in_gemm = g_q1_in_gemm && g_gemm_ksplit_on();
-    auto launch_b2 = [&](int ll, hipStream_t sx) -> int {
-      GemmArgs j[3] = {
-          gemm_args(w.q1bl, nE, 0, 128, nE, LW(ll, DD_BL_W2q), LW(ll, DD_BL_b2q), LW(ll, DD_BL_lnq), w.qb, nE, 0, 128, 128, 0),
-          gemm_args(w.P + 512, B * N, 0, 640, B * N, LW(ll, DD_NE_W2q), LW(ll, DD_NE_b2q), LW(ll, DD_NE_lnq), w.qn, B * N, 0, 128, 128, 0),
-          gemm_args(w.PL + 512, B * NL, 0, 1280, B * NL, LW(ll, DD_NB_W2q), LW(ll, DD_NB_b2q), LW(ll, DD_NB_lnq), w.qlnb, B * NL, 0, 128, 128, 0)};
-      if (q1_in_gemm) return launch_queries_q1(s, w, ll, w.P, w.qn, sx);
-      return launch_gemm128_batch(j, 3, sx);
-    };
+    auto launch_b2 = [&](int ll, hipStream_t sx) -> int { return f.launch_queries(ll, q1_in_gemm, sx); };
     // (schedule 3) the query GEMMs of this layer already ran on the side stream behind its projections
     const bool b2_ahead = ahead_b2 && q1_in_gemm && l > 0;
     bool b1_joined = false;
     if (q1_in_gemm && !b2_ahead) {
       if (ahead && l > 0) {                              // (schedules 1/2: this layer's projections ran on the side stream)
-        if (hipStreamWaitEvent(st, g_ev_join[l], 0) != hipSuccess) return DD_ERR_HIP;
+        if (hipStreamWaitEvent(st, dc.ev_join[l], 0) != hipSuccess) return DD_ERR_HIP;
         b1_joined = true;
       }
       if (!l0_here) DD_TRYP(DD_PROF_GEMM, launch_b2(l, st));
     }
     DD_TRY(flush_pos());                                 // previous layer's coordinate launch (side stream)
     if (pending_join >= 0) {
-      if (hipStreamWaitEvent(st, g_ev_join[pending_join], 0) != hipSuccess) return DD_ERR_HIP;
+      if (hipStreamWaitEvent(st, dc.ev_join[pending_join], 0) != hipSuccess) return DD_ERR_HIP;
       pending_join = -1;
     }
     const bool late_join = two_joins && b2_ahead && !b1_joined;
-    if (ahead && l > 0 && !b1_joined && hipStreamWaitEvent(st, late_join ? g_ev_qb_fork[l] : g_ev_join[l], 0) != hipSuccess)
+    if (ahead && l > 0 && !b1_joined && hipStreamWaitEvent(st, late_join ? dc.ev_qb_fork[l] : dc.ev_join[l], 0) != hipSuccess)
       return DD_ERR_HIP;                                 // projections of this layer
     // (a deferred coordinate update of the previous layer is applied here: xcur's ligand rows are written by this launch)
-    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev,
+    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, f.LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev,
                                                   q1_in_gemm ? nullptr : w.q1bl, w.Rk, w.Rv, st, xup_prev, w.dxe, w.dxb,
                                                   xup_prev ? xcur : nullptr));
     xup_prev = nullptr;
     if (!q1_in_gemm) DD_TRYP(DD_PROF_GEMM, launch_b2(l, st));
     if (head_join) {                                     // kNN graph + edge weights: first needed by the node attention
-      if (hipStreamWaitEvent(st, g_ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
+      if (hipStreamWaitEvent(st, dc.ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
       head_join = false;
     }
-    if (late_join && hipStreamWaitEvent(st, g_ev_join[l], 0) != hipSuccess) return DD_ERR_HIP;   // this layer's query GEMMs
+    if (late_join && hipStreamWaitEvent(st, dc.ev_join[l], 0) != hipSuccess) return DD_ERR_HIP;   // this layer's query GEMMs
     // ---- node_layer_with_edge + node_layer_with_bond + bond_layer: one launch
     {
-      AttnArgs ne, nb, bl;
-      memset(&ne, 0, sizeof(ne)); memset(&nb, 0, sizeof(nb)); memset(&bl, 0, sizeof(bl));
-      ne.np_real = nb.np_real = bl.np_real = s->np_real; ne.nl_real = nb.nl_real = bl.nl_real = s->nl_real;
-      bl.bl_prefix = s->bl_prefix;
-      ne.B = B; ne.NP = NP; ne.NL = NL; ne.K = K; ne.x = xcur; ne.nbr = w.nbr; ne.ew = w.ew;
-      const float* Pn = l0_here ? s->l0_P : w.P;
-      ne.kd = Pn; ne.ks = Pn + 128; ne.vd = Pn + 256; ne.vs = Pn + 384; ne.ld_kd = ne.ld_ks = ne.ld_vd = ne.ld_vs = 640;
-      ne.q = l0_here ? s->l0_qn : w.qn; ne.Akp = LW(l, DD_NE_Akp); ne.Avp = LW(l, DD_NE_Avp); ne.lnk = LW(l, DD_NE_lnk); ne.lnv = LW(l, DD_NE_lnv);
-      ne.W2k = LW(l, DD_NE_W2k); ne.W2v = LW(l, DD_NE_W2v); ne.b2v = LW(l, DD_NE_b2v); ne.out = w.A;
-      ne.work_counter = (l < 32) ? w.counters + 128 + 2 * l : nullptr;   // persistent node_layer_with_edge workgroups (two block counters)
-      nb.B = B; nb.NP = NP; nb.NL = NL; nb.K = K; nb.x = xcur;
-      nb.kd = w.PL; nb.ks = w.PL + 128; nb.vd = w.PL + 256; nb.vs = w.PL + 384; nb.ld_kd = nb.ld_ks = nb.ld_vd = nb.ld_vs = 1280;
-      nb.ke = w.PB; nb.ve = w.PB + 128; nb.ld_ke = nb.ld_ve = 640;
-      nb.q = w.qlnb; nb.lnk = LW(l, DD_NB_lnk); nb.lnv = LW(l, DD_NB_lnv);
-      nb.W2k = LW(l, DD_NB_W2k); nb.W2v = LW(l, DD_NB_W2v); nb.b2v = LW(l, DD_NB_b2v); nb.out = w.Anb; nb.out_assign = 1;
+      AttnArgs ne = f.attn_ne(l, xcur, l0_here), nb = f.attn_nb(l, xcur);
       if (lin_in_node) {
-        ne.out = hcur; ne.lin_W = LW(l, DD_W_lin); ne.lin_b = LW(l, DD_b_lin); ne.lin_add = anb_prev;
-        nb.out = anb_cur; nb.lin_W = LW(l, DD_W_lin);
+        ne.out = hcur; ne.lin_W = f.LW(l, DD_W_lin); ne.lin_b = f.LW(l, DD_b_lin); ne.lin_add = anb_prev;
+        nb.out = f.anb_buf(l); nb.lin_W = f.LW(l, DD_W_lin);
       }
-      bl.B = B; bl.NP = NP; bl.NL = NL; bl.K = K; bl.x = xcur;
-      bl.ke = w.Ek; bl.ve = w.Ev; bl.ld_ke = bl.ld_ve = 128;
-      bl.q = w.qb; bl.Wakp = LW(l, DD_BL_Wakp); bl.Wavp = LW(l, DD_BL_Wavp);
-      bl.lnk = LW(l, DD_BL_lnk); bl.lnv = LW(l, DD_BL_lnv);
-      bl.W2k = LW(l, DD_BL_W2k); bl.W2v = LW(l, DD_BL_W2v); bl.b2v = LW(l, DD_BL_b2v); bl.out = w.hb;
-      bl.Rk = w.Rk; bl.Rv = w.Rv;
-      bl.work_counter = (l < 64) ? w.counters + l : nullptr;
-      DD_TRYP(DD_PROF_ATTN_BL, launch_attn2_node(ne, nb, bl, st));
+      DD_TRYP(DD_PROF_ATTN_BL, launch_attn2_node(ne, nb, f.attn_bl(l, xcur), st));
     }
-    if (ahead_split && l + 1 < s->num_layers && hipEventRecord(g_ev_qa_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // h_bond final
+    if (ahead_split && !last && hipEventRecord(dc.ev_qa_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // h_bond final
     // ---- h += lin_node(A + A_nb on ligand rows)
     // One-fork schedule: the new h goes to the ping-pong partner (h_new = h_old + ...), because the side stream forms the same
     // rows from h_old at the same time (side_lin job below: identical arithmetic, its own output buffer) -- the main stream's
     // lin_node launch then has no successor on the other queue (every such edge costs the main chain ~5 us, EXPERIMENTS.md R3-2)
-    const bool side_lin = g_side_lin && ahead_split && ahead_b2 && l + 1 < s->num_layers;
+    const bool side_lin = g_side_lin && ahead_split && ahead_b2 && !last;
     float* const hold = hcur;
     GemmArgs lin_dup;
     if (out_fc) {
@@ -809,8 +855,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       NodeOutArgs na{w.A, w.Anb, hcur, hcur, no->layer[l], B, NP, NL};
       DD_TRYP(DD_PROF_GEMM, launch_node_out_fc(na, st));
     } else if (!lin_in_node) {
-      GemmArgs g = gemm_args(w.A, B * N, 0, 128, B * N, LW(l, DD_W_lin), LW(l, DD_b_lin), nullptr, hcur, B * N, 0, 128, 128, 1);
-      g.X2 = w.Anb; g.x2_N = N; g.x2_NP = NP;
+      GemmArgs g = f.lin(l, hcur, w.Anb);
       if (side_lin) {
         float* hnew = (hcur == w.h) ? w.h2 : w.h;
         g.Y = hnew; g.acc_src = hold;
@@ -823,116 +868,68 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       if (g_lin_with_pb2) {
         // the bond projections of the coordinate sub-layer only need the new h_bond: they share this launch, so that
         // the launch behind lin_node (projections of the new h) is a third of its former size
-        GemmArgs j[3] = {g, gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0),
-                         gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0)};
-        const bool more = pb_early && l + 1 < s->num_layers;
-        if (more)                                          // ... and so do the next layer's bond projections (h_bond is final)
-          j[2] = gemm_args(w.hb, nE, 0, 128, nE, LW(l + 1, DD_W_b1), LW(l + 1, DD_b_b1), nullptr, w.PB, nE, 0, 640, 640, 0);
-        DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(j, more ? 3 : 2, st));
+        GemmList j;
+        j.add(g);
+        j.add(f.b2(l));
+        if (pb_early && !last) j.add(f.b1(l + 1));         // ... and so do the next layer's bond projections (h_bond is final)
+        DD_TRYP(DD_PROF_GEMM, j.launch(st));
       } else {
         DD_TRYP(DD_PROF_GEMM, launch_gemm128(g, st));
       }
     }
-    if (ahead && !side_lin && !proj_main && l + 1 < s->num_layers && hipEventRecord(g_ev_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // h, h_bond final
-    // ---- projections of the new h / h_bond: one launch.  In the LAST layer the heads' first Linear (decompdiff.py:194-211:
-    //      bond head on the final h_bond, v head on the ligand rows of the final h) rides along: it needs nothing the coordinate
-    //      sub-layers produce, and as a launch of its own behind them it sat on the step's critical chain (8 us per step)
-    GemmArgs p2j[4] = {
-        gemm_args(hcur, B * N, 0, 128, B * N, LW(l, DD_W_n2), LW(l, DD_b_n2), nullptr, w.P2, B * N, 0, 256, 256, 0),
-        gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l2), LW(l, DD_b_l2), nullptr, w.PL2, B * NL, 0, 1024, 1024, 0),
-        gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0),
-        gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0)};
-    int p2n = g_lin_with_pb2 ? 2 : 3;
-    GemmArgs p2x[6];                                     // (lin_in_node: + the coordinate sub-layer's bond projections, which rode with lin_node)
-    if (g_heads_early && g_lin_with_pb2 && l + 1 == s->num_layers) {
-      p2j[2] = gemm_args(w.hb, nE, 0, 128, nE, GW(DD_G_BH_W1), GW(DD_G_BH_b1), nullptr, w.qb, nE, 0, 128, 128, 0);
-      if (pre_att)                                       // (pre_att: P = W_p h of the ligand rows; w.P is free after the node launch)
-        p2j[2] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, bh->W_p, nullptr, nullptr, w.P, B * NL, 0, 128, 128, 0);
-      p2j[3] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, GW(DD_G_VH_W1), GW(DD_G_VH_b1), nullptr, w.qn, B * NL, 0, 128, 128, 0);
-      p2n = 4;
+    if (ahead && !side_lin && !proj_main && !last && hipEventRecord(dc.ev_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // h, h_bond final
+    // ---- projections of the new h / h_bond: one launch -- {P2, PL2}, and the coordinate sub-layer's bond projections where they
+    //      did not ride with the lin_node GEMM.  In the LAST layer the heads' first Linear (decompdiff.py:194-211: bond head on the
+    //      final h_bond, v head on the ligand rows of the final h) rides along: it needs nothing the coordinate sub-layers produce,
+    //      and as a launch of its own behind them it sat on the step's critical chain (8 us per step).  (lin_in_node: this layer's
+    //      W_lin . A_nb is pending on every job that reads the ligand rows of h.)
+    GemmList p2;
+    p2.add(f.add_anb(f.n2(l, hcur), anb_new, true));
+    p2.add(f.add_anb(f.l2(l, hcur), anb_new, false));
+    if (!g_lin_with_pb2 || lin_in_node || out_fc) p2.add(f.b2(l));
+    if (g_heads_early && g_lin_with_pb2 && last) {
+      p2.add(pre_att ? f.add_anb(f.pre_att_p(bh, hcur), anb_new, false) : f.bond_head1());
+      p2.add(f.add_anb(f.v_head1(hcur), anb_new, false));
       heads_done = true;
     }
-    int p2xn = 0;
-    if (lin_in_node) {
-      p2x[p2xn++] = p2j[0]; add_anb(p2x[0], true);
-      p2x[p2xn++] = p2j[1]; add_anb(p2x[1], false);
-      p2x[p2xn++] = gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0);
-      if (p2n == 4) {
-        p2x[p2xn] = p2j[2];
-        if (pre_att) add_anb(p2x[p2xn], false);
-        ++p2xn;
-        p2x[p2xn] = p2j[3]; add_anb(p2x[p2xn], false); ++p2xn;
-      }
-      if (proj_main && l + 1 < s->num_layers) {           // the next layer's node projections (the side stream is the longer branch otherwise)
-        p2x[p2xn] = gemm_args(hcur, B * N, 0, 128, B * N, LW(l + 1, DD_W_n1), LW(l + 1, DD_b_n1), nullptr, w.P, B * N, 0, 640, 640, 0);
-        add_anb(p2x[p2xn], true); ++p2xn;
-        p2x[p2xn] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, LW(l + 1, DD_W_l1), LW(l + 1, DD_b_l1), nullptr, w.PL, B * NL, 0, 1280, 1280, 0);
-        add_anb(p2x[p2xn], false); ++p2xn;
-      }
+    if (proj_main && !last) {                            // the next layer's node projections (the side stream is the longer branch otherwise)
+      p2.add(f.add_anb(f.n1(l + 1, hcur), anb_new, true));
+      p2.add(f.add_anb(f.l1(l + 1, hcur), anb_new, false));
     }
+    if (out_fc && pb_early && !last) p2.add(f.b1(l + 1));  // (would have shared the lin_node launch)
     // (round 5) these jobs ride INSIDE the coordinate launch below when it can take them (launch_attn2_pos_g): the attention
     // workgroups wait for the first two, the heads' tiles trail behind them
     bool p2_in_pos = g_p2_in_pos && g_lin_with_pb2 && g_q_in_pos && !g_xup_in_pos && g_pos_waves == 4 && NL <= 65 && l < 64 &&
-                     !(overlap && !ahead);
-    if (out_fc) {
-      // {P2, PL2} of the new h, the coordinate sub-layer's bond projections, the heads' first Linear (last layer) or the next
-      // layer's bond projections where they would have shared the lin_node launch: one launch, at most five jobs
-      p2_in_pos = false;
-      p2x[p2xn++] = p2j[0];
-      p2x[p2xn++] = p2j[1];
-      p2x[p2xn++] = gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0);
-      if (p2n == 4) { p2x[p2xn++] = p2j[2]; p2x[p2xn++] = p2j[3]; }
-      if (pb_early && g_lin_with_pb2 && l + 1 < s->num_layers)
-        p2x[p2xn++] = gemm_args(w.hb, nE, 0, 128, nE, LW(l + 1, DD_W_b1), LW(l + 1, DD_b_b1), nullptr, w.PB, nE, 0, 640, 640, 0);
-      DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(p2x, p2xn, st));
-    } else if (lin_in_node) {
-      p2_in_pos = false;
-      DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(p2x, p2xn, st));
-      if (proj_main && l + 1 < s->num_layers && hipEventRecord(g_ev_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // P, PL of the next layer
-    }
-    else if (!p2_in_pos) DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(p2j, p2n, st));
+                     !(overlap && !ahead) && !out_fc && !lin_in_node;
+    if (!p2_in_pos) DD_TRYP(DD_PROF_GEMM, p2.launch(st));
+    if (proj_main && !last && hipEventRecord(dc.ev_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // P, PL of the next layer
     const bool q_in_pos = g_q_in_pos;           // second layer of the coordinate query MLPs inside attn_pos
     if (!q_in_pos) {
-      GemmArgs j[2] = {
-          gemm_args(w.PL2 + 256, B * NL, 0, 1024, B * NL, LW(l, DD_PE_W2q), LW(l, DD_PE_b2q), LW(l, DD_PE_lnq), w.ql, B * NL, 0, 128, 128, 0),
-          gemm_args(w.PL2 + 896, B * NL, 0, 1024, B * NL, LW(l, DD_PB_W2q), LW(l, DD_PB_b2q), LW(l, DD_PB_lnq), w.ql2, B * NL, 0, 128, 128, 0)};
-      DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(j, 2, st));
+      GemmList j;
+      j.add(f.q_pe(l));
+      j.add(f.q_pb(l));
+      DD_TRYP(DD_PROF_GEMM, j.launch(st));
     }
     // ---- pos_layer_with_edge + pos_layer_with_bond: one launch, then the coordinate update (ligand rows only)
     {
-      AttnArgs pe, pb;
-      memset(&pe, 0, sizeof(pe)); memset(&pb, 0, sizeof(pb));
-      pe.np_real = pb.np_real = s->np_real; pe.nl_real = pb.nl_real = s->nl_real;
-      pe.B = B; pe.NP = NP; pe.NL = NL; pe.K = K; pe.x = xcur; pe.nbr = w.nbr; pe.ew = w.ew;
-      pe.kd = w.PL2; pe.vd = w.PL2 + 128; pe.ld_kd = pe.ld_vd = 1024; pe.ks = w.P2; pe.vs = w.P2 + 128; pe.ld_ks = pe.ld_vs = 256;
-      pe.q = w.ql; pe.Akp = LW(l, DD_PE_Akp); pe.Avp = LW(l, DD_PE_Avp); pe.lnk = LW(l, DD_PE_lnk); pe.lnv = LW(l, DD_PE_lnv);
-      pe.W2k = LW(l, DD_PE_W2k); pe.W2v16 = LW(l, DD_PE_W2v); pe.b2v16 = LW(l, DD_PE_b2v); pe.out = w.dxe;
-      pb.B = B; pb.NP = NP; pb.NL = NL; pb.K = K; pb.x = xcur;
-      pb.kd = w.PL2 + 384; pb.ks = w.PL2 + 512; pb.vd = w.PL2 + 640; pb.vs = w.PL2 + 768; pb.ld_kd = pb.ld_ks = pb.ld_vd = pb.ld_vs = 1024;
-      pb.ke = w.PB2; pb.ve = w.PB2 + 128; pb.ld_ke = pb.ld_ve = 256;
-      pb.q = w.ql2; pb.lnk = LW(l, DD_PB_lnk); pb.lnv = LW(l, DD_PB_lnv);
-      pb.W2k = LW(l, DD_PB_W2k); pb.W2v16 = LW(l, DD_PB_W2v); pb.b2v16 = LW(l, DD_PB_b2v); pb.out = w.dxb; pb.x_next = nullptr;
+      AttnArgs pe = f.attn_pe(l, xcur), pb = f.attn_pb(l, xcur);
       const bool xup_in_pos = g_xup_in_pos != 0;           // x update by the last workgroup of the coordinate launch
       // ... or by the next layer's assemble launch, the first consumer of the new x (one launch less on the chain)
-      const bool xup_in_asm = !xup_in_pos && ((g_xup_in_asm && l + 1 < s->num_layers) ||
-                                              (fold && fold->fold_tail && l + 1 == s->num_layers));   // (... or by the step kernel)
+      const bool xup_in_asm = !xup_in_pos && ((g_xup_in_asm && !last) || (fold && fold->fold_tail && last));   // (... or by the step kernel)
       if (xup_in_pos) { pe.work_counter = w.counters + 32 + (l & 15); pe.x_next = xnext; }
-      if (q_in_pos) {
-        pe.qhid = w.PL2 + 256; pe.ld_qhid = 1024; pe.lnq = LW(l, DD_PE_lnq); pe.W2q = LW(l, DD_PE_W2qT); pe.b2q = LW(l, DD_PE_b2q);
-        pb.qhid = w.PL2 + 896; pb.ld_qhid = 1024; pb.lnq = LW(l, DD_PB_lnq); pb.W2q = LW(l, DD_PB_W2qT); pb.b2q = LW(l, DD_PB_b2q);
-      }
+      if (q_in_pos) f.set_q_in_pos(l, pe, pb);
       if (overlap && !ahead) {
         // fork: the coordinate sub-layers run on the side stream and are joined before the next consumer of x
-        if (hipEventRecord(g_ev_fork[l], st) != hipSuccess) return DD_ERR_HIP;
+        if (hipEventRecord(dc.ev_fork[l], st) != hipSuccess) return DD_ERR_HIP;
         dpos.armed = true; dpos.pe = pe; dpos.pb = pb; dpos.xcur = xcur; dpos.xnext = xnext; dpos.layer = l; dpos.xup = xup_in_pos || xup_in_asm;
         if (!g_defer_pos) DD_TRY(flush_pos());
       } else {
         if (p2_in_pos) {
           int rc_g;
-          { ProfScope prof_scope__(DD_PROF_ATTN_PE, st); rc_g = launch_attn2_pos_g(pe, pb, p2j, p2n, 2, w.counters + 64 + l, st); }
+          { ProfScope prof_scope__(DD_PROF_ATTN_PE, st); rc_g = launch_attn2_pos_g(pe, pb, p2.j, p2.n, 2, w.counters + 64 + l, st); }
           if (rc_g == DD_ERR_UNSUPPORTED_SHAPE) {          // (e.g. padded output rows): the two launches
             p2_in_pos = false;
-            DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(p2j, p2n, st));
+            DD_TRYP(DD_PROF_GEMM, p2.launch(st));
           } else if (rc_g != DD_OK) {
             return rc_g;
           }
@@ -942,115 +939,74 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       }
       if (xup_in_asm) xup_prev = xcur;
     }
-    if (ahead && l + 1 < s->num_layers) {                // (recorded after the main-stream nodes on purpose)
+    if (ahead && !last) {                                // (recorded after the main-stream nodes on purpose)
       if (ahead_split) {
-        if (hipStreamWaitEvent(g_side, g_ev_qa_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;
-        DD_TRY(launch_batch1_part(l + 1, 0, g_side, nullptr, side_lin ? &lin_dup : nullptr));
-        if (!side_lin && !lin_in_node && hipStreamWaitEvent(g_side, g_ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;   // (lin_in_node: h is final with h_bond)
-        if (!proj_main) DD_TRY(launch_batch1_part(l + 1, 1, g_side, side_lin ? w.hs : hcur, nullptr));
-        if (two_joins && hipEventRecord(g_ev_qb_fork[l + 1], g_side) != hipSuccess) return DD_ERR_HIP;
-        if (proj_main && hipStreamWaitEvent(g_side, g_ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;   // the main stream's P, PL
-        if (ahead_b2) DD_TRY(launch_b2(l + 1, g_side));
+        if (hipStreamWaitEvent(dc.side, dc.ev_qa_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;
+        DD_TRY(launch_batch1_part(l + 1, 0, dc.side, nullptr, side_lin ? &lin_dup : nullptr));
+        if (!side_lin && !lin_in_node && hipStreamWaitEvent(dc.side, dc.ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;   // (lin_in_node: h is final with h_bond)
+        if (!proj_main) DD_TRY(launch_batch1_part(l + 1, 1, dc.side, side_lin ? w.hs : hcur, nullptr));
+        if (two_joins && hipEventRecord(dc.ev_qb_fork[l + 1], dc.side) != hipSuccess) return DD_ERR_HIP;
+        if (proj_main && hipStreamWaitEvent(dc.side, dc.ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;   // the main stream's P, PL
+        if (ahead_b2) DD_TRY(launch_b2(l + 1, dc.side));
       } else {
-        if (hipStreamWaitEvent(g_side, g_ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;
-        DD_TRY(launch_batch1(l + 1, g_side));
+        if (hipStreamWaitEvent(dc.side, dc.ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;
+        DD_TRY(launch_batch1(l + 1, dc.side));
       }
-      if (hipEventRecord(g_ev_join[l + 1], g_side) != hipSuccess) return DD_ERR_HIP;
+      if (hipEventRecord(dc.ev_join[l + 1], dc.side) != hipSuccess) return DD_ERR_HIP;
     }
     float* t = xcur; xcur = xnext; xnext = t;
   }
-  for (int l = 0; l < s->num_layers && !fused; ++l) {
+  // One launch per sub-layer (per-kernel timing, the cross-check of the fused launches): the coordinate sub-layers' projections and
+  // queries reuse the node sub-layers' buffers, and both NB and PB queries go through w.ql -- the same builders on aliased buffers
+  Fwd u = f;
+  u.w.P2 = w.P; u.w.PL2 = w.PL; u.w.PB2 = w.PB; u.w.qlnb = u.w.ql2 = w.ql;
+  for (int l = 0; l < L && !fused; ++l) {
     // ---- projections of the old h / h_bond
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.h, B * N, 0, 128, B * N, LW(l, DD_W_n1), LW(l, DD_b_n1), nullptr, w.P, B * N, 0, 640, 640, 0}, st));
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.h + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l1), LW(l, DD_b_l1), nullptr, w.PL,
-                           B * NL, 0, 1280, 1280, 0}, st));
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.hb, (int)(B * Eb), 0, 128, (int)(B * Eb), LW(l, DD_W_b1), LW(l, DD_b_b1), nullptr, w.PB,
-                           (int)(B * Eb), 0, 640, 640, 0}, st));
-    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev, w.q1bl, w.Rk, w.Rv, st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.n1(l, w.h), st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.l1(l, w.h), st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.b1(l), st));
+    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, u.LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev, w.q1bl, w.Rk, w.Rv, st));
     // ---- queries: second Linear of the q MLPs (LayerNorm+ReLU prologue)
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.P + 512, B * N, 0, 640, B * N, LW(l, DD_NE_W2q), LW(l, DD_NE_b2q), LW(l, DD_NE_lnq), w.qn,
-                           B * N, 0, 128, 128, 0}, st));
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.PL + 512, B * NL, 0, 1280, B * NL, LW(l, DD_NB_W2q), LW(l, DD_NB_b2q), LW(l, DD_NB_lnq), w.ql,
-                           B * NL, 0, 128, 128, 0}, st));
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.q1bl, (int)(B * Eb), 0, 128, (int)(B * Eb), LW(l, DD_BL_W2q), LW(l, DD_BL_b2q),
-                           LW(l, DD_BL_lnq), w.qb, (int)(B * Eb), 0, 128, 128, 0}, st));
-    // ---- node_layer_with_edge
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.np_real = s->np_real; a.nl_real = s->nl_real;
-    a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = xcur; a.nbr = w.nbr; a.ew = w.ew;
-    a.kd = w.P; a.ks = w.P + 128; a.vd = w.P + 256; a.vs = w.P + 384; a.ld_kd = a.ld_ks = a.ld_vd = a.ld_vs = 640;
-    a.q = w.qn; a.Akp = LW(l, DD_NE_Akp); a.Avp = LW(l, DD_NE_Avp); a.lnk = LW(l, DD_NE_lnk); a.lnv = LW(l, DD_NE_lnv);
-    a.W2k = LW(l, DD_NE_W2k); a.W2v = LW(l, DD_NE_W2v); a.b2v = LW(l, DD_NE_b2v); a.out = w.A;
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.q_ne(l), st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.q_nb(l), st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.q_bl(l, false), st));
+    // ---- node_layer_with_edge (no persistent workgroups)
+    AttnArgs a = u.attn_ne(l, xcur, false);
+    a.work_counter = nullptr;
     DD_TRYP(DD_PROF_ATTN_NE, attn_dispatch(M_NE, a, st));
     // ---- node_layer_with_bond (adds into the ligand rows of A)
-    memset(&a, 0, sizeof(a));
-    a.np_real = s->np_real; a.nl_real = s->nl_real;
-    a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = xcur;
-    a.kd = w.PL; a.ks = w.PL + 128; a.vd = w.PL + 256; a.vs = w.PL + 384; a.ld_kd = a.ld_ks = a.ld_vd = a.ld_vs = 1280;
-    a.ke = w.PB; a.ve = w.PB + 128; a.ld_ke = a.ld_ve = 640;
-    a.q = w.ql; a.lnk = LW(l, DD_NB_lnk); a.lnv = LW(l, DD_NB_lnv);
-    a.W2k = LW(l, DD_NB_W2k); a.W2v = LW(l, DD_NB_W2v); a.b2v = LW(l, DD_NB_b2v); a.out = w.A;
+    a = u.attn_nb(l, xcur);
+    a.out = w.A; a.out_assign = 0;
     DD_TRYP(DD_PROF_ATTN_NB, attn_dispatch(M_NB, a, st));
-    // ---- bond_layer (residual add into h_bond)
-    memset(&a, 0, sizeof(a));
-    a.np_real = s->np_real; a.nl_real = s->nl_real;
-    a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = xcur;
-    a.ke = w.Ek; a.ve = w.Ev; a.ld_ke = a.ld_ve = 128;
-    a.q = w.qb; a.Wakp = LW(l, DD_BL_Wakp); a.Wavp = LW(l, DD_BL_Wavp);
-    a.lnk = LW(l, DD_BL_lnk); a.lnv = LW(l, DD_BL_lnv);
-    a.W2k = LW(l, DD_BL_W2k); a.W2v = LW(l, DD_BL_W2v); a.b2v = LW(l, DD_BL_b2v); a.out = w.hb;
-    a.Rk = w.Rk; a.Rv = w.Rv;
-    a.work_counter = (l < 64) ? w.counters + l : nullptr;   // (small ligands: the fused launch's persistent cooperative workgroups)
-    a.bl_prefix = s->bl_prefix;
-    DD_TRYP(DD_PROF_ATTN_BL, attn_dispatch(M_BL, a, st));
+    // ---- bond_layer (residual add into h_bond; small ligands: the fused launch's persistent cooperative workgroups)
+    DD_TRYP(DD_PROF_ATTN_BL, attn_dispatch(M_BL, u.attn_bl(l, xcur), st));
     // ---- h += lin_node(A)
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.A, B * N, 0, 128, B * N, LW(l, DD_W_lin), LW(l, DD_b_lin), nullptr, w.h, B * N, 0, 128, 128, 1}, st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.lin(l, w.h, nullptr), st));
     // ---- projections of the new h / h_bond
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.h, B * N, 0, 128, B * N, LW(l, DD_W_n2), LW(l, DD_b_n2), nullptr, w.P, B * N, 0, 256, 256, 0}, st));
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.h + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l2), LW(l, DD_b_l2), nullptr, w.PL,
-                           B * NL, 0, 1024, 1024, 0}, st));
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.hb, (int)(B * Eb), 0, 128, (int)(B * Eb), LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB,
-                           (int)(B * Eb), 0, 256, 256, 0}, st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.n2(l, w.h), st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.l2(l, w.h), st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.b2(l), st));
     // ---- pos_layer_with_edge
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.PL + 256, B * NL, 0, 1024, B * NL, LW(l, DD_PE_W2q), LW(l, DD_PE_b2q), LW(l, DD_PE_lnq), w.ql,
-                           B * NL, 0, 128, 128, 0}, st));
-    memset(&a, 0, sizeof(a));
-    a.np_real = s->np_real; a.nl_real = s->nl_real;
-    a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = xcur; a.nbr = w.nbr; a.ew = w.ew;
-    a.kd = w.PL; a.vd = w.PL + 128; a.ld_kd = a.ld_vd = 1024; a.ks = w.P; a.vs = w.P + 128; a.ld_ks = a.ld_vs = 256;
-    a.q = w.ql; a.Akp = LW(l, DD_PE_Akp); a.Avp = LW(l, DD_PE_Avp); a.lnk = LW(l, DD_PE_lnk); a.lnv = LW(l, DD_PE_lnv);
-    a.W2k = LW(l, DD_PE_W2k); a.W2v16 = LW(l, DD_PE_W2v); a.b2v16 = LW(l, DD_PE_b2v); a.out = w.dxe;
-    DD_TRYP(DD_PROF_ATTN_PE, attn_dispatch(M_PE, a, st));
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.q_pe(l), st));
+    DD_TRYP(DD_PROF_ATTN_PE, attn_dispatch(M_PE, u.attn_pe(l, xcur), st));
     // ---- pos_layer_with_bond + coordinate update (ligand rows only: mask_ligand_atom)
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128({w.PL + 896, B * NL, 0, 1024, B * NL, LW(l, DD_PB_W2q), LW(l, DD_PB_b2q), LW(l, DD_PB_lnq), w.ql,
-                           B * NL, 0, 128, 128, 0}, st));
-    memset(&a, 0, sizeof(a));
-    a.np_real = s->np_real; a.nl_real = s->nl_real;
-    a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = xcur;
-    a.kd = w.PL + 384; a.ks = w.PL + 512; a.vd = w.PL + 640; a.vs = w.PL + 768; a.ld_kd = a.ld_ks = a.ld_vd = a.ld_vs = 1024;
-    a.ke = w.PB; a.ve = w.PB + 128; a.ld_ke = a.ld_ve = 256;
-    a.q = w.ql; a.lnk = LW(l, DD_PB_lnk); a.lnv = LW(l, DD_PB_lnv);
-    a.W2k = LW(l, DD_PB_W2k); a.W2v16 = LW(l, DD_PB_W2v); a.b2v16 = LW(l, DD_PB_b2v); a.dxe = w.dxe; a.x_next = xnext;
+    DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.q_pb(l), st));
+    a = u.attn_pb(l, xcur);
+    a.out = nullptr; a.dxe = w.dxe; a.x_next = xnext;
     DD_TRYP(DD_PROF_ATTN_PB, attn_dispatch(M_PB, a, st));
     float* t = xcur; xcur = xnext; xnext = t;
   }
   if (head_join) {                                     // (no layer consumed the graph)
-    if (hipStreamWaitEvent(st, g_ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
+    if (hipStreamWaitEvent(st, dc.ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
     head_join = false;
   }
-  // heads, first Linear (decompdiff.py:194-211): v head on ligand rows of h, bond head on h_bond
+  // heads, first Linear, where the last layer's projection launch did not carry them
   if (!heads_done) {
-    GemmArgs j[2] = {
-        gemm_args(w.hb, (int)(B * Eb), 0, 128, (int)(B * Eb), GW(DD_G_BH_W1), GW(DD_G_BH_b1), nullptr, w.qb, (int)(B * Eb), 0, 128, 128, 0),
-        gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, GW(DD_G_VH_W1), GW(DD_G_VH_b1), nullptr, w.qn, B * NL, 0, 128, 128, 0)};
-    if (pre_att)
-      j[0] = gemm_args(hcur + (long)NP * 128, NL, hN, 128, B * NL, bh->W_p, nullptr, nullptr, w.P, B * NL, 0, 128, 128, 0);
-    if (fused && !out_fc && lin_in_node_for(B, NL) && g_lin_with_pb2 && !g_side_lin && g_heads_early) {   // (lin_in_node: the last layer's W_lin . A_nb is pending)
-      j[1].X2 = ((s->num_layers - 1) & 1) ? w.A : w.Anb; j[1].x2_N = NL; j[1].x2_NP = 0;
-      if (pre_att) { j[0].X2 = j[1].X2; j[0].x2_N = NL; j[0].x2_NP = 0; }
-    }
-    DD_TRYP(DD_PROF_GEMM, launch_gemm128_batch(j, 2, st));   // (v-head hidden -> qn: ql may still be read by the overlapped pos sub-layer)
+    const float* const anb_last = lin_in_node ? f.anb_buf(L - 1) : nullptr;   // (lin_in_node: the last layer's W_lin . A_nb is pending)
+    GemmList j;
+    j.add(pre_att ? f.add_anb(f.pre_att_p(bh, hcur), anb_last, false) : f.bond_head1());
+    j.add(f.add_anb(f.v_head1(hcur), anb_last, false));
+    DD_TRYP(DD_PROF_GEMM, j.launch(st));
   }
   {
     if (hcur != w.h && hipMemcpyAsync(w.h, hcur, sizeof(float) * (size_t)B * N * 128, hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -1058,7 +1014,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   }
   DD_TRY(flush_pos());                                   // last layer's coordinate launch (recorded after the head GEMMs)
   if (pending_join >= 0) {
-    if (hipStreamWaitEvent(st, g_ev_join[pending_join], 0) != hipSuccess) return DD_ERR_HIP;
+    if (hipStreamWaitEvent(st, dc.ev_join[pending_join], 0) != hipSuccess) return DD_ERR_HIP;
     pending_join = -1;
   }
   // x0-hat = ligand rows of the final x
@@ -1075,55 +1031,71 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   return DD_OK;
 }
 
-static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr) {
+// Drift gradients of the enabled guidance terms into w.ga / w.gc / w.gr, evaluated at x_t BEFORE the position update
+// (decompdiff.py:638-677); NULL where a term is off.  profiled: the launches count towards dd_profile_step's step category.
+struct DriftGrads { const float *ga = nullptr, *gc = nullptr, *gr = nullptr; };
+static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled, hipStream_t st, DriftGrads* d) {
   const int B = s->B, NL = s->NL;
-  const long Eb = (long)NL * (NL - 1);
-  Workspace w = carve(s->workspace, B, s->NP, NL, s->K);
-  const float* W = s->weights;
-  const int64_t* off = s->slot_off;
-  auto GW = [&](int slot) { return W + off[(long)s->num_layers * DD_NUM_LAYER_SLOTS + slot]; };
-  StepRowsArgs r;
-  memset(&r, 0, sizeof(r));
-  r.hid = w.qn; r.W2 = GW(DD_G_VH_W2); r.b2 = GW(DD_G_VH_b2); r.rows = B * NL; r.NC = num_v(s); r.rows_per_sample = NL;
-  r.tab = s->tab_v; r.T = s->T; r.step_counter = s->step_counter;
-  r.counter_bias = (fold && fold->advance) ? 1 : 0;
-  r.state = s->lig_v; r.uniforms = s->u_v; r.stream_id = 1;
-  r.logits_out = s->pred_v; r.traj_recon = s->traj_v0; r.traj_prob = s->traj_vt; r.traj_state = s->traj_v;
-  StepRowsArgs rb = r;
-  rb.hid = w.qb; rb.W2 = GW(DD_G_BH_W2); rb.b2 = GW(DD_G_BH_b2); rb.rows = (int)(B * Eb); rb.NC = DD_NUM_B;
-  rb.rows_per_sample = (int)Eb; rb.tab = s->tab_b; rb.state = s->lig_bond; rb.uniforms = s->u_b; rb.stream_id = 2;
-  rb.logits_out = s->pred_bond; rb.traj_recon = nullptr; rb.traj_prob = s->traj_bt; rb.traj_state = s->traj_bond;
-  // drift gradients are evaluated at x_t BEFORE the position update (decompdiff.py:638-677)
-  const float* ga = nullptr;
-  const float* gc = nullptr;
+  auto run = [&](auto&& launch) -> int {
+    ProfScope prof_scope(DD_PROF_STEP, st, profiled);
+    return launch();
+  };
   if (s->drift_armsca) {
     if (!s->decomp_index) return DD_ERR_BAD_ARG;
-    DD_TRYP(DD_PROF_STEP, launch_drift_armsca(s->lig_pos, s->decomp_index, B, NL, s->armsca_min_d, s->armsca_max_d, w.ga, 0,
-                                              s->drift_norm_batch, st));
-    ga = w.ga;
+    DD_TRY(run([&] { return launch_drift_armsca(s->lig_pos, s->decomp_index, B, NL, s->armsca_min_d, s->armsca_max_d, w.ga, 0,
+                                                s->drift_norm_batch, st); }));
+    d->ga = w.ga;
   }
   if (s->drift_clash) {
     if (!s->full_protein_pos || s->NF <= 0) return DD_ERR_BAD_ARG;
-    DD_TRYP(DD_PROF_STEP, launch_drift_clash(s->lig_pos, s->offset, s->full_protein_pos, B, NL, s->NF, s->clash_sigma, s->clash_gamma,
-                                             w.gc, 0, s->nl_real, st));
-    gc = w.gc;
+    DD_TRY(run([&] { return launch_drift_clash(s->lig_pos, s->offset, s->full_protein_pos, B, NL, s->NF, s->clash_sigma, s->clash_gamma,
+                                               w.gc, 0, s->nl_real, st); }));
+    d->gc = w.gc;
   }
-  const float* gr = nullptr;
   if (s->drift_repul) {
     if (!s->decomp_index || (s->drift_repul != 1 && s->drift_repul != 2)) return DD_ERR_BAD_ARG;
-    DD_TRYP(DD_PROF_STEP, launch_drift_arms_repul(s->lig_pos, s->decomp_index, B, NL, s->repul_max_d, s->drift_repul, w.gr, 0,
-                                                  s->drift_norm_batch, st));
-    gr = w.gr;
+    DD_TRY(run([&] { return launch_drift_arms_repul(s->lig_pos, s->decomp_index, B, NL, s->repul_max_d, s->drift_repul, w.gr, 0,
+                                                    s->drift_norm_batch, st); }));
+    d->gr = w.gr;
   }
+  return DD_OK;
+}
+
+// The sampler's part of the step kernels' arguments: atom rows `r`, bond rows `rb`, positions `p`.  The callers add where the
+// head outputs come from (hid / W2 / b2 or logits_in), logits_out, x0 and, with a folded step boundary, counter_bias and x0_*.
+static void fill_step_args(const dd_sampler* s, const DriftGrads& d, StepRowsArgs* r, StepRowsArgs* rb, StepPosArgs* p) {
+  const int B = s->B, NL = s->NL;
+  const long Eb = (long)NL * (NL - 1);
+  memset(r, 0, sizeof(*r));
+  r->rows = B * NL; r->NC = num_v(s); r->rows_per_sample = NL;
+  r->tab = s->tab_v; r->T = s->T; r->step_counter = s->step_counter;
+  r->state = s->lig_v; r->uniforms = s->u_v; r->stream_id = 1;
+  r->traj_recon = s->traj_v0; r->traj_prob = s->traj_vt; r->traj_state = s->traj_v;
+  *rb = *r;
+  rb->rows = (int)(B * Eb); rb->NC = DD_NUM_B; rb->rows_per_sample = (int)Eb; rb->tab = s->tab_b;
+  rb->state = s->lig_bond; rb->uniforms = s->u_b; rb->stream_id = 2;
+  rb->traj_recon = nullptr; rb->traj_prob = s->traj_bt; rb->traj_state = s->traj_bond;
+  memset(p, 0, sizeof(*p));
+  p->B = B; p->NL = NL; p->T = s->T; p->step_counter = s->step_counter; p->NP = s->NP;
+  p->xt = s->lig_pos; p->tab_pos = s->tab_pos; p->tab_score = s->tab_score;
+  p->atom_std = s->atom_std; p->offset = s->offset; p->grad_a = d.ga; p->scale_a = s->armsca_scale; p->grad_c = d.gc;
+  p->scale_c = s->clash_scale; p->grad_r = d.gr; p->scale_r = s->repul_scale; p->eps = s->eps; p->traj_pos = s->traj_pos;
+}
+
+static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr) {
+  const Fwd f(s);
+  const Workspace& w = f.w;
+  DriftGrads d;
+  DD_TRY(launch_drifts(s, w, true, st, &d));
+  StepRowsArgs r, rb;
   StepPosArgs p;
-  memset(&p, 0, sizeof(p));
-  p.B = B; p.NL = NL; p.T = s->T; p.step_counter = s->step_counter;
-  p.counter_bias = r.counter_bias; p.NP = s->NP;
-  if (fold && fold->xprev) { p.x0_prev = fold->xprev; p.x0_dxe = w.dxe; p.x0_dxb = w.dxb; p.x0_out = s->pred_pos; }
-  p.x0 = s->pred_pos; p.xt = s->lig_pos; p.tab_pos = s->tab_pos; p.tab_score = s->tab_score;
-  p.atom_std = s->atom_std; p.offset = s->offset; p.grad_a = ga; p.scale_a = s->armsca_scale; p.grad_c = gc;
-  p.scale_c = s->clash_scale; p.grad_r = gr; p.scale_r = s->repul_scale; p.eps = s->eps; p.traj_pos = s->traj_pos;
+  fill_step_args(s, d, &r, &rb, &p);
   const bool advanced = fold && fold->advance;
+  r.counter_bias = rb.counter_bias = p.counter_bias = advanced ? 1 : 0;
+  r.hid = w.qn; r.W2 = f.GW(DD_G_VH_W2); r.b2 = f.GW(DD_G_VH_b2); r.logits_out = s->pred_v;
+  rb.hid = w.qb; rb.W2 = f.GW(DD_G_BH_W2); rb.b2 = f.GW(DD_G_BH_b2); rb.logits_out = s->pred_bond;
+  p.x0 = s->pred_pos;
+  if (fold && fold->xprev) { p.x0_prev = fold->xprev; p.x0_dxe = w.dxe; p.x0_dxb = w.dxb; p.x0_out = s->pred_pos; }
   if (g_step_fused) {
     DD_TRYP(DD_PROF_STEP, launch_step_all(rb, r, p, st));
     if (!advanced) DD_TRYP(DD_PROF_STEP, launch_advance(s->step_counter, st));
@@ -1139,44 +1111,15 @@ static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* f
 // One reverse step from head outputs the host computed itself (dd_reverse_step): the transitions of heads_and_step
 // without the network -- unfused launches, the step counter advanced behind them.
 static int reverse_step_from_logits(const dd_sampler* s, const float* logits_v, const float* logits_b, const float* x0, hipStream_t st) {
-  const int B = s->B, NL = s->NL;
-  const long Eb = (long)NL * (NL - 1);
-  Workspace w = carve(s->workspace, B, s->NP, NL, s->K);
-  StepRowsArgs r;
-  memset(&r, 0, sizeof(r));
-  r.logits_in = logits_v; r.rows = B * NL; r.NC = num_v(s); r.rows_per_sample = NL;
-  r.tab = s->tab_v; r.T = s->T; r.step_counter = s->step_counter;
-  r.state = s->lig_v; r.uniforms = s->u_v; r.stream_id = 1;
-  r.logits_out = nullptr; r.traj_recon = s->traj_v0; r.traj_prob = s->traj_vt; r.traj_state = s->traj_v;
-  StepRowsArgs rb = r;
-  rb.logits_in = logits_b; rb.rows = (int)(B * Eb); rb.NC = DD_NUM_B; rb.rows_per_sample = (int)Eb; rb.tab = s->tab_b;
-  rb.state = s->lig_bond; rb.uniforms = s->u_b; rb.stream_id = 2;
-  rb.traj_recon = nullptr; rb.traj_prob = s->traj_bt; rb.traj_state = s->traj_bond;
-  const float* ga = nullptr;
-  const float* gc = nullptr;
-  if (s->drift_armsca) {
-    if (!s->decomp_index) return DD_ERR_BAD_ARG;
-    DD_TRY(launch_drift_armsca(s->lig_pos, s->decomp_index, B, NL, s->armsca_min_d, s->armsca_max_d, w.ga, 0, s->drift_norm_batch, st));
-    ga = w.ga;
-  }
-  if (s->drift_clash) {
-    if (!s->full_protein_pos || s->NF <= 0) return DD_ERR_BAD_ARG;
-    DD_TRY(launch_drift_clash(s->lig_pos, s->offset, s->full_protein_pos, B, NL, s->NF, s->clash_sigma, s->clash_gamma, w.gc, 0,
-                              s->nl_real, st));
-    gc = w.gc;
-  }
-  const float* gr = nullptr;
-  if (s->drift_repul) {
-    if (!s->decomp_index || (s->drift_repul != 1 && s->drift_repul != 2)) return DD_ERR_BAD_ARG;
-    DD_TRY(launch_drift_arms_repul(s->lig_pos, s->decomp_index, B, NL, s->repul_max_d, s->drift_repul, w.gr, 0, s->drift_norm_batch, st));
-    gr = w.gr;
-  }
+  const Workspace w = carve(s->workspace, s->B, s->NP, s->NL, s->K);
+  DriftGrads d;
+  DD_TRY(launch_drifts(s, w, false, st, &d));
+  StepRowsArgs r, rb;
   StepPosArgs p;
-  memset(&p, 0, sizeof(p));
-  p.B = B; p.NL = NL; p.T = s->T; p.step_counter = s->step_counter; p.NP = s->NP;
-  p.x0 = x0; p.xt = s->lig_pos; p.tab_pos = s->tab_pos; p.tab_score = s->tab_score;
-  p.atom_std = s->atom_std; p.offset = s->offset; p.grad_a = ga; p.scale_a = s->armsca_scale; p.grad_c = gc;
-  p.scale_c = s->clash_scale; p.grad_r = gr; p.scale_r = s->repul_scale; p.eps = s->eps; p.traj_pos = s->traj_pos;
+  fill_step_args(s, d, &r, &rb, &p);
+  r.logits_in = logits_v;
+  rb.logits_in = logits_b;
+  p.x0 = x0;
   DD_TRY(launch_step_rows(r, st));
   DD_TRY(launch_step_rows(rb, st));
   DD_TRY(launch_step_pos(p, st));
@@ -1240,14 +1183,13 @@ extern "C" int dd_layer0_tables(const dd_sampler* m, float* tables, void* stream
   int rc = dd::check_shapes(m);
   if (rc != DD_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  dd::Workspace w = dd::carve(m->workspace, 1, 0, 16, m->K);
-  const float* W = m->weights;
-  auto GW = [&](int slot) { return W + m->slot_off[(long)m->num_layers * DD_NUM_LAYER_SLOTS + slot]; };
-  rc = dd::launch_embed_all(m->protein_h, m->protein_pos, m->lig_pos, m->lig_v, m->lig_aux, GW(DD_G_W_lemb), GW(DD_G_b_lemb), 1, 0, 16,
-                            w.h, w.xa, w.xb, m->lig_bond, 240, GW(DD_G_W_bemb), GW(DD_G_b_bemb), w.hb, w.counters, st, nullptr);
+  const dd::Fwd f(m);
+  const dd::Workspace& w = f.w;
+  rc = dd::launch_embed_all(m->protein_h, m->protein_pos, m->lig_pos, m->lig_v, m->lig_aux, f.GW(DD_G_W_lemb), f.GW(DD_G_b_lemb), 1, 0, 16,
+                            w.h, w.xa, w.xb, m->lig_bond, 240, f.GW(DD_G_W_bemb), f.GW(DD_G_b_bemb), w.hb, w.counters, st, nullptr);
   if (rc != DD_OK) return rc;
-  if ((rc = dd::launch_projections1(m, w, 0, w.h, w.P, st)) != DD_OK) return rc;
-  if ((rc = dd::launch_queries_q1(m, w, 0, w.P, w.qn, st)) != DD_OK) return rc;
+  if ((rc = f.launch_projections1(0, w.h, st)) != DD_OK) return rc;
+  if ((rc = f.launch_queries(0, true, st)) != DD_OK) return rc;
   // atom i has combination i; bonds dst*15 + s have type s % 5 (s < 5: type s)
   auto cp = [&](float* dst, const float* src, size_t n) {
     return hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
@@ -1263,17 +1205,11 @@ extern "C" int dd_layer0_prepare(const dd_sampler* s, void* stream) {
   if (!s || !s->weights || !s->slot_off || !s->l0_P || !s->l0_qn) return DD_ERR_BAD_ARG;
   if (s->NP <= 0) return DD_OK;
   if (!s->protein_h) return DD_ERR_BAD_ARG;
-  const int B = s->B, NP = s->NP, N = s->NP + s->NL;
-  const float* W = s->weights;
-  auto LW = [&](int l, int slot) { return W + s->slot_off[(long)l * DD_NUM_LAYER_SLOTS + slot]; };
-  using dd::gemm_args;
   // the protein rows of the layer-0 node projections and node queries: same GEMM tile code, rows mapped into the [B, N] tables
-  dd::GemmArgs g1 = gemm_args(s->protein_h, NP, (long)NP * 128, 128, B * NP, LW(0, DD_W_n1), LW(0, DD_b_n1), nullptr, s->l0_P, NP,
-                              (long)N * 640, 640, 640, 0);
+  const dd::Fwd f(s);
+  const dd::GemmArgs g1 = f.n1_l0_protein(), g2 = f.q_ne_l0_protein();
   int rc = dd::launch_gemm128_batch(&g1, 1, (hipStream_t)stream);
   if (rc != DD_OK) return rc;
-  dd::GemmArgs g2 = gemm_args(s->l0_P + 512, NP, (long)N * 640, 640, B * NP, LW(0, DD_NE_W2q), LW(0, DD_NE_b2q), LW(0, DD_NE_lnq),
-                              s->l0_qn, NP, (long)N * 128, 128, 128, 0);
   return dd::launch_gemm128_batch(&g2, 1, (hipStream_t)stream);
 }
 
@@ -1295,7 +1231,7 @@ extern "C" int dd_workspace_view(const dd_sampler* s, dd_ws_view* out) {
   out->h = w.h; out->hb = w.hb; out->ew = w.ew; out->A = w.A; out->nbr = w.nbr;
   out->Anb = (dd::g_fuse && s->NL <= dd::g_fused_max_nl) ? w.Anb : nullptr;
   out->lin_in_node = 0;
-  if (out->Anb && dd::lin_in_node_for(s->B, s->NL) && dd::g_lin_with_pb2 && !dd::g_side_lin && dd::g_heads_early) {
+  if (dd::uses_lin_in_node(s->B, s->NL, false, out->Anb != nullptr)) {
     // lin_node inside the node launch: `h` lacks the last layer's W_lin . A_nb on the ligand rows -- it is in `Anb`; `A` is not formed
     out->lin_in_node = 1;
     out->Anb = ((s->num_layers - 1) & 1) ? w.A : w.Anb;
@@ -1315,16 +1251,14 @@ extern "C" int dd_forward_ex2(const dd_sampler* s, const dd_bond_head* bh, const
   rc = dd::forward_impl(s, st, nullptr, bh, no);
   if (rc != DD_OK) return rc;
   if (!s->pred_pos || !s->pred_v || !s->pred_bond) return DD_ERR_BAD_ARG;
-  dd::Workspace w = dd::carve(s->workspace, s->B, s->NP, s->NL, s->K);
-  const float* W = s->weights;
-  const int64_t* off = s->slot_off;
-  auto GW = [&](int slot) { return W + off[(long)s->num_layers * DD_NUM_LAYER_SLOTS + slot]; };
+  const dd::Fwd f(s);
+  const dd::Workspace& w = f.w;
   const int rows_v = s->B * s->NL;
   const long rows_b = (long)s->B * s->NL * (s->NL - 1);
-  hipLaunchKernelGGL(dd::k_head_logits, dim3((rows_v + 3) / 4), dim3(256), 0, st, w.qn, GW(DD_G_VH_W2), GW(DD_G_VH_b2),
+  hipLaunchKernelGGL(dd::k_head_logits, dim3((rows_v + 3) / 4), dim3(256), 0, st, w.qn, f.GW(DD_G_VH_W2), f.GW(DD_G_VH_b2),
                      rows_v, dd::num_v(s), s->pred_v);
-  hipLaunchKernelGGL(dd::k_head_logits, dim3((unsigned)((rows_b + 3) / 4)), dim3(256), 0, st, w.qb, GW(DD_G_BH_W2),
-                     GW(DD_G_BH_b2), (int)rows_b, DD_NUM_B, s->pred_bond);
+  hipLaunchKernelGGL(dd::k_head_logits, dim3((unsigned)((rows_b + 3) / 4)), dim3(256), 0, st, w.qb, f.GW(DD_G_BH_W2),
+                     f.GW(DD_G_BH_b2), (int)rows_b, DD_NUM_B, s->pred_bond);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
@@ -1505,6 +1439,11 @@ extern "C" int dd_debug_node_split_cache_path(char* out, int cap) {
   return DD_OK;
 }
 
+// What every entry point that takes reverse steps needs of the sampler (beside check_shapes)
+static bool check_step_sampler(const dd_sampler* s) {
+  return s && s->step_counter && s->tab_pos && s->tab_v && s->tab_b && s->atom_std && s->offset && s->pred_pos;
+}
+
 static int one_step(const dd_sampler* s, hipStream_t st, const dd_bond_head* bh = nullptr, const dd_node_out* no = nullptr) {
   dd::StepFold fold;
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
@@ -1530,9 +1469,7 @@ extern "C" int dd_sample_steps_ex(const dd_sampler* s, const dd_bond_head* bh, i
 
 extern "C" int dd_sample_steps_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int n_steps, void* stream) {
   if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
-  if (!s || n_steps < 0 || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
-      !s->pred_pos)
-    return DD_ERR_BAD_ARG;
+  if (!check_step_sampler(s) || n_steps < 0) return DD_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_steps; ++i) {
     int rc = one_step(s, st, bh, no);
@@ -1549,39 +1486,46 @@ extern "C" int dd_sample_steps_graph_ex(const dd_sampler* s, const dd_bond_head*
   return dd_sample_steps_graph_ex2(s, bh, nullptr, n_steps, stream);
 }
 
+// `steps` reverse steps of `s` captured from `st` into a graph and instantiated.  Measures the node split of the shape first
+// (eager passes), then holds the capture mutex while the stream captures: the side stream / events of the device are shared.
+// On any failure nothing is left behind: what was made is destroyed, *graph / *exec are NULL and the sticky HIP error is cleared.
+static int capture_steps(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int steps, hipStream_t st, hipGraph_t* graph,
+                         hipGraphExec_t* exec) {
+  *graph = nullptr;
+  *exec = nullptr;
+  int rc = autotune_node_split(s, st);
+  if (rc != DD_OK) return rc;
+  {
+    std::lock_guard<std::mutex> capture_lock(dd::g_capture_mutex);
+    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+      (void)hipGetLastError();                     // do not leave a sticky error behind for the caller
+      return DD_ERR_HIP;
+    }
+    for (int i = 0; i < steps && rc == DD_OK; ++i) rc = one_step(s, st, bh, no);
+    if (hipStreamEndCapture(st, graph) != hipSuccess || !*graph) rc = rc != DD_OK ? rc : DD_ERR_HIP;
+  }
+  if (rc == DD_OK && hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) rc = DD_ERR_HIP;
+  if (rc != DD_OK) {
+    if (*graph) (void)hipGraphDestroy(*graph);
+    *graph = nullptr;
+    *exec = nullptr;
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
 extern "C" int dd_sample_steps_graph_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int n_steps, void* stream) {
   if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
-  if (!s || n_steps < 0 || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
-      !s->pred_pos)
-    return DD_ERR_BAD_ARG;
+  if (!check_step_sampler(s) || n_steps < 0) return DD_ERR_BAD_ARG;
   if (n_steps == 0) return DD_OK;
   hipStream_t st = (hipStream_t)stream;
   int rc = dd::check_shapes(s);
   if (rc != DD_OK) return rc;
+  if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
-  rc = autotune_node_split(s, st);
+  rc = capture_steps(s, bh, no, 1, st, &graph, &exec);
   if (rc != DD_OK) return rc;
-  std::unique_lock<std::mutex> capture_lock(dd::g_capture_mutex);   // (the side stream / events of the device are shared)
-  if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();                     // do not leave a sticky error behind for the caller
-    return DD_ERR_HIP;
-  }
-  rc = one_step(s, st, bh, no);
-  hipError_t e = hipStreamEndCapture(st, &graph);
-  capture_lock.unlock();
-  if (rc != DD_OK || e != hipSuccess || !graph) {
-    if (graph) (void)hipGraphDestroy(graph);
-    (void)hipGetLastError();
-    return rc != DD_OK ? rc : DD_ERR_HIP;
-  }
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-    (void)hipGraphDestroy(graph);
-    (void)hipGetLastError();
-    return DD_ERR_HIP;
-  }
-  rc = DD_OK;
   for (int i = 0; i < n_steps; ++i) {
     if (hipGraphLaunch(exec, st) != hipSuccess) { rc = DD_ERR_HIP; break; }
   }
@@ -1605,30 +1549,14 @@ extern "C" int dd_graph_create_ex(const dd_sampler* s, const dd_bond_head* bh, i
 extern "C" int dd_graph_create_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int steps_per_graph, void* stream,
                                    void** graph_out) {
   if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
-  if (!s || !graph_out || steps_per_graph < 1 || steps_per_graph > 64 || !s->step_counter || !s->tab_pos || !s->tab_v ||
-      !s->tab_b || !s->atom_std || !s->offset || !s->pred_pos)
-    return DD_ERR_BAD_ARG;
+  if (!check_step_sampler(s) || !graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   int rc = dd::check_shapes(s);
   if (rc != DD_OK) return rc;
-  rc = autotune_node_split(s, st);
-  if (rc != DD_OK) return rc;
   StepGraph* g = new StepGraph();
-  std::unique_lock<std::mutex> capture_lock(dd::g_capture_mutex);   // (the side stream / events of the device are shared)
-  if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();
-    delete g;
-    return DD_ERR_HIP;
-  }
-  for (int i = 0; i < steps_per_graph && rc == DD_OK; ++i) rc = one_step(s, st, bh, no);
-  hipError_t e = hipStreamEndCapture(st, &g->graph);
-  capture_lock.unlock();
-  if (rc == DD_OK && (e != hipSuccess || !g->graph)) rc = DD_ERR_HIP;
-  if (rc == DD_OK && hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0) != hipSuccess) rc = DD_ERR_HIP;
+  rc = capture_steps(s, bh, no, steps_per_graph, st, &g->graph, &g->exec);
   if (rc != DD_OK) {
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    (void)hipGetLastError();
     delete g;
     return rc;
   }
@@ -1670,9 +1598,7 @@ extern "C" int dd_sample_steps_graph_multi_ex2(const dd_sampler* const* ss, cons
     if (bhs && dd::check_bond_head(bhs[i]) != DD_OK) return DD_ERR_BAD_ARG;
     if (nos && dd::check_node_out(nos[i], ss[i]) != DD_OK) return DD_ERR_BAD_ARG;
     const dd_sampler* s = ss[i];
-    if (!s || !streams[i] || !s->step_counter || !s->tab_pos || !s->tab_v || !s->tab_b || !s->atom_std || !s->offset ||
-        !s->pred_pos)
-      return DD_ERR_BAD_ARG;
+    if (!check_step_sampler(s) || !streams[i]) return DD_ERR_BAD_ARG;
     for (int j = 0; j < i; ++j)
       if (streams[j] == streams[i] || ss[j]->workspace == s->workspace) return DD_ERR_BAD_ARG;
     int rc = dd::check_shapes(s);
@@ -1684,17 +1610,8 @@ extern "C" int dd_sample_steps_graph_multi_ex2(const dd_sampler* const* ss, cons
   int rc = DD_OK;
   // the side streams / events used inside a step are shared, which is fine: they only shape each graph while it
   // is being captured, one chain at a time; the replays below do not touch them
-  for (int i = 0; i < n && rc == DD_OK; ++i) {
-    hipStream_t st = (hipStream_t)streams[i];
-    rc = autotune_node_split(ss[i], st);
-    if (rc != DD_OK) break;
-    std::lock_guard<std::mutex> capture_lock(dd::g_capture_mutex);
-    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { rc = DD_ERR_HIP; break; }
-    int rs = one_step(ss[i], st, bhs ? bhs[i] : nullptr, nos ? nos[i] : nullptr);
-    hipError_t e = hipStreamEndCapture(st, &graph[i]);
-    if (rs != DD_OK || e != hipSuccess || !graph[i]) { rc = rs != DD_OK ? rs : DD_ERR_HIP; break; }
-    if (hipGraphInstantiate(&exec[i], graph[i], nullptr, nullptr, 0) != hipSuccess) rc = DD_ERR_HIP;
-  }
+  for (int i = 0; i < n && rc == DD_OK; ++i)
+    rc = capture_steps(ss[i], bhs ? bhs[i] : nullptr, nos ? nos[i] : nullptr, 1, (hipStream_t)streams[i], &graph[i], &exec[i]);
   if (rc == DD_OK) {
     static const int threaded = [] { const char* e = getenv("DD_MULTI_THREADS"); return e ? atoi(e) : 1; }();
     if (threaded) {
