@@ -240,11 +240,13 @@ __global__ __launch_bounds__(DD_NL_MAX) void k_drift_armsca(const float* __restr
       const float best = __uint_as_float(key);
       const int bs = who;
       if (l == 0 && ba >= 0) {
+        // The clamps pass their gradient at equality (torch.clamp backward is inclusive; min_d == max_d == d: the two
+        // cancel), and a winner at distance 0 gives nothing (torch's norm has a zero subgradient there), as in arms_repul.
         float coef = 0.f;
-        if (min_d - best > 0.f) coef -= 1.f;
-        if (best - max_d > 0.f) coef += 1.f;
+        if (min_d - best >= 0.f) coef -= 1.f;
+        if (best - max_d >= 0.f) coef += 1.f;
         coef /= ((float)n_arms * (float)norm_B);          // the loss is averaged over the caller's whole batch
-        if (coef != 0.f) {
+        if (coef != 0.f && best > 0.f) {
           float dx = px[ba] - px[bs], dy = py[ba] - py[bs], dz = pz[ba] - pz[bs];
           float inv = 1.0f / best;
           // (products rounded before the add, as the atomic adds of the serial form took them; arms in ascending order,

@@ -77,7 +77,9 @@ def scatter_min(src, index, dim=0, dim_size=None):
     """torch_scatter.scatter_min for dim=0 → (min values, argmin positions along dim 0).
 
     Differentiable w.r.t. ``src`` through a gather on the arg-min positions, which is how
-    torch_scatter's autograd routes the gradient (one winner per output slot).
+    torch_scatter's autograd routes the gradient (one winner per output slot).  A destination
+    that no source row maps to holds 0 with arg ``src.size(0)`` and passes no gradient
+    (torch_scatter's convention; decompdiff_amd.functional.scatter_min keeps the same one).
     """
     assert dim == 0
     n = _dim_size(index, dim_size)
@@ -93,6 +95,8 @@ def scatter_min(src, index, dim=0, dim_size=None):
         arg = arg.scatter_reduce(0, idx, cand, reduce="amin", include_self=True)
     safe = arg.clamp(max=max(src.size(0) - 1, 0))
     vals = torch.gather(src, 0, safe)
+    if bool((arg == big).any()):                       # (non-empty slots keep the gathered value bit for bit)
+        vals = torch.where(arg == big, torch.zeros_like(vals), vals)
     return vals, arg
 
 
