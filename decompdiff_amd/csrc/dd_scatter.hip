@@ -91,6 +91,127 @@ __global__ __launch_bounds__(256) void k_attn_aggregate(const float* __restrict_
   }
 }
 
+// ---- backward of k_attn_aggregate, same mapping (a wave per destination, lane l = channels 2l, 2l+1, 4 members in flight).
+// With g = d_out, alpha = the forward's softmax weight, w = e_w (1 without), per member e and head h:
+//   node form:        t = w * sum_{c in h} g[s,c] v[e,c]          D = sum_{c in h} g[s,c] out[s,c]   (= sum_e alpha t)
+//   coordinate form:  t = w * v16[e,h] * (g[s] . rel[e]) / 16     D = sum_e alpha t
+//   ds = alpha (t - D);   dk[e] = scale ds q[s];   dq[s] = scale sum_e ds k[e]   (q per edge: dq[e] = scale ds k[e])
+// Nothing is saved by the forward: pass 1 reads the segment's k rows (coordinate form: v16, rel_x, e_w too, for D) and forms
+// the running maximum and denominator as the forward does, pass 2 reads the members again, forms alpha and writes every
+// gradient.  No atomics: each output element is written by one lane, once -- reproducible bit for bit, and the buffers
+// need no initialisation.  An empty segment writes its zero dq row (q per segment) and nothing else.
+template <bool POS>
+__global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
+                                                            const float* __restrict__ v, const float* __restrict__ e_w,
+                                                            const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
+                                                            int n_seg, const float* __restrict__ out, const float* __restrict__ d_out,
+                                                            float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv,
+                                                            float* __restrict__ d_ew, float* __restrict__ d_rel) {
+  const int lane = threadIdx.x & 63;
+  const int seg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (seg >= n_seg) return;
+  const int e0 = __builtin_amdgcn_readfirstlane(seg_ptr[seg]), e1 = __builtin_amdgcn_readfirstlane(seg_ptr[seg + 1]);
+  if (e1 <= e0) {
+    if (!q_per_edge) *reinterpret_cast<float2*>(dq + (long)seg * 128 + 2 * lane) = make_float2(0.f, 0.f);
+    return;
+  }
+  const float2 qv = *reinterpret_cast<const float2*>(q + (long)(q_per_edge ? e0 : seg) * 128 + 2 * lane);
+  const float scale = 0.35355339059327373f;              // 1 / sqrt(8)
+  const int head = lane >> 2;
+  const bool lead = (lane & 3) == 0;
+  float2 gc = make_float2(0.f, 0.f);                     // !POS: g[s, 2l], g[s, 2l+1]
+  float g0 = 0.f, g1 = 0.f, g2 = 0.f, gl = 0.f;          // POS: g[s, 0..2] (wave-uniform) and g[s, lane] on lanes 0..2
+  if (POS) {
+    g0 = d_out[(long)seg * 3]; g1 = d_out[(long)seg * 3 + 1]; g2 = d_out[(long)seg * 3 + 2];
+    gl = lane == 0 ? g0 : (lane == 1 ? g1 : (lane == 2 ? g2 : 0.f));
+  } else {
+    gc = *reinterpret_cast<const float2*>(d_out + (long)seg * 128 + 2 * lane);
+  }
+  // ---- pass 1: running maximum and denominator in the forward's order (POS: D rides along)
+  float mx = -INFINITY, den = 0.f, dacc = 0.f;
+  for (int e = e0; e < e1; e += UNROLL) {
+    float2 kk[UNROLL];
+    float t[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const long ee = e + u < e1 ? e + u : e1 - 1;       // clamped, masked below
+      kk[u] = *reinterpret_cast<const float2*>(k + ee * 128 + 2 * lane);
+      if (POS) {
+        const float ue = fmaf(g0, rel_x[ee * 3], fmaf(g1, rel_x[ee * 3 + 1], g2 * rel_x[ee * 3 + 2])) * 0.0625f;
+        t[u] = (v[ee * 16 + head] * (e_w ? e_w[ee] : 1.0f)) * ue;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      if (e + u >= e1) break;
+      const float s = head_sum(fmaf(qv.y, kk[u].y, qv.x * kk[u].x)) * scale;
+      const float mn = fmaxf(mx, s);
+      const float corr = __expf(mx - mn), p = __expf(s - mn);
+      den = fmaf(den, corr, p);
+      if (POS) dacc = fmaf(dacc, corr, p * t[u]);
+      mx = mn;
+    }
+  }
+  const float inv = 1.0f / den;
+  float D;
+  if (POS) {
+    D = dacc * inv;
+  } else {
+    const float2 ov = *reinterpret_cast<const float2*>(out + (long)seg * 128 + 2 * lane);
+    D = head_sum(fmaf(gc.y, ov.y, gc.x * ov.x));
+  }
+  // ---- pass 2: alpha and every gradient (the k rows of the segment come from cache)
+  float aq0 = 0.f, aq1 = 0.f;
+  for (int e = e0; e < e1; e += UNROLL) {
+    float2 kk[UNROLL], vv[UNROLL];
+    float w[UNROLL], ue[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const long ee = e + u < e1 ? e + u : e1 - 1;       // clamped: nothing is stored for a replayed member
+      kk[u] = *reinterpret_cast<const float2*>(k + ee * 128 + 2 * lane);
+      if (POS) {
+        vv[u].x = v[ee * 16 + head];
+        ue[u] = fmaf(g0, rel_x[ee * 3], fmaf(g1, rel_x[ee * 3 + 1], g2 * rel_x[ee * 3 + 2])) * 0.0625f;
+      } else {
+        vv[u] = *reinterpret_cast<const float2*>(v + ee * 128 + 2 * lane);
+      }
+      w[u] = e_w ? e_w[ee] : 1.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      if (e + u >= e1) break;
+      const long ee = e + u;
+      const float s = head_sum(fmaf(qv.y, kk[u].y, qv.x * kk[u].x)) * scale;
+      const float a = __expf(s - mx) * inv;
+      float ds;
+      if (POS) {
+        ds = a * ((vv[u].x * w[u]) * ue[u] - D);
+        const float av = wave_sum(lead ? a * vv[u].x : 0.f);                   // sum_h alpha v16
+        if (lead) dv[ee * 16 + head] = a * w[u] * ue[u];
+        if (d_ew && lane == 0) d_ew[ee] = ue[u] * av;
+        if (lane < 3) d_rel[ee * 3 + lane] = gl * (w[u] * 0.0625f) * av;
+      } else {
+        const float gv = head_sum(fmaf(gc.y, vv[u].y, gc.x * vv[u].x));
+        ds = a * (w[u] * gv - D);
+        const float aw = a * w[u];
+        *reinterpret_cast<float2*>(dv + ee * 128 + 2 * lane) = make_float2(aw * gc.x, aw * gc.y);
+        if (d_ew) {
+          const float x = wave_sum(lead ? a * gv : 0.f);
+          if (lane == 0) d_ew[ee] = x;
+        }
+      }
+      const float dsq = ds * scale;
+      *reinterpret_cast<float2*>(dk + ee * 128 + 2 * lane) = make_float2(dsq * qv.x, dsq * qv.y);
+      if (q_per_edge) {
+        *reinterpret_cast<float2*>(dq + ee * 128 + 2 * lane) = make_float2(dsq * kk[u].x, dsq * kk[u].y);
+      } else {
+        aq0 = fmaf(dsq, kk[u].x, aq0); aq1 = fmaf(dsq, kk[u].y, aq1);
+      }
+    }
+  }
+  if (!q_per_edge) *reinterpret_cast<float2*>(dq + (long)seg * 128 + 2 * lane) = make_float2(aq0, aq1);
+}
+
 
 // ---- stand-alone torch_scatter drop-ins: scatter_sum / scatter_mean / scatter_min / scatter_max and
 // scatter_softmax over dim 0 of a [E, F] fp32 tensor whose rows are grouped by destination (CSR segments).  Call sites in
@@ -181,6 +302,31 @@ extern "C" int dd_attn_aggregate_pos(const float* q, const float* k, const float
   if (n_seg == 0) return DD_OK;
   hipLaunchKernelGGL(dd::k_attn_aggregate<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w, rel_x,
                      seg_ptr, n_seg, out);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+extern "C" int dd_attn_aggregate_node_bwd(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
+                                          const int32_t* seg_ptr, int n_seg, const float* out, const float* d_out, float* dq,
+                                          float* dk, float* dv, float* d_ew, void* stream) {
+  if (!q || !k || !v || !seg_ptr || !out || !d_out || !dq || !dk || !dv || (e_w == nullptr) != (d_ew == nullptr) || n_seg < 0)
+    return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd<false>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, q_per_edge, k, v,
+                     e_w, nullptr, seg_ptr, n_seg, out, d_out, dq, dk, dv, d_ew, nullptr);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+extern "C" int dd_attn_aggregate_pos_bwd(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
+                                         const int32_t* seg_ptr, int n_seg, const float* d_out, float* dq, float* dk, float* dv16,
+                                         float* d_ew, float* d_rel, void* stream) {
+  if (!q || !k || !v16 || !rel_x || !seg_ptr || !d_out || !dq || !dk || !dv16 || !d_rel || (e_w == nullptr) != (d_ew == nullptr) ||
+      n_seg < 0)
+    return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w,
+                     rel_x, seg_ptr, n_seg, nullptr, d_out, dq, dk, dv16, d_ew, d_rel);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }

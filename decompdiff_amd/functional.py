@@ -120,28 +120,57 @@ def _knn_graph_csr(xc: torch.Tensor, k: int, batch: Optional[torch.Tensor], B: i
 
 def _seg_ptr(index: torch.Tensor, dim_size: int) -> torch.Tensor:
     if index.numel() > 1 and bool((index[1:] < index[:-1]).any().item()):
-        raise NotImplementedError("scatter_attention: edges must be grouped by destination (sorted index), as knn_graph, "
-                                  "the dst-major bond list and the SparseTensor triplets are")
+        raise NotImplementedError(_UNSORTED)
     ptr = torch.zeros(dim_size + 1, dtype=torch.int32, device=index.device)
     ptr[1:] = torch.bincount(index, minlength=dim_size).cumsum(0)
     return ptr
 
 
-def scatter_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, index: torch.Tensor, dim_size: int,
-                      e_w: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``scatter_sum(scatter_softmax((q_e * k / sqrt(8)).sum(-1), index)[..., None] * (v * e_w), index, dim_size)``
-    flattened to ``[dim_size,128]`` (16 heads x 8).  ``q`` is ``[dim_size,128]`` (gathered as ``q[index]`` by the
-    reference's node / coordinate layers) or per edge ``[E,128]`` (bond layer: rows of a segment are identical)."""
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        hip_lib.require_gpu(t, name)
-    E = k.size(0)
-    per_edge = q.size(0) == E and q.size(0) != dim_size
-    f = lambda t: t.detach().to(torch.float32).reshape(t.size(0), -1).contiguous()
+_UNSORTED = ("scatter_attention: edges must be grouped by destination (sorted index), as knn_graph, "
+             "the dst-major bond list and the SparseTensor triplets are")
+
+
+def _attn_seg(index, dim_size: int, E: int) -> torch.Tensor:
+    """Segment pointer of an index vector, or of a SegmentPlan (no device -> host round trip: usable in a captured step)."""
+    if isinstance(index, SegmentPlan):
+        if index.perm is not None:
+            raise NotImplementedError(_UNSORTED)
+        if int(dim_size) != index.n or index.E != E:
+            raise ValueError("SegmentPlan does not match k / dim_size")
+        return index.ptr
+    if index.dim() != 1 or index.numel() != E:
+        raise ValueError("scatter_attention: index must have one entry per row of k")
+    return _seg_ptr(index, dim_size)
+
+
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to(torch.float32).reshape(t.size(0), -1).contiguous()
+
+
+def _ew32(e_w: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if e_w is None else e_w.detach().to(torch.float32).reshape(-1).contiguous()
+
+
+def _needs_grad(*tensors) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _grad_like(g: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """A gradient computed on the fp32 contiguous copy of t, in t's own shape and dtype."""
+    return g.view(t.shape).to(t.dtype)
+
+
+def _per_edge(q: torch.Tensor, E: int, dim_size: int) -> bool:
+    return q.size(0) == E and q.size(0) != dim_size
+
+
+def _attention_node(q, k, v, e_w, seg: torch.Tensor, dim_size: int) -> torch.Tensor:
+    per_edge = _per_edge(q, k.size(0), dim_size)
     out = torch.empty(dim_size, 128, device=k.device)
-    ew = None if e_w is None else e_w.detach().to(torch.float32).reshape(-1).contiguous()
+    ew = _ew32(e_w)
     # converted copies are bound to locals that outlive the launch: a temporary freed before the kernel is enqueued
     # would hand its block to the next same-size allocation (k and v would alias)
-    qf, kf, vf, seg = f(q), f(k), f(v), _seg_ptr(index, dim_size)
+    qf, kf, vf = _f32(q), _f32(k), _f32(v)
     ext = torch_ext()
     if ext is not None:
         return ext.attn_aggregate_node(qf, bool(per_edge), kf, vf, ew, seg)
@@ -151,16 +180,10 @@ def scatter_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, index: 
     return out
 
 
-def scatter_attention_pos(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_x: torch.Tensor, index: torch.Tensor,
-                          dim_size: int, e_w: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """PosUpdateLayer's aggregation: ``v`` is ``[E,16]`` (one scalar per head), ``rel_x`` ``[E,3]``; returns
-    ``scatter_sum(alpha[..., None] * (v * e_w)[..., None] * rel_x[:, None], index).mean(1)`` — ``[dim_size,3]``."""
-    for name, t in (("q", q), ("k", k), ("v", v), ("rel_x", rel_x)):
-        hip_lib.require_gpu(t, name)
-    f = lambda t: t.detach().to(torch.float32).reshape(t.size(0), -1).contiguous()
+def _attention_pos(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int) -> torch.Tensor:
     out = torch.empty(dim_size, 3, device=k.device)
-    ew = None if e_w is None else e_w.detach().to(torch.float32).reshape(-1).contiguous()
-    qf, kf, vf, rf, seg = f(q), f(k), f(v), f(rel_x), _seg_ptr(index, dim_size)      # (alive past the launch, see above)
+    ew = _ew32(e_w)
+    qf, kf, vf, rf = _f32(q), _f32(k), _f32(v), _f32(rel_x)                          # (alive past the launch, see above)
     ext = torch_ext()
     if ext is not None:
         return ext.attn_aggregate_pos(qf, kf, vf, ew, rf, seg)
@@ -168,6 +191,116 @@ def scatter_attention_pos(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel
                                                        hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
                                                        hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_pos")
     return out
+
+
+def _attention_node_bwd(q, k, v, e_w, seg: torch.Tensor, dim_size: int, out, g):
+    """(dq, dk, dv, d_ew or None) of `_attention_node`, each in its input's shape and dtype (dd_attn_aggregate_node_bwd)."""
+    E, dev = k.size(0), k.device
+    per_edge = _per_edge(q, E, dim_size)
+    qf, kf, vf, ew, of, gf = _f32(q), _f32(k), _f32(v), _ew32(e_w), _f32(out), _f32(g)
+    if qf.shape != ((E if per_edge else dim_size), 128) or kf.shape != (E, 128) or vf.shape != (E, 128) or \
+            of.shape != (dim_size, 128) or gf.shape != (dim_size, 128) or (ew is not None and ew.numel() != E) or seg.numel() != dim_size + 1:
+        raise ValueError("scatter_attention backward: shapes of q / k / v / e_w / out / grad disagree")
+    dq, dk, dv = torch.empty_like(qf), torch.empty_like(kf), torch.empty_like(vf)
+    d_ew = None if ew is None else torch.empty_like(ew)
+    hip_lib.check(hip_lib.load().dd_attn_aggregate_node_bwd(
+        hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size, hip_lib.ptr(of),
+        hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.stream_ptr(dev)),
+        "dd_attn_aggregate_node_bwd")
+    return _grad_like(dq, q), _grad_like(dk, k), _grad_like(dv, v), (None if d_ew is None else _grad_like(d_ew, e_w))
+
+
+def _attention_pos_bwd(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, g):
+    """(dq, dk, dv16, d_rel, d_ew or None) of `_attention_pos` (dd_attn_aggregate_pos_bwd)."""
+    E, dev = k.size(0), k.device
+    qf, kf, vf, rf, ew, gf = _f32(q), _f32(k), _f32(v), _f32(rel_x), _ew32(e_w), _f32(g)
+    if qf.shape != (dim_size, 128) or kf.shape != (E, 128) or vf.shape != (E, 16) or rf.shape != (E, 3) or gf.shape != (dim_size, 3) or \
+            (ew is not None and ew.numel() != E) or seg.numel() != dim_size + 1:
+        raise ValueError("scatter_attention_pos backward: shapes of q / k / v / rel_x / e_w / grad disagree")
+    dq, dk, dv, dr = torch.empty_like(qf), torch.empty_like(kf), torch.empty_like(vf), torch.empty_like(rf)
+    d_ew = None if ew is None else torch.empty_like(ew)
+    hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_bwd(
+        hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size, hip_lib.ptr(gf),
+        hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.ptr(dr), hip_lib.stream_ptr(dev)),
+        "dd_attn_aggregate_pos_bwd")
+    return _grad_like(dq, q), _grad_like(dk, k), _grad_like(dv, v), _grad_like(dr, rel_x), (None if d_ew is None else _grad_like(d_ew, e_w))
+
+
+def _only_needed(ctx, grads):
+    return tuple(g if g is not None and need else None for g, need in zip(grads, ctx.needs_input_grad))
+
+
+class _ScatterAttention(torch.autograd.Function):
+    """scatter_attention with the HIP backward; the forward is the no-grad code path (same kernel, same result)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, e_w, seg, dim_size):
+        out = _attention_node(q, k, v, e_w, seg, dim_size)
+        ctx.save_for_backward(q, k, v, e_w, seg, out)
+        ctx.dim_size = dim_size
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        q, k, v, e_w, seg, out = ctx.saved_tensors
+        dq, dk, dv, d_ew = _attention_node_bwd(q, k, v, e_w, seg, ctx.dim_size, out, g)
+        return _only_needed(ctx, (dq, dk, dv, d_ew, None, None))
+
+
+class _ScatterAttentionPos(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, rel_x, e_w, seg, dim_size):
+        ctx.save_for_backward(q, k, v, rel_x, e_w, seg)
+        ctx.dim_size = dim_size
+        return _attention_pos(q, k, v, rel_x, e_w, seg, dim_size)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        q, k, v, rel_x, e_w, seg = ctx.saved_tensors
+        dq, dk, dv, dr, d_ew = _attention_pos_bwd(q, k, v, rel_x, e_w, seg, ctx.dim_size, g)
+        return _only_needed(ctx, (dq, dk, dv, dr, d_ew, None, None))
+
+
+def scatter_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, index, dim_size: int,
+                      e_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``scatter_sum(scatter_softmax((q_e * k / sqrt(8)).sum(-1), index)[..., None] * (v * e_w), index, dim_size)``
+    flattened to ``[dim_size,128]`` (16 heads x 8).  ``q`` is ``[dim_size,128]`` (gathered as ``q[index]`` by the
+    reference's node / coordinate layers) or per edge ``[E,128]`` (bond layer: rows of a segment are identical).
+    ``index``: the sorted destination vector, or its :class:`SegmentPlan` (no device -> host round trip per call).
+    Differentiable w.r.t. ``q``, ``k``, ``v`` and ``e_w`` (dd_attn_aggregate_node_bwd; no double backward)."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        hip_lib.require_gpu(t, name)
+    dim_size = int(dim_size)
+    seg = _attn_seg(index, dim_size, k.size(0))
+    if _needs_grad(q, k, v, e_w):
+        return _ScatterAttention.apply(q, k, v, e_w, seg, dim_size)
+    return _attention_node(q, k, v, e_w, seg, dim_size)
+
+
+def scatter_attention_pos(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_x: torch.Tensor, index,
+                          dim_size: int, e_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PosUpdateLayer's aggregation: ``v`` is ``[E,16]`` (one scalar per head), ``rel_x`` ``[E,3]``; returns
+    ``scatter_sum(alpha[..., None] * (v * e_w)[..., None] * rel_x[:, None], index).mean(1)`` — ``[dim_size,3]``.
+    ``index`` as for :func:`scatter_attention`; differentiable w.r.t. ``q``, ``k``, ``v``, ``rel_x`` and ``e_w``."""
+    for name, t in (("q", q), ("k", k), ("v", v), ("rel_x", rel_x)):
+        hip_lib.require_gpu(t, name)
+    dim_size = int(dim_size)
+    seg = _attn_seg(index, dim_size, k.size(0))
+    if _needs_grad(q, k, v, rel_x, e_w):
+        return _ScatterAttentionPos.apply(q, k, v, rel_x, e_w, seg, dim_size)
+    return _attention_pos(q, k, v, rel_x, e_w, seg, dim_size)
+
+
+def scatter_attention_backward(q, k, v, index, dim_size: int, e_w, out, grad_out):
+    """``(dq, dk, dv, d_ew or None)`` of :func:`scatter_attention` given its result ``out`` and the gradient of it."""
+    return _attention_node_bwd(q, k, v, e_w, _attn_seg(index, int(dim_size), k.size(0)), int(dim_size), out, grad_out)
+
+
+def scatter_attention_pos_backward(q, k, v, rel_x, index, dim_size: int, e_w, grad_out):
+    """``(dq, dk, dv, d_rel, d_ew or None)`` of :func:`scatter_attention_pos` given the gradient of its result."""
+    return _attention_pos_bwd(q, k, v, rel_x, e_w, _attn_seg(index, int(dim_size), k.size(0)), int(dim_size), grad_out)
 
 
 # ------------------------------------------------------------------------------------------------------------------

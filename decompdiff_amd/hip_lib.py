@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "dd_forward_ex", "dd_sample_steps_ex", "dd_sample_steps_graph_ex", "dd_graph_create_ex", "dd_sample_steps_graph_multi_ex",
     "dd_node_out_fc",
     "dd_forward_ex2", "dd_sample_steps_ex2", "dd_sample_steps_graph_ex2", "dd_graph_create_ex2", "dd_sample_steps_graph_multi_ex2",
+    "dd_attn_aggregate_node_bwd", "dd_attn_aggregate_pos_bwd",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -178,6 +179,8 @@ def load():
         "dd_attn_aggregate_node": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
         "dd_attn_aggregate_triplet": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
         "dd_attn_aggregate_pos": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+        "dd_attn_aggregate_node_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7,
+        "dd_attn_aggregate_pos_bwd": [c_void_p] * 6 + [c_int] + [c_void_p] * 7,
         "dd_segment_reduce": [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p],
         "dd_segment_softmax": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
         "dd_debug_philox": [c_uint64, c_int, c_long, c_int, c_void_p, c_void_p],

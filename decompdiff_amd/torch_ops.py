@@ -40,7 +40,8 @@ def _(x, k, batch=None, loop=False, flow="source_to_target"):
 
 @torch.library.custom_op(f"{_NS}::scatter_attention", mutates_args=(), device_types="cuda")
 def scatter_attention(q: Tensor, k: Tensor, v: Tensor, index: Tensor, dim_size: int, e_w: Optional[Tensor] = None) -> Tensor:
-    return F.scatter_attention(q, k, v, index, dim_size, e_w)
+    with torch.no_grad():                                   # (the autograd formula is registered below)
+        return F.scatter_attention(q, k, v, index, dim_size, e_w)
 
 
 @scatter_attention.register_fake
@@ -51,12 +52,40 @@ def _(q, k, v, index, dim_size, e_w=None):
 @torch.library.custom_op(f"{_NS}::scatter_attention_pos", mutates_args=(), device_types="cuda")
 def scatter_attention_pos(q: Tensor, k: Tensor, v: Tensor, rel_x: Tensor, index: Tensor, dim_size: int,
                           e_w: Optional[Tensor] = None) -> Tensor:
-    return F.scatter_attention_pos(q, k, v, rel_x, index, dim_size, e_w)
+    with torch.no_grad():
+        return F.scatter_attention_pos(q, k, v, rel_x, index, dim_size, e_w)
 
 
 @scatter_attention_pos.register_fake
 def _(q, k, v, rel_x, index, dim_size, e_w=None):
     return k.new_empty((dim_size, 3), dtype=torch.float32)
+
+
+# The backward passes of the two attention ops are ops themselves (dd_attn_aggregate_node_bwd / _pos_bwd behind them), so a
+# traced backward graph holds them as single nodes.  An absent e_w comes back as an empty tensor (an op cannot return None).
+@torch.library.custom_op(f"{_NS}::scatter_attention_backward", mutates_args=(), device_types="cuda")
+def scatter_attention_backward(q: Tensor, k: Tensor, v: Tensor, index: Tensor, dim_size: int, e_w: Optional[Tensor], out: Tensor,
+                               grad_out: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    dq, dk, dv, d_ew = F.scatter_attention_backward(q, k, v, index, dim_size, e_w, out, grad_out)
+    return dq, dk, dv, (d_ew if d_ew is not None else k.new_empty(0))
+
+
+@scatter_attention_backward.register_fake
+def _(q, k, v, index, dim_size, e_w, out, grad_out):
+    return torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), (torch.empty_like(e_w) if e_w is not None else k.new_empty(0))
+
+
+@torch.library.custom_op(f"{_NS}::scatter_attention_pos_backward", mutates_args=(), device_types="cuda")
+def scatter_attention_pos_backward(q: Tensor, k: Tensor, v: Tensor, rel_x: Tensor, index: Tensor, dim_size: int, e_w: Optional[Tensor],
+                                   grad_out: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    dq, dk, dv, dr, d_ew = F.scatter_attention_pos_backward(q, k, v, rel_x, index, dim_size, e_w, grad_out)
+    return dq, dk, dv, dr, (d_ew if d_ew is not None else k.new_empty(0))
+
+
+@scatter_attention_pos_backward.register_fake
+def _(q, k, v, rel_x, index, dim_size, e_w, grad_out):
+    return (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), torch.empty_like(rel_x),
+            (torch.empty_like(e_w) if e_w is not None else k.new_empty(0)))
 
 
 def _n_out(index, dim_size):
@@ -156,6 +185,40 @@ def _bw_softmax(ctx, g):
 
 
 scatter_softmax.register_autograd(_bw_softmax, setup_context=_setup_softmax)
+
+
+def _setup_attention(ctx, inputs, output):
+    q, k, v, index, dim_size, e_w = inputs
+    ctx.save_for_backward(q, k, v, index, e_w, output)
+    ctx.dim_size = dim_size
+
+
+def _bw_attention(ctx, g):
+    q, k, v, index, e_w, out = ctx.saved_tensors
+    dq, dk, dv, d_ew = torch.ops.decompdiff_amd.scatter_attention_backward(q, k, v, index, ctx.dim_size, e_w, out, g.contiguous())
+    need = ctx.needs_input_grad
+    return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None,
+            d_ew if e_w is not None and need[5] else None)
+
+
+scatter_attention.register_autograd(_bw_attention, setup_context=_setup_attention)
+
+
+def _setup_attention_pos(ctx, inputs, output):
+    q, k, v, rel_x, index, dim_size, e_w = inputs
+    ctx.save_for_backward(q, k, v, rel_x, index, e_w)
+    ctx.dim_size = dim_size
+
+
+def _bw_attention_pos(ctx, g):
+    q, k, v, rel_x, index, e_w = ctx.saved_tensors
+    dq, dk, dv, dr, d_ew = torch.ops.decompdiff_amd.scatter_attention_pos_backward(q, k, v, rel_x, index, ctx.dim_size, e_w, g.contiguous())
+    need = ctx.needs_input_grad
+    return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, dr if need[3] else None, None, None,
+            d_ew if e_w is not None and need[6] else None)
+
+
+scatter_attention_pos.register_autograd(_bw_attention_pos, setup_context=_setup_attention_pos)
 
 
 def _setup_min(ctx, inputs, output):

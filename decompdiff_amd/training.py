@@ -532,6 +532,10 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
     e_w = torch.sigmoid(P.mlp("refine_net.edge_pred_layer", _gauss(d0)))
     NLm1, Ebs = NL - 1, NL * (NL - 1)
     mask_l = is_lig.float().unsqueeze(-1)
+    # DD_TRAIN_FUSED_ATTN=1 (opt-in, unpadded passes): each attention site is ONE differentiable op on the op-level kernels
+    # (FN.scatter_attention / scatter_attention_pos: dd_attn_aggregate_* forward, dd_attn_aggregate_*_bwd backward) instead of
+    # gather, product, segment softmax, product, segment sum.  Padded passes keep the composed path: the kernels have no member mask.
+    fused = pad is None and os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1"
     out_fc = bool(getattr(cfg, "x2h_out_fc", False))
     for l in range(int(cfg.num_layers)):
         p = f"refine_net.base_block.{l}"
@@ -565,13 +569,19 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         # node_layer_with_edge (NodeUpdateLayer, :42-74)
         k_e, v_e = node_layer_edge("node_layer_with_edge", h, H)
         q_e = P.mlp(f"{p}.node_layer_with_edge.hq_func", h)
-        alpha = _attention(gather(q_e, p_dst), k_e, v_e, p_dst)
-        a_edge = scatter_sum((alpha.unsqueeze(-1) * (v_e * e_w).view(-1, NH, H // NH)).reshape(-1, H), p_dst)
+        if fused:
+            a_edge = FN.scatter_attention(q_e, k_e, v_e, p_dst, B * N, e_w)
+        else:
+            alpha = _attention(gather(q_e, p_dst), k_e, v_e, p_dst)
+            a_edge = scatter_sum((alpha.unsqueeze(-1) * (v_e * e_w).view(-1, NH, H // NH)).reshape(-1, H), p_dst)
         # node_layer_with_bond
         k_b, v_b = node_layer_bond("node_layer_with_bond", h, h_bond)
         q_b = P.mlp(f"{p}.node_layer_with_bond.hq_func", h)
-        alpha = _attention(gather(q_b, p_bdst), k_b, v_b, p_bdst, member_real=real_b)
-        a_bond = scatter_sum((alpha.unsqueeze(-1) * v_b.view(-1, NH, H // NH)).reshape(-1, H), p_bdst)
+        if fused:
+            a_bond = FN.scatter_attention(q_b, k_b, v_b, p_bdst, B * N)
+        else:
+            alpha = _attention(gather(q_b, p_bdst), k_b, v_b, p_bdst, member_real=real_b)
+            a_bond = scatter_sum((alpha.unsqueeze(-1) * v_b.view(-1, NH, H // NH)).reshape(-1, H), p_bdst)
         # bond_layer (BondUpdateLayer, :125-167): kv = [h_bond[kj](128), G(d_kj)(20), G(d_ji)(20), angle(13), h[k], h[j]]
         if trip is not None:
             nm_b = f"{p}.bond_layer"
@@ -593,8 +603,11 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
                 kv.append(P.mlp_tail(f"{nm_b}.{f_}", pre))
             # hq depends on the (j -> i) bond only: evaluated per bond, gathered per triplet (exact)
             q_bond = P.mlp(f"{nm_b}.hq_func", torch.cat([h_bond, gather(h, p_bdst)], -1))
-            alpha = _attention(gather(q_bond, p_ji), kv[0], kv[1], p_ji, member_real=real_t)
-            d_hb = scatter_sum((alpha.unsqueeze(-1) * kv[1].view(-1, NH, H // NH)).reshape(-1, H), p_ji)
+            if fused:
+                d_hb = FN.scatter_attention(q_bond, kv[0], kv[1], p_ji, Eb_tot)
+            else:
+                alpha = _attention(gather(q_bond, p_ji), kv[0], kv[1], p_ji, member_real=real_t)
+                d_hb = scatter_sum((alpha.unsqueeze(-1) * kv[1].view(-1, NH, H // NH)).reshape(-1, H), p_ji)
         else:
             d_hb = torch.zeros_like(h_bond)
         new_h_bond = h_bond + d_hb
@@ -610,13 +623,20 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         # pos_layer_with_edge / pos_layer_with_bond (PosUpdateLayer, :188-210), with the NEW h / h_bond
         k_pe, v_pe = node_layer_edge("pos_layer_with_edge", new_h, NH)
         q_pe = P.mlp(f"{p}.pos_layer_with_edge.xq_func", new_h)
-        alpha = _attention(gather(q_pe, p_dst), k_pe, None, p_dst)
-        dx_e = scatter_sum(((alpha * (v_pe * e_w)).unsqueeze(-1) * rel.unsqueeze(1)).reshape(-1, NH * 3), p_dst).view(-1, NH, 3).mean(1)
+        if fused:
+            dx_e = FN.scatter_attention_pos(q_pe, k_pe, v_pe, rel, p_dst, B * N, e_w)
+        else:
+            alpha = _attention(gather(q_pe, p_dst), k_pe, None, p_dst)
+            dx_e = scatter_sum(((alpha * (v_pe * e_w)).unsqueeze(-1) * rel.unsqueeze(1)).reshape(-1, NH * 3), p_dst).view(-1, NH, 3).mean(1)
         k_pb, v_pb = node_layer_bond("pos_layer_with_bond", new_h, new_h_bond)
         q_pb = P.mlp(f"{p}.pos_layer_with_bond.xq_func", new_h)
-        alpha = _attention(gather(q_pb, p_bdst), k_pb, None, p_bdst, member_real=real_b)
-        rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
-        dx_b = scatter_sum(((alpha * v_pb).unsqueeze(-1) * rel_b.unsqueeze(1)).reshape(-1, NH * 3), p_bdst).view(-1, NH, 3).mean(1)
+        if fused:
+            rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
+            dx_b = FN.scatter_attention_pos(q_pb, k_pb, v_pb, rel_b, p_bdst, B * N)
+        else:
+            alpha = _attention(gather(q_pb, p_bdst), k_pb, None, p_bdst, member_real=real_b)
+            rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
+            dx_b =scatter_sum(((alpha * v_pb).unsqueeze(-1) * rel_b.unsqueeze(1)).reshape(-1, NH * 3), p_bdst).view(-1, NH, 3).mean(1)
         x = x + (dx_e + dx_b) * mask_l
         h, h_bond = new_h, new_h_bond
     softplus = lambda t: F.softplus(t) - math.log(2.0)                              # ShiftedSoftplus (common.py:66-72)
@@ -1028,7 +1048,9 @@ class GraphedTrainStep:
         if os.environ.get("DD_TRAIN_GRAPH", "1") == "0":
             return self._eager(prep)
         if dense:
-            key = (tuple(n_p), tuple(n_l), int(prior_centers.shape[0]), str(dev), model.model_mean_type)
+            # (DD_TRAIN_FUSED_ATTN is read by `network` during the capture: a graph belongs to the setting it was captured under)
+            key = (tuple(n_p), tuple(n_l), int(prior_centers.shape[0]), str(dev), model.model_mean_type,
+                   os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1")
             data, names, fn = prep, PREP_TENSORS, objective
         else:
             # samples of different sizes: the padded layout of their shape bucket (sizes rounded up to `bucket`) -- all batches

@@ -263,6 +263,20 @@ int dd_attn_aggregate_triplet(const float* q /*[E3,128]*/, const float* k, const
 /* PosUpdateLayer form: v16 [E,16] per head, rel_x [E,3]; out[s] = mean_heads(sum_e alpha * v16 * e_w * rel_x) [n_seg,3]. */
 int dd_attn_aggregate_pos(const float* q /*[n_seg,128]*/, const float* k, const float* v16, const float* e_w, const float* rel_x,
                           const int32_t* seg_ptr, int n_seg, float* out /*[n_seg,3]*/, void* stream);
+/* Backward of the pair above (training hosts): gradients of q, k, v (v16), e_w and rel_x from d_out, the gradient of the
+ * output.  The scores are recomputed (nothing is saved by the forward); the node form also reads `out`, the forward's result.
+ * dq has q's shape ([n_seg,128], or [E,128] with q_per_edge != 0: dq[e] = scale * ds[e] * k[e] per edge).  d_ew is NULL
+ * exactly when e_w is NULL (DD_ERR_BAD_ARG otherwise).  No atomics: every element of every output is written once, except
+ * that an empty segment writes only its zero dq row (q per segment) -- bitwise reproducible, and the buffers need no
+ * initialisation.  The triplet form is the node form with q_per_edge = 1 and e_w = NULL.  (New entry points, ABI unchanged.) */
+int dd_attn_aggregate_node_bwd(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w /*NULL ok*/,
+                               const int32_t* seg_ptr, int n_seg, const float* out /*[n_seg,128]*/, const float* d_out /*[n_seg,128]*/,
+                               float* dq, float* dk /*[E,128]*/, float* dv /*[E,128]*/, float* d_ew /*[E]; NULL iff e_w NULL*/,
+                               void* stream);
+int dd_attn_aggregate_pos_bwd(const float* q /*[n_seg,128]*/, const float* k, const float* v16, const float* e_w /*NULL ok*/,
+                              const float* rel_x, const int32_t* seg_ptr, int n_seg, const float* d_out /*[n_seg,3]*/,
+                              float* dq /*[n_seg,128]*/, float* dk /*[E,128]*/, float* dv16 /*[E,16]*/,
+                              float* d_ew /*[E]; NULL iff e_w NULL*/, float* d_rel /*[E,3]*/, void* stream);
 
 /* Stand-alone torch_scatter drop-ins over dim 0 of a [E,F] fp32 tensor whose rows are grouped by destination (CSR
  * segments seg_ptr [n_seg+1]); reference call sites: scatter_softmax / scatter_sum uni_transformer_edge.py:64,68,160,164,
