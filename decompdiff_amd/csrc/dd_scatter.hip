@@ -29,22 +29,38 @@ __device__ __forceinline__ float head_sum(float v) {
   return v;
 }
 
-template <bool POS>
-__global__ __launch_bounds__(256) void k_attn_aggregate(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
-                                                        const float* __restrict__ v, const float* __restrict__ e_w,
-                                                        const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
-                                                        int n_seg, float* __restrict__ out) {
+// Member masks (MASK; padded batches): member_mask[e] != 0 means member e is real.  A masked member does not exist: its byte is
+// wave-uniform, and a scalar branch steps over everything that would use its k / v / e_w / rel_x (and per-edge q) rows, so
+// whatever those rows hold -- NaN included -- reaches no result.  The real members run through the same recurrence, in member
+// order, with the same expressions: the results are bit for bit those of the segment compacted to its real members.
+
+// first real member of the segment e0 .. e1, or -1 (wave-uniform): 64 mask bytes per ballot
+__device__ __forceinline__ int first_real(const uint8_t* __restrict__ member_mask, int e0, int e1, int lane) {
+  for (int b = e0; b < e1; b += 64) {
+    const int ee = b + lane;
+    const unsigned long long real = __ballot(ee < e1 && member_mask[ee] != 0);
+    if (real) return __builtin_amdgcn_readfirstlane(b + __ffsll(real) - 1);
+  }
+  return -1;
+}
+
+template <bool POS, bool MASK>
+__device__ __forceinline__ void attn_aggregate(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
+                                               const float* __restrict__ v, const float* __restrict__ e_w,
+                                               const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
+                                               const uint8_t* __restrict__ member_mask, int n_seg, float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   // the segment and its edge range are wave-uniform: kept in SGPRs, so e_w / rel_x / seg_ptr become scalar loads
   const int seg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (seg >= n_seg) return;
   const int e0 = __builtin_amdgcn_readfirstlane(seg_ptr[seg]), e1 = __builtin_amdgcn_readfirstlane(seg_ptr[seg + 1]);
-  if (e1 <= e0) {                                        // scatter_sum leaves untouched rows at zero
+  const int ef = MASK ? first_real(member_mask, e0, e1, lane) : e0;                // (per-edge q is read from this member's row)
+  if (e1 <= e0 || (MASK && ef < 0)) {                    // scatter_sum leaves untouched rows at zero
     if (POS) { if (lane < 3) out[(long)seg * 3 + lane] = 0.f; }
     else *reinterpret_cast<float2*>(out + (long)seg * 128 + 2 * lane) = make_float2(0.f, 0.f);
     return;
   }
-  const float2 qv = *reinterpret_cast<const float2*>(q + (long)(q_per_edge ? e0 : seg) * 128 + 2 * lane);
+  const float2 qv = *reinterpret_cast<const float2*>(q + (long)(q_per_edge ? ef : seg) * 128 + 2 * lane);
   const float scale = 0.35355339059327373f;              // 1 / sqrt(8)
   float mx = -INFINITY, den = 0.f;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f;                    // !POS: a0, a1 = channels 2l, 2l+1; POS: xyz of head l/4
@@ -52,9 +68,11 @@ __global__ __launch_bounds__(256) void k_attn_aggregate(const float* __restrict_
   for (int e = e0; e < e1; e += UNROLL) {
     float2 kk[UNROLL], vv[UNROLL];
     float w[UNROLL], r[UNROLL][3];
+    int real[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const long ee = e + u < e1 ? e + u : e1 - 1;       // clamped: the tail replays the last edge and is masked below
+      real[u] = MASK ? __builtin_amdgcn_readfirstlane(member_mask[ee]) : 1;
       kk[u] = *reinterpret_cast<const float2*>(k + ee * 128 + 2 * lane);
       if (POS) {
         vv[u].x = v[ee * 16 + head];
@@ -67,6 +85,7 @@ __global__ __launch_bounds__(256) void k_attn_aggregate(const float* __restrict_
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       if (e + u >= e1) break;
+      if (MASK && !real[u]) continue;
       const float s = head_sum(fmaf(qv.y, kk[u].y, qv.x * kk[u].x)) * scale;
       const float mn = fmaxf(mx, s);
       const float corr = __expf(mx - mn), p = __expf(s - mn);    // (mx = -inf on the first edge: corr = 0)
@@ -91,6 +110,23 @@ __global__ __launch_bounds__(256) void k_attn_aggregate(const float* __restrict_
   }
 }
 
+template <bool POS>
+__global__ __launch_bounds__(256) void k_attn_aggregate(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
+                                                        const float* __restrict__ v, const float* __restrict__ e_w,
+                                                        const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
+                                                        int n_seg, float* __restrict__ out) {
+  attn_aggregate<POS, false>(q, q_per_edge, k, v, e_w, rel_x, seg_ptr, nullptr, n_seg, out);
+}
+
+template <bool POS>
+__global__ __launch_bounds__(256) void k_attn_aggregate_masked(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
+                                                               const float* __restrict__ v, const float* __restrict__ e_w,
+                                                               const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
+                                                               const uint8_t* __restrict__ member_mask, int n_seg,
+                                                               float* __restrict__ out) {
+  attn_aggregate<POS, true>(q, q_per_edge, k, v, e_w, rel_x, seg_ptr, member_mask, n_seg, out);
+}
+
 // ---- backward of k_attn_aggregate, same mapping (a wave per destination, lane l = channels 2l, 2l+1, 4 members in flight).
 // With g = d_out, alpha = the forward's softmax weight, w = e_w (1 without), per member e and head h:
 //   node form:        t = w * sum_{c in h} g[s,c] v[e,c]          D = sum_{c in h} g[s,c] out[s,c]   (= sum_e alpha t)
@@ -100,13 +136,31 @@ __global__ __launch_bounds__(256) void k_attn_aggregate(const float* __restrict_
 // the running maximum and denominator as the forward does, pass 2 reads the members again, forms alpha and writes every
 // gradient.  No atomics: each output element is written by one lane, once -- reproducible bit for bit, and the buffers
 // need no initialisation.  An empty segment writes its zero dq row (q per segment) and nothing else.
+// MASK: a masked member takes no part in either pass and gets zeros in its dk, dv, d_ew, d_rel (and per-edge dq) rows -- still
+// one write per element; a segment whose members are all masked does that for every member and writes its zero dq row.
+// the gradient rows of a member that does not exist (MASK)
 template <bool POS>
-__global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
-                                                            const float* __restrict__ v, const float* __restrict__ e_w,
-                                                            const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
-                                                            int n_seg, const float* __restrict__ out, const float* __restrict__ d_out,
-                                                            float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv,
-                                                            float* __restrict__ d_ew, float* __restrict__ d_rel) {
+__device__ __forceinline__ void zero_member(long ee, int lane, int q_per_edge, float* __restrict__ dq, float* __restrict__ dk,
+                                            float* __restrict__ dv, float* __restrict__ d_ew, float* __restrict__ d_rel) {
+  const float2 z = make_float2(0.f, 0.f);
+  *reinterpret_cast<float2*>(dk + ee * 128 + 2 * lane) = z;
+  if (q_per_edge) *reinterpret_cast<float2*>(dq + ee * 128 + 2 * lane) = z;
+  if (POS) {
+    if ((lane & 3) == 0) dv[ee * 16 + (lane >> 2)] = 0.f;
+    if (lane < 3) d_rel[ee * 3 + lane] = 0.f;
+  } else {
+    *reinterpret_cast<float2*>(dv + ee * 128 + 2 * lane) = z;
+  }
+  if (d_ew && lane == 0) d_ew[ee] = 0.f;
+}
+
+template <bool POS, bool MASK>
+__device__ __forceinline__ void attn_aggregate_bwd(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
+                                                   const float* __restrict__ v, const float* __restrict__ e_w,
+                                                   const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
+                                                   const uint8_t* __restrict__ member_mask, int n_seg, const float* __restrict__ out,
+                                                   const float* __restrict__ d_out, float* __restrict__ dq, float* __restrict__ dk,
+                                                   float* __restrict__ dv, float* __restrict__ d_ew, float* __restrict__ d_rel) {
   const int lane = threadIdx.x & 63;
   const int seg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (seg >= n_seg) return;
@@ -115,7 +169,13 @@ __global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restr
     if (!q_per_edge) *reinterpret_cast<float2*>(dq + (long)seg * 128 + 2 * lane) = make_float2(0.f, 0.f);
     return;
   }
-  const float2 qv = *reinterpret_cast<const float2*>(q + (long)(q_per_edge ? e0 : seg) * 128 + 2 * lane);
+  const int ef = MASK ? first_real(member_mask, e0, e1, lane) : e0;
+  if (MASK && ef < 0) {
+    for (int e = e0; e < e1; ++e) zero_member<POS>(e, lane, q_per_edge, dq, dk, dv, d_ew, d_rel);
+    if (!q_per_edge) *reinterpret_cast<float2*>(dq + (long)seg * 128 + 2 * lane) = make_float2(0.f, 0.f);
+    return;
+  }
+  const float2 qv = *reinterpret_cast<const float2*>(q + (long)(q_per_edge ? ef : seg) * 128 + 2 * lane);
   const float scale = 0.35355339059327373f;              // 1 / sqrt(8)
   const int head = lane >> 2;
   const bool lead = (lane & 3) == 0;
@@ -132,9 +192,11 @@ __global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restr
   for (int e = e0; e < e1; e += UNROLL) {
     float2 kk[UNROLL];
     float t[UNROLL];
+    int real[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const long ee = e + u < e1 ? e + u : e1 - 1;       // clamped, masked below
+      real[u] = MASK ? __builtin_amdgcn_readfirstlane(member_mask[ee]) : 1;
       kk[u] = *reinterpret_cast<const float2*>(k + ee * 128 + 2 * lane);
       if (POS) {
         const float ue = fmaf(g0, rel_x[ee * 3], fmaf(g1, rel_x[ee * 3 + 1], g2 * rel_x[ee * 3 + 2])) * 0.0625f;
@@ -144,6 +206,7 @@ __global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restr
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       if (e + u >= e1) break;
+      if (MASK && !real[u]) continue;
       const float s = head_sum(fmaf(qv.y, kk[u].y, qv.x * kk[u].x)) * scale;
       const float mn = fmaxf(mx, s);
       const float corr = __expf(mx - mn), p = __expf(s - mn);
@@ -165,9 +228,11 @@ __global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restr
   for (int e = e0; e < e1; e += UNROLL) {
     float2 kk[UNROLL], vv[UNROLL];
     float w[UNROLL], ue[UNROLL];
+    int real[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const long ee = e + u < e1 ? e + u : e1 - 1;       // clamped: nothing is stored for a replayed member
+      real[u] = MASK ? __builtin_amdgcn_readfirstlane(member_mask[ee]) : 1;
       kk[u] = *reinterpret_cast<const float2*>(k + ee * 128 + 2 * lane);
       if (POS) {
         vv[u].x = v[ee * 16 + head];
@@ -181,6 +246,7 @@ __global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restr
     for (int u = 0; u < UNROLL; ++u) {
       if (e + u >= e1) break;
       const long ee = e + u;
+      if (MASK && !real[u]) { zero_member<POS>(ee, lane, q_per_edge, dq, dk, dv, d_ew, d_rel); continue; }
       const float s = head_sum(fmaf(qv.y, kk[u].y, qv.x * kk[u].x)) * scale;
       const float a = __expf(s - mx) * inv;
       float ds;
@@ -210,6 +276,27 @@ __global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restr
     }
   }
   if (!q_per_edge) *reinterpret_cast<float2*>(dq + (long)seg * 128 + 2 * lane) = make_float2(aq0, aq1);
+}
+
+template <bool POS>
+__global__ __launch_bounds__(256) void k_attn_aggregate_bwd(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
+                                                            const float* __restrict__ v, const float* __restrict__ e_w,
+                                                            const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
+                                                            int n_seg, const float* __restrict__ out, const float* __restrict__ d_out,
+                                                            float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv,
+                                                            float* __restrict__ d_ew, float* __restrict__ d_rel) {
+  attn_aggregate_bwd<POS, false>(q, q_per_edge, k, v, e_w, rel_x, seg_ptr, nullptr, n_seg, out, d_out, dq, dk, dv, d_ew, d_rel);
+}
+
+template <bool POS>
+__global__ __launch_bounds__(256) void k_attn_aggregate_bwd_masked(const float* __restrict__ q, int q_per_edge, const float* __restrict__ k,
+                                                                   const float* __restrict__ v, const float* __restrict__ e_w,
+                                                                   const float* __restrict__ rel_x, const int32_t* __restrict__ seg_ptr,
+                                                                   const uint8_t* __restrict__ member_mask, int n_seg,
+                                                                   const float* __restrict__ out, const float* __restrict__ d_out,
+                                                                   float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv,
+                                                                   float* __restrict__ d_ew, float* __restrict__ d_rel) {
+  attn_aggregate_bwd<POS, true>(q, q_per_edge, k, v, e_w, rel_x, seg_ptr, member_mask, n_seg, out, d_out, dq, dk, dv, d_ew, d_rel);
 }
 
 
@@ -327,6 +414,56 @@ extern "C" int dd_attn_aggregate_pos_bwd(const float* q, const float* k, const f
   if (n_seg == 0) return DD_OK;
   hipLaunchKernelGGL(dd::k_attn_aggregate_bwd<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w,
                      rel_x, seg_ptr, n_seg, nullptr, d_out, dq, dk, dv16, d_ew, d_rel);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+// ---- masked forms: member_mask [E], non-zero = the member is real; NULL = all real, which IS the unmasked launch
+extern "C" int dd_attn_aggregate_node_masked(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
+                                             const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, float* out, void* stream) {
+  if (!member_mask) return dd_attn_aggregate_node(q, q_per_edge, k, v, e_w, seg_ptr, n_seg, out, stream);
+  if (!q || !k || !v || !seg_ptr || !out || n_seg < 0) return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  hipLaunchKernelGGL(dd::k_attn_aggregate_masked<false>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, q_per_edge, k, v,
+                     e_w, nullptr, seg_ptr, member_mask, n_seg, out);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+extern "C" int dd_attn_aggregate_pos_masked(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
+                                            const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, float* out, void* stream) {
+  if (!member_mask) return dd_attn_aggregate_pos(q, k, v16, e_w, rel_x, seg_ptr, n_seg, out, stream);
+  if (!q || !k || !v16 || !rel_x || !seg_ptr || !out || n_seg < 0) return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  hipLaunchKernelGGL(dd::k_attn_aggregate_masked<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w,
+                     rel_x, seg_ptr, member_mask, n_seg, out);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+extern "C" int dd_attn_aggregate_node_bwd_masked(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
+                                                 const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, const float* out,
+                                                 const float* d_out, float* dq, float* dk, float* dv, float* d_ew, void* stream) {
+  if (!member_mask) return dd_attn_aggregate_node_bwd(q, q_per_edge, k, v, e_w, seg_ptr, n_seg, out, d_out, dq, dk, dv, d_ew, stream);
+  if (!q || !k || !v || !seg_ptr || !out || !d_out || !dq || !dk || !dv || (e_w == nullptr) != (d_ew == nullptr) || n_seg < 0)
+    return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd_masked<false>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, q_per_edge, k,
+                     v, e_w, nullptr, seg_ptr, member_mask, n_seg, out, d_out, dq, dk, dv, d_ew, nullptr);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+extern "C" int dd_attn_aggregate_pos_bwd_masked(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
+                                                const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, const float* d_out,
+                                                float* dq, float* dk, float* dv16, float* d_ew, float* d_rel, void* stream) {
+  if (!member_mask) return dd_attn_aggregate_pos_bwd(q, k, v16, e_w, rel_x, seg_ptr, n_seg, d_out, dq, dk, dv16, d_ew, d_rel, stream);
+  if (!q || !k || !v16 || !rel_x || !seg_ptr || !d_out || !dq || !dk || !dv16 || !d_rel || (e_w == nullptr) != (d_ew == nullptr) ||
+      n_seg < 0)
+    return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd_masked<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w,
+                     rel_x, seg_ptr, member_mask, n_seg, nullptr, d_out, dq, dk, dv16, d_ew, d_rel);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }

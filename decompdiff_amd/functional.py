@@ -164,13 +164,32 @@ def _per_edge(q: torch.Tensor, E: int, dim_size: int) -> bool:
     return q.size(0) == E and q.size(0) != dim_size
 
 
-def _attention_node(q, k, v, e_w, seg: torch.Tensor, dim_size: int) -> torch.Tensor:
+def _member_mask(member_mask, k: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    """The mask as the kernels read it: one byte per member (uint8; a bool tensor is viewed, not copied), non-zero = real."""
+    if member_mask is None:
+        return None
+    if not torch.is_tensor(member_mask) or member_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{what}: member_mask must be a bool or uint8 tensor")
+    if member_mask.dim() != 1 or member_mask.numel() != k.size(0):
+        raise ValueError(f"{what}: member_mask must be [E], one entry per row of k")
+    if member_mask.device != k.device:
+        raise ValueError(f"{what}: member_mask must be on the device of k ({k.device}, got {member_mask.device})")
+    m = member_mask.detach().contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _attention_node(q, k, v, e_w, seg: torch.Tensor, dim_size: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     per_edge = _per_edge(q, k.size(0), dim_size)
     out = torch.empty(dim_size, 128, device=k.device)
     ew = _ew32(e_w)
     # converted copies are bound to locals that outlive the launch: a temporary freed before the kernel is enqueued
     # would hand its block to the next same-size allocation (k and v would alias)
     qf, kf, vf = _f32(q), _f32(k), _f32(v)
+    if mask is not None:                                                            # (masked calls: the ctypes binding alone)
+        hip_lib.check(hip_lib.load().dd_attn_aggregate_node_masked(
+            hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size,
+            hip_lib.ptr(mask), hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_node_masked")
+        return out
     ext = torch_ext()
     if ext is not None:
         return ext.attn_aggregate_node(qf, bool(per_edge), kf, vf, ew, seg)
@@ -180,10 +199,15 @@ def _attention_node(q, k, v, e_w, seg: torch.Tensor, dim_size: int) -> torch.Ten
     return out
 
 
-def _attention_pos(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int) -> torch.Tensor:
+def _attention_pos(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     out = torch.empty(dim_size, 3, device=k.device)
     ew = _ew32(e_w)
     qf, kf, vf, rf = _f32(q), _f32(k), _f32(v), _f32(rel_x)                          # (alive past the launch, see above)
+    if mask is not None:
+        hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_masked(
+            hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
+            hip_lib.ptr(mask), hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_pos_masked")
+        return out
     ext = torch_ext()
     if ext is not None:
         return ext.attn_aggregate_pos(qf, kf, vf, ew, rf, seg)
@@ -193,8 +217,9 @@ def _attention_pos(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int) -> tor
     return out
 
 
-def _attention_node_bwd(q, k, v, e_w, seg: torch.Tensor, dim_size: int, out, g):
-    """(dq, dk, dv, d_ew or None) of `_attention_node`, each in its input's shape and dtype (dd_attn_aggregate_node_bwd)."""
+def _attention_node_bwd(q, k, v, e_w, seg: torch.Tensor, dim_size: int, out, g, mask: Optional[torch.Tensor] = None):
+    """(dq, dk, dv, d_ew or None) of `_attention_node`, each in its input's shape and dtype (dd_attn_aggregate_node_bwd; with a
+    member mask dd_attn_aggregate_node_bwd_masked)."""
     E, dev = k.size(0), k.device
     per_edge = _per_edge(q, E, dim_size)
     qf, kf, vf, ew, of, gf = _f32(q), _f32(k), _f32(v), _ew32(e_w), _f32(out), _f32(g)
@@ -203,15 +228,22 @@ def _attention_node_bwd(q, k, v, e_w, seg: torch.Tensor, dim_size: int, out, g):
         raise ValueError("scatter_attention backward: shapes of q / k / v / e_w / out / grad disagree")
     dq, dk, dv = torch.empty_like(qf), torch.empty_like(kf), torch.empty_like(vf)
     d_ew = None if ew is None else torch.empty_like(ew)
-    hip_lib.check(hip_lib.load().dd_attn_aggregate_node_bwd(
-        hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size, hip_lib.ptr(of),
-        hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.stream_ptr(dev)),
-        "dd_attn_aggregate_node_bwd")
+    if mask is not None:
+        hip_lib.check(hip_lib.load().dd_attn_aggregate_node_bwd_masked(
+            hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size,
+            hip_lib.ptr(mask), hip_lib.ptr(of), hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew),
+            hip_lib.stream_ptr(dev)), "dd_attn_aggregate_node_bwd_masked")
+    else:
+        hip_lib.check(hip_lib.load().dd_attn_aggregate_node_bwd(
+            hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size, hip_lib.ptr(of),
+            hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.stream_ptr(dev)),
+            "dd_attn_aggregate_node_bwd")
     return _grad_like(dq, q), _grad_like(dk, k), _grad_like(dv, v), (None if d_ew is None else _grad_like(d_ew, e_w))
 
 
-def _attention_pos_bwd(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, g):
-    """(dq, dk, dv16, d_rel, d_ew or None) of `_attention_pos` (dd_attn_aggregate_pos_bwd)."""
+def _attention_pos_bwd(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, g, mask: Optional[torch.Tensor] = None):
+    """(dq, dk, dv16, d_rel, d_ew or None) of `_attention_pos` (dd_attn_aggregate_pos_bwd; with a member mask
+    dd_attn_aggregate_pos_bwd_masked)."""
     E, dev = k.size(0), k.device
     qf, kf, vf, rf, ew, gf = _f32(q), _f32(k), _f32(v), _f32(rel_x), _ew32(e_w), _f32(g)
     if qf.shape != (dim_size, 128) or kf.shape != (E, 128) or vf.shape != (E, 16) or rf.shape != (E, 3) or gf.shape != (dim_size, 3) or \
@@ -219,10 +251,16 @@ def _attention_pos_bwd(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, g)
         raise ValueError("scatter_attention_pos backward: shapes of q / k / v / rel_x / e_w / grad disagree")
     dq, dk, dv, dr = torch.empty_like(qf), torch.empty_like(kf), torch.empty_like(vf), torch.empty_like(rf)
     d_ew = None if ew is None else torch.empty_like(ew)
-    hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_bwd(
-        hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size, hip_lib.ptr(gf),
-        hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.ptr(dr), hip_lib.stream_ptr(dev)),
-        "dd_attn_aggregate_pos_bwd")
+    if mask is not None:
+        hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_bwd_masked(
+            hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
+            hip_lib.ptr(mask), hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.ptr(dr),
+            hip_lib.stream_ptr(dev)), "dd_attn_aggregate_pos_bwd_masked")
+    else:
+        hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_bwd(
+            hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size, hip_lib.ptr(gf),
+            hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.ptr(dr), hip_lib.stream_ptr(dev)),
+            "dd_attn_aggregate_pos_bwd")
     return _grad_like(dq, q), _grad_like(dk, k), _grad_like(dv, v), _grad_like(dr, rel_x), (None if d_ew is None else _grad_like(d_ew, e_w))
 
 
@@ -234,73 +272,83 @@ class _ScatterAttention(torch.autograd.Function):
     """scatter_attention with the HIP backward; the forward is the no-grad code path (same kernel, same result)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, e_w, seg, dim_size):
-        out = _attention_node(q, k, v, e_w, seg, dim_size)
-        ctx.save_for_backward(q, k, v, e_w, seg, out)
+    def forward(ctx, q, k, v, e_w, seg, dim_size, mask):
+        out = _attention_node(q, k, v, e_w, seg, dim_size, mask)
+        ctx.save_for_backward(q, k, v, e_w, seg, out, mask)
         ctx.dim_size = dim_size
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        q, k, v, e_w, seg, out = ctx.saved_tensors
-        dq, dk, dv, d_ew = _attention_node_bwd(q, k, v, e_w, seg, ctx.dim_size, out, g)
-        return _only_needed(ctx, (dq, dk, dv, d_ew, None, None))
+        q, k, v, e_w, seg, out, mask = ctx.saved_tensors
+        dq, dk, dv, d_ew = _attention_node_bwd(q, k, v, e_w, seg, ctx.dim_size, out, g, mask)
+        return _only_needed(ctx, (dq, dk, dv, d_ew, None, None, None))     # (the mask is not differentiable)
 
 
 class _ScatterAttentionPos(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, rel_x, e_w, seg, dim_size):
-        ctx.save_for_backward(q, k, v, rel_x, e_w, seg)
+    def forward(ctx, q, k, v, rel_x, e_w, seg, dim_size, mask):
+        ctx.save_for_backward(q, k, v, rel_x, e_w, seg, mask)
         ctx.dim_size = dim_size
-        return _attention_pos(q, k, v, rel_x, e_w, seg, dim_size)
+        return _attention_pos(q, k, v, rel_x, e_w, seg, dim_size, mask)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        q, k, v, rel_x, e_w, seg = ctx.saved_tensors
-        dq, dk, dv, dr, d_ew = _attention_pos_bwd(q, k, v, rel_x, e_w, seg, ctx.dim_size, g)
-        return _only_needed(ctx, (dq, dk, dv, dr, d_ew, None, None))
+        q, k, v, rel_x, e_w, seg, mask = ctx.saved_tensors
+        dq, dk, dv, dr, d_ew = _attention_pos_bwd(q, k, v, rel_x, e_w, seg, ctx.dim_size, g, mask)
+        return _only_needed(ctx, (dq, dk, dv, dr, d_ew, None, None, None))
 
 
 def scatter_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, index, dim_size: int,
-                      e_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      e_w: Optional[torch.Tensor] = None, member_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``scatter_sum(scatter_softmax((q_e * k / sqrt(8)).sum(-1), index)[..., None] * (v * e_w), index, dim_size)``
     flattened to ``[dim_size,128]`` (16 heads x 8).  ``q`` is ``[dim_size,128]`` (gathered as ``q[index]`` by the
     reference's node / coordinate layers) or per edge ``[E,128]`` (bond layer: rows of a segment are identical).
     ``index``: the sorted destination vector, or its :class:`SegmentPlan` (no device -> host round trip per call).
-    Differentiable w.r.t. ``q``, ``k``, ``v`` and ``e_w`` (dd_attn_aggregate_node_bwd; no double backward)."""
+    Differentiable w.r.t. ``q``, ``k``, ``v`` and ``e_w`` (dd_attn_aggregate_node_bwd; no double backward).
+    ``member_mask`` (``[E]`` bool or uint8 on the device of ``k``; padded batches): True / non-zero members are real, the
+    others do not exist -- the softmax runs over the real members of a segment only, a segment without one gives a zero row,
+    and whatever the masked rows of ``k``, ``v``, ``e_w`` (and of a per-edge ``q``) hold, NaN included, reaches no result;
+    their gradients are exactly zero (dd_attn_aggregate_node_masked / _bwd_masked).  Not differentiable itself."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         hip_lib.require_gpu(t, name)
     dim_size = int(dim_size)
     seg = _attn_seg(index, dim_size, k.size(0))
+    mask = _member_mask(member_mask, k, "scatter_attention")                       # (None stays None: the unmasked launch)
     if _needs_grad(q, k, v, e_w):
-        return _ScatterAttention.apply(q, k, v, e_w, seg, dim_size)
-    return _attention_node(q, k, v, e_w, seg, dim_size)
+        return _ScatterAttention.apply(q, k, v, e_w, seg, dim_size, mask)
+    return _attention_node(q, k, v, e_w, seg, dim_size, mask)
 
 
 def scatter_attention_pos(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_x: torch.Tensor, index,
-                          dim_size: int, e_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          dim_size: int, e_w: Optional[torch.Tensor] = None, member_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """PosUpdateLayer's aggregation: ``v`` is ``[E,16]`` (one scalar per head), ``rel_x`` ``[E,3]``; returns
     ``scatter_sum(alpha[..., None] * (v * e_w)[..., None] * rel_x[:, None], index).mean(1)`` — ``[dim_size,3]``.
-    ``index`` as for :func:`scatter_attention`; differentiable w.r.t. ``q``, ``k``, ``v``, ``rel_x`` and ``e_w``."""
+    ``index`` and ``member_mask`` as for :func:`scatter_attention` (a masked member's ``rel_x`` row is not read into any
+    result either); differentiable w.r.t. ``q``, ``k``, ``v``, ``rel_x`` and ``e_w``."""
     for name, t in (("q", q), ("k", k), ("v", v), ("rel_x", rel_x)):
         hip_lib.require_gpu(t, name)
     dim_size = int(dim_size)
     seg = _attn_seg(index, dim_size, k.size(0))
+    mask = _member_mask(member_mask, k, "scatter_attention_pos")
     if _needs_grad(q, k, v, rel_x, e_w):
-        return _ScatterAttentionPos.apply(q, k, v, rel_x, e_w, seg, dim_size)
-    return _attention_pos(q, k, v, rel_x, e_w, seg, dim_size)
+        return _ScatterAttentionPos.apply(q, k, v, rel_x, e_w, seg, dim_size, mask)
+    return _attention_pos(q, k, v, rel_x, e_w, seg, dim_size, mask)
 
 
-def scatter_attention_backward(q, k, v, index, dim_size: int, e_w, out, grad_out):
-    """``(dq, dk, dv, d_ew or None)`` of :func:`scatter_attention` given its result ``out`` and the gradient of it."""
-    return _attention_node_bwd(q, k, v, e_w, _attn_seg(index, int(dim_size), k.size(0)), int(dim_size), out, grad_out)
+def scatter_attention_backward(q, k, v, index, dim_size: int, e_w, out, grad_out, member_mask=None):
+    """``(dq, dk, dv, d_ew or None)`` of :func:`scatter_attention` given its result ``out`` and the gradient of it
+    (``member_mask``: the forward's; masked members get exact zeros)."""
+    return _attention_node_bwd(q, k, v, e_w, _attn_seg(index, int(dim_size), k.size(0)), int(dim_size), out, grad_out,
+                               _member_mask(member_mask, k, "scatter_attention_backward"))
 
 
-def scatter_attention_pos_backward(q, k, v, rel_x, index, dim_size: int, e_w, grad_out):
+def scatter_attention_pos_backward(q, k, v, rel_x, index, dim_size: int, e_w, grad_out, member_mask=None):
     """``(dq, dk, dv, d_rel, d_ew or None)`` of :func:`scatter_attention_pos` given the gradient of its result."""
-    return _attention_pos_bwd(q, k, v, rel_x, e_w, _attn_seg(index, int(dim_size), k.size(0)), int(dim_size), grad_out)
+    return _attention_pos_bwd(q, k, v, rel_x, e_w, _attn_seg(index, int(dim_size), k.size(0)), int(dim_size), grad_out,
+                              _member_mask(member_mask, k, "scatter_attention_pos_backward"))
 
 
 # ------------------------------------------------------------------------------------------------------------------

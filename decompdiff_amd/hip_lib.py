@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "dd_node_out_fc",
     "dd_forward_ex2", "dd_sample_steps_ex2", "dd_sample_steps_graph_ex2", "dd_graph_create_ex2", "dd_sample_steps_graph_multi_ex2",
     "dd_attn_aggregate_node_bwd", "dd_attn_aggregate_pos_bwd",
+    "dd_attn_aggregate_node_masked", "dd_attn_aggregate_pos_masked", "dd_attn_aggregate_node_bwd_masked", "dd_attn_aggregate_pos_bwd_masked",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -181,6 +182,11 @@ def load():
         "dd_attn_aggregate_pos": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
         "dd_attn_aggregate_node_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 7,
         "dd_attn_aggregate_pos_bwd": [c_void_p] * 6 + [c_int] + [c_void_p] * 7,
+        # (the siblings' lists with member_mask after seg_ptr / n_seg)
+        "dd_attn_aggregate_node_masked": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+        "dd_attn_aggregate_pos_masked": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+        "dd_attn_aggregate_node_bwd_masked": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 8,
+        "dd_attn_aggregate_pos_bwd_masked": [c_void_p] * 6 + [c_int] + [c_void_p] * 8,
         "dd_segment_reduce": [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p],
         "dd_segment_softmax": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
         "dd_debug_philox": [c_uint64, c_int, c_long, c_int, c_void_p, c_void_p],

@@ -39,25 +39,26 @@ def _(x, k, batch=None, loop=False, flow="source_to_target"):
 
 
 @torch.library.custom_op(f"{_NS}::scatter_attention", mutates_args=(), device_types="cuda")
-def scatter_attention(q: Tensor, k: Tensor, v: Tensor, index: Tensor, dim_size: int, e_w: Optional[Tensor] = None) -> Tensor:
+def scatter_attention(q: Tensor, k: Tensor, v: Tensor, index: Tensor, dim_size: int, e_w: Optional[Tensor] = None,
+                      member_mask: Optional[Tensor] = None) -> Tensor:
     with torch.no_grad():                                   # (the autograd formula is registered below)
-        return F.scatter_attention(q, k, v, index, dim_size, e_w)
+        return F.scatter_attention(q, k, v, index, dim_size, e_w, member_mask)
 
 
 @scatter_attention.register_fake
-def _(q, k, v, index, dim_size, e_w=None):
+def _(q, k, v, index, dim_size, e_w=None, member_mask=None):
     return k.new_empty((dim_size, 128), dtype=torch.float32)
 
 
 @torch.library.custom_op(f"{_NS}::scatter_attention_pos", mutates_args=(), device_types="cuda")
 def scatter_attention_pos(q: Tensor, k: Tensor, v: Tensor, rel_x: Tensor, index: Tensor, dim_size: int,
-                          e_w: Optional[Tensor] = None) -> Tensor:
+                          e_w: Optional[Tensor] = None, member_mask: Optional[Tensor] = None) -> Tensor:
     with torch.no_grad():
-        return F.scatter_attention_pos(q, k, v, rel_x, index, dim_size, e_w)
+        return F.scatter_attention_pos(q, k, v, rel_x, index, dim_size, e_w, member_mask)
 
 
 @scatter_attention_pos.register_fake
-def _(q, k, v, rel_x, index, dim_size, e_w=None):
+def _(q, k, v, rel_x, index, dim_size, e_w=None, member_mask=None):
     return k.new_empty((dim_size, 3), dtype=torch.float32)
 
 
@@ -65,25 +66,25 @@ def _(q, k, v, rel_x, index, dim_size, e_w=None):
 # traced backward graph holds them as single nodes.  An absent e_w comes back as an empty tensor (an op cannot return None).
 @torch.library.custom_op(f"{_NS}::scatter_attention_backward", mutates_args=(), device_types="cuda")
 def scatter_attention_backward(q: Tensor, k: Tensor, v: Tensor, index: Tensor, dim_size: int, e_w: Optional[Tensor], out: Tensor,
-                               grad_out: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    dq, dk, dv, d_ew = F.scatter_attention_backward(q, k, v, index, dim_size, e_w, out, grad_out)
+                               grad_out: Tensor, member_mask: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    dq, dk, dv, d_ew = F.scatter_attention_backward(q, k, v, index, dim_size, e_w, out, grad_out, member_mask)
     return dq, dk, dv, (d_ew if d_ew is not None else k.new_empty(0))
 
 
 @scatter_attention_backward.register_fake
-def _(q, k, v, index, dim_size, e_w, out, grad_out):
+def _(q, k, v, index, dim_size, e_w, out, grad_out, member_mask=None):
     return torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), (torch.empty_like(e_w) if e_w is not None else k.new_empty(0))
 
 
 @torch.library.custom_op(f"{_NS}::scatter_attention_pos_backward", mutates_args=(), device_types="cuda")
 def scatter_attention_pos_backward(q: Tensor, k: Tensor, v: Tensor, rel_x: Tensor, index: Tensor, dim_size: int, e_w: Optional[Tensor],
-                                   grad_out: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    dq, dk, dv, dr, d_ew = F.scatter_attention_pos_backward(q, k, v, rel_x, index, dim_size, e_w, grad_out)
+                                   grad_out: Tensor, member_mask: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    dq, dk, dv, dr, d_ew = F.scatter_attention_pos_backward(q, k, v, rel_x, index, dim_size, e_w, grad_out, member_mask)
     return dq, dk, dv, dr, (d_ew if d_ew is not None else k.new_empty(0))
 
 
 @scatter_attention_pos_backward.register_fake
-def _(q, k, v, rel_x, index, dim_size, e_w, grad_out):
+def _(q, k, v, rel_x, index, dim_size, e_w, grad_out, member_mask=None):
     return (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), torch.empty_like(rel_x),
             (torch.empty_like(e_w) if e_w is not None else k.new_empty(0)))
 
@@ -188,34 +189,36 @@ scatter_softmax.register_autograd(_bw_softmax, setup_context=_setup_softmax)
 
 
 def _setup_attention(ctx, inputs, output):
-    q, k, v, index, dim_size, e_w = inputs
-    ctx.save_for_backward(q, k, v, index, e_w, output)
+    q, k, v, index, dim_size, e_w, member_mask = inputs
+    ctx.save_for_backward(q, k, v, index, e_w, output, member_mask)
     ctx.dim_size = dim_size
 
 
 def _bw_attention(ctx, g):
-    q, k, v, index, e_w, out = ctx.saved_tensors
-    dq, dk, dv, d_ew = torch.ops.decompdiff_amd.scatter_attention_backward(q, k, v, index, ctx.dim_size, e_w, out, g.contiguous())
+    q, k, v, index, e_w, out, member_mask = ctx.saved_tensors
+    dq, dk, dv, d_ew = torch.ops.decompdiff_amd.scatter_attention_backward(q, k, v, index, ctx.dim_size, e_w, out, g.contiguous(),
+                                                                           member_mask)
     need = ctx.needs_input_grad
     return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None,
-            d_ew if e_w is not None and need[5] else None)
+            d_ew if e_w is not None and need[5] else None, None)
 
 
 scatter_attention.register_autograd(_bw_attention, setup_context=_setup_attention)
 
 
 def _setup_attention_pos(ctx, inputs, output):
-    q, k, v, rel_x, index, dim_size, e_w = inputs
-    ctx.save_for_backward(q, k, v, rel_x, index, e_w)
+    q, k, v, rel_x, index, dim_size, e_w, member_mask = inputs
+    ctx.save_for_backward(q, k, v, rel_x, index, e_w, member_mask)
     ctx.dim_size = dim_size
 
 
 def _bw_attention_pos(ctx, g):
-    q, k, v, rel_x, index, e_w = ctx.saved_tensors
-    dq, dk, dv, dr, d_ew = torch.ops.decompdiff_amd.scatter_attention_pos_backward(q, k, v, rel_x, index, ctx.dim_size, e_w, g.contiguous())
+    q, k, v, rel_x, index, e_w, member_mask = ctx.saved_tensors
+    dq, dk, dv, dr, d_ew = torch.ops.decompdiff_amd.scatter_attention_pos_backward(q, k, v, rel_x, index, ctx.dim_size, e_w, g.contiguous(),
+                                                                                   member_mask)
     need = ctx.needs_input_grad
     return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, dr if need[3] else None, None, None,
-            d_ew if e_w is not None and need[6] else None)
+            d_ew if e_w is not None and need[6] else None, None)
 
 
 scatter_attention_pos.register_autograd(_bw_attention_pos, setup_context=_setup_attention_pos)

@@ -532,10 +532,11 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
     e_w = torch.sigmoid(P.mlp("refine_net.edge_pred_layer", _gauss(d0)))
     NLm1, Ebs = NL - 1, NL * (NL - 1)
     mask_l = is_lig.float().unsqueeze(-1)
-    # DD_TRAIN_FUSED_ATTN=1 (opt-in, unpadded passes): each attention site is ONE differentiable op on the op-level kernels
+    # DD_TRAIN_FUSED_ATTN=1 (opt-in): each attention site is ONE differentiable op on the op-level kernels
     # (FN.scatter_attention / scatter_attention_pos: dd_attn_aggregate_* forward, dd_attn_aggregate_*_bwd backward) instead of
-    # gather, product, segment softmax, product, segment sum.  Padded passes keep the composed path: the kernels have no member mask.
-    fused = pad is None and os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1"
+    # gather, product, segment softmax, product, segment sum.  Padded passes hand the bond-graph and triplet sites their member
+    # masks (real_b / real_t; None in a dense pass); the kNN sites need none: dd_knn_masked keeps padding atoms out of the graph.
+    fused = os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1"
     out_fc = bool(getattr(cfg, "x2h_out_fc", False))
     for l in range(int(cfg.num_layers)):
         p = f"refine_net.base_block.{l}"
@@ -578,7 +579,7 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         k_b, v_b = node_layer_bond("node_layer_with_bond", h, h_bond)
         q_b = P.mlp(f"{p}.node_layer_with_bond.hq_func", h)
         if fused:
-            a_bond = FN.scatter_attention(q_b, k_b, v_b, p_bdst, B * N)
+            a_bond = FN.scatter_attention(q_b, k_b, v_b, p_bdst, B * N, member_mask=real_b)
         else:
             alpha = _attention(gather(q_b, p_bdst), k_b, v_b, p_bdst, member_real=real_b)
             a_bond = scatter_sum((alpha.unsqueeze(-1) * v_b.view(-1, NH, H // NH)).reshape(-1, H), p_bdst)
@@ -604,7 +605,7 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
             # hq depends on the (j -> i) bond only: evaluated per bond, gathered per triplet (exact)
             q_bond = P.mlp(f"{nm_b}.hq_func", torch.cat([h_bond, gather(h, p_bdst)], -1))
             if fused:
-                d_hb = FN.scatter_attention(q_bond, kv[0], kv[1], p_ji, Eb_tot)
+                d_hb = FN.scatter_attention(q_bond, kv[0], kv[1], p_ji, Eb_tot, member_mask=real_t)
             else:
                 alpha = _attention(gather(q_bond, p_ji), kv[0], kv[1], p_ji, member_real=real_t)
                 d_hb = scatter_sum((alpha.unsqueeze(-1) * kv[1].view(-1, NH, H // NH)).reshape(-1, H), p_ji)
@@ -632,7 +633,7 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         q_pb = P.mlp(f"{p}.pos_layer_with_bond.xq_func", new_h)
         if fused:
             rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
-            dx_b = FN.scatter_attention_pos(q_pb, k_pb, v_pb, rel_b, p_bdst, B * N)
+            dx_b = FN.scatter_attention_pos(q_pb, k_pb, v_pb, rel_b, p_bdst, B * N, member_mask=real_b)
         else:
             alpha = _attention(gather(q_pb, p_bdst), k_pb, None, p_bdst, member_real=real_b)
             rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
@@ -1058,7 +1059,8 @@ class GraphedTrainStep:
             data = pad_prepared(model, prep, self.bucket)
             if data is None:
                 return self._eager(prep)
-            key = ("padded", data["B"], data["NPm"], data["NLm"], str(dev), model.model_mean_type)
+            key = ("padded", data["B"], data["NPm"], data["NLm"], str(dev), model.model_mean_type,
+                   os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1")
             names, fn = PAD_TENSORS, objective_padded
         ent = self._graphs.get(key)
         if ent is not None and ent["lrs"] != self._float_lrs():   # a float lr changed since the capture: it is baked into the graph

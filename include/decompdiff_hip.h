@@ -277,6 +277,29 @@ int dd_attn_aggregate_pos_bwd(const float* q /*[n_seg,128]*/, const float* k, co
                               const float* rel_x, const int32_t* seg_ptr, int n_seg, const float* d_out /*[n_seg,3]*/,
                               float* dq /*[n_seg,128]*/, float* dk /*[E,128]*/, float* dv16 /*[E,16]*/,
                               float* d_ew /*[E]; NULL iff e_w NULL*/, float* d_rel /*[E,3]*/, void* stream);
+/* Member masks (padded batches): the four entry points above with member_mask [E] after seg_ptr / n_seg; a non-zero byte
+ * means the member is real.  A masked member does not exist: the softmax of a segment runs over its real members only, in
+ * member order, with bit for bit the results of the same call on arrays compacted to the real members; a segment without a
+ * real member (empty or all masked) gives a zero output row.  The k, v (v16), e_w and rel_x rows of a masked member -- with
+ * q_per_edge != 0 its q row too: q is read from the segment's first real member -- reach no result, whatever they hold (NaN
+ * and Inf included).  Backward: a masked member gets exactly 0 in dk, dv, d_ew, d_rel (and in its dq row with
+ * q_per_edge != 0); a segment without a real member writes those zeros and its zero dq row (q per segment).  Every element
+ * is still written exactly once, without atomics.  member_mask == NULL: all members are real -- the unmasked entry point's
+ * launch and results.  Argument checks as for the siblings.  (New entry points, ABI unchanged.) */
+int dd_attn_aggregate_node_masked(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w /*NULL ok*/,
+                                  const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask /*[E] or NULL*/,
+                                  float* out /*[n_seg,128]*/, void* stream);
+int dd_attn_aggregate_pos_masked(const float* q, const float* k, const float* v16, const float* e_w /*NULL ok*/, const float* rel_x,
+                                 const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask /*[E] or NULL*/,
+                                 float* out /*[n_seg,3]*/, void* stream);
+int dd_attn_aggregate_node_bwd_masked(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w /*NULL ok*/,
+                                      const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask /*[E] or NULL*/,
+                                      const float* out, const float* d_out, float* dq, float* dk, float* dv, float* d_ew,
+                                      void* stream);
+int dd_attn_aggregate_pos_bwd_masked(const float* q, const float* k, const float* v16, const float* e_w /*NULL ok*/,
+                                     const float* rel_x, const int32_t* seg_ptr, int n_seg,
+                                     const uint8_t* member_mask /*[E] or NULL*/, const float* d_out, float* dq, float* dk,
+                                     float* dv16, float* d_ew, float* d_rel, void* stream);
 
 /* Stand-alone torch_scatter drop-ins over dim 0 of a [E,F] fp32 tensor whose rows are grouped by destination (CSR
  * segments seg_ptr [n_seg+1]); reference call sites: scatter_softmax / scatter_sum uni_transformer_edge.py:64,68,160,164,

@@ -8,7 +8,7 @@ import argparse, sys, time, torch
 sys.path.insert(0, ".")
 from decompdiff_amd import DecompScorePosNet3D, shipped_config, synth
 ap = argparse.ArgumentParser(); ap.add_argument("--batch", type=int, default=4); ap.add_argument("--steps", type=int, default=10)
-ap.add_argument("--ragged", action="store_true", help="four DIFFERENT complexes per batch (what the reference's loader yields): one dense sub-batch per size, eager")
+ap.add_argument("--ragged", action="store_true", help="four DIFFERENT complexes per batch (what the reference's loader yields): one padded dense pass (training.network_padded), eager and captured")
 args = ap.parse_args()
 cfg = shipped_config()
 torch.manual_seed(0)
