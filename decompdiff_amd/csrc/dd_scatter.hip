@@ -13,6 +13,12 @@
 // seg_ptr[s] .. seg_ptr[s+1] are the edges of destination s.  One wavefront owns one destination; lane l holds
 // channels 2l, 2l+1 (head l / 4), so a k or v row is one 512-byte wave load.  Softmax is the single-pass form
 // (running maximum, rescaled running sum) in edge order; 4 edges are in flight per wave.
+//
+// The bodies attn_aggregate<POS, MASK> and attn_aggregate_bwd<POS, MASK> (POS: the coordinate form; MASK: the member masks of
+// padded batches, below) sit behind four thin kernels per direction pair -- k_attn_aggregate<POS>, k_attn_aggregate_masked<POS> and
+// their _bwd forms; the unmasked ones take no mask argument.  One host launcher per direction, launch_attn_aggregate<POS> and
+// launch_attn_aggregate_bwd<POS>, holds the argument check, the grid and the launch: the nine exported dd_attn_aggregate_* entry
+// points forward to these, and a NULL member_mask launches the unmasked kernel.
 #include "dd_common.hpp"
 #include "dd_kernels.hpp"
 
@@ -299,6 +305,42 @@ __global__ __launch_bounds__(256) void k_attn_aggregate_bwd_masked(const float* 
   attn_aggregate_bwd<POS, true>(q, q_per_edge, k, v, e_w, rel_x, seg_ptr, member_mask, n_seg, out, d_out, dq, dk, dv, d_ew, d_rel);
 }
 
+// ---- host side: the argument check of the node (!POS) or coordinate (POS) entry points, and the masked or the unmasked
+// kernel by member_mask != NULL (NULL: all members are real -- the unmasked kernel, which has no mask argument)
+template <bool POS>
+int launch_attn_aggregate(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w, const float* rel_x,
+                          const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, float* out, void* stream) {
+  if (!q || !k || !v || (POS && !rel_x) || !seg_ptr || !out || n_seg < 0) return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  const dim3 grid((n_seg + 3) / 4), block(256);
+  if (member_mask)
+    hipLaunchKernelGGL(k_attn_aggregate_masked<POS>, grid, block, 0, (hipStream_t)stream, q, q_per_edge, k, v, e_w, rel_x, seg_ptr,
+                       member_mask, n_seg, out);
+  else
+    hipLaunchKernelGGL(k_attn_aggregate<POS>, grid, block, 0, (hipStream_t)stream, q, q_per_edge, k, v, e_w, rel_x, seg_ptr, n_seg, out);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+// (the node form reads `out` and has no rel_x / d_rel; the coordinate form recomputes D and has no `out`)
+template <bool POS>
+int launch_attn_aggregate_bwd(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w, const float* rel_x,
+                              const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, const float* out, const float* d_out,
+                              float* dq, float* dk, float* dv, float* d_ew, float* d_rel, void* stream) {
+  if (!q || !k || !v || (POS ? !rel_x || !d_rel : !out) || !seg_ptr || !d_out || !dq || !dk || !dv ||
+      (e_w == nullptr) != (d_ew == nullptr) || n_seg < 0)
+    return DD_ERR_BAD_ARG;
+  if (n_seg == 0) return DD_OK;
+  const dim3 grid((n_seg + 3) / 4), block(256);
+  if (member_mask)
+    hipLaunchKernelGGL(k_attn_aggregate_bwd_masked<POS>, grid, block, 0, (hipStream_t)stream, q, q_per_edge, k, v, e_w, rel_x, seg_ptr,
+                       member_mask, n_seg, out, d_out, dq, dk, dv, d_ew, d_rel);
+  else
+    hipLaunchKernelGGL(k_attn_aggregate_bwd<POS>, grid, block, 0, (hipStream_t)stream, q, q_per_edge, k, v, e_w, rel_x, seg_ptr, n_seg, out,
+                       d_out, dq, dk, dv, d_ew, d_rel);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
 
 // ---- stand-alone torch_scatter drop-ins: scatter_sum / scatter_mean / scatter_min / scatter_max and
 // scatter_softmax over dim 0 of a [E, F] fp32 tensor whose rows are grouped by destination (CSR segments).  Call sites in
@@ -368,104 +410,56 @@ __global__ __launch_bounds__(256) void k_segment_softmax(const float* __restrict
 
 }  // namespace dd
 
-extern "C" int dd_attn_aggregate_node(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
-                                      const int32_t* seg_ptr, int n_seg, float* out, void* stream) {
-  if (!q || !k || !v || !seg_ptr || !out || n_seg < 0) return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate<false>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, q_per_edge, k, v, e_w,
-                     nullptr, seg_ptr, n_seg, out);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
-}
-
-extern "C" int dd_attn_aggregate_triplet(const float* q, const float* k, const float* v, const int32_t* seg_ptr, int n_seg,
-                                         float* out, void* stream) {
-  return dd_attn_aggregate_node(q, 1, k, v, nullptr, seg_ptr, n_seg, out, stream);
-}
-
-extern "C" int dd_attn_aggregate_pos(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
-                                     const int32_t* seg_ptr, int n_seg, float* out, void* stream) {
-  if (!q || !k || !v16 || !rel_x || !seg_ptr || !out || n_seg < 0) return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w, rel_x,
-                     seg_ptr, n_seg, out);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
-}
-
-extern "C" int dd_attn_aggregate_node_bwd(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
-                                          const int32_t* seg_ptr, int n_seg, const float* out, const float* d_out, float* dq,
-                                          float* dk, float* dv, float* d_ew, void* stream) {
-  if (!q || !k || !v || !seg_ptr || !out || !d_out || !dq || !dk || !dv || (e_w == nullptr) != (d_ew == nullptr) || n_seg < 0)
-    return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd<false>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, q_per_edge, k, v,
-                     e_w, nullptr, seg_ptr, n_seg, out, d_out, dq, dk, dv, d_ew, nullptr);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
-}
-
-extern "C" int dd_attn_aggregate_pos_bwd(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
-                                         const int32_t* seg_ptr, int n_seg, const float* d_out, float* dq, float* dk, float* dv16,
-                                         float* d_ew, float* d_rel, void* stream) {
-  if (!q || !k || !v16 || !rel_x || !seg_ptr || !d_out || !dq || !dk || !dv16 || !d_rel || (e_w == nullptr) != (d_ew == nullptr) ||
-      n_seg < 0)
-    return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w,
-                     rel_x, seg_ptr, n_seg, nullptr, d_out, dq, dk, dv16, d_ew, d_rel);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
-}
-
-// ---- masked forms: member_mask [E], non-zero = the member is real; NULL = all real, which IS the unmasked launch
+// ---- the attention entry points: member_mask [E], non-zero = the member is real; NULL (and every unmasked form) = all real
 extern "C" int dd_attn_aggregate_node_masked(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
                                              const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, float* out, void* stream) {
-  if (!member_mask) return dd_attn_aggregate_node(q, q_per_edge, k, v, e_w, seg_ptr, n_seg, out, stream);
-  if (!q || !k || !v || !seg_ptr || !out || n_seg < 0) return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate_masked<false>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, q_per_edge, k, v,
-                     e_w, nullptr, seg_ptr, member_mask, n_seg, out);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  return dd::launch_attn_aggregate<false>(q, q_per_edge, k, v, e_w, nullptr, seg_ptr, n_seg, member_mask, out, stream);
 }
 
 extern "C" int dd_attn_aggregate_pos_masked(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
                                             const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, float* out, void* stream) {
-  if (!member_mask) return dd_attn_aggregate_pos(q, k, v16, e_w, rel_x, seg_ptr, n_seg, out, stream);
-  if (!q || !k || !v16 || !rel_x || !seg_ptr || !out || n_seg < 0) return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate_masked<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w,
-                     rel_x, seg_ptr, member_mask, n_seg, out);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  return dd::launch_attn_aggregate<true>(q, 0, k, v16, e_w, rel_x, seg_ptr, n_seg, member_mask, out, stream);
 }
 
 extern "C" int dd_attn_aggregate_node_bwd_masked(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
                                                  const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, const float* out,
                                                  const float* d_out, float* dq, float* dk, float* dv, float* d_ew, void* stream) {
-  if (!member_mask) return dd_attn_aggregate_node_bwd(q, q_per_edge, k, v, e_w, seg_ptr, n_seg, out, d_out, dq, dk, dv, d_ew, stream);
-  if (!q || !k || !v || !seg_ptr || !out || !d_out || !dq || !dk || !dv || (e_w == nullptr) != (d_ew == nullptr) || n_seg < 0)
-    return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd_masked<false>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, q_per_edge, k,
-                     v, e_w, nullptr, seg_ptr, member_mask, n_seg, out, d_out, dq, dk, dv, d_ew, nullptr);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  return dd::launch_attn_aggregate_bwd<false>(q, q_per_edge, k, v, e_w, nullptr, seg_ptr, n_seg, member_mask, out, d_out, dq, dk, dv, d_ew,
+                                              nullptr, stream);
 }
 
 extern "C" int dd_attn_aggregate_pos_bwd_masked(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
                                                 const int32_t* seg_ptr, int n_seg, const uint8_t* member_mask, const float* d_out,
                                                 float* dq, float* dk, float* dv16, float* d_ew, float* d_rel, void* stream) {
-  if (!member_mask) return dd_attn_aggregate_pos_bwd(q, k, v16, e_w, rel_x, seg_ptr, n_seg, d_out, dq, dk, dv16, d_ew, d_rel, stream);
-  if (!q || !k || !v16 || !rel_x || !seg_ptr || !d_out || !dq || !dk || !dv16 || !d_rel || (e_w == nullptr) != (d_ew == nullptr) ||
-      n_seg < 0)
-    return DD_ERR_BAD_ARG;
-  if (n_seg == 0) return DD_OK;
-  hipLaunchKernelGGL(dd::k_attn_aggregate_bwd_masked<true>, dim3((n_seg + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, 0, k, v16, e_w,
-                     rel_x, seg_ptr, member_mask, n_seg, nullptr, d_out, dq, dk, dv16, d_ew, d_rel);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  return dd::launch_attn_aggregate_bwd<true>(q, 0, k, v16, e_w, rel_x, seg_ptr, n_seg, member_mask, nullptr, d_out, dq, dk, dv16, d_ew,
+                                             d_rel, stream);
+}
+
+extern "C" int dd_attn_aggregate_node(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
+                                      const int32_t* seg_ptr, int n_seg, float* out, void* stream) {
+  return dd_attn_aggregate_node_masked(q, q_per_edge, k, v, e_w, seg_ptr, n_seg, nullptr, out, stream);
+}
+
+extern "C" int dd_attn_aggregate_triplet(const float* q, const float* k, const float* v, const int32_t* seg_ptr, int n_seg,
+                                         float* out, void* stream) {
+  return dd_attn_aggregate_node_masked(q, 1, k, v, nullptr, seg_ptr, n_seg, nullptr, out, stream);
+}
+
+extern "C" int dd_attn_aggregate_pos(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
+                                     const int32_t* seg_ptr, int n_seg, float* out, void* stream) {
+  return dd_attn_aggregate_pos_masked(q, k, v16, e_w, rel_x, seg_ptr, n_seg, nullptr, out, stream);
+}
+
+extern "C" int dd_attn_aggregate_node_bwd(const float* q, int q_per_edge, const float* k, const float* v, const float* e_w,
+                                          const int32_t* seg_ptr, int n_seg, const float* out, const float* d_out, float* dq,
+                                          float* dk, float* dv, float* d_ew, void* stream) {
+  return dd_attn_aggregate_node_bwd_masked(q, q_per_edge, k, v, e_w, seg_ptr, n_seg, nullptr, out, d_out, dq, dk, dv, d_ew, stream);
+}
+
+extern "C" int dd_attn_aggregate_pos_bwd(const float* q, const float* k, const float* v16, const float* e_w, const float* rel_x,
+                                         const int32_t* seg_ptr, int n_seg, const float* d_out, float* dq, float* dk, float* dv16,
+                                         float* d_ew, float* d_rel, void* stream) {
+  return dd_attn_aggregate_pos_bwd_masked(q, k, v16, e_w, rel_x, seg_ptr, n_seg, nullptr, d_out, dq, dk, dv16, d_ew, d_rel, stream);
 }
 
 extern "C" int dd_segment_reduce(const float* src, const int32_t* seg_ptr, int n_seg, int F, int op, long E, float* out,

@@ -68,29 +68,41 @@ at::Tensor segment_softmax(const at::Tensor& src, const at::Tensor& seg_ptr) {
   return out;
 }
 
+// member mask of the two attention ops (padded batches): one byte per row of k, non-zero = real; absent = all real (NULL)
+const uint8_t* mask_ptr(const c10::optional<at::Tensor>& member_mask, const at::Tensor& k, const char* what) {
+  if (!member_mask.has_value()) return nullptr;
+  TORCH_CHECK(member_mask->scalar_type() == at::kByte && member_mask->is_contiguous() && member_mask->device() == k.device() &&
+                  member_mask->dim() == 1 && member_mask->numel() == k.size(0),
+              what, ": member_mask must be a contiguous uint8 [E] tensor on the device of k, one byte per row of k");
+  return member_mask->data_ptr<uint8_t>();
+}
+
 // scatter_softmax + scatter_sum pair of NodeUpdateLayer / BondUpdateLayer (uni_transformer_edge.py:63-68,158-164)
 at::Tensor attn_aggregate_node(const at::Tensor& q, bool q_per_edge, const at::Tensor& k, const at::Tensor& v,
-                               const c10::optional<at::Tensor>& e_w, const at::Tensor& seg_ptr) {
+                               const c10::optional<at::Tensor>& e_w, const at::Tensor& seg_ptr,
+                               const c10::optional<at::Tensor>& member_mask) {
   const at::Tensor qc = f32c(q), kc = f32c(k), vc = f32c(v);
   const int64_t n = seg_ptr.numel() - 1;
   at::Tensor out = at::empty({n, 128}, kc.options());
   at::Tensor ew;
   if (e_w.has_value()) ew = f32c(*e_w).reshape({-1});
-  check(dd_attn_aggregate_node(fptr(qc), q_per_edge ? 1 : 0, fptr(kc), fptr(vc), e_w.has_value() ? fptr(ew) : nullptr,
-                               seg_ptr.data_ptr<int32_t>(), (int)n, out.data_ptr<float>(), cur_stream(k)), "dd_attn_aggregate_node");
+  check(dd_attn_aggregate_node_masked(fptr(qc), q_per_edge ? 1 : 0, fptr(kc), fptr(vc), e_w.has_value() ? fptr(ew) : nullptr,
+                                      seg_ptr.data_ptr<int32_t>(), (int)n, mask_ptr(member_mask, k, "attn_aggregate_node"),
+                                      out.data_ptr<float>(), cur_stream(k)), "dd_attn_aggregate_node_masked");
   return out;
 }
 
 // PosUpdateLayer's pair (uni_transformer_edge.py:205-211): v16 [E,16], rel_x [E,3] -> [n,3]
 at::Tensor attn_aggregate_pos(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v16, const c10::optional<at::Tensor>& e_w,
-                              const at::Tensor& rel_x, const at::Tensor& seg_ptr) {
+                              const at::Tensor& rel_x, const at::Tensor& seg_ptr, const c10::optional<at::Tensor>& member_mask) {
   const at::Tensor qc = f32c(q), kc = f32c(k), vc = f32c(v16), rc = f32c(rel_x);
   const int64_t n = seg_ptr.numel() - 1;
   at::Tensor out = at::empty({n, 3}, kc.options());
   at::Tensor ew;
   if (e_w.has_value()) ew = f32c(*e_w).reshape({-1});
-  check(dd_attn_aggregate_pos(fptr(qc), fptr(kc), fptr(vc), e_w.has_value() ? fptr(ew) : nullptr, fptr(rc), seg_ptr.data_ptr<int32_t>(),
-                              (int)n, out.data_ptr<float>(), cur_stream(k)), "dd_attn_aggregate_pos");
+  check(dd_attn_aggregate_pos_masked(fptr(qc), fptr(kc), fptr(vc), e_w.has_value() ? fptr(ew) : nullptr, fptr(rc),
+                                     seg_ptr.data_ptr<int32_t>(), (int)n, mask_ptr(member_mask, k, "attn_aggregate_pos"),
+                                     out.data_ptr<float>(), cur_stream(k)), "dd_attn_aggregate_pos_masked");
   return out;
 }
 
@@ -101,8 +113,8 @@ TORCH_LIBRARY(decompdiff_hip, m) {
   m.def("knn_csr(Tensor x, Tensor ptr, Tensor out_off, int E, int n_max, int k, bool loop) -> Tensor");
   m.def("segment_reduce(Tensor src, Tensor seg_ptr, int op) -> (Tensor, Tensor)");
   m.def("segment_softmax(Tensor src, Tensor seg_ptr) -> Tensor");
-  m.def("attn_aggregate_node(Tensor q, bool q_per_edge, Tensor k, Tensor v, Tensor? e_w, Tensor seg_ptr) -> Tensor");
-  m.def("attn_aggregate_pos(Tensor q, Tensor k, Tensor v16, Tensor? e_w, Tensor rel_x, Tensor seg_ptr) -> Tensor");
+  m.def("attn_aggregate_node(Tensor q, bool q_per_edge, Tensor k, Tensor v, Tensor? e_w, Tensor seg_ptr, Tensor? member_mask=None) -> Tensor");
+  m.def("attn_aggregate_pos(Tensor q, Tensor k, Tensor v16, Tensor? e_w, Tensor rel_x, Tensor seg_ptr, Tensor? member_mask=None) -> Tensor");
   m.def("abi_version() -> int", []() -> int64_t { return dd_abi_version(); });
 }
 

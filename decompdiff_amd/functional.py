@@ -180,46 +180,36 @@ def _member_mask(member_mask, k: torch.Tensor, what: str) -> Optional[torch.Tens
 
 def _attention_node(q, k, v, e_w, seg: torch.Tensor, dim_size: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     per_edge = _per_edge(q, k.size(0), dim_size)
-    out = torch.empty(dim_size, 128, device=k.device)
     ew = _ew32(e_w)
     # converted copies are bound to locals that outlive the launch: a temporary freed before the kernel is enqueued
     # would hand its block to the next same-size allocation (k and v would alias)
     qf, kf, vf = _f32(q), _f32(k), _f32(v)
-    if mask is not None:                                                            # (masked calls: the ctypes binding alone)
-        hip_lib.check(hip_lib.load().dd_attn_aggregate_node_masked(
-            hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size,
-            hip_lib.ptr(mask), hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_node_masked")
-        return out
     ext = torch_ext()
     if ext is not None:
-        return ext.attn_aggregate_node(qf, bool(per_edge), kf, vf, ew, seg)
-    hip_lib.check(hip_lib.load().dd_attn_aggregate_node(hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf),
-                                                        hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size,
-                                                        hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_node")
+        return ext.attn_aggregate_node(qf, bool(per_edge), kf, vf, ew, seg, mask)
+    out = torch.empty(dim_size, 128, device=k.device)
+    hip_lib.check(hip_lib.load().dd_attn_aggregate_node_masked(                     # (mask None = NULL: all members are real)
+        hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size,
+        hip_lib.ptr(mask), hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_node_masked")
     return out
 
 
 def _attention_pos(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    out = torch.empty(dim_size, 3, device=k.device)
     ew = _ew32(e_w)
     qf, kf, vf, rf = _f32(q), _f32(k), _f32(v), _f32(rel_x)                          # (alive past the launch, see above)
-    if mask is not None:
-        hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_masked(
-            hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
-            hip_lib.ptr(mask), hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_pos_masked")
-        return out
     ext = torch_ext()
     if ext is not None:
-        return ext.attn_aggregate_pos(qf, kf, vf, ew, rf, seg)
-    hip_lib.check(hip_lib.load().dd_attn_aggregate_pos(hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew),
-                                                       hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
-                                                       hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_pos")
+        return ext.attn_aggregate_pos(qf, kf, vf, ew, rf, seg, mask)
+    out = torch.empty(dim_size, 3, device=k.device)
+    hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_masked(
+        hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
+        hip_lib.ptr(mask), hip_lib.ptr(out), hip_lib.stream_ptr(k.device)), "dd_attn_aggregate_pos_masked")
     return out
 
 
 def _attention_node_bwd(q, k, v, e_w, seg: torch.Tensor, dim_size: int, out, g, mask: Optional[torch.Tensor] = None):
-    """(dq, dk, dv, d_ew or None) of `_attention_node`, each in its input's shape and dtype (dd_attn_aggregate_node_bwd; with a
-    member mask dd_attn_aggregate_node_bwd_masked)."""
+    """(dq, dk, dv, d_ew or None) of `_attention_node`, each in its input's shape and dtype (dd_attn_aggregate_node_bwd_masked;
+    mask None = NULL: all members are real)."""
     E, dev = k.size(0), k.device
     per_edge = _per_edge(q, E, dim_size)
     qf, kf, vf, ew, of, gf = _f32(q), _f32(k), _f32(v), _ew32(e_w), _f32(out), _f32(g)
@@ -228,22 +218,15 @@ def _attention_node_bwd(q, k, v, e_w, seg: torch.Tensor, dim_size: int, out, g, 
         raise ValueError("scatter_attention backward: shapes of q / k / v / e_w / out / grad disagree")
     dq, dk, dv = torch.empty_like(qf), torch.empty_like(kf), torch.empty_like(vf)
     d_ew = None if ew is None else torch.empty_like(ew)
-    if mask is not None:
-        hip_lib.check(hip_lib.load().dd_attn_aggregate_node_bwd_masked(
-            hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size,
-            hip_lib.ptr(mask), hip_lib.ptr(of), hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew),
-            hip_lib.stream_ptr(dev)), "dd_attn_aggregate_node_bwd_masked")
-    else:
-        hip_lib.check(hip_lib.load().dd_attn_aggregate_node_bwd(
-            hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size, hip_lib.ptr(of),
-            hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.stream_ptr(dev)),
-            "dd_attn_aggregate_node_bwd")
+    hip_lib.check(hip_lib.load().dd_attn_aggregate_node_bwd_masked(
+        hip_lib.ptr(qf), int(per_edge), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(seg), dim_size,
+        hip_lib.ptr(mask), hip_lib.ptr(of), hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew),
+        hip_lib.stream_ptr(dev)), "dd_attn_aggregate_node_bwd_masked")
     return _grad_like(dq, q), _grad_like(dk, k), _grad_like(dv, v), (None if d_ew is None else _grad_like(d_ew, e_w))
 
 
 def _attention_pos_bwd(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, g, mask: Optional[torch.Tensor] = None):
-    """(dq, dk, dv16, d_rel, d_ew or None) of `_attention_pos` (dd_attn_aggregate_pos_bwd; with a member mask
-    dd_attn_aggregate_pos_bwd_masked)."""
+    """(dq, dk, dv16, d_rel, d_ew or None) of `_attention_pos` (dd_attn_aggregate_pos_bwd_masked)."""
     E, dev = k.size(0), k.device
     qf, kf, vf, rf, ew, gf = _f32(q), _f32(k), _f32(v), _f32(rel_x), _ew32(e_w), _f32(g)
     if qf.shape != (dim_size, 128) or kf.shape != (E, 128) or vf.shape != (E, 16) or rf.shape != (E, 3) or gf.shape != (dim_size, 3) or \
@@ -251,16 +234,10 @@ def _attention_pos_bwd(q, k, v, rel_x, e_w, seg: torch.Tensor, dim_size: int, g,
         raise ValueError("scatter_attention_pos backward: shapes of q / k / v / rel_x / e_w / grad disagree")
     dq, dk, dv, dr = torch.empty_like(qf), torch.empty_like(kf), torch.empty_like(vf), torch.empty_like(rf)
     d_ew = None if ew is None else torch.empty_like(ew)
-    if mask is not None:
-        hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_bwd_masked(
-            hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
-            hip_lib.ptr(mask), hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.ptr(dr),
-            hip_lib.stream_ptr(dev)), "dd_attn_aggregate_pos_bwd_masked")
-    else:
-        hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_bwd(
-            hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size, hip_lib.ptr(gf),
-            hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.ptr(dr), hip_lib.stream_ptr(dev)),
-            "dd_attn_aggregate_pos_bwd")
+    hip_lib.check(hip_lib.load().dd_attn_aggregate_pos_bwd_masked(
+        hip_lib.ptr(qf), hip_lib.ptr(kf), hip_lib.ptr(vf), hip_lib.ptr(ew), hip_lib.ptr(rf), hip_lib.ptr(seg), dim_size,
+        hip_lib.ptr(mask), hip_lib.ptr(gf), hip_lib.ptr(dq), hip_lib.ptr(dk), hip_lib.ptr(dv), hip_lib.ptr(d_ew), hip_lib.ptr(dr),
+        hip_lib.stream_ptr(dev)), "dd_attn_aggregate_pos_bwd_masked")
     return _grad_like(dq, q), _grad_like(dk, k), _grad_like(dv, v), _grad_like(dr, rel_x), (None if d_ew is None else _grad_like(d_ew, e_w))
 
 

@@ -285,8 +285,9 @@ class _P:
         return self.mlp_tail(name, self.lin(name + ".net.0", x))
 
 
-def _attention(q_e, k, v, seg, n_seg=None, member_real=None):
-    """alpha = scatter_softmax((q k / sqrt(d)).sum(-1)); out = scatter_sum(alpha v)  (uni_transformer_edge.py:63-68).
+def _attention(q_e, k, v, seg, member_real=None):
+    """alpha = scatter_softmax((q k / sqrt(d)).sum(-1)), [E, NH] -- the weights of out = scatter_sum(alpha v), which the caller forms
+    (uni_transformer_edge.py:63-68).  `v` is not read (callers pass the k, v pair).
     `seg`: the SegmentPlan of the destination index.  `member_real` (padded batches): bool per member -- padding members get a
     score of -1e30 (their exponential is exactly 0: the softmax is the softmax over the real members, same sums) and a weight of
     exactly 0 afterwards (a segment without any real member then contributes nothing)."""
@@ -537,6 +538,22 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
     # gather, product, segment softmax, product, segment sum.  Padded passes hand the bond-graph and triplet sites their member
     # masks (real_b / real_t; None in a dense pass); the kNN sites need none: dd_knn_masked keeps padding atoms out of the graph.
     fused = os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1"
+
+    def attend(q, k, v, plan, n, e_w=None, real=None):
+        """[n, 128]: softmax over each destination's members of q . k per head, times v (* e_w), summed per destination."""
+        if fused:
+            return FN.scatter_attention(q, k, v, plan, n, e_w, member_mask=real)
+        alpha = _attention(gather(q, plan), k, v, plan, member_real=real)
+        return scatter_sum((alpha.unsqueeze(-1) * (v * e_w if e_w is not None else v).view(-1, NH, H // NH)).reshape(-1, H), plan)
+
+    def attend_pos(q, k, v16, rel, plan, n, e_w=None, real=None):
+        """[n, 3]: the same weights on v16 (* e_w) times the member's rel vector, mean over the heads."""
+        if fused:
+            return FN.scatter_attention_pos(q, k, v16, rel, plan, n, e_w, member_mask=real)
+        alpha = _attention(gather(q, plan), k, v16, plan, member_real=real)
+        return scatter_sum(((alpha * (v16 * e_w if e_w is not None else v16)).unsqueeze(-1) * rel.unsqueeze(1)).reshape(-1, NH * 3),
+                           plan).view(-1, NH, 3).mean(1)
+
     out_fc = bool(getattr(cfg, "x2h_out_fc", False))
     for l in range(int(cfg.num_layers)):
         p = f"refine_net.base_block.{l}"
@@ -570,19 +587,11 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         # node_layer_with_edge (NodeUpdateLayer, :42-74)
         k_e, v_e = node_layer_edge("node_layer_with_edge", h, H)
         q_e = P.mlp(f"{p}.node_layer_with_edge.hq_func", h)
-        if fused:
-            a_edge = FN.scatter_attention(q_e, k_e, v_e, p_dst, B * N, e_w)
-        else:
-            alpha = _attention(gather(q_e, p_dst), k_e, v_e, p_dst)
-            a_edge = scatter_sum((alpha.unsqueeze(-1) * (v_e * e_w).view(-1, NH, H // NH)).reshape(-1, H), p_dst)
+        a_edge = attend(q_e, k_e, v_e, p_dst, B * N, e_w=e_w)
         # node_layer_with_bond
         k_b, v_b = node_layer_bond("node_layer_with_bond", h, h_bond)
         q_b = P.mlp(f"{p}.node_layer_with_bond.hq_func", h)
-        if fused:
-            a_bond = FN.scatter_attention(q_b, k_b, v_b, p_bdst, B * N, member_mask=real_b)
-        else:
-            alpha = _attention(gather(q_b, p_bdst), k_b, v_b, p_bdst, member_real=real_b)
-            a_bond = scatter_sum((alpha.unsqueeze(-1) * v_b.view(-1, NH, H // NH)).reshape(-1, H), p_bdst)
+        a_bond = attend(q_b, k_b, v_b, p_bdst, B * N, real=real_b)
         # bond_layer (BondUpdateLayer, :125-167): kv = [h_bond[kj](128), G(d_kj)(20), G(d_ji)(20), angle(13), h[k], h[j]]
         if trip is not None:
             nm_b = f"{p}.bond_layer"
@@ -604,11 +613,7 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
                 kv.append(P.mlp_tail(f"{nm_b}.{f_}", pre))
             # hq depends on the (j -> i) bond only: evaluated per bond, gathered per triplet (exact)
             q_bond = P.mlp(f"{nm_b}.hq_func", torch.cat([h_bond, gather(h, p_bdst)], -1))
-            if fused:
-                d_hb = FN.scatter_attention(q_bond, kv[0], kv[1], p_ji, Eb_tot, member_mask=real_t)
-            else:
-                alpha = _attention(gather(q_bond, p_ji), kv[0], kv[1], p_ji, member_real=real_t)
-                d_hb = scatter_sum((alpha.unsqueeze(-1) * kv[1].view(-1, NH, H // NH)).reshape(-1, H), p_ji)
+            d_hb = attend(q_bond, kv[0], kv[1], p_ji, Eb_tot, real=real_t)
         else:
             d_hb = torch.zeros_like(h_bond)
         new_h_bond = h_bond + d_hb
@@ -624,20 +629,11 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
         # pos_layer_with_edge / pos_layer_with_bond (PosUpdateLayer, :188-210), with the NEW h / h_bond
         k_pe, v_pe = node_layer_edge("pos_layer_with_edge", new_h, NH)
         q_pe = P.mlp(f"{p}.pos_layer_with_edge.xq_func", new_h)
-        if fused:
-            dx_e = FN.scatter_attention_pos(q_pe, k_pe, v_pe, rel, p_dst, B * N, e_w)
-        else:
-            alpha = _attention(gather(q_pe, p_dst), k_pe, None, p_dst)
-            dx_e = scatter_sum(((alpha * (v_pe * e_w)).unsqueeze(-1) * rel.unsqueeze(1)).reshape(-1, NH * 3), p_dst).view(-1, NH, 3).mean(1)
+        dx_e = attend_pos(q_pe, k_pe, v_pe, rel, p_dst, B * N, e_w=e_w)
         k_pb, v_pb = node_layer_bond("pos_layer_with_bond", new_h, new_h_bond)
         q_pb = P.mlp(f"{p}.pos_layer_with_bond.xq_func", new_h)
-        if fused:
-            rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
-            dx_b = FN.scatter_attention_pos(q_pb, k_pb, v_pb, rel_b, p_bdst, B * N, member_mask=real_b)
-        else:
-            alpha = _attention(gather(q_pb, p_bdst), k_pb, None, p_bdst, member_real=real_b)
-            rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
-            dx_b =scatter_sum(((alpha * v_pb).unsqueeze(-1) * rel_b.unsqueeze(1)).reshape(-1, NH * 3), p_bdst).view(-1, NH, 3).mean(1)
+        rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
+        dx_b = attend_pos(q_pb, k_pb, v_pb, rel_b, p_bdst, B * N, real=real_b)
         x = x + (dx_e + dx_b) * mask_l
         h, h_bond = new_h, new_h_bond
     softplus = lambda t: F.softplus(t) - math.log(2.0)                              # ShiftedSoftplus (common.py:66-72)

@@ -7,9 +7,11 @@ The cases, the mask, the float64 reference and the bound: tests/attention_mask_c
    members, and masked members get exact zeros;
 3. NaN in every row of a masked member changes no bit of any result;
 4. member_mask=None and an all-ones mask give bitwise the unmasked op;
-5. argument checks of the C ABI and of `functional`.
+5. argument checks of the C ABI and of `functional`;
+6. the two routes of `functional` -- the compiled extension's ops and, without it, the ctypes binding -- give the same bits.
 Every measured error is printed before it is judged."""
 import ctypes
+import os
 
 import pytest
 import torch
@@ -239,6 +241,29 @@ def test_functional_refuses_a_wrong_mask():
         FN.scatter_attention_backward(x["q"], x["k"], x["v"], index, n, x["e_w"], out, out, member_mask=good.float())
     with pytest.raises(ValueError):
         FN.scatter_attention_pos_backward(y["q"], y["k"], y["v"], y["rel_x"], index, n, y["e_w"], tp["cot"].to(dev()), member_mask=good[:-1])
+
+
+# ---- 6. extension route == ctypes route
+@pytest.mark.parametrize("form,per_edge", [("node", False), ("node", True), ("pos", False)])
+def test_ctypes_route_equals_the_extension_route_bit_for_bit(form, per_edge, monkeypatch):
+    """With the extension built every call of functional._attention_* goes through its ops, masked ones included; the ctypes
+    branch is what a host without the extension (or with DD_HIP_LIB / DD_TORCH_EXT=0) runs.  Same entry point, same bits:
+    the masked case (empty, all-masked and mixed segments) and the unmasked call, forward and every gradient.  The two routes differ
+    in the forward alone -- functional._attention_*_bwd always calls over ctypes -- so the gradients compared here show that the
+    backward is handed the same inputs (the node form reads the forward's `out`) on both."""
+    t = AM.reference(form, "unit", True, *((per_edge,) if form == "node" else ()))["t"]
+    # (with DD_HIP_LIB or DD_TORCH_EXT=0 set both halves run over ctypes and the comparison says nothing; a default run sets neither)
+    assert FN.torch_ext() is not None or os.environ.get("DD_HIP_LIB") or os.environ.get("DD_TORCH_EXT") == "0", \
+        "the compiled torch extension did not load: build it (python -m decompdiff_amd.build)"
+    by_ext = [_run(form, "functional", t), _run(form, "functional", t, mask=None)]
+    monkeypatch.setitem(FN._ext_state, "ops", None)
+    assert FN.torch_ext() is None
+    by_ctypes = [_run(form, "functional", t), _run(form, "functional", t, mask=None)]
+    for (out_e, grads_e), (out_c, grads_c) in zip(by_ext, by_ctypes):
+        assert torch.equal(out_e, out_c), "out"
+        for name in t["names"]:
+            assert torch.equal(grads_e[name], grads_c[name]), f"d{name}"
+    _masked_are_zero(t, *by_ctypes[0])
 
 
 def test_masked_ops_trace_with_fake_tensors():
