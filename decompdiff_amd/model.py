@@ -960,7 +960,9 @@ class DecompScorePosNet3D(nn.Module):
         ``torch.no_grad()`` (the reference's validation loop) the network output comes from the fused ``dd_forward``
         kernels instead.  The batch layout is validated on every call for both paths (`training.check_batch_layout`,
         i.e. `batch_layout.BatchLayout.from_batch`); samples of different sizes -- the reference's
-        training batches -- run as one dense sub-batch per distinct size (`training.network_grouped`)."""
+        training batches -- run as one padded, masked dense pass by default (`training.network_padded`), and as one dense
+        sub-batch per distinct size (`training.network_grouped`) with ``DD_TRAIN_PAD=0`` or when `batch_layout.fits_padded`
+        says no."""
         from . import training
         _check_ligand_atom_mask(ligand_atom_mask, batch_ligand.numel())
         if ligand_fc_bond_index is None or ligand_fc_bond_type is None or batch_ligand_bond is None:

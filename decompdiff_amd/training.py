@@ -285,9 +285,9 @@ class _P:
         return self.mlp_tail(name, self.lin(name + ".net.0", x))
 
 
-def _attention(q_e, k, v, seg, member_real=None):
+def _attention(q_e, k, seg, member_real=None):
     """alpha = scatter_softmax((q k / sqrt(d)).sum(-1)), [E, NH] -- the weights of out = scatter_sum(alpha v), which the caller forms
-    (uni_transformer_edge.py:63-68).  `v` is not read (callers pass the k, v pair).
+    (uni_transformer_edge.py:63-68).
     `seg`: the SegmentPlan of the destination index.  `member_real` (padded batches): bool per member -- padding members get a
     score of -1e30 (their exponential is exactly 0: the softmax is the softmax over the real members, same sums) and a weight of
     exactly 0 afterwards (a segment without any real member then contributes nothing)."""
@@ -299,6 +299,12 @@ def _attention(q_e, k, v, seg, member_real=None):
     if member_real is not None:
         alpha = alpha * member_real.unsqueeze(-1).to(alpha.dtype)
     return alpha
+
+
+def _fused_attn() -> bool:
+    """DD_TRAIN_FUSED_ATTN=1 (opt-in): `network` runs each attention site as one op.  Read at call time; a captured step belongs
+    to the setting it was captured under, so the setting is part of `GraphedTrainStep`'s graph keys."""
+    return os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1"
 
 
 def _edge_mlp_pre(P, name, W_off, dst_tab, src_tab, dst, src, extra):
@@ -365,6 +371,12 @@ def _far_positions(B, NPm, NLm, dev):
     return far_p, far_l
 
 
+def _padded(n, rows, src, fill=0):
+    """[n, ...] array with `src`'s rows at `rows` and `fill` everywhere else: a number, or the array to copy onto (`_far_positions`)."""
+    base = fill if torch.is_tensor(fill) else torch.full((n,) + tuple(src.shape[1:]), fill, device=src.device, dtype=src.dtype)
+    return base.index_copy(0, rows, src)
+
+
 def network_padded(model, protein_pos, protein_v, ligand_pos, ligand_v, ligand_v_aux, ligand_bond_type, n_p, n_l):
     """A batch whose samples differ in size -- what the reference's loader yields (batch_size 4 different complexes,
     configs/training.yml:62) -- as ONE dense pass: every sample is padded to the batch's largest protein / ligand, padding atoms
@@ -379,12 +391,10 @@ def network_padded(model, protein_pos, protein_v, ligand_pos, ligand_v, ligand_v
         return None
     rows_p, rows_l, rows_b = (r.to(dev) for r in lay.padded_rows())
     far_p, far_l = _far_positions(B, NPm, NLm, dev)
-    pp = far_p.index_copy(0, rows_p, protein_pos.to(torch.float32))
-    lp = far_l.index_copy(0, rows_l, ligand_pos.to(torch.float32))
-    pv = torch.zeros(B * NPm, protein_v.shape[1], device=dev, dtype=protein_v.dtype).index_copy(0, rows_p, protein_v)
-    lv = torch.zeros(B * NLm, device=dev, dtype=ligand_v.dtype).index_copy(0, rows_l, ligand_v)
-    la = torch.zeros(B * NLm, ligand_v_aux.shape[1], device=dev, dtype=ligand_v_aux.dtype).index_copy(0, rows_l, ligand_v_aux)
-    bt = torch.zeros(B * NLm * (NLm - 1), device=dev, dtype=ligand_bond_type.dtype).index_copy(0, rows_b, ligand_bond_type)
+    pp = _padded(B * NPm, rows_p, protein_pos.float(), far_p)
+    lp = _padded(B * NLm, rows_l, ligand_pos.float(), far_l)
+    pv, lv, la = _padded(B * NPm, rows_p, protein_v), _padded(B * NLm, rows_l, ligand_v), _padded(B * NLm, rows_l, ligand_v_aux)
+    bt = _padded(B * NLm * (NLm - 1), rows_b, ligand_bond_type)
     b_p, b_l, fc = model._expected_layout(B, NPm, NLm, dev)
     pad = dict(np_real=torch.tensor(n_p, dtype=torch.int32, device=dev), nl_real=torch.tensor(n_l, dtype=torch.int32, device=dev))
     out = network(model, pp, pv, b_p, lp, lv, la, b_l, fc, bt, checked_B=B, pad=pad)
@@ -537,20 +547,20 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
     # (FN.scatter_attention / scatter_attention_pos: dd_attn_aggregate_* forward, dd_attn_aggregate_*_bwd backward) instead of
     # gather, product, segment softmax, product, segment sum.  Padded passes hand the bond-graph and triplet sites their member
     # masks (real_b / real_t; None in a dense pass); the kNN sites need none: dd_knn_masked keeps padding atoms out of the graph.
-    fused = os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1"
+    fused = _fused_attn()
 
     def attend(q, k, v, plan, n, e_w=None, real=None):
         """[n, 128]: softmax over each destination's members of q . k per head, times v (* e_w), summed per destination."""
         if fused:
             return FN.scatter_attention(q, k, v, plan, n, e_w, member_mask=real)
-        alpha = _attention(gather(q, plan), k, v, plan, member_real=real)
+        alpha = _attention(gather(q, plan), k, plan, member_real=real)
         return scatter_sum((alpha.unsqueeze(-1) * (v * e_w if e_w is not None else v).view(-1, NH, H // NH)).reshape(-1, H), plan)
 
     def attend_pos(q, k, v16, rel, plan, n, e_w=None, real=None):
         """[n, 3]: the same weights on v16 (* e_w) times the member's rel vector, mean over the heads."""
         if fused:
             return FN.scatter_attention_pos(q, k, v16, rel, plan, n, e_w, member_mask=real)
-        alpha = _attention(gather(q, plan), k, v16, plan, member_real=real)
+        alpha = _attention(gather(q, plan), k, plan, member_real=real)
         return scatter_sum(((alpha * (v16 * e_w if e_w is not None else v16)).unsqueeze(-1) * rel.unsqueeze(1)).reshape(-1, NH * 3),
                            plan).view(-1, NH, 3).mean(1)
 
@@ -869,20 +879,16 @@ def pad_prepared(model, prep: Dict, bucket=(32, 4)) -> Optional[Dict]:
     rows_p, rows_l, rows_b = (r.to(dev) for r in lay.padded_rows(NPm, NLm))
     Ebm = NLm * (NLm - 1)
     far_p, far_l = _far_positions(B, NPm, NLm, dev)
-    z = lambda n, like, fill=0: torch.full((n,) + tuple(like.shape[1:]), fill, device=dev, dtype=like.dtype)
     dec = prep["ligand_decomp_batch"]
+    per_p = lambda src, fill=0: _padded(B * NPm, rows_p, src, fill)
+    per_l = lambda src, fill=0: _padded(B * NLm, rows_l, src, fill)
+    per_b = lambda src, fill=0: _padded(B * Ebm, rows_b, src, fill)
     out = dict(B=B, NPm=NPm, NLm=NLm, time_step=prep["time_step"],
-               protein_pos=far_p.index_copy(0, rows_p, prep["protein_pos"].float()),
-               protein_v=z(B * NPm, prep["protein_v"]).index_copy(0, rows_p, prep["protein_v"]),
-               ligand_pos=far_l.index_copy(0, rows_l, prep["ligand_pos"].float()),
-               ligand_v=z(B * NLm, prep["ligand_v"]).index_copy(0, rows_l, prep["ligand_v"]),
-               ligand_v_aux=z(B * NLm, prep["ligand_v_aux"]).index_copy(0, rows_l, prep["ligand_v_aux"]),
-               bond_type=z(B * Ebm, prep["ligand_fc_bond_type"]).index_copy(0, rows_b, prep["ligand_fc_bond_type"]),
-               pos_noise=z(B * NLm, prep["pos_noise"]).index_copy(0, rows_l, prep["pos_noise"]),
-               u_v=z(B * NLm, prep["u_v"], 0.5).index_copy(0, rows_l, prep["u_v"]),
-               u_b=z(B * Ebm, prep["u_b"], 0.5).index_copy(0, rows_b, prep["u_b"]),
-               centers=torch.zeros(B * NLm, 3, device=dev).index_copy(0, rows_l, prep["prior_centers"][dec].float()),
-               stds=torch.ones(B * NLm, 3, device=dev).index_copy(0, rows_l, prep["prior_stds"][dec].float()),
+               protein_pos=per_p(prep["protein_pos"].float(), far_p), protein_v=per_p(prep["protein_v"]),
+               ligand_pos=per_l(prep["ligand_pos"].float(), far_l), ligand_v=per_l(prep["ligand_v"]),
+               ligand_v_aux=per_l(prep["ligand_v_aux"]), bond_type=per_b(prep["ligand_fc_bond_type"]),
+               pos_noise=per_l(prep["pos_noise"]), u_v=per_l(prep["u_v"], 0.5), u_b=per_b(prep["u_b"], 0.5),
+               centers=per_l(prep["prior_centers"][dec].float()), stds=per_l(prep["prior_stds"][dec].float(), 1),
                w_p=torch.zeros(B * NPm, device=dev).index_fill(0, rows_p, 1.0),
                w_l=torch.zeros(B * NLm, device=dev).index_fill(0, rows_l, 1.0),
                w_b=torch.zeros(B * Ebm, device=dev).index_fill(0, rows_b, 1.0),
@@ -1044,10 +1050,10 @@ class GraphedTrainStep:
         dev = protein_pos.device
         if os.environ.get("DD_TRAIN_GRAPH", "1") == "0":
             return self._eager(prep)
+        # (`network` reads DD_TRAIN_FUSED_ATTN during the capture: a graph belongs to the setting it was captured under)
+        key_tail = (str(dev), model.model_mean_type, _fused_attn())
         if dense:
-            # (DD_TRAIN_FUSED_ATTN is read by `network` during the capture: a graph belongs to the setting it was captured under)
-            key = (tuple(n_p), tuple(n_l), int(prior_centers.shape[0]), str(dev), model.model_mean_type,
-                   os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1")
+            key = (tuple(n_p), tuple(n_l), int(prior_centers.shape[0])) + key_tail
             data, names, fn = prep, PREP_TENSORS, objective
         else:
             # samples of different sizes: the padded layout of their shape bucket (sizes rounded up to `bucket`) -- all batches
@@ -1055,8 +1061,7 @@ class GraphedTrainStep:
             data = pad_prepared(model, prep, self.bucket)
             if data is None:
                 return self._eager(prep)
-            key = ("padded", data["B"], data["NPm"], data["NLm"], str(dev), model.model_mean_type,
-                   os.environ.get("DD_TRAIN_FUSED_ATTN", "0") == "1")
+            key = ("padded", data["B"], data["NPm"], data["NLm"]) + key_tail
             names, fn = PAD_TENSORS, objective_padded
         ent = self._graphs.get(key)
         if ent is not None and ent["lrs"] != self._float_lrs():   # a float lr changed since the capture: it is baked into the graph

@@ -149,7 +149,7 @@ def test_gather_rejects_a_plan_of_another_table_height():
 @pytest.mark.parametrize("masked", [False, True])
 @pytest.mark.parametrize("kind", ["sorted", "knn_src"])
 def test_attention_and_aggregation_as_the_network_forms_them(kind, masked):
-    """alpha = _attention(gather(q, plan), k, v, plan[, member_real]) (16 heads x 8) and out = scatter_sum(alpha . v) against the
+    """alpha = _attention(gather(q, plan), k, plan[, member_real]) (16 heads x 8) and out = scatter_sum(alpha . v) against the
     float64 softmax over the real members only: alpha, out and the gradients with respect to q (through q_e), k and v."""
     idx, n, check = _index(kind, seed=3)
     plan = _plan(idx, n, check)
@@ -159,7 +159,7 @@ def test_attention_and_aggregation_as_the_network_forms_them(kind, masked):
     q, k, v = torch.randn(n, 128, generator=g), torch.randn(E, 128, generator=g), torch.randn(E, 128, generator=g)
     c = torch.randn(n, 128, generator=g)
     qd, kd, vd = (t.to(_dev()).requires_grad_(True) for t in (q, k, v))
-    alpha = training._attention(training.gather(qd, plan), kd, vd, plan, member_real=real.to(_dev()) if masked else None)
+    alpha = training._attention(training.gather(qd, plan), kd, plan, member_real=real.to(_dev()) if masked else None)
     out = training.scatter_sum((alpha.unsqueeze(-1) * vd.view(-1, 16, 8)).reshape(-1, 128), plan)
     (out * c.to(_dev())).sum().backward()
     q64, k64, v64 = (t.double().requires_grad_(True) for t in (q, k, v))

@@ -425,23 +425,27 @@ def test_padded_heterogeneous_training_batch_equals_size_groups(monkeypatch):
     _grads_agree(ga, gb, g)
 
 
-@pytest.mark.parametrize("bucket", [(1, 1), (32, 4)])
-def test_padded_objective_equals_the_ragged_objective(bucket):
-    """training.objective_padded on pad_prepared(...) -- fixed shapes, per-sample means over the real rows -- against
-    training.objective on the same prepared ragged batch: same losses, same gradients (also with sizes rounded up to a bucket,
-    i.e. whole padding atoms beyond the batch's largest sample), and the reference's own losses (`loss_grad_ragged`)."""
+_PREP_ARGS = ("protein_pos", "protein_v", "batch_protein", "ligand_pos", "ligand_v", "ligand_v_aux", "batch_ligand", "prior_centers",
+              "prior_stds", "prior_num_atoms", "batch_prior", "ligand_decomp_batch", "ligand_fc_bond_index", "ligand_fc_bond_type",
+              "batch_ligand_bond")
+_BOTH = {}
+
+
+def _both_objectives(fixture, bucket):
+    """training.objective on prepare_batch(...) and training.objective_padded on pad_prepared(..., bucket) of the same fixture,
+    same seed, a fresh model each: {"flat" / "padded": (result, gradients)} and the padded batch.  Run once per (fixture, bucket)
+    and shared by the tests below, which only read it."""
+    if (fixture, bucket) in _BOTH:
+        return _BOTH[(fixture, bucket)]
     from decompdiff_amd import training
-    g = GU.load("loss_grad_ragged")
+    g = GU.load(fixture)
     kw = _loss_kwargs(g)
-    names = ("protein_pos", "protein_v", "batch_protein", "ligand_pos", "ligand_v", "ligand_v_aux", "batch_ligand", "prior_centers",
-             "prior_stds", "prior_num_atoms", "batch_prior", "ligand_decomp_batch", "ligand_fc_bond_index", "ligand_fc_bond_type",
-             "batch_ligand_bond")
     out = {}
-    for mode in ("ragged", "padded"):
+    for mode in ("flat", "padded"):
         m = _fresh_model(); m.train()
         torch.manual_seed(int(g["noise_seed"]))
-        prep = training.prepare_batch(m, *[kw[n] for n in names], time_step=kw["time_step"])
-        if mode == "ragged":
+        prep = training.prepare_batch(m, *[kw[n] for n in _PREP_ARGS], time_step=kw["time_step"])
+        if mode == "flat":
             r = training.objective(m, prep)
         else:
             pp = training.pad_prepared(m, prep, bucket)
@@ -450,11 +454,50 @@ def test_padded_objective_equals_the_ragged_objective(bucket):
         loss = r["losses"]["pos"] + 100.0 * r["losses"]["v"] + 100.0 * r["losses"]["bond"]
         loss.backward()
         out[mode] = (r, {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.grad is not None})
-    (ra, ga), (rb, gb) = out["padded"], out["ragged"]
+    _BOTH[(fixture, bucket)] = (g, out, pp)
+    return _BOTH[(fixture, bucket)]
+
+
+def _padded_equals_flat(g, out):
+    (ra, ga), (rb, gb) = out["padded"], out["flat"]
+    for k in ("pos", "v", "bond"):
+        print(f"loss {k}: padded {float(ra['losses'][k]):.9g}  flat {float(rb['losses'][k]):.9g}  reference {float(g['loss_' + k]):.9g}")
     for k in ("pos", "v", "bond"):
         assert abs(float(ra["losses"][k]) - float(rb["losses"][k])) <= 2e-6 * max(1.0, abs(float(rb["losses"][k]))), k
         assert abs(float(ra["losses"][k]) - float(g["loss_" + k])) <= 1e-4 * max(1.0, abs(float(g["loss_" + k])))
     _grads_agree(ga, gb, g)
+
+
+@pytest.mark.parametrize("bucket", [(1, 1), (32, 4)])
+def test_padded_objective_equals_the_ragged_objective(bucket):
+    """training.objective_padded on pad_prepared(...) -- fixed shapes, per-sample means over the real rows -- against
+    training.objective on the same prepared ragged batch: same losses, same gradients (also with sizes rounded up to a bucket,
+    i.e. whole padding atoms beyond the batch's largest sample), and the reference's own losses (`loss_grad_ragged`)."""
+    g, out, _ = _both_objectives("loss_grad_ragged", bucket)
+    _padded_equals_flat(g, out)
+
+
+def test_padded_objective_without_padding_equals_the_dense_objective():
+    """`loss_grad` (3 samples of 90 + 12 atoms, time steps 700 / 12 / 0: the KL and the t == 0 NLL branch) through
+    pad_prepared(..., bucket=(1, 1)) -- no padding row at all, every weight 1 -- and objective_padded against prepare_batch ->
+    objective on the same dense batch: the two statements of the loss on the one input both accept.  Bounds: those of the same
+    comparison on the ragged fixture above."""
+    g, out, pp = _both_objectives("loss_grad", (1, 1))
+    assert pp["NPm"] == 90 and pp["NLm"] == 12
+    for w in ("w_p", "w_l", "w_b"):
+        assert bool((pp[w] == 1).all()), w
+    _padded_equals_flat(g, out)
+
+
+@pytest.mark.parametrize("fixture,bucket", [("loss_grad", (1, 1)), ("loss_grad_ragged", (1, 1)), ("loss_grad_ragged", (32, 4))])
+def test_objective_result_keys(fixture, bucket):
+    """The exact result keys of both objectives (callers read them by name; neither has the other's extra keys -- a softmax more in
+    `objective_padded` would be a change to the captured graph), so that folding the two cannot silently drop one."""
+    _, out, _ = _both_objectives(fixture, bucket)
+    common = {"losses", "x0", "pred_ligand_pos", "pred_ligand_v", "time_step"}
+    assert set(out["flat"][0]) == common | {"pred_pos_noise", "ligand_v_recon", "ligand_b_recon"}
+    assert set(out["padded"][0]) == common | {"pred_bond"}
+    assert set(out["flat"][0]["losses"]) == set(out["padded"][0]["losses"]) == {"pos", "v", "bond"}
 
 
 def test_graphed_train_step_with_batches_of_different_complexes():
