@@ -8,6 +8,8 @@ reference call                                          here
 ``torch_geometric.nn.knn_graph(x, k, batch, flow)``     :func:`knn_graph`         (uni_transformer_edge.py:353)
 ``scatter_softmax(...); scatter_sum(alpha * v, ...)``   :func:`scatter_attention` (uni_transformer_edge.py:63-68,158-164)
 the same with ``v.unsqueeze(-1) * rel_x`` and ``mean``  :func:`scatter_attention_pos` (uni_transformer_edge.py:199-211)
+``BondUpdateLayer.triplets(edge_index, num_nodes)``     :func:`triplets`          (uni_transformer_edge.py:103-123)
+``torch_sparse.SparseTensor`` as that method uses it    :class:`SparseTensor`     (uni_transformer_edge.py:108-122)
 =====================================================  ==========================================================
 """
 from __future__ import annotations
@@ -485,3 +487,134 @@ def scatter_softmax(src: torch.Tensor, index: torch.Tensor, dim: int = -1, dim_s
             inv[perm] = torch.arange(E, device=perm.device)
         res = res[inv]
     return res.view(src.shape).to(src.dtype)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# torch_sparse at its one call site: the k -> j -> i triplet lists of the ligand bond graph,
+# BondUpdateLayer.triplets (uni_transformer_edge.py:103-123), and the SparseTensor that method builds them with.  Both sit on
+# one primitive of the library, dd_csr_select_*: a CSR built on the device and rows selected from it, with an optional key
+# to leave out per selected row.  ctypes only (the compiled extension has no op for it).
+# ------------------------------------------------------------------------------------------------------------------
+def _csr_select(node: torch.Tensor, key: torch.Tensor, n_rows: int, n_cols: int, sel: torch.Tensor, skip: Optional[torch.Tensor],
+                what: str, with_sel: bool = False):
+    """``(out_row, out_key, out_entry[, out_sel, out_skip])`` of include/decompdiff_hip.h: dd_csr_select_count, ONE host read
+    (the total and the count of ids out of range, together), dd_csr_select_fill.  All arguments int64, contiguous, on one device."""
+    lib, dev = hip_lib.load(), node.device
+    E, R = node.numel(), sel.numel()
+    nbytes = lib.dd_csr_select_scratch_bytes(E, n_rows, n_cols, R)
+    if nbytes == 0:
+        raise NotImplementedError(f"{what}: sizes at or above 2**31 (the kernels index with int32)")
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    st = hip_lib.stream_ptr(dev)
+    hip_lib.check(lib.dd_csr_select_count(hip_lib.ptr(node), hip_lib.ptr(key), E, n_rows, n_cols, hip_lib.ptr(sel), hip_lib.ptr(skip), R,
+                                          hip_lib.ptr(scratch), nbytes, st), "dd_csr_select_count")
+    total, bad = scratch[:2].tolist()
+    if bad:
+        raise IndexError(f"{what}: {bad} ids out of range")
+    outs = [torch.empty(total, dtype=torch.int64, device=dev) for _ in range(5 if with_sel else 3)]
+    hip_lib.check(lib.dd_csr_select_fill(hip_lib.ptr(sel), hip_lib.ptr(skip), E, n_rows, n_cols, R, hip_lib.ptr(scratch), total,
+                                         *[hip_lib.ptr(o) for o in outs], *([] if with_sel else [None, None]), st), "dd_csr_select_fill")
+    return outs
+
+
+def triplets(edge_index: torch.Tensor, num_nodes: int):
+    """``BondUpdateLayer.triplets``: ``(i, j, idx_i, idx_j, idx_k, idx_kj, idx_ji)`` of the directed graph whose edge ``e`` is
+    ``edge_index[0, e] -> edge_index[1, e]`` (j -> i).  For every edge in edge order, the edges ``k -> j`` into its source with
+    ``k`` ascending (equal ``(k, j)`` pairs in edge order) and ``k == i`` dropped: ``idx_kj`` is the id of the edge ``k -> j``,
+    ``idx_ji`` is ``e`` -- non-decreasing, so it is accepted as the index of :func:`scatter_attention`.  ``i`` and ``j`` are
+    ``edge_index[1]`` and ``edge_index[0]`` themselves.  The edge list need not be sorted and nodes without edges are normal
+    (``decomp_fc`` / ``scaffold_fc`` bond lists, ligand rows among protein rows).  Node ids outside ``[0, num_nodes)`` raise
+    ``IndexError``.  The length of the lists depends on the data: every call reads it back from the device (one device ->
+    host copy), so it cannot run while a stream is being captured."""
+    if not torch.is_tensor(edge_index) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError("triplets: edge_index must be an int64 tensor [2,E]")
+    n = int(num_nodes)
+    if n < 0:
+        raise ValueError("triplets: num_nodes < 0")
+    hip_lib.require_gpu(edge_index, "edge_index")
+    j, i = edge_index[0], edge_index[1]
+    if edge_index.size(1) == 0 or n == 0:
+        if edge_index.size(1):
+            raise IndexError("triplets: edges of a graph without nodes")
+        return (i, j) + tuple(torch.empty(0, dtype=torch.int64, device=edge_index.device) for _ in range(5))
+    row, col = j.contiguous(), i.contiguous()
+    idx_ji, idx_k, idx_kj, idx_j, idx_i = _csr_select(col, row, n, n, row, col, "triplets", with_sel=True)
+    return i, j, idx_i, idx_j, idx_k, idx_kj, idx_ji
+
+
+class _SparseStorage:
+    def __init__(self, row, col, value):
+        self._row, self._col, self._value = row, col, value
+
+    def row(self):
+        return self._row
+
+    def col(self):
+        return self._col
+
+    def value(self):
+        return self._value
+
+
+class SparseTensor:
+    """``torch_sparse.SparseTensor`` as far as ``BondUpdateLayer.triplets`` touches it (uni_transformer_edge.py:108-122), on
+    device tensors: the constructor with ``row=``, ``col=``, ``value=``, ``sparse_sizes=`` (entries kept sorted by (row, col),
+    stable), ``t[index]`` with an int64 index tensor (new row ``r`` is old row ``index[r]``; repeats and empty rows allowed),
+    ``set_value(None)``, ``sum(dim=1)`` of a value-less tensor (entries per row, float), ``storage.row() / col() / value()`` and
+    ``sparse_sizes()``.  Anything else raises ``NotImplementedError``.  The constructor and ``t[index]`` each run the
+    dd_csr_select kernels and read one pair of counters back from the device."""
+
+    def __init__(self, row: Optional[torch.Tensor] = None, col: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None,
+                 sparse_sizes=None, **kwargs):
+        if kwargs or row is None or col is None or sparse_sizes is None:
+            raise NotImplementedError("SparseTensor: construct with row=, col=, value=, sparse_sizes= (" + ", ".join(kwargs) + ")")
+        if row.dtype != torch.int64 or col.dtype != torch.int64 or row.dim() != 1 or col.shape != row.shape:
+            raise ValueError("SparseTensor: row and col must be int64 vectors of one length")
+        hip_lib.require_gpu(row, "row")
+        hip_lib.require_gpu(col, "col")
+        if value is not None and (value.size(0) != row.numel() or value.device != row.device):
+            raise ValueError("SparseTensor: value must have one entry per row / col entry, on their device")
+        self._sizes = (int(sparse_sizes[0]), int(sparse_sizes[1]))
+        if row.numel() == 0:
+            self.storage = _SparseStorage(row, col, value)
+            return
+        every_row = torch.arange(self._sizes[0], device=row.device)
+        srow, scol, perm = _csr_select(row.contiguous(), col.contiguous(), self._sizes[0], self._sizes[1], every_row, None, "SparseTensor")
+        self.storage = _SparseStorage(srow, scol, None if value is None else value[perm])
+
+    @classmethod
+    def _sorted(cls, row, col, value, sizes):
+        t = cls.__new__(cls)
+        t.storage, t._sizes = _SparseStorage(row, col, value), sizes
+        return t
+
+    def sparse_sizes(self):
+        return self._sizes
+
+    def __getitem__(self, index):
+        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1:
+            raise NotImplementedError("SparseTensor.__getitem__: an int64 index vector selecting rows")
+        row, col, value = self.storage.row(), self.storage.col(), self.storage.value()
+        hip_lib.require_gpu(index, "index")
+        sizes = (index.numel(), self._sizes[1])
+        if index.numel() == 0 or self._sizes[0] == 0:
+            if index.numel():
+                raise IndexError("SparseTensor.__getitem__: rows of a tensor without rows")
+            return SparseTensor._sorted(row[:0], col[:0], None if value is None else value[:0], sizes)
+        nrow, ncol, entry = _csr_select(row, col, self._sizes[0], self._sizes[1], index.contiguous(), None, "SparseTensor.__getitem__")
+        return SparseTensor._sorted(nrow, ncol, None if value is None else value[entry], sizes)
+
+    def set_value(self, value, layout=None):
+        if value is not None:
+            raise NotImplementedError("SparseTensor.set_value: only set_value(None)")
+        return SparseTensor._sorted(self.storage.row(), self.storage.col(), None, self._sizes)
+
+    def sum(self, dim=None):
+        if dim != 1 or self.storage.value() is not None:
+            raise NotImplementedError("SparseTensor.sum: only sum(dim=1) of a tensor without values")
+        return torch.bincount(self.storage.row(), minlength=self._sizes[0]).to(torch.float32)
+
+    def __getattr__(self, name):
+        if name.startswith("__") or name in ("storage", "_sizes"):      # (Python's own protocol lookups; a half-built object)
+            raise AttributeError(name)
+        raise NotImplementedError(f"SparseTensor.{name}: not part of the decompdiff_amd drop-in")

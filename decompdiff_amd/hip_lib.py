@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "dd_forward_ex2", "dd_sample_steps_ex2", "dd_sample_steps_graph_ex2", "dd_graph_create_ex2", "dd_sample_steps_graph_multi_ex2",
     "dd_attn_aggregate_node_bwd", "dd_attn_aggregate_pos_bwd",
     "dd_attn_aggregate_node_masked", "dd_attn_aggregate_pos_masked", "dd_attn_aggregate_node_bwd_masked", "dd_attn_aggregate_pos_bwd_masked",
+    "dd_csr_select_scratch_bytes", "dd_csr_select_count", "dd_csr_select_fill",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -187,12 +188,16 @@ def load():
         "dd_attn_aggregate_pos_masked": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
         "dd_attn_aggregate_node_bwd_masked": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 8,
         "dd_attn_aggregate_pos_bwd_masked": [c_void_p] * 6 + [c_int] + [c_void_p] * 8,
+        "dd_csr_select_scratch_bytes": [c_int64] * 4,
+        "dd_csr_select_count": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p],
+        "dd_csr_select_fill": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64] + [c_void_p] * 6,
         "dd_segment_reduce": [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p],
         "dd_segment_softmax": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
         "dd_debug_philox": [c_uint64, c_int, c_long, c_int, c_void_p, c_void_p],
         "dd_profile_step": [S, c_int, POINTER(c_float), c_void_p],
     }
-    restypes = {"dd_workspace_floats": c_size_t, "dd_gemm128_tn_scratch_floats": c_size_t, "dd_ln_relu_scratch_floats": c_size_t}
+    restypes = {"dd_workspace_floats": c_size_t, "dd_gemm128_tn_scratch_floats": c_size_t, "dd_ln_relu_scratch_floats": c_size_t,
+                "dd_csr_select_scratch_bytes": c_size_t}
     for name in EXPORTED_SYMBOLS + DEBUG_SYMBOLS:
         if name in ("dd_status_string", "dd_abi_version"):
             continue

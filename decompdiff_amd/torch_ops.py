@@ -11,10 +11,13 @@ there is no CPU implementation — CPU tensors raise.
 :func:`patch_reference_imports` installs module objects named ``torch_scatter`` and ``torch_cluster`` exposing these ops
 under the names the reference imports (``from torch_scatter import scatter_softmax, scatter_sum``:
 models/encoders/uni_transformer_edge.py:9; ``scatter_mean``: models/decompdiff.py:9; ``scatter_min``:
-utils/guidance_funcs.py:9), for hosts that keep the reference's Python layers.
+utils/guidance_funcs.py:9), and -- where the real package is not importable -- a ``torch_sparse`` module holding
+:class:`decompdiff_amd.functional.SparseTensor` (``from torch_sparse import SparseTensor``:
+models/encoders/uni_transformer_edge.py:13), for hosts that keep the reference's Python layers.
 """
 from __future__ import annotations
 
+import importlib
 import sys
 import types
 from typing import Optional, Tuple
@@ -36,6 +39,19 @@ def knn_graph(x: Tensor, k: int, batch: Optional[Tensor] = None, loop: bool = Fa
 def _(x, k, batch=None, loop=False, flow="source_to_target"):
     ctx = torch.library.get_ctx()
     return x.new_empty((2, ctx.new_dynamic_size()), dtype=torch.long)
+
+
+# The five triplet lists (idx_i, idx_j, idx_k, idx_kj, idx_ji) of functional.triplets; its first two results are rows of
+# edge_index itself, which an op may not return (outputs must not alias inputs).  Integer outputs: no autograd formula.
+@torch.library.custom_op(f"{_NS}::triplets", mutates_args=(), device_types="cuda")
+def triplets(edge_index: Tensor, num_nodes: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return F.triplets(edge_index, num_nodes)[2:]
+
+
+@triplets.register_fake
+def _(edge_index, num_nodes):
+    n = torch.library.get_ctx().new_dynamic_size()
+    return tuple(edge_index.new_empty((n,), dtype=torch.long) for _ in range(5))
 
 
 @torch.library.custom_op(f"{_NS}::scatter_attention", mutates_args=(), device_types="cuda")
@@ -246,7 +262,8 @@ scatter_min.register_autograd(_bw_min, setup_context=_setup_min)
 
 def patch_reference_imports(force: bool = False) -> None:
     """Make ``import torch_scatter`` / ``from torch_geometric.nn import knn_graph``-style imports of a host that keeps the
-    reference's Python resolve to these ops.  Existing real packages are left alone unless ``force``."""
+    reference's Python resolve to these ops.  Existing real packages are left alone unless ``force``.  ``torch_sparse`` is
+    installed (one name, ``SparseTensor``: functional.SparseTensor) when the real package cannot be imported, or with ``force``."""
     ops = torch.ops.decompdiff_amd
 
     def _with_out(op):
@@ -267,3 +284,18 @@ def patch_reference_imports(force: bool = False) -> None:
         c = types.ModuleType("torch_cluster")
         c.knn_graph = lambda x, k, batch=None, loop=False, flow="source_to_target", **kw: ops.knn_graph(x, k, batch, loop, flow)
         sys.modules["torch_cluster"] = c
+    if force or not _importable("torch_sparse"):
+        t = types.ModuleType("torch_sparse")
+        t.SparseTensor = F.SparseTensor
+        t.__doc__ = "decompdiff_amd drop-in (HIP, gfx950) for the SparseTensor the reference's BondUpdateLayer.triplets builds"
+        sys.modules["torch_sparse"] = t
+
+
+def _importable(name: str) -> bool:
+    if name in sys.modules:
+        return True
+    try:
+        importlib.import_module(name)
+    except (ImportError, OSError):                            # absent, or a wheel built against another runtime
+        return False
+    return True

@@ -311,6 +311,36 @@ int dd_segment_reduce(const float* src, const int32_t* seg_ptr, int n_seg, int F
                       int64_t* arg_out, void* stream);
 int dd_segment_softmax(const float* src, const int32_t* seg_ptr, int n_seg, int F, float* out, void* stream);
 
+/* torch_sparse.SparseTensor at its one call site, BondUpdateLayer.triplets (uni_transformer_edge.py:103-123): a CSR built on the
+ * device and rows selected from it, with an optional key to leave out per selected row.
+ *   CSR: entry e of a COO list sits in row node[e] with key key[e] (int64, E entries; any order; rows without entries are
+ *        normal).  Every row's run is ordered by (key, e): the stable (row, col) order of the SparseTensor.
+ *   Selection: for r < R, in order, the members of row sel[r] in run order, except those whose key equals skip[r] (skip NULL:
+ *        none left out).  Per surviving member t: out_row[t] = r, out_key[t] = its key, out_entry[t] = its entry id e,
+ *        out_sel[t] = sel[r], out_skip[t] = skip[r]; each out_* may be NULL (not written).
+ * The triplets (k->j->i) of the directed graph row[e] -> col[e] (j -> i) are the selection node = col, key = row, sel = row,
+ * skip = col, R = E over n_rows = n_cols = num_nodes:  idx_ji = out_row, idx_k = out_key, idx_kj = out_entry, idx_j = out_sel,
+ * idx_i = out_skip -- for every edge in edge order the edges into its source, k ascending (equal (k, j) in edge order), k == i
+ * dropped; a self loop is an edge like any other.  `t[index]` of the SparseTensor is the selection with skip = NULL.
+ * Two phases, because the size of the result depends on the data:
+ *   dd_csr_select_scratch_bytes: bytes of scratch for these sizes (0: refused, see below);
+ *   dd_csr_select_count: builds the CSR and the offsets in `scratch` (8-byte aligned, caller-owned) and leaves two int64 at its
+ *        start: scratch[0] = total, the number of surviving members, scratch[1] = bad, the number of entries with node[e]
+ *        outside [0, n_rows) or key[e] outside [0, n_cols) plus the number of sel[r] outside [0, n_rows).  Such entries belong
+ *        to no row and such a selection is empty: nothing outside the caller's buffers is read or written, whatever the ids hold;
+ *   dd_csr_select_fill: after the caller has read `total` and allocated the lists, with the same sel / skip / sizes / scratch.
+ *        At most `total` and at most the counted number of elements of each list are written.
+ * Internally int32: E, n_rows, n_cols, R or a total at or above 2^31 give DD_ERR_UNSUPPORTED_SHAPE.  Runs may have any length
+ * (no per-row buffer); ordering a run costs its length squared.  Integer atomics only place entries before the ordering, so
+ * the results are bit-identical from run to run.  (New entry points, ABI unchanged.) */
+size_t dd_csr_select_scratch_bytes(int64_t E, int64_t n_rows, int64_t n_cols, int64_t R);
+int dd_csr_select_count(const int64_t* node /*[E]*/, const int64_t* key /*[E]*/, int64_t E, int64_t n_rows, int64_t n_cols,
+                        const int64_t* sel /*[R]*/, const int64_t* skip /*[R] or NULL*/, int64_t R, void* scratch,
+                        size_t scratch_bytes, void* stream);
+int dd_csr_select_fill(const int64_t* sel, const int64_t* skip, int64_t E, int64_t n_rows, int64_t n_cols, int64_t R,
+                       const void* scratch, int64_t total, int64_t* out_row, int64_t* out_key, int64_t* out_entry,
+                       int64_t* out_sel, int64_t* out_skip, void* stream);
+
 /* Embeddings (decompdiff.py:219-256, 296-297). protein_h is step-invariant. */
 int dd_embed_protein(const float* protein_v /*[B*NP,29]*/, int rows, const float* W /*[128,29]*/, const float* b,
                      float* protein_h /*[rows,128]*/, void* stream);
