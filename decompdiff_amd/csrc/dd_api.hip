@@ -4,6 +4,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include <stdio.h>
@@ -129,7 +130,7 @@ static bool g_gemm_ksplit_on() { return g_gemm_ksplit != 0; }   // (the addend f
 // serialised by g_capture_mutex, so one set per device is enough for any number of samplers.
 struct DevCtx {
   hipStream_t side = nullptr;
-  hipEvent_t ev_qa_fork[8], ev_qb_fork[8], ev_fork[9], ev_join[9];
+  hipEvent_t ev_qa_fork[8], ev_qb_fork[8], ev_fork[9], ev_join[9];   // per-layer events: slot (step & 7), see forward_impl
 };
 static DevCtx g_dev_ctx[16];
 static std::mutex g_capture_mutex;
@@ -356,8 +357,9 @@ struct Fwd {
   explicit Fwd(const dd_sampler* s_)
       : s(s_), w(carve(s_->workspace, s_->B, s_->NP, s_->NL, s_->K)), B(s_->B), NP(s_->NP), NL(s_->NL), K(s_->K), N(s_->NP + s_->NL),
         nE((int)((long)s_->B * s_->NL * (s_->NL - 1))), Eb((long)s_->NL * (s_->NL - 1)), hN((long)(s_->NP + s_->NL) * 128) {}
-  const float* LW(int l, int slot) const { return s->weights + s->slot_off[(long)l * DD_NUM_LAYER_SLOTS + slot]; }
-  const float* GW(int slot) const { return LW(s->num_layers, slot); }
+  // (l: the step of the forward -- block b, layer l % num_layers of it: the blocks of a refine net share their weights)
+  const float* LW(int l, int slot) const { return s->weights + s->slot_off[(long)(l % s->num_layers) * DD_NUM_LAYER_SLOTS + slot]; }
+  const float* GW(int slot) const { return s->weights + s->slot_off[(long)s->num_layers * DD_NUM_LAYER_SLOTS + slot]; }
   GemmArgs add_anb(const GemmArgs& g, const float* anb, bool all_nodes) const { return dd::add_anb(g, anb, all_nodes, NP, NL); }
   float* anb_buf(int l) const { return (l & 1) ? w.A : w.Anb; }   // lin_in_node: where layer l's NB blocks leave W_lin . A_nb
 
@@ -479,7 +481,7 @@ struct Fwd {
     bl.lnk = LW(l, DD_BL_lnk); bl.lnv = LW(l, DD_BL_lnv);
     bl.W2k = LW(l, DD_BL_W2k); bl.W2v = LW(l, DD_BL_W2v); bl.b2v = LW(l, DD_BL_b2v); bl.out = w.hb;
     bl.Rk = w.Rk; bl.Rv = w.Rv;
-    bl.work_counter = w.counters + l;                    // persistent workgroups; [0, 64) of the counters: check_shapes keeps num_layers <= 64
+    bl.work_counter = w.counters + l;                    // persistent workgroups; [0, 64) of the counters: num_blocks * num_layers <= 64
     return bl;
   }
   // pos_layer_with_edge / pos_layer_with_bond
@@ -513,6 +515,11 @@ struct Fwd {
                            w.nbr, w.ew, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2), GW(DD_G_EW_b2),
                            s->np_real, s->nl_real, l0 ? s->l0_tables : nullptr, s->l0_P, w.PL, s->l0_qn, w.qlnb, w.PB, w.qb, sx, parts,
                            num_v(s));
+  }
+  // block boundary (num_blocks > 1; dd_graph.hip): the next block's kNN graph + edge weights from the current coordinates x
+  int launch_block(const float* x, hipStream_t sx) const {
+    return launch_block_graph(x, B, NP, NL, K, w.nbr, w.ew, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2), GW(DD_G_EW_b2),
+                              s->np_real, s->nl_real, sx);
   }
 };
 
@@ -672,26 +679,49 @@ static int check_node_out(const dd_node_out* no, const dd_sampler* s) {
   return DD_OK;
 }
 
-static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nullptr, const dd_bond_head* bh = nullptr,
-                        const dd_node_out* no = nullptr) {
+// What the model is beyond the dd_sampler: the contents of a dd_model_opts (include/decompdiff_hip.h), checked.
+struct ModelOpts {
+  const dd_bond_head* bh = nullptr;
+  const dd_node_out* no = nullptr;
+  int num_blocks = 1;
+};
+static int check_blocks(const dd_sampler* s, int num_blocks) {
+  if (!s || num_blocks < 1) return DD_ERR_BAD_ARG;
+  // every step of a forward has a bond-layer work counter of its own (Workspace::counters [0, 64))
+  return (long)num_blocks * s->num_layers <= 64 ? DD_OK : DD_ERR_UNSUPPORTED_SHAPE;
+}
+
+// The score network: num_blocks * num_layers steps; step l runs layer l % num_layers (shared weights), and every step with
+// l % num_layers == 0, l > 0 opens a new block: its kNN graph and edge weights are rebuilt from the coordinates the previous
+// block left (uni_transformer_edge.py:402-437).  Everything that ping-pongs by layer parity (x, A / Anb) and every per-layer
+// counter goes by the step, so one block is exactly the former loop.
+static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nullptr, const ModelOpts& mo = ModelOpts()) {
+  const dd_bond_head* bh = mo.bh;
+  const dd_node_out* no = mo.no;
   DD_TRY(check_shapes(s));
   DD_TRY(check_node_out(no, s));
+  DD_TRY(check_blocks(s, mo.num_blocks));
   const bool pre_att = is_pre_att(bh);
   // x2h_out_fc: k_node_out_fc (node output MLPs + lin_node, one launch) takes the place of the lin_node GEMM job; the node
   // launch's in-kernel lin_node has no node-output stage, so lin_in_node is off for such a model
   const bool out_fc = no != nullptr;
   const Fwd f(s);
   const Workspace& w = f.w;
-  const int B = f.B, NP = f.NP, NL = f.NL, N = f.N, L = s->num_layers;
+  const int B = f.B, NP = f.NP, NL = f.NL, N = f.N;
+  const int LB = s->num_layers, L = mo.num_blocks * LB;  // layers of a block; steps of the forward
   DevCtx& dc = dev_ctx();                                // side stream + fork / join events of this device
 
   float* xcur = w.xa;
   float* xnext = w.xb;
   float* hcur = w.h;                                     // (ping-pong with w.h2 under the one-fork schedule only)
   const bool fused = g_fuse && NL <= g_fused_max_nl && g_dbg_clock == nullptr;
-  const bool overlap = fused && g_overlap && g_prof == nullptr && L <= 8;
+  // (the per-layer fork / join events are taken round robin, slot step & 7: an event is waited for at most one step after it
+  //  was recorded, and recording it again later -- eager or while capturing -- makes a new dependency)
+  const bool overlap = fused && g_overlap && g_prof == nullptr && LB <= 8;
+  auto ev = [](int l) { return l & 7; };
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
   if (out_fc && (g_sched >= 5 || g_side_lin)) return DD_ERR_UNSUPPORTED_SHAPE;   // (measurement schedules without the node-output stage)
+  if (mo.num_blocks > 1 && (g_sched >= 5 || g_side_lin)) return DD_ERR_UNSUPPORTED_SHAPE;   // (... and without the block boundary)
   if (fused && !pre_att && g_sched >= 5 && L <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
       g_xup_in_asm && !g_xup_in_pos)
     return forward_tail(f, dc, st, fold, overlap);
@@ -757,12 +787,12 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   auto flush_pos = [&]() -> int {
     if (!dpos.armed) return DD_OK;
     dpos.armed = false;
-    if (hipStreamWaitEvent(dc.side, dc.ev_fork[dpos.layer], 0) != hipSuccess) return DD_ERR_HIP;
+    if (hipStreamWaitEvent(dc.side, dc.ev_fork[ev(dpos.layer)], 0) != hipSuccess) return DD_ERR_HIP;
     int rc = launch_attn2_pos(dpos.pe, dpos.pb, dc.side);
     if (rc == DD_OK && !dpos.xup) rc = launch_xupdate(dpos.xcur, w.dxe, w.dxb, B, NP, NL, dpos.xnext, dc.side);
     if (rc != DD_OK) return rc;
-    if (hipEventRecord(dc.ev_join[dpos.layer], dc.side) != hipSuccess) return DD_ERR_HIP;
-    pending_join = dpos.layer;
+    if (hipEventRecord(dc.ev_join[ev(dpos.layer)], dc.side) != hipSuccess) return DD_ERR_HIP;
+    pending_join = ev(dpos.layer);
     return DD_OK;
   };
   const float* xup_prev = nullptr;                       // != nullptr: x of the previous layer, its update still pending
@@ -809,7 +839,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     bool b1_joined = false;
     if (q1_in_gemm && !b2_ahead) {
       if (ahead && l > 0) {                              // (schedules 1/2: this layer's projections ran on the side stream)
-        if (hipStreamWaitEvent(st, dc.ev_join[l], 0) != hipSuccess) return DD_ERR_HIP;
+        if (hipStreamWaitEvent(st, dc.ev_join[ev(l)], 0) != hipSuccess) return DD_ERR_HIP;
         b1_joined = true;
       }
       if (!l0_here) DD_TRYP(DD_PROF_GEMM, launch_b2(l, st));
@@ -820,19 +850,25 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       pending_join = -1;
     }
     const bool late_join = two_joins && b2_ahead && !b1_joined;
-    if (ahead && l > 0 && !b1_joined && hipStreamWaitEvent(st, late_join ? dc.ev_qb_fork[l] : dc.ev_join[l], 0) != hipSuccess)
+    if (ahead && l > 0 && !b1_joined && hipStreamWaitEvent(st, late_join ? dc.ev_qb_fork[ev(l)] : dc.ev_join[ev(l)], 0) != hipSuccess)
       return DD_ERR_HIP;                                 // projections of this layer
     // (a deferred coordinate update of the previous layer is applied here: xcur's ligand rows are written by this launch)
     DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, f.LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev,
                                                   q1_in_gemm ? nullptr : w.q1bl, w.Rk, w.Rv, st, xup_prev, w.dxe, w.dxb,
                                                   xup_prev ? xcur : nullptr));
     xup_prev = nullptr;
+    // ---- block boundary: the new block's kNN graph + edge weights from x as the previous block left it.  xcur is complete here
+    //      by construction: the previous layer's coordinate launch was flushed and joined above, and its update is applied by
+    //      the assemble launch in front of this one (or was, by a launch of its own, on this stream or behind that join).  The
+    //      readers of the old graph (previous node launch, previous coordinate launch) are ordered before this launch the same
+    //      way; the next ones (this step's node launch, its coordinate launch behind a fork recorded after it) follow it.
+    if (l > 0 && l % LB == 0) DD_TRYP(DD_PROF_MISC, f.launch_block(xcur, st));
     if (!q1_in_gemm) DD_TRYP(DD_PROF_GEMM, launch_b2(l, st));
     if (head_join) {                                     // kNN graph + edge weights: first needed by the node attention
       if (hipStreamWaitEvent(st, dc.ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
       head_join = false;
     }
-    if (late_join && hipStreamWaitEvent(st, dc.ev_join[l], 0) != hipSuccess) return DD_ERR_HIP;   // this layer's query GEMMs
+    if (late_join && hipStreamWaitEvent(st, dc.ev_join[ev(l)], 0) != hipSuccess) return DD_ERR_HIP;   // this layer's query GEMMs
     // ---- node_layer_with_edge + node_layer_with_bond + bond_layer: one launch
     {
       AttnArgs ne = f.attn_ne(l, xcur, l0_here), nb = f.attn_nb(l, xcur);
@@ -842,7 +878,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       }
       DD_TRYP(DD_PROF_ATTN_BL, launch_attn2_node(ne, nb, f.attn_bl(l, xcur), st));
     }
-    if (ahead_split && !last && hipEventRecord(dc.ev_qa_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // h_bond final
+    if (ahead_split && !last && hipEventRecord(dc.ev_qa_fork[ev(l + 1)], st) != hipSuccess) return DD_ERR_HIP;   // h_bond final
     // ---- h += lin_node(A + A_nb on ligand rows)
     // One-fork schedule: the new h goes to the ping-pong partner (h_new = h_old + ...), because the side stream forms the same
     // rows from h_old at the same time (side_lin job below: identical arithmetic, its own output buffer) -- the main stream's
@@ -852,7 +888,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     GemmArgs lin_dup;
     if (out_fc) {
       // the jobs that ride with the lin_node GEMM (PB2, next layer's PB) ride with the projections behind this launch instead
-      NodeOutArgs na{w.A, w.Anb, hcur, hcur, no->layer[l], B, NP, NL};
+      NodeOutArgs na{w.A, w.Anb, hcur, hcur, no->layer[l % LB], B, NP, NL};
       DD_TRYP(DD_PROF_GEMM, launch_node_out_fc(na, st));
     } else if (!lin_in_node) {
       GemmArgs g = f.lin(l, hcur, w.Anb);
@@ -877,7 +913,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
         DD_TRYP(DD_PROF_GEMM, launch_gemm128(g, st));
       }
     }
-    if (ahead && !side_lin && !proj_main && !last && hipEventRecord(dc.ev_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // h, h_bond final
+    if (ahead && !side_lin && !proj_main && !last && hipEventRecord(dc.ev_fork[ev(l + 1)], st) != hipSuccess) return DD_ERR_HIP;   // h, h_bond final
     // ---- projections of the new h / h_bond: one launch -- {P2, PL2}, and the coordinate sub-layer's bond projections where they
     //      did not ride with the lin_node GEMM.  In the LAST layer the heads' first Linear (decompdiff.py:194-211: bond head on the
     //      final h_bond, v head on the ligand rows of the final h) rides along: it needs nothing the coordinate sub-layers produce,
@@ -902,7 +938,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     bool p2_in_pos = g_p2_in_pos && g_lin_with_pb2 && g_q_in_pos && !g_xup_in_pos && g_pos_waves == 4 && NL <= 65 && l < 64 &&
                      !(overlap && !ahead) && !out_fc && !lin_in_node;
     if (!p2_in_pos) DD_TRYP(DD_PROF_GEMM, p2.launch(st));
-    if (proj_main && !last && hipEventRecord(dc.ev_fork[l + 1], st) != hipSuccess) return DD_ERR_HIP;   // P, PL of the next layer
+    if (proj_main && !last && hipEventRecord(dc.ev_fork[ev(l + 1)], st) != hipSuccess) return DD_ERR_HIP;   // P, PL of the next layer
     const bool q_in_pos = g_q_in_pos;           // second layer of the coordinate query MLPs inside attn_pos
     if (!q_in_pos) {
       GemmList j;
@@ -920,7 +956,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       if (q_in_pos) f.set_q_in_pos(l, pe, pb);
       if (overlap && !ahead) {
         // fork: the coordinate sub-layers run on the side stream and are joined before the next consumer of x
-        if (hipEventRecord(dc.ev_fork[l], st) != hipSuccess) return DD_ERR_HIP;
+        if (hipEventRecord(dc.ev_fork[ev(l)], st) != hipSuccess) return DD_ERR_HIP;
         dpos.armed = true; dpos.pe = pe; dpos.pb = pb; dpos.xcur = xcur; dpos.xnext = xnext; dpos.layer = l; dpos.xup = xup_in_pos || xup_in_asm;
         if (!g_defer_pos) DD_TRY(flush_pos());
       } else {
@@ -941,18 +977,18 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     }
     if (ahead && !last) {                                // (recorded after the main-stream nodes on purpose)
       if (ahead_split) {
-        if (hipStreamWaitEvent(dc.side, dc.ev_qa_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;
+        if (hipStreamWaitEvent(dc.side, dc.ev_qa_fork[ev(l + 1)], 0) != hipSuccess) return DD_ERR_HIP;
         DD_TRY(launch_batch1_part(l + 1, 0, dc.side, nullptr, side_lin ? &lin_dup : nullptr));
-        if (!side_lin && !lin_in_node && hipStreamWaitEvent(dc.side, dc.ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;   // (lin_in_node: h is final with h_bond)
+        if (!side_lin && !lin_in_node && hipStreamWaitEvent(dc.side, dc.ev_fork[ev(l + 1)], 0) != hipSuccess) return DD_ERR_HIP;   // (lin_in_node: h is final with h_bond)
         if (!proj_main) DD_TRY(launch_batch1_part(l + 1, 1, dc.side, side_lin ? w.hs : hcur, nullptr));
-        if (two_joins && hipEventRecord(dc.ev_qb_fork[l + 1], dc.side) != hipSuccess) return DD_ERR_HIP;
-        if (proj_main && hipStreamWaitEvent(dc.side, dc.ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;   // the main stream's P, PL
+        if (two_joins && hipEventRecord(dc.ev_qb_fork[ev(l + 1)], dc.side) != hipSuccess) return DD_ERR_HIP;
+        if (proj_main && hipStreamWaitEvent(dc.side, dc.ev_fork[ev(l + 1)], 0) != hipSuccess) return DD_ERR_HIP;   // the main stream's P, PL
         if (ahead_b2) DD_TRY(launch_b2(l + 1, dc.side));
       } else {
-        if (hipStreamWaitEvent(dc.side, dc.ev_fork[l + 1], 0) != hipSuccess) return DD_ERR_HIP;
+        if (hipStreamWaitEvent(dc.side, dc.ev_fork[ev(l + 1)], 0) != hipSuccess) return DD_ERR_HIP;
         DD_TRY(launch_batch1(l + 1, dc.side));
       }
-      if (hipEventRecord(dc.ev_join[l + 1], dc.side) != hipSuccess) return DD_ERR_HIP;
+      if (hipEventRecord(dc.ev_join[ev(l + 1)], dc.side) != hipSuccess) return DD_ERR_HIP;
     }
     float* t = xcur; xcur = xnext; xnext = t;
   }
@@ -961,6 +997,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   Fwd u = f;
   u.w.P2 = w.P; u.w.PL2 = w.PL; u.w.PB2 = w.PB; u.w.qlnb = u.w.ql2 = w.ql;
   for (int l = 0; l < L && !fused; ++l) {
+    if (l > 0 && l % LB == 0) DD_TRYP(DD_PROF_MISC, u.launch_block(xcur, st));   // block boundary (every launch is on this stream)
     // ---- projections of the old h / h_bond
     DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.n1(l, w.h), st));
     DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.l1(l, w.h), st));
@@ -1224,17 +1261,46 @@ extern "C" size_t dd_workspace_floats(int B, int NP, int NL, int K) {
   return dd::carve(nullptr, B, NP, NL, K).total;
 }
 
-extern "C" int dd_workspace_view(const dd_sampler* s, dd_ws_view* out) {
+// The descriptors and the block count of a dd_model_opts (NULL: one block, no descriptors).  `size` is the caller's
+// sizeof(dd_model_opts): fields beyond it are not read, so a caller built against a shorter struct keeps working.
+static int read_model_opts(const dd_model_opts* o, dd::ModelOpts* mo) {
+  *mo = dd::ModelOpts();
+  if (o == nullptr) return DD_OK;
+  const size_t size = o->size > 0 ? (size_t)o->size : 0;
+  auto has = [&](size_t off, size_t n) { return size >= off + n; };
+  if (!has(0, sizeof(int32_t))) return DD_ERR_BAD_ARG;
+  if (has(offsetof(dd_model_opts, bond_head), sizeof(o->bond_head))) mo->bh = o->bond_head;
+  if (has(offsetof(dd_model_opts, node_out), sizeof(o->node_out))) mo->no = o->node_out;
+  if (has(offsetof(dd_model_opts, num_blocks), sizeof(o->num_blocks))) mo->num_blocks = o->num_blocks;
+  return mo->num_blocks >= 1 ? DD_OK : DD_ERR_BAD_ARG;
+}
+// ... checked against the sampler (what every entry point that runs the network asks first)
+static int check_model(const dd_sampler* s, const dd::ModelOpts& mo) {
+  if (dd::check_bond_head(mo.bh) != DD_OK || dd::check_node_out(mo.no, s) != DD_OK) return DD_ERR_BAD_ARG;
+  return dd::check_blocks(s, mo.num_blocks);
+}
+static dd_model_opts opts_of(const dd_bond_head* bh, const dd_node_out* no) {
+  dd_model_opts o;
+  o.size = (int32_t)sizeof(dd_model_opts); o.bond_head = bh; o.node_out = no; o.num_blocks = 1;
+  return o;
+}
+
+extern "C" int dd_workspace_view(const dd_sampler* s, dd_ws_view* out) { return dd_workspace_view_opts(s, nullptr, out); }
+
+extern "C" int dd_workspace_view_opts(const dd_sampler* s, const dd_model_opts* opts, dd_ws_view* out) {
   if (!s || !out || !s->workspace) return DD_ERR_BAD_ARG;
+  dd::ModelOpts mo;
+  if (read_model_opts(opts, &mo) != DD_OK) return DD_ERR_BAD_ARG;
+  const int steps = mo.num_blocks * s->num_layers;       // x and Anb ping-pong by the step
   dd::Workspace w = dd::carve(s->workspace, s->B, s->NP, s->NL, s->K);
-  out->x = (s->num_layers & 1) ? w.xb : w.xa;
+  out->x = (steps & 1) ? w.xb : w.xa;
   out->h = w.h; out->hb = w.hb; out->ew = w.ew; out->A = w.A; out->nbr = w.nbr;
   out->Anb = (dd::g_fuse && s->NL <= dd::g_fused_max_nl) ? w.Anb : nullptr;
   out->lin_in_node = 0;
-  if (dd::uses_lin_in_node(s->B, s->NL, false, out->Anb != nullptr)) {
+  if (dd::uses_lin_in_node(s->B, s->NL, mo.no != nullptr, out->Anb != nullptr)) {
     // lin_node inside the node launch: `h` lacks the last layer's W_lin . A_nb on the ligand rows -- it is in `Anb`; `A` is not formed
     out->lin_in_node = 1;
-    out->Anb = ((s->num_layers - 1) & 1) ? w.A : w.Anb;
+    out->Anb = ((steps - 1) & 1) ? w.A : w.Anb;
     out->A = nullptr;
   }
   return DD_OK;
@@ -1245,10 +1311,18 @@ extern "C" int dd_forward(const dd_sampler* s, void* stream) { return dd_forward
 extern "C" int dd_forward_ex(const dd_sampler* s, const dd_bond_head* bh, void* stream) { return dd_forward_ex2(s, bh, nullptr, stream); }
 
 extern "C" int dd_forward_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, void* stream) {
+  const dd_model_opts o = opts_of(bh, no);
+  return dd_forward_opts(s, &o, stream);
+}
+
+extern "C" int dd_forward_opts(const dd_sampler* s, const dd_model_opts* opts, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = dd::check_bond_head(bh);
+  dd::ModelOpts mo;
+  int rc = read_model_opts(opts, &mo);
   if (rc != DD_OK) return rc;
-  rc = dd::forward_impl(s, st, nullptr, bh, no);
+  rc = dd::check_bond_head(mo.bh);
+  if (rc != DD_OK) return rc;
+  rc = dd::forward_impl(s, st, nullptr, mo);
   if (rc != DD_OK) return rc;
   if (!s->pred_pos || !s->pred_v || !s->pred_bond) return DD_ERR_BAD_ARG;
   const dd::Fwd f(s);
@@ -1335,7 +1409,9 @@ static void node_split_cache_append(const std::string& path, int B, int NP, int 
   if (!ok || rename(t.c_str(), path.c_str()) != 0) (void)unlink(t.c_str());
 }
 
-static int autotune_node_split(const dd_sampler* s, hipStream_t st) {
+static int autotune_node_split(const dd_sampler* s, int num_blocks, hipStream_t st) {
+  dd::ModelOpts mo;                                      // (the timed passes run the caller's block count, without descriptors as before)
+  mo.num_blocks = num_blocks;
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;
@@ -1364,7 +1440,7 @@ static int autotune_node_split(const dd_sampler* s, hipStream_t st) {
     best = 1e30f;
     for (int rep = 0; rep < 3 && rc == DD_OK; ++rep) {
       if (hipEventRecord(e0, st) != hipSuccess) { rc = DD_ERR_HIP; break; }
-      rc = dd::forward_impl(s, st);
+      rc = dd::forward_impl(s, st, nullptr, mo);
       if (rc != DD_OK) break;
       float ms = 0.f;
       if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
@@ -1444,10 +1520,10 @@ static bool check_step_sampler(const dd_sampler* s) {
   return s && s->step_counter && s->tab_pos && s->tab_v && s->tab_b && s->atom_std && s->offset && s->pred_pos;
 }
 
-static int one_step(const dd_sampler* s, hipStream_t st, const dd_bond_head* bh = nullptr, const dd_node_out* no = nullptr) {
+static int one_step(const dd_sampler* s, hipStream_t st, const dd::ModelOpts& mo = dd::ModelOpts()) {
   dd::StepFold fold;
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
-  int rc = dd::forward_impl(s, st, &fold, bh, no);
+  int rc = dd::forward_impl(s, st, &fold, mo);
   if (rc != DD_OK) return rc;
   return dd::heads_and_step(s, st, &fold);
 }
@@ -1468,11 +1544,17 @@ extern "C" int dd_sample_steps_ex(const dd_sampler* s, const dd_bond_head* bh, i
 }
 
 extern "C" int dd_sample_steps_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int n_steps, void* stream) {
-  if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
+  const dd_model_opts o = opts_of(bh, no);
+  return dd_sample_steps_opts(s, &o, n_steps, stream);
+}
+
+extern "C" int dd_sample_steps_opts(const dd_sampler* s, const dd_model_opts* opts, int n_steps, void* stream) {
+  dd::ModelOpts mo;
+  if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || n_steps < 0) return DD_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_steps; ++i) {
-    int rc = one_step(s, st, bh, no);
+    int rc = one_step(s, st, mo);
     if (rc != DD_OK) return rc;
   }
   return DD_OK;
@@ -1489,11 +1571,11 @@ extern "C" int dd_sample_steps_graph_ex(const dd_sampler* s, const dd_bond_head*
 // `steps` reverse steps of `s` captured from `st` into a graph and instantiated.  Measures the node split of the shape first
 // (eager passes), then holds the capture mutex while the stream captures: the side stream / events of the device are shared.
 // On any failure nothing is left behind: what was made is destroyed, *graph / *exec are NULL and the sticky HIP error is cleared.
-static int capture_steps(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int steps, hipStream_t st, hipGraph_t* graph,
+static int capture_steps(const dd_sampler* s, const dd::ModelOpts& mo, int steps, hipStream_t st, hipGraph_t* graph,
                          hipGraphExec_t* exec) {
   *graph = nullptr;
   *exec = nullptr;
-  int rc = autotune_node_split(s, st);
+  int rc = autotune_node_split(s, mo.num_blocks, st);
   if (rc != DD_OK) return rc;
   {
     std::lock_guard<std::mutex> capture_lock(dd::g_capture_mutex);
@@ -1501,7 +1583,7 @@ static int capture_steps(const dd_sampler* s, const dd_bond_head* bh, const dd_n
       (void)hipGetLastError();                     // do not leave a sticky error behind for the caller
       return DD_ERR_HIP;
     }
-    for (int i = 0; i < steps && rc == DD_OK; ++i) rc = one_step(s, st, bh, no);
+    for (int i = 0; i < steps && rc == DD_OK; ++i) rc = one_step(s, st, mo);
     if (hipStreamEndCapture(st, graph) != hipSuccess || !*graph) rc = rc != DD_OK ? rc : DD_ERR_HIP;
   }
   if (rc == DD_OK && hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) rc = DD_ERR_HIP;
@@ -1515,7 +1597,13 @@ static int capture_steps(const dd_sampler* s, const dd_bond_head* bh, const dd_n
 }
 
 extern "C" int dd_sample_steps_graph_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int n_steps, void* stream) {
-  if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
+  const dd_model_opts o = opts_of(bh, no);
+  return dd_sample_steps_graph_opts(s, &o, n_steps, stream);
+}
+
+extern "C" int dd_sample_steps_graph_opts(const dd_sampler* s, const dd_model_opts* opts, int n_steps, void* stream) {
+  dd::ModelOpts mo;
+  if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || n_steps < 0) return DD_ERR_BAD_ARG;
   if (n_steps == 0) return DD_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -1524,7 +1612,7 @@ extern "C" int dd_sample_steps_graph_ex2(const dd_sampler* s, const dd_bond_head
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  rc = capture_steps(s, bh, no, 1, st, &graph, &exec);
+  rc = capture_steps(s, mo, 1, st, &graph, &exec);
   if (rc != DD_OK) return rc;
   for (int i = 0; i < n_steps; ++i) {
     if (hipGraphLaunch(exec, st) != hipSuccess) { rc = DD_ERR_HIP; break; }
@@ -1548,14 +1636,20 @@ extern "C" int dd_graph_create_ex(const dd_sampler* s, const dd_bond_head* bh, i
 
 extern "C" int dd_graph_create_ex2(const dd_sampler* s, const dd_bond_head* bh, const dd_node_out* no, int steps_per_graph, void* stream,
                                    void** graph_out) {
-  if (dd::check_bond_head(bh) != DD_OK || dd::check_node_out(no, s) != DD_OK) return DD_ERR_BAD_ARG;
+  const dd_model_opts o = opts_of(bh, no);
+  return dd_graph_create_opts(s, &o, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_graph_create_opts(const dd_sampler* s, const dd_model_opts* opts, int steps_per_graph, void* stream, void** graph_out) {
+  dd::ModelOpts mo;
+  if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || !graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   int rc = dd::check_shapes(s);
   if (rc != DD_OK) return rc;
   StepGraph* g = new StepGraph();
-  rc = capture_steps(s, bh, no, steps_per_graph, st, &g->graph, &g->exec);
+  rc = capture_steps(s, mo, steps_per_graph, st, &g->graph, &g->exec);
   if (rc != DD_OK) {
     delete g;
     return rc;
@@ -1593,10 +1687,22 @@ extern "C" int dd_sample_steps_graph_multi_ex(const dd_sampler* const* ss, const
 
 extern "C" int dd_sample_steps_graph_multi_ex2(const dd_sampler* const* ss, const dd_bond_head* const* bhs, const dd_node_out* const* nos,
                                                int n, int n_steps, void* const* streams) {
-  if (!ss || !streams || n <= 0 || n > 64 || n_steps < 0) return DD_ERR_BAD_ARG;
+  if (n <= 0 || n > 64) return DD_ERR_BAD_ARG;
+  dd_model_opts o[64];
+  const dd_model_opts* po[64];
   for (int i = 0; i < n; ++i) {
-    if (bhs && dd::check_bond_head(bhs[i]) != DD_OK) return DD_ERR_BAD_ARG;
-    if (nos && dd::check_node_out(nos[i], ss[i]) != DD_OK) return DD_ERR_BAD_ARG;
+    o[i] = opts_of(bhs ? bhs[i] : nullptr, nos ? nos[i] : nullptr);
+    po[i] = &o[i];
+  }
+  return dd_sample_steps_graph_multi_opts(ss, po, n, n_steps, streams);
+}
+
+extern "C" int dd_sample_steps_graph_multi_opts(const dd_sampler* const* ss, const dd_model_opts* const* opts, int n, int n_steps,
+                                                void* const* streams) {
+  if (!ss || !streams || n <= 0 || n > 64 || n_steps < 0) return DD_ERR_BAD_ARG;
+  dd::ModelOpts mos[64];
+  for (int i = 0; i < n; ++i) {
+    if (read_model_opts(opts ? opts[i] : nullptr, &mos[i]) != DD_OK || !ss[i] || check_model(ss[i], mos[i]) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
     const dd_sampler* s = ss[i];
     if (!check_step_sampler(s) || !streams[i]) return DD_ERR_BAD_ARG;
     for (int j = 0; j < i; ++j)
@@ -1611,7 +1717,7 @@ extern "C" int dd_sample_steps_graph_multi_ex2(const dd_sampler* const* ss, cons
   // the side streams / events used inside a step are shared, which is fine: they only shape each graph while it
   // is being captured, one chain at a time; the replays below do not touch them
   for (int i = 0; i < n && rc == DD_OK; ++i)
-    rc = capture_steps(ss[i], bhs ? bhs[i] : nullptr, nos ? nos[i] : nullptr, 1, (hipStream_t)streams[i], &graph[i], &exec[i]);
+    rc = capture_steps(ss[i], mos[i], 1, (hipStream_t)streams[i], &graph[i], &exec[i]);
   if (rc == DD_OK) {
     static const int threaded = [] { const char* e = getenv("DD_MULTI_THREADS"); return e ? atoi(e) : 1; }();
     if (threaded) {

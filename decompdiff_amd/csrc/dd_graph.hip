@@ -495,6 +495,46 @@ __global__ __launch_bounds__(256) void k_head_rows(const HeadArgs a) {
                     a.atom_f4);
 }
 
+// ------------------------------------------------------------------------------ block boundary: one launch
+// A refine net with num_blocks > 1 rebuilds the kNN graph and the edge weights from the CURRENT context coordinates before
+// every block but the first (uni_transformer_edge.py:402-427).  k_block_graph is k_head_graph on one [B, N, 3] block of the
+// workspace (w.xa / w.xb, whichever holds x behind the previous block's last layer) instead of the sampler's separate
+// protein / ligand buffers: the same knn_wave / ew_wave bodies with the same template arguments, so equal coordinates give
+// the same nbr rows and the same e_w bits as the head's launch.  Padding atoms are neither centres nor candidates.
+// All N atoms are candidates again.  The protein-protein distances do not change between blocks, but that is not exploited:
+// a centre's list is ONE selection over protein and ligand candidates in (distance, index) order, so a protein centre near
+// the ligand needs the moved ligand atoms ranked among its protein neighbours anyway (EXPERIMENTS.md).
+struct BlockGraphArgs {
+  int B, NP, NL, K;
+  const float* x;           // [B, NP + NL, 3]
+  int32_t* nbr;
+  float* ew;
+  const float *EW_W1T, *EW_b1, *EW_ln, *EW_w2, *EW_b2;
+  const int32_t *np_real, *nl_real;
+};
+template <int CAND, int KW>
+__global__ __launch_bounds__(256, 3) void k_block_graph(const BlockGraphArgs a) {
+  __shared__ unsigned long long sel[4][64];
+  __shared__ int32_t srt[4][KW];
+  __shared__ __attribute__((aligned(16))) float lw[512];
+  ew_stage(lw, a.EW_b1, a.EW_ln, a.EW_w2);
+  __syncthreads();                                       // (before any wave leaves)
+  const int N = a.NP + a.NL, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int centre = (int)blockIdx.x * 4 + w;
+  if (centre >= a.B * N) return;
+  const int b = centre / N, i = centre % N;
+  const bool masked = a.nl_real != nullptr;
+  const int npb = masked && a.np_real ? a.np_real[b] : a.NP, nlb = masked ? a.nl_real[b] : a.NL;
+  if (masked && !atom_is_real(i, a.NP, npb, nlb)) {        // a padding atom is no centre: its list is never read
+    if (lane < a.K) a.nbr[(long)centre * a.K + lane] = 0;
+    return;
+  }
+  const float* xb = a.x + (long)b * N * 3;
+  const PosView pv{xb, xb + 3 * (long)a.NP, a.NP};
+  knn_wave<CAND>(pv, i, N, a.K, a.nbr + (long)centre * a.K, masked, npb, nlb, sel[w], srt[w]);
+  ew_wave(pv, i, a.K, srt[w], a.EW_W1T, lw, a.EW_b2, a.ew + (long)centre * a.K);
+}
+
 // --------------------------------------------------------------------------- bond-layer assemble
 // For bond edge e = (src s -> dst t) of sample b (dst-major id e = t*(NL-1) + s'):
 //   Ek[e] = PB.k_hb[e] + Wg1k . G(d_e) + PL[s].k_hk + PL[t].k_hj        (b1 folded into PB bias)
@@ -716,6 +756,32 @@ int launch_head_all(const float* protein_h, const float* protein_pos, const floa
     if (K <= 32) launch_head_graph<32>(a, N, grid, block, st);
     else launch_head_graph<64>(a, N, grid, block, st);
   }
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+template <int KW>
+static void launch_block_graph_kw(const BlockGraphArgs& a, int N, dim3 grid, dim3 block, hipStream_t st) {
+  const int cand = (N + 63) / 64;                          // (the head launch's classes: same CAND for the same N)
+  if (cand <= 2) hipLaunchKernelGGL((k_block_graph<2, KW>), grid, block, 0, st, a);
+  else if (cand <= 4) hipLaunchKernelGGL((k_block_graph<4, KW>), grid, block, 0, st, a);
+  else if (cand <= 6) hipLaunchKernelGGL((k_block_graph<6, KW>), grid, block, 0, st, a);
+  else if (cand <= 11) hipLaunchKernelGGL((k_block_graph<11, KW>), grid, block, 0, st, a);
+  else if (cand <= 16) hipLaunchKernelGGL((k_block_graph<16, KW>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_block_graph<DD_N_MAX / 64, KW>), grid, block, 0, st, a);
+}
+int launch_block_graph(const float* x, int B, int NP, int NL, int K, int32_t* nbr, float* ew, const float* EW_W1T, const float* EW_b1,
+                       const float* EW_ln, const float* EW_w2, const float* EW_b2, const int32_t* np_real, const int32_t* nl_real,
+                       hipStream_t st) {
+  const int N = NP + NL;
+  if (!x || !nbr || !ew || B <= 0 || NP < 0 || NL <= 0) return DD_ERR_BAD_ARG;
+  if (K <= 0 || K > DD_KNN_MAX || K > N - 1 || N > DD_N_MAX) return DD_ERR_UNSUPPORTED_SHAPE;
+  BlockGraphArgs a;
+  a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = x; a.nbr = nbr; a.ew = ew;
+  a.EW_W1T = EW_W1T; a.EW_b1 = EW_b1; a.EW_ln = EW_ln; a.EW_w2 = EW_w2; a.EW_b2 = EW_b2;
+  a.np_real = np_real; a.nl_real = nl_real;
+  const dim3 grid((unsigned)((B * N + 3) / 4)), block(256);
+  if (K <= 32) launch_block_graph_kw<32>(a, N, grid, block, st);
+  else launch_block_graph_kw<64>(a, N, grid, block, st);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }

@@ -95,6 +95,10 @@ int launch_bl_assemble(const float* x, const float* PB, const float* PL, const f
 int launch_layer0_rows(const float* tables, const int32_t* lig_v, const float* lig_aux, const int32_t* bond, int B, int NP, int NL,
                        float* l0_P, float* PL, float* l0_qn, float* qlnb, float* PB, float* qb, hipStream_t st);
 // head of a forward: kNN graph + edge weights (parts & 1), embeddings / context + layer-0 rows (parts & 2; l0_tables may be NULL)
+// block boundary of a num_blocks > 1 refine net: kNN graph + edge weights from the workspace's current x (dd_graph.hip)
+int launch_block_graph(const float* x, int B, int NP, int NL, int K, int32_t* nbr, float* ew, const float* EW_W1T, const float* EW_b1,
+                       const float* EW_ln, const float* EW_w2, const float* EW_b2, const int32_t* np_real, const int32_t* nl_real,
+                       hipStream_t st);
 int launch_head_all(const float* protein_h, const float* protein_pos, const float* lig_pos, const int32_t* lig_v,
                     const float* lig_aux, const float* Wl, const float* bl, int B, int NP, int NL, int K, float* h, float* xa, float* xb,
                     const int32_t* bond, long bond_rows, const float* Wb, const float* bb, float* hb, int32_t* counters,

@@ -34,10 +34,11 @@ EXPORTED_SYMBOLS = [
     "dd_attn_aggregate_node_bwd", "dd_attn_aggregate_pos_bwd",
     "dd_attn_aggregate_node_masked", "dd_attn_aggregate_pos_masked", "dd_attn_aggregate_node_bwd_masked", "dd_attn_aggregate_pos_bwd_masked",
     "dd_csr_select_scratch_bytes", "dd_csr_select_count", "dd_csr_select_fill",
+    "dd_forward_opts", "dd_sample_steps_opts", "dd_sample_steps_graph_opts", "dd_graph_create_opts", "dd_sample_steps_graph_multi_opts",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
-    "dd_workspace_view", "dd_profile_step", "dd_debug_set_clock_buffer", "dd_debug_set_fusion", "dd_debug_set_option",
+    "dd_workspace_view", "dd_workspace_view_opts", "dd_profile_step", "dd_debug_set_clock_buffer", "dd_debug_set_fusion", "dd_debug_set_option",
     "dd_debug_node_split", "dd_debug_node_split_cache_path", "dd_debug_schedule", "dd_debug_philox", "dd_debug_options_epoch", "dd_queue_error",
 ]
 # exported by the measurement build only (-DDD_DEBUG_OPTIONS=1): the tile-queue schedule's sticky error word
@@ -82,6 +83,23 @@ class DDNodeOut(ctypes.Structure):
     """struct dd_node_out (include/decompdiff_hip.h): the node output MLPs of an x2h_out_fc model, handed to the *_ex2 entry
     points (NULL = a model without them); layer[l]: device block of packing.node_out_block."""
     _fields_ = [("num_layers", c_int32), ("reserved", c_int32), ("layer", c_void_p * 64)]
+
+
+class DDModelOpts(ctypes.Structure):
+    """struct dd_model_opts (include/decompdiff_hip.h): what a model is beyond its dd_sampler, handed to the *_opts entry points;
+    `size` = sizeof of this struct (see `model_opts`)."""
+    _fields_ = [("size", c_int32), ("bond_head", POINTER(DDBondHead)), ("node_out", POINTER(DDNodeOut)), ("num_blocks", c_int32)]
+
+
+def model_opts(bond_head=None, node_out=None, num_blocks=1) -> DDModelOpts:
+    """A filled dd_model_opts.  bond_head / node_out: the descriptor structs or None; the result keeps them alive."""
+    o = DDModelOpts()
+    o.size, o.num_blocks = ctypes.sizeof(DDModelOpts), int(num_blocks)
+    if bond_head is not None:
+        o.bond_head = ctypes.pointer(bond_head)
+    if node_out is not None:
+        o.node_out = ctypes.pointer(node_out)
+    return o
 
 
 L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128      # DD_L0_TABLE_FLOATS
@@ -167,10 +185,16 @@ def load():
         "dd_graph_create_ex2": [S, POINTER(DDBondHead), POINTER(DDNodeOut), c_int, c_void_p, POINTER(c_void_p)],
         "dd_sample_steps_graph_multi_ex2": [POINTER(S), POINTER(POINTER(DDBondHead)), POINTER(POINTER(DDNodeOut)), c_int, c_int,
                                             POINTER(c_void_p)],
+        "dd_forward_opts": [S, POINTER(DDModelOpts), c_void_p],
+        "dd_sample_steps_opts": [S, POINTER(DDModelOpts), c_int, c_void_p],
+        "dd_sample_steps_graph_opts": [S, POINTER(DDModelOpts), c_int, c_void_p],
+        "dd_graph_create_opts": [S, POINTER(DDModelOpts), c_int, c_void_p, POINTER(c_void_p)],
+        "dd_sample_steps_graph_multi_opts": [POINTER(S), POINTER(POINTER(DDModelOpts)), c_int, c_int, POINTER(c_void_p)],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],
         "dd_workspace_view": [S, POINTER(DDWsView)],
+        "dd_workspace_view_opts": [S, POINTER(DDModelOpts), POINTER(DDWsView)],
         "dd_debug_set_clock_buffer": [c_void_p, c_int],
         "dd_debug_set_fusion": [c_int],
         "dd_debug_set_option": [c_int, c_int],

@@ -178,7 +178,9 @@ class DecompScorePosNet3D(nn.Module):
         need(not getattr(config, "add_prior_node", False), "add_prior_node=False")
         need(config.time_emb_dim == 0, "time_emb_dim=0")
         need(config.node_indicator, "node_indicator=True")
-        need(config.num_blocks == 1, "num_blocks=1")
+        # (every step of a forward -- num_blocks * num_layers of them -- has a work counter of its own in the workspace: 64 slots)
+        need(int(config.num_blocks) >= 1 and 1 <= int(config.num_blocks) * int(config.num_layers) <= 64,
+             "1 <= num_blocks and num_blocks * num_layers <= 64")
         need(config.edge_feat_dim == 4 and config.num_r_gaussian == 20, "edge_feat_dim=4, num_r_gaussian=20")
         need(getattr(config, "h_node_in_bond_net", False), "h_node_in_bond_net=True")
         need(config.x2h_out_fc in (False, True) and config.norm and config.act_fn == "relu", "x2h_out_fc in {False, True}, norm, relu")
@@ -278,6 +280,7 @@ class DecompScorePosNet3D(nn.Module):
                                 tab_score=self.pos_score_coef.detach().float().contiguous().to(dev))
             self._packed["bond_head"] = self._bond_head_descriptor(sd, self._packed)
             self._packed["node_out"] = self._node_out_descriptor(sd, self._packed)
+            self._packed["model_opts"] = hip_lib.model_opts(self._packed["bond_head"], self._packed["node_out"], self.config.num_blocks)
             self._packed_key = key
         return self._packed
 
@@ -325,6 +328,11 @@ class DecompScorePosNet3D(nn.Module):
         pw = self._packed if pw is None else pw
         no = pw.get("node_out") if pw else None
         return None if no is None else ctypes.pointer(no)
+
+    def _model_opts(self, pw=None):
+        """ctypes pointer to this model's dd_model_opts (both descriptors and num_blocks), what every *_opts entry point takes."""
+        pw = self._packed if pw is None else pw
+        return ctypes.pointer(pw["model_opts"])
 
     def _layer0_tables(self, pw, dev):
         """dd_sampler.l0_tables for this weight set (built once): the first layer's projection / query rows of the 16
@@ -694,7 +702,7 @@ class DecompScorePosNet3D(nn.Module):
             hint = int(getattr(self, "traj_capacity_hint", 0) or 0)
             cap = max(32, 1 << (max(int(n_steps), hint) - 1).bit_length())   # trajectory capacity: 5 and 20 steps share buffers
         key = (str(dev), B, NP, NL, K, NF, cap if keep_traj else 0, bool(keep_traj), decomp_index is not None, arena.data_ptr(),
-               masks is not None, int(cache_slot), self.bond_net_type, self.x2h_out_fc)     # cache_slot: chains of ONE call that share a shape need separate buffers
+               masks is not None, int(cache_slot), self.bond_net_type, self.x2h_out_fc, int(self.config.num_blocks))     # cache_slot: chains of ONE call that share a shape need separate buffers
         cache = DecompScorePosNet3D._chain_cache
         ent = cache.pop(key, None) if cacheable else None
         if ent is None:
@@ -879,7 +887,7 @@ class DecompScorePosNet3D(nn.Module):
             pw = self._packed_weights()
             s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, torch.ones(B * NL, 3, device=dev),
                                             torch.zeros(B, 3, device=dev), None, None, 0, masks=pad["masks"])
-            hip_lib.check(hip_lib.load().dd_forward_ex2(ctypes.byref(s), self._bond_head(pw), self._node_out(pw), hip_lib.stream_ptr(dev)), "dd_forward")
+            hip_lib.check(hip_lib.load().dd_forward_opts(ctypes.byref(s), self._model_opts(pw), hip_lib.stream_ptr(dev)), "dd_forward")
             _check_queue(s, dev)
             preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3).index_select(0, d_l),
                      "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes).index_select(0, d_l)}
@@ -934,7 +942,7 @@ class DecompScorePosNet3D(nn.Module):
             dummy3 = torch.ones(B * NL, 3, device=dev)
             s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, dummy3,
                                             torch.zeros(B, 3, device=dev), None, None, 0)
-            hip_lib.check(hip_lib.load().dd_forward_ex2(ctypes.byref(s), self._bond_head(pw), self._node_out(pw), hip_lib.stream_ptr(dev)), "dd_forward")
+            hip_lib.check(hip_lib.load().dd_forward_opts(ctypes.byref(s), self._model_opts(pw), hip_lib.stream_ptr(dev)), "dd_forward")
             _check_queue(s, dev)
             preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3),
                      "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes)}
@@ -1125,8 +1133,8 @@ class DecompScorePosNet3D(nn.Module):
                         if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                             self._drop_cached_graphs()
                         graph = ctypes.c_void_p()
-                        hip_lib.check(lib.dd_graph_create_ex2(ctypes.byref(c["s"]), self._bond_head(), self._node_out(), 1, side.cuda_stream,
-                                                             ctypes.byref(graph)), "dd_graph_create")
+                        hip_lib.check(lib.dd_graph_create_opts(ctypes.byref(c["s"]), self._model_opts(), 1, side.cuda_stream,
+                                                              ctypes.byref(graph)), "dd_graph_create")
                         ent["graph"], ent["graph_sig"] = graph, gsig
                         DecompScorePosNet3D._graph_counter += 1
                         ent["graph_id"] = DecompScorePosNet3D._graph_counter
@@ -1140,8 +1148,8 @@ class DecompScorePosNet3D(nn.Module):
             else:
                 with torch.cuda.stream(side):
                     for c in chains:
-                        hip_lib.check(lib.dd_sample_steps_ex2(ctypes.byref(c["s"]), self._bond_head(), self._node_out(), int(num_steps),
-                                                             hip_lib.stream_ptr(dev)), "dd_sample_steps")
+                        hip_lib.check(lib.dd_sample_steps_opts(ctypes.byref(c["s"]), self._model_opts(), int(num_steps),
+                                                              hip_lib.stream_ptr(dev)), "dd_sample_steps")
             cur.wait_stream(side)
             return
         if len(chains) > 64:                            # dd_sample_steps_graph_multi takes at most 64 chains
@@ -1157,11 +1165,8 @@ class DecompScorePosNet3D(nn.Module):
         # (the C entry point captures one graph per chain and destroys them at the end: no other graph may be alive across
         #  that, see _parked_graphs -- cached entries re-capture theirs on next use)
         self._drop_cached_graphs()
-        bh = self._bond_head()
-        bhs = None if bh is None else (ctypes.POINTER(hip_lib.DDBondHead) * n)(*([bh] * n))
-        no = self._node_out()
-        nos = None if no is None else (ctypes.POINTER(hip_lib.DDNodeOut) * n)(*([no] * n))
-        hip_lib.check(lib.dd_sample_steps_graph_multi_ex2(ss, bhs, nos, n, int(num_steps), sts), "dd_sample_steps_graph_multi")
+        opts = (ctypes.POINTER(hip_lib.DDModelOpts) * n)(*([self._model_opts()] * n))
+        hip_lib.check(lib.dd_sample_steps_graph_multi_opts(ss, opts, n, int(num_steps), sts), "dd_sample_steps_graph_multi")
         for st in pool:
             cur.wait_stream(st)
 
@@ -1204,7 +1209,7 @@ class DecompScorePosNet3D(nn.Module):
             if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                 self._drop_cached_graphs()                 # (all live graphs, newest first; cached entries re-capture on next use)
             graph = ctypes.c_void_p()
-            hip_lib.check(lib.dd_graph_create_ex2(ctypes.byref(s), self._bond_head(), self._node_out(), spg, side.cuda_stream, ctypes.byref(graph)),
+            hip_lib.check(lib.dd_graph_create_opts(ctypes.byref(s), self._model_opts(), spg, side.cuda_stream, ctypes.byref(graph)),
                           "dd_graph_create")
             ent["graph"], ent["graph_sig"] = graph, gsig
             DecompScorePosNet3D._graph_counter += 1

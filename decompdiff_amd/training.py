@@ -528,19 +528,12 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
     p_dst, p_bdst, p_ji, trip = S["p_dst"], S["p_bdst"], S["p_ji"], S["trip"]
     h_bond = P.lin("ligand_bond_emb", F.one_hot(ligand_bond_type, model.num_bond_classes).float())
     Eb_tot = h_bond.shape[0]
-    # ---- graph of the step (uni_transformer_edge.py:404-427): kNN among all atoms of a sample, fixed for all layers
-    src = _knn_src(x.detach(), B, N, K, S["base"], NP=NP, pad=pad)
     real_b = real_t = None
     if pad is not None:                                    # members of the bond-graph / triplet segments that are real atoms
         nl_r = pad["nl_real"].long()
         real_b = S["bsrc_loc"] < nl_r.index_select(0, S["b_of_bond"])
         if trip is not None:
             real_t = S["tk_loc"] < nl_r.index_select(0, S["b_of_trip"])
-    p_src = seg_plan(src, B * N, check=False)              # rows gathered by source: backward = sorted segment sum, no atomics
-    etype = 2 * (~is_lig.index_select(0, src)).long() + S["dst_is_prot"]  # 0 ll, 1 l->p(dst p), 2 p->l, 3 pp
-    etype_1h = F.one_hot(etype, 4).float()
-    d0 = (x.index_select(0, dst) - x.index_select(0, src)).norm(dim=-1)
-    e_w = torch.sigmoid(P.mlp("refine_net.edge_pred_layer", _gauss(d0)))
     NLm1, Ebs = NL - 1, NL * (NL - 1)
     mask_l = is_lig.float().unsqueeze(-1)
     # DD_TRAIN_FUSED_ATTN=1 (opt-in): each attention site is ONE differentiable op on the op-level kernels
@@ -565,87 +558,99 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
                            plan).view(-1, NH, 3).mean(1)
 
     out_fc = bool(getattr(cfg, "x2h_out_fc", False))
-    for l in range(int(cfg.num_layers)):
-        p = f"refine_net.base_block.{l}"
-        rel = gather(x, p_dst) - x.index_select(0, src)
-        dist = rel.norm(dim=-1)
-        g = _gauss(dist)
-        ef_type = torch.cat([(etype_1h.unsqueeze(-1) * g.unsqueeze(1)).reshape(-1, 80), etype_1h], -1)      # [E, 84]
+    for blk in range(int(cfg.num_blocks)):
+        # ---- graph of a block (uni_transformer_edge.py:402-427): kNN among all atoms of a sample, edge types and edge weights -- built
+        #      from the current coordinates at the head of EVERY block (num_blocks > 1: the same num_layers layers run again on it, with
+        #      the same weights).  The neighbour indices are a discrete function of x (x.detach(), as in the reference); from the
+        #      second block on e_w and rel depend on the parameters through x, and autograd flows through them.  dd_knn / dd_knn_masked
+        #      need no host read, so a captured step still captures.
+        src = _knn_src(x.detach(), B, N, K, S["base"], NP=NP, pad=pad)
+        p_src = seg_plan(src, B * N, check=False)              # rows gathered by source: backward = sorted segment sum, no atomics
+        etype = 2 * (~is_lig.index_select(0, src)).long() + S["dst_is_prot"]  # 0 ll, 1 l->p(dst p), 2 p->l, 3 pp
+        etype_1h = F.one_hot(etype, 4).float()
+        d0 = (x.index_select(0, dst) - x.index_select(0, src)).norm(dim=-1)
+        e_w = torch.sigmoid(P.mlp("refine_net.edge_pred_layer", _gauss(d0)))
+        for l in range(int(cfg.num_layers)):
+            p = f"refine_net.base_block.{l}"
+            rel = gather(x, p_dst) - x.index_select(0, src)
+            dist = rel.norm(dim=-1)
+            g = _gauss(dist)
+            ef_type = torch.cat([(etype_1h.unsqueeze(-1) * g.unsqueeze(1)).reshape(-1, 80), etype_1h], -1)      # [E, 84]
 
-        def node_layer_edge(name, hh, v_width):
-            """kNN sub-layers: first Linear columns [0:84] edge feature, [84:212] h[dst], [212:340] h[src]."""
-            outs = []
-            for f_ in ("k", "v"):
-                nm = f"{p}.{name}.{'h' if name.startswith('node') else 'x'}{f_}_func"
-                W = P.w(nm + ".net.0")
-                pre = _edge_mlp_pre(P, nm, None, linear128(hh, W[:, 84:212]), linear128(hh, W[:, 212:340]), p_dst, p_src,
-                                    linear_feat(ef_type, W[:, 0:84]))
-                outs.append(P.mlp_tail(nm, pre))
-            return outs
+            def node_layer_edge(name, hh, v_width):
+                """kNN sub-layers: first Linear columns [0:84] edge feature, [84:212] h[dst], [212:340] h[src]."""
+                outs = []
+                for f_ in ("k", "v"):
+                    nm = f"{p}.{name}.{'h' if name.startswith('node') else 'x'}{f_}_func"
+                    W = P.w(nm + ".net.0")
+                    pre = _edge_mlp_pre(P, nm, None, linear128(hh, W[:, 84:212]), linear128(hh, W[:, 212:340]), p_dst, p_src,
+                                        linear_feat(ef_type, W[:, 0:84]))
+                    outs.append(P.mlp_tail(nm, pre))
+                return outs
 
-        def node_layer_bond(name, hh, hb):
-            """bond sub-layers: columns [0:128] h_bond[e], [128:256] h[dst], [256:384] h[src]."""
-            outs = []
-            for f_ in ("k", "v"):
-                nm = f"{p}.{name}.{'h' if name.startswith('node') else 'x'}{f_}_func"
-                W = P.w(nm + ".net.0")
-                pre = _edge_mlp_pre(P, nm, None, linear128(hh, W[:, 128:256]), linear128(hh, W[:, 256:384]), p_bdst, S["p_bsrc"],
-                                    linear128(hb, W[:, 0:128]))
-                outs.append(P.mlp_tail(nm, pre))
-            return outs
+            def node_layer_bond(name, hh, hb):
+                """bond sub-layers: columns [0:128] h_bond[e], [128:256] h[dst], [256:384] h[src]."""
+                outs = []
+                for f_ in ("k", "v"):
+                    nm = f"{p}.{name}.{'h' if name.startswith('node') else 'x'}{f_}_func"
+                    W = P.w(nm + ".net.0")
+                    pre = _edge_mlp_pre(P, nm, None, linear128(hh, W[:, 128:256]), linear128(hh, W[:, 256:384]), p_bdst, S["p_bsrc"],
+                                        linear128(hb, W[:, 0:128]))
+                    outs.append(P.mlp_tail(nm, pre))
+                return outs
 
-        # node_layer_with_edge (NodeUpdateLayer, :42-74)
-        k_e, v_e = node_layer_edge("node_layer_with_edge", h, H)
-        q_e = P.mlp(f"{p}.node_layer_with_edge.hq_func", h)
-        a_edge = attend(q_e, k_e, v_e, p_dst, B * N, e_w=e_w)
-        # node_layer_with_bond
-        k_b, v_b = node_layer_bond("node_layer_with_bond", h, h_bond)
-        q_b = P.mlp(f"{p}.node_layer_with_bond.hq_func", h)
-        a_bond = attend(q_b, k_b, v_b, p_bdst, B * N, real=real_b)
-        # bond_layer (BondUpdateLayer, :125-167): kv = [h_bond[kj](128), G(d_kj)(20), G(d_ji)(20), angle(13), h[k], h[j]]
-        if trip is not None:
-            nm_b = f"{p}.bond_layer"
-            d_bond = (gather(x, p_bdst) - x.index_select(0, bond_src)).norm(dim=-1)
-            gb = _gauss(d_bond)
-            x_i = x.index_select(0, trip["i"])
-            v_ji, v_ki = x.index_select(0, trip["j"]) - x_i, x.index_select(0, trip["k"]) - x_i
-            theta = torch.atan2(torch.cross(v_ji, v_ki, dim=-1).norm(dim=-1), (v_ji * v_ki).sum(-1))
-            code = _angle_code(theta)
-            kv = []
-            for f_ in ("hk_func", "hv_func"):
-                W = P.w(f"{nm_b}.{f_}.net.0")
-                # every triplet (k -> j -> i) term is a per-BOND row: h[k] rides with bond (k -> j) (its source atom), h[j] and the bias
-                # with bond (j -> i) -- two gathers of [Eb, 128] tables per MLP instead of four [E3, 128] ones, and no per-atom
-                # index_add_ of 812 rows per atom in the backward
-                per_kj = linear128(h_bond, W[:, 0:128]) + linear_feat(gb, W[:, 128:148]) + gather(linear128(h, W[:, 181:309]), S["p_bsrc"])
-                per_ji = linear_feat(gb, W[:, 148:168]) + P.b(f"{nm_b}.{f_}.net.0") + gather(linear128(h, W[:, 309:437]), S["p_bsrc"])
-                pre = gather(per_kj, S["p_tkj"]) + gather(per_ji, p_ji) + linear_feat(code, W[:, 168:181])
-                kv.append(P.mlp_tail(f"{nm_b}.{f_}", pre))
-            # hq depends on the (j -> i) bond only: evaluated per bond, gathered per triplet (exact)
-            q_bond = P.mlp(f"{nm_b}.hq_func", torch.cat([h_bond, gather(h, p_bdst)], -1))
-            d_hb = attend(q_bond, kv[0], kv[1], p_ji, Eb_tot, real=real_t)
-        else:
-            d_hb = torch.zeros_like(h_bond)
-        new_h_bond = h_bond + d_hb
-        if out_fc:
-            # x2h_out_fc: node_output = MLP(cat([aggregate, h])) at the end of both NodeUpdateLayers (:39-40, 70-71), the first
-            # Linear split over the two halves of the concatenation (a_bond is zero on protein rows, its MLP output is not)
-            def node_output(name, agg):
-                nm = f"{p}.{name}.node_output"
-                W = P.w(nm + ".net.0")
-                return P.mlp_tail(nm, linear128(agg, W[:, 0:H]) + linear128(h, W[:, H:2 * H]) + P.b(nm + ".net.0"))
-            a_edge, a_bond = node_output("node_layer_with_edge", a_edge), node_output("node_layer_with_bond", a_bond)
-        new_h = h + P.lin(f"{p}.lin_node", a_edge + a_bond)
-        # pos_layer_with_edge / pos_layer_with_bond (PosUpdateLayer, :188-210), with the NEW h / h_bond
-        k_pe, v_pe = node_layer_edge("pos_layer_with_edge", new_h, NH)
-        q_pe = P.mlp(f"{p}.pos_layer_with_edge.xq_func", new_h)
-        dx_e = attend_pos(q_pe, k_pe, v_pe, rel, p_dst, B * N, e_w=e_w)
-        k_pb, v_pb = node_layer_bond("pos_layer_with_bond", new_h, new_h_bond)
-        q_pb = P.mlp(f"{p}.pos_layer_with_bond.xq_func", new_h)
-        rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
-        dx_b = attend_pos(q_pb, k_pb, v_pb, rel_b, p_bdst, B * N, real=real_b)
-        x = x + (dx_e + dx_b) * mask_l
-        h, h_bond = new_h, new_h_bond
+            # node_layer_with_edge (NodeUpdateLayer, :42-74)
+            k_e, v_e = node_layer_edge("node_layer_with_edge", h, H)
+            q_e = P.mlp(f"{p}.node_layer_with_edge.hq_func", h)
+            a_edge = attend(q_e, k_e, v_e, p_dst, B * N, e_w=e_w)
+            # node_layer_with_bond
+            k_b, v_b = node_layer_bond("node_layer_with_bond", h, h_bond)
+            q_b = P.mlp(f"{p}.node_layer_with_bond.hq_func", h)
+            a_bond = attend(q_b, k_b, v_b, p_bdst, B * N, real=real_b)
+            # bond_layer (BondUpdateLayer, :125-167): kv = [h_bond[kj](128), G(d_kj)(20), G(d_ji)(20), angle(13), h[k], h[j]]
+            if trip is not None:
+                nm_b = f"{p}.bond_layer"
+                d_bond = (gather(x, p_bdst) - x.index_select(0, bond_src)).norm(dim=-1)
+                gb = _gauss(d_bond)
+                x_i = x.index_select(0, trip["i"])
+                v_ji, v_ki = x.index_select(0, trip["j"]) - x_i, x.index_select(0, trip["k"]) - x_i
+                theta = torch.atan2(torch.cross(v_ji, v_ki, dim=-1).norm(dim=-1), (v_ji * v_ki).sum(-1))
+                code = _angle_code(theta)
+                kv = []
+                for f_ in ("hk_func", "hv_func"):
+                    W = P.w(f"{nm_b}.{f_}.net.0")
+                    # every triplet (k -> j -> i) term is a per-BOND row: h[k] rides with bond (k -> j) (its source atom), h[j] and the bias
+                    # with bond (j -> i) -- two gathers of [Eb, 128] tables per MLP instead of four [E3, 128] ones, and no per-atom
+                    # index_add_ of 812 rows per atom in the backward
+                    per_kj = linear128(h_bond, W[:, 0:128]) + linear_feat(gb, W[:, 128:148]) + gather(linear128(h, W[:, 181:309]), S["p_bsrc"])
+                    per_ji = linear_feat(gb, W[:, 148:168]) + P.b(f"{nm_b}.{f_}.net.0") + gather(linear128(h, W[:, 309:437]), S["p_bsrc"])
+                    pre = gather(per_kj, S["p_tkj"]) + gather(per_ji, p_ji) + linear_feat(code, W[:, 168:181])
+                    kv.append(P.mlp_tail(f"{nm_b}.{f_}", pre))
+                # hq depends on the (j -> i) bond only: evaluated per bond, gathered per triplet (exact)
+                q_bond = P.mlp(f"{nm_b}.hq_func", torch.cat([h_bond, gather(h, p_bdst)], -1))
+                d_hb = attend(q_bond, kv[0], kv[1], p_ji, Eb_tot, real=real_t)
+            else:
+                d_hb = torch.zeros_like(h_bond)
+            new_h_bond = h_bond + d_hb
+            if out_fc:
+                # x2h_out_fc: node_output = MLP(cat([aggregate, h])) at the end of both NodeUpdateLayers (:39-40, 70-71), the first
+                # Linear split over the two halves of the concatenation (a_bond is zero on protein rows, its MLP output is not)
+                def node_output(name, agg):
+                    nm = f"{p}.{name}.node_output"
+                    W = P.w(nm + ".net.0")
+                    return P.mlp_tail(nm, linear128(agg, W[:, 0:H]) + linear128(h, W[:, H:2 * H]) + P.b(nm + ".net.0"))
+                a_edge, a_bond = node_output("node_layer_with_edge", a_edge), node_output("node_layer_with_bond", a_bond)
+            new_h = h + P.lin(f"{p}.lin_node", a_edge + a_bond)
+            # pos_layer_with_edge / pos_layer_with_bond (PosUpdateLayer, :188-210), with the NEW h / h_bond
+            k_pe, v_pe = node_layer_edge("pos_layer_with_edge", new_h, NH)
+            q_pe = P.mlp(f"{p}.pos_layer_with_edge.xq_func", new_h)
+            dx_e = attend_pos(q_pe, k_pe, v_pe, rel, p_dst, B * N, e_w=e_w)
+            k_pb, v_pb = node_layer_bond("pos_layer_with_bond", new_h, new_h_bond)
+            q_pb = P.mlp(f"{p}.pos_layer_with_bond.xq_func", new_h)
+            rel_b = gather(x, p_bdst) - x.index_select(0, bond_src)
+            dx_b = attend_pos(q_pb, k_pb, v_pb, rel_b, p_bdst, B * N, real=real_b)
+            x = x + (dx_e + dx_b) * mask_l
+            h, h_bond = new_h, new_h_bond
     softplus = lambda t: F.softplus(t) - math.log(2.0)                              # ShiftedSoftplus (common.py:66-72)
     final_h = h.index_select(0, lig_rows)
     if getattr(model, "bond_net_type", "lin") == "pre_att":

@@ -454,6 +454,33 @@ int dd_graph_create_ex2(const dd_sampler* s, const dd_bond_head* bh /*HOST*/, co
 int dd_sample_steps_graph_multi_ex2(const dd_sampler* const* s /*HOST [n]*/, const dd_bond_head* const* bh /*HOST [n]*/,
                                     const dd_node_out* const* no /*HOST [n]*/, int n, int n_steps, void* const* streams /*HOST [n]*/);
 
+/* Model options: everything a model is beyond its dd_sampler, in ONE struct that can grow -- the end of the _ex / _ex2 suffix
+ * chain.  `size` is the caller's sizeof(dd_model_opts): the library reads no field beyond it and takes the default for the
+ * rest (NULL descriptors, one block), so a program built against this version keeps running on a library that knows more
+ * fields.  opts == NULL: all defaults.
+ *   num_blocks: blocks of the refine net (uni_transformer_edge.py:402-437).  The network runs num_blocks * num_layers steps;
+ *   step l uses the weight slots of layer l % num_layers (the blocks share their weights), and in front of every block but
+ *   the first the kNN graph and the edge weights are rebuilt from the coordinates the previous block left (one launch; the
+ *   same neighbour order and e_w arithmetic as the first block's).  The layer-0 tables serve the very first step only.
+ *   num_blocks >= 1 and num_blocks * num_layers <= 64 (DD_ERR_BAD_ARG / DD_ERR_UNSUPPORTED_SHAPE otherwise); node_out keeps
+ *   describing ONE block (node_out->num_layers == dd_sampler.num_layers).  dd_workspace_floats sizes the workspace for any
+ *   block count.  Every entry point without a dd_model_opts means num_blocks = 1.  (New entry points, ABI unchanged.) */
+typedef struct dd_model_opts {
+  int32_t size;                  /* sizeof(dd_model_opts) of the caller */
+  const dd_bond_head* bond_head; /* HOST, may be NULL (the lin head) */
+  const dd_node_out* node_out;   /* HOST, may be NULL (no x2h_out_fc) */
+  int32_t num_blocks;            /* >= 1 */
+} dd_model_opts;
+/* The _ex2 entry points with the options struct (the _ex2 functions call these with num_blocks = 1).  opts of the multi
+ * variant: HOST array of n pointers (entries may be NULL), or NULL. */
+int dd_forward_opts(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, void* stream);
+int dd_sample_steps_opts(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, int n_steps, void* stream);
+int dd_sample_steps_graph_opts(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, int n_steps, void* stream);
+int dd_graph_create_opts(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, int steps_per_graph, void* stream,
+                         void** graph_out /*HOST*/);
+int dd_sample_steps_graph_multi_opts(const dd_sampler* const* s /*HOST [n]*/, const dd_model_opts* const* opts /*HOST [n]*/, int n,
+                                     int n_steps, void* const* streams /*HOST [n]*/);
+
 /* Drift guidance gradients at x_t (utils/guidance_funcs.py:24-78), analytic. grad [B,NL,3]. */
 int dd_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                     float* grad, int accumulate, void* stream);

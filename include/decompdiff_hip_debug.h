@@ -74,6 +74,9 @@ typedef struct dd_ws_view {
                             ligand rows, `Anb` holds exactly that pending term (add it to h[:, NP:]), `A` is NULL (never materialised) */
 } dd_ws_view;
 int dd_workspace_view(const dd_sampler* s, dd_ws_view* out);
+/* ... of a model with options (num_blocks > 1: x and Anb are where the LAST step left them -- they ping-pong by the step,
+ * num_blocks * num_layers of them; opts == NULL: dd_workspace_view). */
+int dd_workspace_view_opts(const dd_sampler* s, const dd_model_opts* opts, dd_ws_view* out);
 
 #ifdef __cplusplus
 }

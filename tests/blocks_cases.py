@@ -1,0 +1,447 @@
+"""GPU cases of refine nets with num_blocks > 1 (the kNN graph, edge types and edge weights rebuilt per block; shared weights):
+frozen coordinates bit for bit against the unrolled one-block model, forward / sampling against the oracle (and, where the
+oracle restates nothing -- pre_att head, node output MLPs, noise parameterisation -- against fixtures of the reference itself,
+tools/make_blocks_golden.py), training against fp32 autograd through the oracle, the C entry points.  Fixtures and their
+kNN-gap condition: tests/blocks_fixtures.py, vetted on the host by tests/test_blocks_host.py.  Run by tests/test_gpu_blocks.py in
+a process of their own; `pytest -m gpu tests/blocks_cases.py` runs them directly."""
+import ctypes
+import re
+
+import pytest
+import torch
+
+import blocks_fixtures as BF
+import golden_utils as GU
+from decompdiff_amd import DecompScorePosNet3D, harness, hip_lib, synth, training
+from oracle import model as OM
+from test_gpu_forward_ragged import PAD_LOGIT_TOL, PAD_POS_TOL, fwd, per_sample
+from test_gpu_parity import LOGIT_TOL, POS_TOL, _forward_hip, _sample_hip, dev, maxabs
+
+pytestmark = pytest.mark.gpu
+KEYS = BF.KEYS
+_MODELS = {}
+
+
+def _load(cfg, sd):
+    m = DecompScorePosNet3D(cfg, 29, 10, 8)
+    full = m.state_dict()
+    full.update(sd)
+    m.load_state_dict(full, strict=True)
+    return m.to(dev())
+
+
+def model(nb, L, **over):
+    key = (nb, L, tuple(sorted(over.items())))
+    if key not in _MODELS:
+        cfg = BF.config(nb, L, **over)
+        _MODELS[key] = _load(cfg, synth.synthetic_state_dict(cfg, 0))
+    return _MODELS[key]
+
+
+def _errs(got, want):
+    return {k: maxabs(got[k], want[k]) for k in KEYS}
+
+
+def _fmt(e):
+    return ", ".join(f"{k} {v:.3g}" for k, v in e.items())
+
+
+# ------------------------------------------------------------------------------------ frozen coordinates: bit for bit
+def _frozen_pair():
+    """(2 x 3 model, 1 x 6 model whose layers 3-5 are copies of 0-2), both with the second Linear of every xv MLP zeroed: no
+    coordinate ever moves, so the second block's graph is the first block's and the two networks are the same function."""
+    if "frozen" not in _MODELS:
+        cfg2, cfg1 = BF.config(2, 3), BF.config(1, 6)
+        sd2 = synth.synthetic_state_dict(cfg2, 0)
+        for k in sd2:
+            if re.search(r"pos_layer_with_(edge|bond)\.xv_func\.net\.3\.(weight|bias)$", k):
+                sd2[k] = torch.zeros_like(sd2[k])
+        sd1 = dict(sd2)
+        for k, v in sd2.items():
+            m = re.match(r"refine_net\.base_block\.(\d)\.(.*)", k)
+            if m:
+                sd1[f"refine_net.base_block.{int(m.group(1)) + 3}.{m.group(2)}"] = v.clone()
+        assert set(sd1) == set(synth.synthetic_state_dict(cfg1, 0))
+        _MODELS["frozen"] = (_load(cfg2, sd2), _load(cfg1, sd1))
+    return _MODELS["frozen"]
+
+
+@pytest.mark.parametrize("layout", ["dense", "padded"])
+def test_frozen_coordinates_two_blocks_equal_the_unrolled_one_block_model(layout):
+    two, one = _frozen_pair()
+    if layout == "dense":
+        b = BF.forward_batch("2x3")
+    else:
+        b = synth.concat_sampling_batches(BF.ragged_parts(BF.FROZEN_RAGGED))
+    a, c = fwd(two, b), fwd(one, b)
+    torch.cuda.synchronize()
+    x0 = torch.cat([b["init_ligand_pos"]]).to(dev())
+    assert torch.equal(a["pred_ligand_pos"], x0)            # frozen indeed
+    for k in KEYS:
+        assert torch.equal(a[k], c[k]), (layout, k, maxabs(a[k], c[k]))
+    assert float(a["pred_ligand_v"].abs().max()) > 0 and float(a["pred_bond"].abs().max()) > 0
+
+
+# ------------------------------------------------------------------------------------ forward
+@pytest.mark.parametrize("name", [n for n in BF.FORWARD if not n.endswith(("preatt", "outfc"))])
+def test_forward_against_the_oracle(name):
+    f = BF.FORWARD[name]
+    cfg, sd = GU.weights(0, BF.config(f["nb"], f["L"], **f["over"]))
+    b = BF.forward_batch(name)
+    want = BF.oracle_forward(sd, cfg, b)
+    got = _forward_hip(model(f["nb"], f["L"], **f["over"]), b)
+    torch.cuda.synchronize()
+    e = _errs(got, want)
+    line = f"blocks forward {name} ({f['nb']} x {f['L']} layers, NL={b['init_ligand_pos'].shape[0] // f['B']}, B={f['B']}) vs oracle: {_fmt(e)}"
+    print(line)
+    assert e["pred_ligand_pos"] < POS_TOL and e["pred_ligand_v"] < LOGIT_TOL and e["pred_bond"] < LOGIT_TOL, line
+    # the second block does something: the one-block model of the same layers computes other coordinates
+    one = _forward_hip(model(1, f["L"], **f["over"]), b)
+    assert maxabs(one["pred_ligand_pos"], want["pred_ligand_pos"]) > 100 * POS_TOL
+
+
+@pytest.mark.parametrize("name", ["2x3_preatt", "2x3_outfc"])
+def test_forward_against_the_reference_fixture(name):
+    f = BF.FORWARD[name]
+    g = GU.load("blocks_ref")
+    b = GU.batch_from_npz(g, prefix=name + "_in_")
+    got = _forward_hip(model(f["nb"], f["L"], **f["over"]), b)
+    torch.cuda.synchronize()
+    e = {k: maxabs(got[k], g[f"{name}_out_{k}"]) for k in KEYS}
+    line = f"blocks forward {name} vs reference: {_fmt(e)}"
+    print(line)
+    assert e["pred_ligand_pos"] < POS_TOL and e["pred_ligand_v"] < LOGIT_TOL and e["pred_bond"] < LOGIT_TOL, line
+
+
+def test_padded_forward_of_three_different_samples_equals_per_sample_calls():
+    parts = BF.ragged_parts(BF.RAGGED, BF.RAGGED_SEED)
+    assert len({p["batch_ligand"].numel() for p in parts}) == 3
+    m = model(2, 3)
+    whole, each = fwd(m, synth.concat_sampling_batches(parts)), per_sample(m, parts)
+    torch.cuda.synchronize()
+    e = _errs(whole, each)
+    line = f"blocks padded forward (2 x 3, three sizes) vs per-sample calls: {_fmt(e)}"
+    print(line)
+    assert e["pred_ligand_pos"] < PAD_POS_TOL and e["pred_ligand_v"] < PAD_LOGIT_TOL and e["pred_bond"] < PAD_LOGIT_TOL, line
+    cfg, sd = GU.weights(0, BF.config(2, 3))
+    want = [BF.oracle_forward(sd, cfg, p) for p in parts]
+    eo = _errs(each, {k: torch.cat([w[k] for w in want], 0) for k in KEYS})
+    print(f"blocks per-sample forward (2 x 3, three sizes) vs oracle: {_fmt(eo)}")
+    assert eo["pred_ligand_pos"] < POS_TOL and eo["pred_ligand_v"] < LOGIT_TOL and eo["pred_bond"] < LOGIT_TOL
+
+
+def test_forward_with_a_sample_below_knn_plus_one_atoms_runs_size_groups():
+    parts = BF.ragged_parts(BF.TINY, BF.TINY_SEED)
+    assert min(p["batch_protein"].numel() + p["batch_ligand"].numel() for p in parts) < 33
+    m = model(2, 3)
+    whole, each = fwd(m, synth.concat_sampling_batches(parts)), per_sample(m, parts)
+    assert all(torch.equal(whole[k], each[k]) for k in KEYS)
+    cfg, sd = GU.weights(0, BF.config(2, 3))
+    want = [BF.oracle_forward(sd, cfg, p) for p in parts]
+    e = _errs(whole, {k: torch.cat([w[k] for w in want], 0) for k in KEYS})
+    line = f"blocks forward with a 26-atom sample (size groups) vs oracle: {_fmt(e)}"
+    print(line)
+    assert e["pred_ligand_pos"] < POS_TOL and e["pred_ligand_v"] < LOGIT_TOL and e["pred_bond"] < LOGIT_TOL, line
+
+
+# ------------------------------------------------------------------------------------ sampling
+def _chain_inputs():
+    if "chain" not in _MODELS:
+        _MODELS["chain"] = BF.sampling_inputs()
+    return _MODELS["chain"]
+
+
+def _cut(noise, a, b=None):
+    return {k: v[a:b] for k, v in noise.items()}
+
+
+@pytest.mark.parametrize("t_start", [999, 500, 0])
+def test_single_steps_against_the_oracle(t_start):
+    s = BF.SAMPLING
+    cfg, sd = GU.weights(0, BF.config(s["nb"], s["L"]))
+    b, noise = _chain_inputs()
+    want = BF.oracle_chain(sd, cfg, b, noise, 1, None, t_start=t_start)
+    r = _sample_hip(model(s["nb"], s["L"]), b, 1, None, _cut(noise, 0, 1), t_start)
+    e_pos = maxabs(r["pos"], want["pos"])
+    e_lp = max(maxabs(r["vt_traj"][0], want["vt_traj"][0]), maxabs(r["bt_traj"][0], want["bt_traj"][0]),
+               maxabs(r["v0_traj"][0], want["v0_traj"][0]))
+    line = f"blocks step t={t_start} (2 x 3) vs oracle: pos {e_pos:.3g} log-probs {e_lp:.3g}"
+    print(line)
+    assert e_pos < POS_TOL and e_lp < LOGIT_TOL, line
+    assert torch.equal(r["v"].cpu(), want["v"]) and torch.equal(r["bond"].cpu(), want["bond"])
+
+
+def test_chain_of_10_steps_with_drift_against_the_oracle():
+    s = BF.SAMPLING
+    cfg, sd = GU.weights(0, BF.config(s["nb"], s["L"]))
+    b, noise = _chain_inputs()
+    want = BF.oracle_chain(sd, cfg, b, noise, 10, GU.DRIFT)
+    r = _sample_hip(model(s["nb"], s["L"]), b, 10, GU.DRIFT, noise)
+    e_traj = max(maxabs(p, q) for p, q in zip(r["pos_traj"], want["pos_traj"]))
+    e_lp = max(maxabs(p, q) for k in ("vt_traj", "bt_traj", "v0_traj") for p, q in zip(r[k], want[k]))
+    line = f"blocks chain of 10 steps with armsca_prox + clash (2 x 3) vs oracle: pos {e_traj:.3g} log-probs {e_lp:.3g}"
+    print(line)
+    assert e_traj < POS_TOL and e_lp < LOGIT_TOL, line
+    assert torch.equal(r["v"].cpu(), want["v"]) and torch.equal(r["bond"].cpu(), want["bond"])
+
+
+def test_noise_parameterisation_step_against_the_reference_fixture():
+    g = GU.load("blocks_ref")
+    p = "noise_step_"
+    b = GU.batch_from_npz(g, prefix=p + "in_")
+    noise = {k: torch.from_numpy(g[p + "noise_" + k]) for k in ("u_v", "u_b", "eps")}
+    s = BF.SAMPLING
+    r = _sample_hip(model(s["nb"], s["L"], model_mean_type="noise"), b, 1, None, noise, int(g[p + "t_start"]))
+    e_pos = maxabs(r["pos"], g[p + "pos"])
+    e_lp = max(maxabs(r["vt_traj"][0], g[p + "log_v_prob"]), maxabs(r["bt_traj"][0], g[p + "log_b_prob"]),
+               maxabs(r["v0_traj"][0], g[p + "log_v_recon"]))
+    line = f"blocks noise-parameterisation step t={int(g[p + 't_start'])} (2 x 3) vs reference: pos {e_pos:.3g} log-probs {e_lp:.3g}"
+    print(line)
+    assert e_pos < POS_TOL and e_lp < LOGIT_TOL, line
+    assert torch.equal(r["v"].cpu(), torch.from_numpy(g[p + "v"])) and torch.equal(r["bond"].cpu(), torch.from_numpy(g[p + "bond"]))
+
+
+def test_graph_replay_equals_eager_launches():
+    b, noise = _chain_inputs()
+    m = model(2, 3)
+    n5 = _cut(noise, 0, 5)
+    eager = _sample_hip(m, b, 5, GU.DRIFT, n5, use_graph=False)
+    graph = _sample_hip(m, b, 5, GU.DRIFT, n5, use_graph=True)
+    for k in ("pos", "v", "bond"):
+        assert torch.equal(eager[k], graph[k]), k
+    for k in ("pos_traj", "vt_traj", "bt_traj"):
+        assert torch.equal(torch.stack(eager[k]), torch.stack(graph[k])), k
+
+
+def test_start_step_resume_equals_the_unsplit_chain():
+    """Philox noise, frame fixed (center_pos_mode='none', as tests/noise_param_cases.py resumes its chains): 6 steps in one call ==
+    2 steps, then 4 with start_step = 2, bit for bit.  (Both sides run the same kernels on the same bits, so no neighbour tie can
+    separate them: this chain needs no kNN-gap condition.)"""
+    b, _ = _chain_inputs()
+    bd = {k: (v.to(dev()) if torch.is_tensor(v) else v) for k, v in b.items()}
+    m = model(2, 3)
+    kw = dict(center_pos_mode="none", energy_drift_opt=GU.DRIFT, seed=77)
+    whole = m.sample_diffusion(num_steps=6, **bd, **kw)
+    head = m.sample_diffusion(num_steps=2, **bd, **kw)
+    bb = dict(bd)
+    bb["init_ligand_pos"], bb["init_ligand_v"], bb["init_ligand_fc_bond_type"] = head["pos"], head["v"], head["bond"]
+    tail = m.sample_diffusion(num_steps=4, start_step=2, **bb, **kw)
+    for k in ("pos", "v", "bond"):
+        assert torch.equal(tail[k], whole[k]), k
+    assert all(torch.equal(x, y) for x, y in zip(list(head["pos_traj"]) + list(tail["pos_traj"]), whole["pos_traj"]))
+    assert bool(torch.isfinite(whole["pos"]).all()) and not torch.equal(whole["pos"], head["pos"])
+
+
+def test_padded_chain_equals_size_groups(monkeypatch):
+    """Three samples of different sizes, 3 steps on injected noise: one padded launch sequence == one dense chain per size, bit for
+    bit in a fixed frame (center_pos_mode='none': the two modes form the pocket centroid in different orders otherwise), and
+    the padded chain in the usual frame against the oracle's per-sample chains."""
+    parts, noises = BF.ragged_chain_inputs(3)
+    b = synth.concat_sampling_batches(parts)
+    bd = {k: (v.to(dev()) if torch.is_tensor(v) else v) for k, v in b.items()}
+    noise = {k: torch.cat([n[k] for n in noises], 1) for k in ("u_v", "u_b", "eps")}
+    m = model(2, 3)
+    outs = {}
+    for mode in ("padded", "groups"):
+        monkeypatch.setenv("DD_RAGGED_MODE", mode)
+        outs[mode] = m.sample_diffusion(num_steps=3, center_pos_mode="none", noise=noise, **bd)
+    for k in ("pos", "v", "bond"):
+        assert torch.equal(outs["padded"][k], outs["groups"][k]), (k, maxabs(outs["padded"][k], outs["groups"][k]))
+    monkeypatch.setenv("DD_RAGGED_MODE", "padded")
+    pad = _sample_hip(m, b, 3, None, noise)
+    cfg, sd = GU.weights(0, BF.config(2, 3))
+    want = [BF.oracle_chain(sd, cfg, p, n, 3) for p, n in zip(parts, noises)]
+    e = maxabs(pad["pos"], torch.cat([w["pos"] for w in want], 0))
+    print(f"blocks padded chain of 3 steps (three sizes) vs oracle: pos {e:.3g}")
+    assert e < POS_TOL
+    assert torch.equal(pad["v"].cpu(), torch.cat([w["v"] for w in want], 0))
+
+
+def test_one_block_model_is_untouched_by_the_two_block_model_of_its_shape():
+    """Cache separation: a one-block model gives the same bits before and after a two-block model of the same layers, weights
+    and batch shape ran in the process -- forward and a cached (device-noise) chain."""
+    b = BF.forward_batch("2x3")
+    bd = {k: (v.to(dev()) if torch.is_tensor(v) else v) for k, v in b.items()}
+    one, two = model(1, 3), model(2, 3)
+    run = lambda m: m.sample_diffusion(num_steps=3, center_pos_mode="protein", seed=7, **bd)
+    f0, c0 = fwd(one, b), run(one)
+    f2, c2 = fwd(two, b), run(two)
+    f1, c1 = fwd(one, b), run(one)
+    assert all(torch.equal(f0[k], f1[k]) for k in KEYS)
+    assert all(torch.equal(c0[k], c1[k]) for k in ("pos", "v", "bond"))
+    assert not torch.equal(f0["pred_ligand_pos"], f2["pred_ligand_pos"]) and not torch.equal(c0["pos"], c2["pos"])
+    assert all(torch.equal(run(two)[k], c2[k]) for k in ("pos", "v", "bond"))
+
+
+def test_harness_runs_a_two_block_model():
+    out = harness.sample_diffusion_ligand_decomp(model(2, 3), BF.pocket(BF.SAMPLING["pocket"]), num_samples=2, batch_size=2,
+                                                 device="cuda:0", num_steps=3, seed=11)
+    assert len(out["pred_pos"]) == 2 and all(bool(torch.isfinite(torch.as_tensor(p)).all()) for p in out["pred_pos"])
+
+
+# ------------------------------------------------------------------------------------ training
+def _oracle_net(cfg, sd_cpu, seen):
+    """The score network of get_diffusion_loss as fp32 autograd through oracle.model.forward on the CPU (`seen`: its inputs)."""
+    def net(model, p_pos, p_v, b_p, x_t, v_t, aux, b_l, fc, b_t):
+        c = lambda t: t.detach().cpu()
+        seen.append(dict(protein_pos=c(p_pos), init_ligand_pos=c(x_t), init_ligand_v=c(v_t), init_ligand_fc_bond_type=c(b_t)))
+        out = OM.forward(sd_cpu, cfg, c(p_pos), c(p_v).float(), c(b_p), c(x_t), c(v_t), c(aux).float(), c(b_l), c(fc), c(b_t))
+        return {k: v.to(p_pos.device) for k, v in out.items()}
+    return net
+
+
+def _total(res):
+    return res["losses"]["pos"] + 100.0 * res["losses"]["v"] + 100.0 * res["losses"]["bond"]
+
+
+_ORACLE_GRADS = {}
+
+
+def _oracle_loss_and_grads(ragged):
+    """Losses and parameter gradients of the training fixture through the oracle: computed once, shared, left unchanged."""
+    if ragged not in _ORACLE_GRADS:
+        b, t = BF.training_batch(ragged)
+        cfg = BF.config(t["nb"], t["L"])
+        sd_cpu = {k: v.clone().requires_grad_(True) for k, v in synth.synthetic_state_dict(cfg, 0).items()}
+        kw = BF.loss_kwargs(b, t["time_step"], dev())
+        for k in ("protein_group_idx", "ligand_group_idx", "prior_group_idx", "ligand_decomp_index"):
+            kw.pop(k)
+        torch.manual_seed(t["seed"])
+        seen = []
+        res = training.diffusion_loss(model(t["nb"], t["L"]), network_fn=_oracle_net(cfg, sd_cpu, seen), **kw)
+        _total(res).backward()
+        if not ragged:
+            # the inputs the host test measured this fixture's kNN gap on are the ones the objective hands to the network
+            x = BF.perturbed_network_inputs(DecompScorePosNet3D(cfg, 29, 10, 8), BF.loss_kwargs(b, t["time_step"], "cpu"), t["seed"])
+            # (to 1e-5 A -- the centring mean is summed in another order on the device --, 50 x below the gap the fixture keeps)
+            errs = {k: maxabs(seen[0][k], x[k]) for k in seen[0]}
+            assert len(seen) == 1 and max(errs["protein_pos"], errs["init_ligand_pos"]) < 1e-5, errs
+            assert errs["init_ligand_v"] == 0 and errs["init_ligand_fc_bond_type"] == 0, errs
+        _ORACLE_GRADS[ragged] = ({k: float(v.detach()) for k, v in res["losses"].items()},
+                                 {k: v.grad.detach().clone() for k, v in sd_cpu.items() if v.grad is not None})
+    return _ORACLE_GRADS[ragged]
+
+
+def _train_model(t):
+    cfg = BF.config(t["nb"], t["L"])
+    return _load(cfg, synth.synthetic_state_dict(cfg, 0)).train()
+
+
+@pytest.mark.parametrize("ragged,fused", [(False, "0"), (True, "0"), (False, "1"), (True, "1")],
+                         ids=["dense", "padded", "dense-fused-attn", "padded-fused-attn"])
+def test_loss_and_gradients_against_autograd_through_the_oracle(ragged, fused, monkeypatch):
+    monkeypatch.setenv("DD_TRAIN_FUSED_ATTN", fused)
+    want_l, want_g = _oracle_loss_and_grads(ragged)
+    b, t = BF.training_batch(ragged)
+    m = _train_model(t)
+    torch.manual_seed(t["seed"])
+    kw = BF.loss_kwargs(b, t["time_step"], dev())
+    res = m.get_diffusion_loss(**kw)
+    tag = f"blocks training ({'padded' if ragged else 'dense'}{', fused attention' if fused == '1' else ''})"
+    for k in ("pos", "v", "bond"):
+        got, want = float(res["losses"][k]), want_l[k]
+        print(f"{tag} loss {k}: {got:.7g} (oracle {want:.7g})")
+        assert abs(got - want) <= 1e-4 * max(1.0, abs(want)), (k, got, want)
+    _total(res).backward()
+    params = dict(m.named_parameters())
+    assert set(want_g) <= set(params)
+    # Bound form of tests/test_gpu_training.py: 2e-3 relative to each tensor's largest entry, for every parameter.  One family
+    # has no such ratio: the output bias of a key MLP (hk_func / xk_func .net.3.bias) shifts all logits of a softmax segment
+    # by the same q . b, so its exact gradient is ZERO and what any implementation stores is the rounding of a cancelling sum
+    # (the oracle itself: ~2e-10).  Those tensors are held to rounding level instead: a sum over at most `rows` member rows
+    # whose terms are bounded by the model's largest gradient entry, each rounded to 2^-24.
+    zero_grad = lambda n: re.search(r"\.(hk|xk)_func\.net\.3\.bias$", n) is not None
+    top = max(float(w.abs().max()) for w in want_g.values())
+    rows = max(int(kw["batch_ligand_bond"].numel()), 32 * (int(kw["batch_protein"].numel()) + int(kw["batch_ligand"].numel())))
+    rels = {}
+    for name, want in want_g.items():
+        assert params[name].grad is not None, name
+        got = params[name].grad.cpu()
+        if zero_grad(name):
+            assert float(got.abs().max()) <= rows * 2.0 ** -24 * top, (name, float(got.abs().max()), float(want.abs().max()))
+        else:
+            rels[name] = float((got - want).abs().max() / want.abs().max().clamp(min=1e-12))
+    order = sorted(rels, key=rels.get, reverse=True)
+    for name in order[:3]:
+        print(f"  {name}: rel {rels[name]:.2g}, largest entry oracle {float(want_g[name].abs().max()):.3g} (model-wide {top:.3g})")
+    worst, worst_name = rels[order[0]], order[0]
+    line = (f"{tag}: {len(rels)} parameter gradients vs oracle autograd, worst relative tensor error {worst:.2g} ({worst_name}); "
+            f"{len(want_g) - len(rels)} key-bias gradients at rounding level")
+    print(line)
+    assert worst < 2e-3, line
+    # autograd reaches the parameters that act through the second block's graph inputs (e_w, rel_x): zero is what a missing edge looks like
+    for name in params:
+        if name.startswith("refine_net.edge_pred_layer.") or re.search(r"base_block\.\d\.pos_layer_with_(edge|bond)\.xv_func\.", name):
+            assert float(params[name].grad.abs().max()) > 0, name
+
+
+def test_no_grad_loss_uses_the_fused_forward_and_agrees():
+    b, t = BF.training_batch(False)
+    want_l, _ = _oracle_loss_and_grads(False)
+    m = model(t["nb"], t["L"])
+    with torch.no_grad():
+        torch.manual_seed(t["seed"])
+        res = m.get_diffusion_loss(**BF.loss_kwargs(b, t["time_step"], dev()))
+    for k in ("pos", "v", "bond"):
+        assert abs(float(res["losses"][k]) - want_l[k]) <= 1e-4 * max(1.0, abs(want_l[k])), k
+    assert not res["losses"]["pos"].requires_grad
+
+
+def test_graphed_train_step_follows_the_eager_steps():
+    b, t = BF.training_batch(False)
+    kw = BF.loss_kwargs(b, t["time_step"], dev())
+    kw.pop("time_step")
+
+    def fresh(capturable):
+        m = _train_model(t)
+        return m, torch.optim.Adam(m.parameters(), lr=1e-4, capturable=capturable)
+    m_e, opt_e = fresh(False)
+    torch.manual_seed(11)
+    eager = []
+    for _ in range(5):
+        opt_e.zero_grad(set_to_none=True)
+        loss = _total(m_e.get_diffusion_loss(**kw))
+        loss.backward()
+        opt_e.step()
+        eager.append(float(loss))
+    m_g, opt_g = fresh(True)
+    gs = training.GraphedTrainStep(m_g, opt_g, loss_weights=(1.0, 100.0, 100.0), warmup=2)
+    torch.manual_seed(11)
+    graphed = [float(gs.step(**kw)["loss"]) for _ in range(5)]
+    assert gs.replays == 3 and gs.eager_steps == 2
+    print("blocks graphed train step vs eager, 5 steps: worst relative loss difference "
+          f"{max(abs(a - c) / max(1.0, abs(a)) for a, c in zip(eager, graphed)):.2g}")
+    for a, c in zip(eager, graphed):
+        assert abs(a - c) <= 2e-4 * max(1.0, abs(a)), (eager, graphed)
+
+
+# ------------------------------------------------------------------------------------ C ABI
+def test_opts_call_with_one_block_equals_the_ex2_call():
+    b = BF.forward_batch("2x3")
+    m = model(1, 3)
+    ref = fwd(m, b)                                         # (through dd_forward_opts with num_blocks = 1)
+    s, bufs = m._last
+    lib = hip_lib.load()
+    st = hip_lib.stream_ptr(dev())
+    for k in ("pred_pos", "pred_v", "pred_bond"):
+        bufs[k].fill_(float("nan"))
+    hip_lib.check(lib.dd_forward_ex2(ctypes.byref(s), m._bond_head(), m._node_out(), st), "dd_forward_ex2")
+    torch.cuda.synchronize()
+    assert torch.equal(bufs["pred_pos"].view(-1, 3), ref["pred_ligand_pos"]) and torch.equal(bufs["pred_v"].view(-1, 8), ref["pred_ligand_v"])
+    assert torch.equal(bufs["pred_bond"], ref["pred_bond"])
+    # a shorter struct (a caller that knows no num_blocks field) means one block; NULL means all defaults
+    short = hip_lib.model_opts(num_blocks=2)
+    short.size = hip_lib.DDModelOpts.num_blocks.offset
+    for opts in (ctypes.pointer(short), None):
+        bufs["pred_pos"].fill_(float("nan"))
+        hip_lib.check(lib.dd_forward_opts(ctypes.byref(s), opts, st), "dd_forward_opts")
+        torch.cuda.synchronize()
+        assert torch.equal(bufs["pred_pos"].view(-1, 3), ref["pred_ligand_pos"])
+    # the bound is checked by the library too
+    assert lib.dd_forward_opts(ctypes.byref(s), ctypes.pointer(hip_lib.model_opts(num_blocks=22)), st) != 0
+    assert lib.dd_forward_opts(ctypes.byref(s), ctypes.pointer(hip_lib.model_opts(num_blocks=0)), st) != 0
+    # the workspace view follows the parity of the total step count (3 vs 6 steps)
+    v1, v2 = hip_lib.DDWsView(), hip_lib.DDWsView()
+    hip_lib.check(lib.dd_workspace_view(ctypes.byref(s), ctypes.byref(v1)))
+    hip_lib.check(lib.dd_workspace_view_opts(ctypes.byref(s), ctypes.pointer(hip_lib.model_opts(num_blocks=2)), ctypes.byref(v2)))
+    assert v1.x != v2.x and v1.h == v2.h
