@@ -507,19 +507,62 @@ struct Fwd {
     pb.qhid = w.PL2 + 896; pb.ld_qhid = 1024; pb.lnq = LW(l, DD_PB_lnq); pb.W2q = LW(l, DD_PB_W2qT); pb.b2q = LW(l, DD_PB_b2q);
   }
 
-  // head of a forward (dd_graph.hip): kNN graph + edge weights (parts & 1), embeddings / context / zeroed counters + layer-0 rows
-  // (parts & 2; l0: gathered from the tables).  advance != NULL: the launch advances the step counter too.
-  int launch_head(hipStream_t sx, int parts, bool l0, int32_t* advance) const {
-    return launch_head_all(s->protein_h, s->protein_pos, s->lig_pos, s->lig_v, s->lig_aux, GW(DD_G_W_lemb), GW(DD_G_b_lemb), B, NP, NL,
-                           K, w.h, w.xa, w.xb, s->lig_bond, (long)B * Eb, GW(DD_G_W_bemb), GW(DD_G_b_bemb), w.hb, w.counters, advance,
-                           w.nbr, w.ew, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2), GW(DD_G_EW_b2),
-                           s->np_real, s->nl_real, l0 ? s->l0_tables : nullptr, s->l0_P, w.PL, s->l0_qn, w.qlnb, w.PB, w.qb, sx, parts,
-                           num_v(s));
+  // -- head of a forward and block boundaries (dd_graph.hip)
+  // kNN graph + edge weights into w.nbr / w.ew: of x_t where the step kernels left it (the sampler's position buffers) ...
+  GraphArgs graph_head() const {
+    GraphArgs g{};
+    g.B = B; g.NP = NP; g.NL = NL; g.K = K;
+    g.prot = s->protein_pos; g.prot_stride = 3 * NP; g.lig = s->lig_pos; g.lig_stride = 3 * NL;
+    g.nbr = w.nbr; g.ew = w.ew;
+    g.EW_W1T = GW(DD_G_EW_W1T); g.EW_b1 = GW(DD_G_EW_b1); g.EW_ln = GW(DD_G_EW_ln); g.EW_w2 = GW(DD_G_EW_w2); g.EW_b2 = GW(DD_G_EW_b2);
+    g.np_real = s->np_real; g.nl_real = s->nl_real;
+    return g;
   }
-  // block boundary (num_blocks > 1; dd_graph.hip): the next block's kNN graph + edge weights from the current coordinates x
-  int launch_block(const float* x, hipStream_t sx) const {
-    return launch_block_graph(x, B, NP, NL, K, w.nbr, w.ew, GW(DD_G_EW_W1T), GW(DD_G_EW_b1), GW(DD_G_EW_ln), GW(DD_G_EW_w2), GW(DD_G_EW_b2),
-                              s->np_real, s->nl_real, sx);
+  // ... or of one [B, N, 3] block x: the current coordinates at a block boundary (num_blocks > 1), the workspace copy of x_t
+  GraphArgs graph_at(const float* x) const {
+    GraphArgs g = graph_head();
+    g.set_block(x);
+    return g;
+  }
+  // embeddings / context / zeroed counters (advance != NULL: the launch advances the step counter too)
+  EmbedArgs embed(int32_t* advance) const {
+    EmbedArgs e{};
+    e.B = B; e.NP = NP; e.NL = NL; e.nv = num_v(s);
+    e.protein_h = s->protein_h; e.protein_pos = s->protein_pos; e.lig_pos = s->lig_pos; e.lig_v = s->lig_v; e.lig_aux = s->lig_aux;
+    e.bond = s->lig_bond;
+    e.Wl = GW(DD_G_W_lemb); e.bl = GW(DD_G_b_lemb); e.Wb = GW(DD_G_W_bemb); e.bb = GW(DD_G_b_bemb);
+    e.h = w.h; e.xa = w.xa; e.xb = w.xb; e.hb = w.hb;
+    e.counters = w.counters; e.advance = advance;
+    e.bond_rows = (long)B * Eb;
+    e.node_blocks = (int)(((long)B * N * 128 + 255) / 256);
+    e.blocks = e.node_blocks + (int)((e.bond_rows * 128 + 255) / 256);
+    return e;
+  }
+  // the first layer's projection / query rows of the ligand atoms and bonds gathered from s->l0_tables
+  Layer0RowsArgs l0_rows() const {
+    Layer0RowsArgs r{};
+    r.B = B; r.NP = NP; r.NL = NL;
+    r.tab = s->l0_tables; r.lig_v = s->lig_v; r.lig_aux = s->lig_aux; r.bond = s->lig_bond;
+    r.l0_P = s->l0_P; r.PL = w.PL; r.l0_qn = s->l0_qn; r.qlnb = w.qlnb; r.PB = w.PB; r.qb = w.qb;
+    r.atom_f4 = (long)B * NL * DD_L0_ATOM_F4;
+    r.blocks = (int)((r.atom_f4 + (long)B * Eb * DD_L0_BOND_F4 + 255) / 256);
+    return r;
+  }
+  // the two in one launch (l0: with the layer-0 rows)
+  int launch_head_rows(bool l0, int32_t* advance, hipStream_t sx) const {
+    const Layer0RowsArgs r = l0_rows();
+    return dd::launch_head_rows(embed(advance), l0 ? &r : nullptr, sx);
+  }
+  // bond-layer assemble of layer l at positions x (q1 NULL: the query GEMM sums its hidden rows itself); the call sites add a
+  // deferred coordinate update (xprev / xout; its addends are w.dxe / w.dxb) and the tile-queue wait
+  AssembleArgs assemble(int l, const float* x, float* q1) const {
+    AssembleArgs a{};
+    a.x = x; a.PB = w.PB; a.PL = w.PL; a.Wgp = LW(l, DD_BL_Wgp);
+    a.B = B; a.NP = NP; a.NL = NL;
+    a.Ek = w.Ek; a.Ev = w.Ev; a.q1 = q1; a.Rk = w.Rk; a.Rv = w.Rv;
+    a.dxe = w.dxe; a.dxb = w.dxb;
+    a.fw = no_wait();
+    return a;
   }
 };
 
@@ -548,13 +591,13 @@ static int forward_tail(const Fwd& f, DevCtx& dc, hipStream_t st, StepFold* fold
   bool head_join = false;
   if (two_streams) {
     if (hipEventRecord(dc.ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(dc.side, dc.ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
-    DD_TRY(f.launch_head(dc.side, 1, l0, advance));
+    DD_TRY(launch_graph(f.graph_head(), dc.side));
     if (hipEventRecord(dc.ev_join[8], dc.side) != hipSuccess) return DD_ERR_HIP;
     head_join = true;
-    DD_TRY(f.launch_head(st, 2, l0, advance));
+    DD_TRY(f.launch_head_rows(l0, advance, st));
   } else {
-    DD_TRYP(DD_PROF_MISC, f.launch_head(st, 2, l0, advance));
-    DD_TRYP(DD_PROF_MISC, f.launch_head(st, 1, l0, advance));
+    DD_TRYP(DD_PROF_MISC, f.launch_head_rows(l0, advance, st));
+    DD_TRYP(DD_PROF_MISC, launch_graph(f.graph_head(), st));
   }
   if (!l0) {                                             // first layer's projections / queries as GEMMs (no tables)
     DD_TRYP(DD_PROF_GEMM, f.launch_projections1(0, w.h, st));
@@ -574,8 +617,9 @@ static int forward_tail(const Fwd& f, DevCtx& dc, hipStream_t st, StepFold* fold
     // ---- assemble (bond_layer first-Linear partial sums; applies the previous layer's coordinate update)
     FlagWait fw = no_wait();
     if (l > 0) fw = FlagWait{flags, FL(l - 1, DD_FLAG_PB1R), n_pb1r, FL(l - 1, DD_FLAG_PL1), n_pl1};
-    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, f.LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev, nullptr, w.Rk, w.Rv, st,
-                                                  xup_prev, w.dxe, w.dxb, xup_prev ? xcur : nullptr, fw));
+    AssembleArgs as = f.assemble(l, xcur, nullptr);
+    as.xprev = xup_prev; as.xout = xup_prev ? xcur : nullptr; as.fw = fw;
+    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(as, st));
     xup_prev = nullptr;
     if (head_join) {                                     // kNN graph + edge weights: first needed by the node attention
       if (hipStreamWaitEvent(st, dc.ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
@@ -736,7 +780,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   int32_t* advance = (fold && fold->advance) ? s->step_counter : nullptr;
   bool head_join = false;
   if (overlap && g_head_fused) {
-    // dd_graph.hip: the graph (k_head_graph: kNN + edge weights, one wave per centre, reading x_t from the sampler's
+    // dd_graph.hip: the graph (k_graph: kNN + edge weights, one wave per centre, reading x_t from the sampler's
     // position buffers) forked to the side stream FIRST, the embeddings / context / counters / layer-0 rows (k_head_rows)
     // on the main stream beside it -- two launches instead of four.  (Measured and dropped: all four bodies in one
     // kernel, +2.5 % step time -- one register allocation for every block kind, and assemble then waits for a graph it
@@ -745,19 +789,15 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     // (option 29: the rows launch is RECORDED first -- same dependencies, the fork point is the event above -- so that the graph
     // runtime, which keeps the first-recorded successor of a node on its hardware queue, leaves the main chain's launch on the
     // previous step kernel's queue and moves the graph construction, which has slack, to the other one)
-    if (g_head_rows_first) DD_TRYP(DD_PROF_MISC, f.launch_head(st, 2, l0, advance));
-    DD_TRYP(DD_PROF_MISC, f.launch_head(dc.side, 1, l0, advance));
+    if (g_head_rows_first) DD_TRYP(DD_PROF_MISC, f.launch_head_rows(l0, advance, st));
+    DD_TRYP(DD_PROF_MISC, launch_graph(f.graph_head(), dc.side));
     if (hipEventRecord(dc.ev_join[8], dc.side) != hipSuccess) return DD_ERR_HIP;
     head_join = true;
-    if (!g_head_rows_first) DD_TRYP(DD_PROF_MISC, f.launch_head(st, 2, l0, advance));
+    if (!g_head_rows_first) DD_TRYP(DD_PROF_MISC, f.launch_head_rows(l0, advance, st));
   } else {
     // embeddings + context (decompdiff.py:219-297) and the zeroed work counters: one launch
-    DD_TRYP(DD_PROF_MISC, launch_embed_all(s->protein_h, s->protein_pos, s->lig_pos, s->lig_v, s->lig_aux, f.GW(DD_G_W_lemb),
-                                           f.GW(DD_G_b_lemb), B, NP, NL, w.h, w.xa, w.xb, s->lig_bond, (long)B * f.Eb, f.GW(DD_G_W_bemb),
-                                           f.GW(DD_G_b_bemb), w.hb, w.counters, st, advance, num_v(s)));
-    if (l0)
-      DD_TRYP(DD_PROF_MISC, launch_layer0_rows(s->l0_tables, s->lig_v, s->lig_aux, s->lig_bond, B, NP, NL, s->l0_P, w.PL, s->l0_qn,
-                                                w.qlnb, w.PB, w.qb, st));
+    DD_TRYP(DD_PROF_MISC, launch_embed(f.embed(advance), st));
+    if (l0) DD_TRYP(DD_PROF_MISC, launch_layer0_rows(f.l0_rows(), st));
     // graph (uni_transformer_edge.py:404-427): only the attention kernels need it, so with two streams it is built
     // beside the bond embedding and the first layer's projections
     hipStream_t gs = st;
@@ -765,9 +805,9 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
       if (hipEventRecord(dc.ev_fork[8], st) != hipSuccess || hipStreamWaitEvent(dc.side, dc.ev_fork[8], 0) != hipSuccess) return DD_ERR_HIP;
       gs = dc.side;
     }
-    DD_TRYP(DD_PROF_MISC, launch_knn(w.xa, B, N, f.K, w.nbr, gs, NP, s->np_real, s->nl_real));
-    DD_TRYP(DD_PROF_MISC, launch_edge_weights(w.xa, w.nbr, B, N, f.K, f.GW(DD_G_EW_W1T), f.GW(DD_G_EW_b1), f.GW(DD_G_EW_ln), f.GW(DD_G_EW_w2),
-                               f.GW(DD_G_EW_b2), w.ew, gs, NP, s->np_real, s->nl_real));
+    const GraphArgs g = f.graph_at(w.xa);                // (the workspace copy of x_t the embedding launch just wrote)
+    DD_TRYP(DD_PROF_MISC, launch_knn(g, gs));
+    DD_TRYP(DD_PROF_MISC, launch_edge_weights(g, gs));
     if (overlap) {
       if (hipEventRecord(dc.ev_join[8], dc.side) != hipSuccess) return DD_ERR_HIP;
       head_join = true;
@@ -853,16 +893,16 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
     if (ahead && l > 0 && !b1_joined && hipStreamWaitEvent(st, late_join ? dc.ev_qb_fork[ev(l)] : dc.ev_join[ev(l)], 0) != hipSuccess)
       return DD_ERR_HIP;                                 // projections of this layer
     // (a deferred coordinate update of the previous layer is applied here: xcur's ligand rows are written by this launch)
-    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, f.LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev,
-                                                  q1_in_gemm ? nullptr : w.q1bl, w.Rk, w.Rv, st, xup_prev, w.dxe, w.dxb,
-                                                  xup_prev ? xcur : nullptr));
+    AssembleArgs as = f.assemble(l, xcur, q1_in_gemm ? nullptr : w.q1bl);
+    as.xprev = xup_prev; as.xout = xup_prev ? xcur : nullptr;
+    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(as, st));
     xup_prev = nullptr;
     // ---- block boundary: the new block's kNN graph + edge weights from x as the previous block left it.  xcur is complete here
     //      by construction: the previous layer's coordinate launch was flushed and joined above, and its update is applied by
     //      the assemble launch in front of this one (or was, by a launch of its own, on this stream or behind that join).  The
     //      readers of the old graph (previous node launch, previous coordinate launch) are ordered before this launch the same
     //      way; the next ones (this step's node launch, its coordinate launch behind a fork recorded after it) follow it.
-    if (l > 0 && l % LB == 0) DD_TRYP(DD_PROF_MISC, f.launch_block(xcur, st));
+    if (l > 0 && l % LB == 0) DD_TRYP(DD_PROF_MISC, launch_graph(f.graph_at(xcur), st));
     if (!q1_in_gemm) DD_TRYP(DD_PROF_GEMM, launch_b2(l, st));
     if (head_join) {                                     // kNN graph + edge weights: first needed by the node attention
       if (hipStreamWaitEvent(st, dc.ev_join[8], 0) != hipSuccess) return DD_ERR_HIP;
@@ -997,12 +1037,12 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   Fwd u = f;
   u.w.P2 = w.P; u.w.PL2 = w.PL; u.w.PB2 = w.PB; u.w.qlnb = u.w.ql2 = w.ql;
   for (int l = 0; l < L && !fused; ++l) {
-    if (l > 0 && l % LB == 0) DD_TRYP(DD_PROF_MISC, u.launch_block(xcur, st));   // block boundary (every launch is on this stream)
+    if (l > 0 && l % LB == 0) DD_TRYP(DD_PROF_MISC, launch_graph(u.graph_at(xcur), st));   // block boundary (every launch is on this stream)
     // ---- projections of the old h / h_bond
     DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.n1(l, w.h), st));
     DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.l1(l, w.h), st));
     DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.b1(l), st));
-    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(xcur, w.PB, w.PL, u.LW(l, DD_BL_Wgp), B, NP, NL, w.Ek, w.Ev, w.q1bl, w.Rk, w.Rv, st));
+    DD_TRYP(DD_PROF_ASSEMBLE, launch_bl_assemble(u.assemble(l, xcur, w.q1bl), st));
     // ---- queries: second Linear of the q MLPs (LayerNorm+ReLU prologue)
     DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.q_ne(l), st));
     DD_TRYP(DD_PROF_GEMM, launch_gemm128(u.q_nb(l), st));
@@ -1216,15 +1256,13 @@ extern "C" int dd_build_flags(void) {
 extern "C" int dd_layer0_tables(const dd_sampler* m, float* tables, void* stream) {
   if (!m || !tables || !m->weights || !m->slot_off || !m->workspace || !m->lig_v || !m->lig_aux || !m->lig_bond || !m->lig_pos)
     return DD_ERR_BAD_ARG;
-  if (m->B != 1 || m->NP != 0 || m->NL != 16) return DD_ERR_BAD_ARG;
+  if (m->B != 1 || m->NP != 0 || m->NL != 16 || dd::num_v(m) != DD_NUM_V) return DD_ERR_BAD_ARG;   // (16 = DD_NUM_V classes x arm flag)
   int rc = dd::check_shapes(m);
   if (rc != DD_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const dd::Fwd f(m);
   const dd::Workspace& w = f.w;
-  rc = dd::launch_embed_all(m->protein_h, m->protein_pos, m->lig_pos, m->lig_v, m->lig_aux, f.GW(DD_G_W_lemb), f.GW(DD_G_b_lemb), 1, 0, 16,
-                            w.h, w.xa, w.xb, m->lig_bond, 240, f.GW(DD_G_W_bemb), f.GW(DD_G_b_bemb), w.hb, w.counters, st, nullptr);
-  if (rc != DD_OK) return rc;
+  if ((rc = dd::launch_embed(f.embed(nullptr), st)) != DD_OK) return rc;
   if ((rc = f.launch_projections1(0, w.h, st)) != DD_OK) return rc;
   if ((rc = f.launch_queries(0, true, st)) != DD_OK) return rc;
   // atom i has combination i; bonds dst*15 + s have type s % 5 (s < 5: type s)

@@ -6,6 +6,8 @@
 //   k_bl_assemble3   per-bond-edge partial sums of the bond_layer first Linear (packing.py docstring)
 // One wavefront (64 lanes) per centre / edge row; feature rows are 128 floats = 2 per lane,
 // so every gather is a single coalesced 512-byte row read.
+#include <type_traits>
+
 #include "dd_kernels.hpp"
 
 namespace dd {
@@ -28,6 +30,15 @@ struct PosView {
   int NP;
   __device__ __forceinline__ float get(int n, int c) const { return n < NP ? p[3 * n + c] : l[3 * (n - NP) + c]; }
 };
+__device__ __forceinline__ PosView pos_view(const GraphArgs& a, int b) {   // sample b of the problem (GraphArgs: both forms)
+  return PosView{a.prot + (long)b * a.prot_stride, a.lig + (long)b * a.lig_stride, a.NP};
+}
+// ... of a problem known to be one [B, N, 3] block at a.prot (k_knn, k_edge_weights2): with l = p + 3 NP in sight the compiler
+// folds PosView::get into one address
+__device__ __forceinline__ PosView block_view(const GraphArgs& a, int b) {
+  const float* xb = a.prot + (long)b * (a.NP + a.NL) * 3;
+  return PosView{xb, xb + 3 * (long)a.NP, a.NP};
+}
 
 // One wave: the K nearest neighbours of centre i, ascending (d2, index), to nbr_row[0..K) (global) and -- when srt is
 // given -- to srt[0..K) (this wave's LDS slice: the edge-weight pass of the fused head launch reads them from there).
@@ -95,22 +106,19 @@ __device__ __forceinline__ void knn_wave(const PosView& pv, int i, int N, int K,
 }
 
 template <int CAND>
-__global__ __launch_bounds__(256) void k_knn(const float* __restrict__ x, int B, int N, int K, int32_t* __restrict__ nbr, int NP,
-                                             const int32_t* __restrict__ np_real, const int32_t* __restrict__ nl_real) {
+__global__ __launch_bounds__(256) void k_knn(const GraphArgs a) {
   __shared__ unsigned long long sel[4][64];
-  const int lane = threadIdx.x & 63;
+  const int N = a.NP + a.NL, lane = threadIdx.x & 63;
   const int centre = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (centre >= B * N) return;
+  if (centre >= a.B * N) return;
   const int b = centre / N, i = centre % N;
-  const bool masked = nl_real != nullptr;
-  const int npb = masked && np_real ? np_real[b] : NP, nlb = masked ? nl_real[b] : N - NP;
-  if (masked && !atom_is_real(i, NP, npb, nlb)) {          // a padding atom is no centre: its list is never read
-    if (lane < K) nbr[(long)centre * K + lane] = 0;
+  const bool masked = a.nl_real != nullptr;
+  const int npb = masked && a.np_real ? a.np_real[b] : a.NP, nlb = masked ? a.nl_real[b] : a.NL;
+  if (masked && !atom_is_real(i, a.NP, npb, nlb)) {        // a padding atom is no centre: its list is never read
+    if (lane < a.K) a.nbr[(long)centre * a.K + lane] = 0;
     return;
   }
-  const float* xb = x + (long)b * N * 3;
-  const PosView pv{xb, xb + 3 * (long)NP, NP};
-  knn_wave<CAND>(pv, i, N, K, nbr + (long)centre * K, masked, npb, nlb, sel[threadIdx.x >> 6], nullptr);
+  knn_wave<CAND>(block_view(a, b), i, N, a.K, a.nbr + (long)centre * a.K, masked, npb, nlb, sel[threadIdx.x >> 6], nullptr);
 }
 
 // ------------------------------------------------------------------- kNN over a flat, ragged batch
@@ -280,22 +288,16 @@ __device__ __forceinline__ void ew_wave(const PosView& pv, int i, int K, const i
     if (cg == 0 && m < K) ew_row[m] = 1.0f / (1.0f + expf(-logit));
   }
 }
-__global__ __launch_bounds__(256, 3) void k_edge_weights2(const float* __restrict__ x, const int32_t* __restrict__ nbr, int B,
-                                                          int N, int K, const float* __restrict__ W1T,
-                                                          const float* __restrict__ b1, const float* __restrict__ ln,
-                                                          const float* __restrict__ w2, const float* __restrict__ b2,
-                                                          float* __restrict__ ew, int NP, const int32_t* __restrict__ np_real,
-                                                          const int32_t* __restrict__ nl_real) {
+__global__ __launch_bounds__(256, 3) void k_edge_weights2(const GraphArgs a) {
   __shared__ __attribute__((aligned(16))) float lw[512];
-  ew_stage(lw, b1, ln, w2);
+  ew_stage(lw, a.EW_b1, a.EW_ln, a.EW_w2);
   __syncthreads();                                       // (before any wave leaves)
+  const int N = a.NP + a.NL;
   const int node = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (node >= B * N) return;
+  if (node >= a.B * N) return;
   const int b = node / N, i = node % N;
-  if (nl_real != nullptr && !atom_is_real(i, NP, np_real ? np_real[b] : NP, nl_real[b])) return;   // padding atom
-  const float* xb = x + (long)b * N * 3;
-  const PosView pv{xb, xb + 3 * (long)NP, NP};
-  ew_wave(pv, i, K, nbr + (long)node * K, W1T, lw, b2, ew + (long)node * K);
+  if (a.nl_real != nullptr && !atom_is_real(i, a.NP, a.np_real ? a.np_real[b] : a.NP, a.nl_real[b])) return;   // padding atom
+  ew_wave(block_view(a, b), i, a.K, a.nbr + (long)node * a.K, a.EW_W1T, lw, a.EW_b2, a.ew + (long)node * a.K);
 }
 
 // -------------------------------------------------------------------------------- embeddings
@@ -315,15 +317,7 @@ __global__ void k_embed_protein(const float* __restrict__ feat, int rows, const 
 
 // One launch at the head of a step: node embedding / context, bond embedding, and the per-forward work counters
 // of the persistent kernels (64 ints) set to zero.
-__device__ __forceinline__ void embed_block(const unsigned blk, const float* __restrict__ protein_h, const float* __restrict__ protein_pos,
-                                                   const float* __restrict__ lig_pos, const int32_t* __restrict__ lig_v,
-                                                   const float* __restrict__ lig_aux, const float* __restrict__ Wl,
-                                                   const float* __restrict__ bl, int B, int NP, int NL, float* __restrict__ h,
-                                                   float* __restrict__ xa, float* __restrict__ xb,
-                                                   const int32_t* __restrict__ bond, long bond_rows,
-                                                   const float* __restrict__ Wb, const float* __restrict__ bb,
-                                                   float* __restrict__ hb, int32_t* __restrict__ counters, int node_blocks,
-                                                   int32_t* __restrict__ advance, int nv) {
+__device__ __forceinline__ void embed_block(const unsigned blk, const EmbedArgs& e) {
   // (measurement build: + the tile-queue schedule's flag words; the error word behind them is sticky: dd_queue_error reads
   // and clears it.  The default library has no such schedule and zeroes the work counters only.)
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
@@ -331,52 +325,42 @@ __device__ __forceinline__ void embed_block(const unsigned blk, const float* __r
 #else
   constexpr int n_zero = DD_NUM_COUNTERS;
 #endif
-  if (blk == 0 && counters)
-    for (int i = threadIdx.x; i < n_zero; i += 256) counters[i] = 0;
+  if (blk == 0 && e.counters)
+    for (int i = threadIdx.x; i < n_zero; i += 256) e.counters[i] = 0;
   // the step index moves on with the first launch of a step's forward (nothing before the step kernels reads it): the
   // step kernels use *advance - 1, and no one-thread launch sits at the end of a step
-  if (blk == 0 && threadIdx.x == 64 && advance) *advance += 1;
-  if ((int)blk < node_blocks) {
+  if (blk == 0 && threadIdx.x == 64 && e.advance) *e.advance += 1;
+  const int NP = e.NP, NL = e.NL, nv = e.nv;
+  if ((int)blk < e.node_blocks) {
     const int N = NP + NL;
     const long idx = (long)blk * 256 + threadIdx.x;
-    if (idx >= (long)B * N * 128) return;
+    if (idx >= (long)e.B * N * 128) return;
     const int c = idx & 127;
     const long node = idx >> 7;
     const int b = node / N, n = node % N;
     float val;
     if (n < NP) {
-      val = protein_h[((long)b * NP + n) * 128 + c];
+      val = e.protein_h[((long)b * NP + n) * 128 + c];
     } else {
       const long a = (long)b * NL + (n - NP);
-      const float* w = Wl + c * (nv + 2);                // ligand_atom_emb row: nv class columns + 2 arm / scaffold indicators
-      val = w[lig_v[a]] + w[nv] * lig_aux[2 * a] + w[nv + 1] * lig_aux[2 * a + 1] + bl[c];
+      const float* w = e.Wl + c * (nv + 2);              // ligand_atom_emb row: nv class columns + 2 arm / scaffold indicators
+      val = w[e.lig_v[a]] + w[nv] * e.lig_aux[2 * a] + w[nv + 1] * e.lig_aux[2 * a + 1] + e.bl[c];
     }
-    h[idx] = val;
+    e.h[idx] = val;
     if (c < 3) {
-      const float p = n < NP ? protein_pos[((long)b * NP + n) * 3 + c] : lig_pos[((long)b * NL + (n - NP)) * 3 + c];
-      xa[node * 3 + c] = p;
-      xb[node * 3 + c] = p;
+      const float p = n < NP ? e.protein_pos[((long)b * NP + n) * 3 + c] : e.lig_pos[((long)b * NL + (n - NP)) * 3 + c];
+      e.xa[node * 3 + c] = p;
+      e.xb[node * 3 + c] = p;
     }
   } else {
-    const long idx = (long)(blk - node_blocks) * 256 + threadIdx.x;
-    if (idx >= bond_rows * 128) return;
+    const long idx = (long)(blk - e.node_blocks) * 256 + threadIdx.x;
+    if (idx >= e.bond_rows * 128) return;
     const int c = idx & 127;
-    const long e = idx >> 7;
-    hb[idx] = Wb[c * 5 + bond[e]] + bb[c];
+    const long r = idx >> 7;
+    e.hb[idx] = e.Wb[c * 5 + e.bond[r]] + e.bb[c];
   }
 }
-__global__ __launch_bounds__(256) void k_embed_all(const float* __restrict__ protein_h, const float* __restrict__ protein_pos,
-                                                   const float* __restrict__ lig_pos, const int32_t* __restrict__ lig_v,
-                                                   const float* __restrict__ lig_aux, const float* __restrict__ Wl,
-                                                   const float* __restrict__ bl, int B, int NP, int NL, float* __restrict__ h,
-                                                   float* __restrict__ xa, float* __restrict__ xb,
-                                                   const int32_t* __restrict__ bond, long bond_rows,
-                                                   const float* __restrict__ Wb, const float* __restrict__ bb,
-                                                   float* __restrict__ hb, int32_t* __restrict__ counters, int node_blocks,
-                                                   int32_t* __restrict__ advance, int nv) {
-  embed_block(blockIdx.x, protein_h, protein_pos, lig_pos, lig_v, lig_aux, Wl, bl, B, NP, NL, h, xa, xb, bond, bond_rows, Wb, bb, hb,
-              counters, node_blocks, advance, nv);
-}
+__global__ __launch_bounds__(256) void k_embed_all(const EmbedArgs e) { embed_block(blockIdx.x, e); }
 
 // --------------------------------------------------------------------------- layer-0 rows from tables
 // One thread per float4 of an output row.  Ligand atom a = b*NL + i with combination c = 8*(arm flag) + class:
@@ -384,86 +368,59 @@ __global__ __launch_bounds__(256) void k_embed_all(const float* __restrict__ pro
 // bond e = b*Eb + t*(NL-1) + s' of type ty with destination atom t:  PB[e] = TB[ty] (640), qb[e] = TQB[c(t)][ty].
 constexpr int L0_TN = 0, L0_TL = 16 * 640, L0_TB = L0_TL + 16 * 1280, L0_TQN = L0_TB + 5 * 640, L0_TQL = L0_TQN + 16 * 128,
               L0_TQB = L0_TQL + 16 * 128;
-__device__ __forceinline__ void layer0_rows_block(const unsigned blk, const float* __restrict__ tab, const int32_t* __restrict__ lig_v,
-                                                     const float* __restrict__ lig_aux, const int32_t* __restrict__ bond, int B,
-                                                     int NP, int NL, float* __restrict__ l0_P, float* __restrict__ PL,
-                                                     float* __restrict__ l0_qn, float* __restrict__ qlnb, float* __restrict__ PB,
-                                                     float* __restrict__ qb, long atom_f4) {
+__device__ __forceinline__ void layer0_rows_block(const unsigned blk, const Layer0RowsArgs& r) {
   const long idx = (long)blk * 256 + threadIdx.x;
-  const int N = NP + NL, Eb = NL * (NL - 1);
-  auto combo = [&](long a) { return (lig_aux[2 * a + 1] > 0.5f ? 8 : 0) + lig_v[a]; };
-  const float4* t4 = reinterpret_cast<const float4*>(tab);
-  if (idx < atom_f4) {
-    constexpr int PER = 160 + 320 + 32 + 32;             // float4 per atom: 640 + 1280 + 128 + 128 floats
+  const int NP = r.NP, NL = r.NL, N = NP + NL, Eb = NL * (NL - 1);
+  auto combo = [&](long a) { return (r.lig_aux[2 * a + 1] > 0.5f ? 8 : 0) + r.lig_v[a]; };
+  const float4* t4 = reinterpret_cast<const float4*>(r.tab);
+  if (idx < r.atom_f4) {
+    constexpr int PER = DD_L0_ATOM_F4;
     const long a = idx / PER;
     const int k = (int)(idx % PER);
     const int b = (int)(a / NL), i = (int)(a % NL);
     const int c = combo(a);
     const long node = (long)b * N + NP + i;
-    if (k < 160) reinterpret_cast<float4*>(l0_P + node * 640)[k] = t4[(L0_TN + c * 640) / 4 + k];
-    else if (k < 480) reinterpret_cast<float4*>(PL + a * 1280)[k - 160] = t4[(L0_TL + c * 1280) / 4 + (k - 160)];
-    else if (k < 512) reinterpret_cast<float4*>(l0_qn + node * 128)[k - 480] = t4[(L0_TQN + c * 128) / 4 + (k - 480)];
-    else reinterpret_cast<float4*>(qlnb + a * 128)[k - 512] = t4[(L0_TQL + c * 128) / 4 + (k - 512)];
+    if (k < 160) reinterpret_cast<float4*>(r.l0_P + node * 640)[k] = t4[(L0_TN + c * 640) / 4 + k];
+    else if (k < 480) reinterpret_cast<float4*>(r.PL + a * 1280)[k - 160] = t4[(L0_TL + c * 1280) / 4 + (k - 160)];
+    else if (k < 512) reinterpret_cast<float4*>(r.l0_qn + node * 128)[k - 480] = t4[(L0_TQN + c * 128) / 4 + (k - 480)];
+    else reinterpret_cast<float4*>(r.qlnb + a * 128)[k - 512] = t4[(L0_TQL + c * 128) / 4 + (k - 512)];
     return;
   }
-  constexpr int PERB = 160 + 32;                         // float4 per bond: 640 + 128 floats
-  const long j = idx - atom_f4;
+  constexpr int PERB = DD_L0_BOND_F4;
+  const long j = idx - r.atom_f4;
   const long e = j / PERB;
-  if (e >= (long)B * Eb) return;
+  if (e >= (long)r.B * Eb) return;
   const int k = (int)(j % PERB);
-  const int ty = bond[e];
+  const int ty = r.bond[e];
   if (k < 160) {
-    reinterpret_cast<float4*>(PB + e * 640)[k] = t4[(L0_TB + ty * 640) / 4 + k];
+    reinterpret_cast<float4*>(r.PB + e * 640)[k] = t4[(L0_TB + ty * 640) / 4 + k];
   } else {
     const int b = (int)(e / Eb), t = (int)((e % Eb) / (NL - 1));
     const int c = combo((long)b * NL + t);
-    reinterpret_cast<float4*>(qb + e * 128)[k - 160] = t4[(L0_TQB + (c * 5 + ty) * 128) / 4 + (k - 160)];
+    reinterpret_cast<float4*>(r.qb + e * 128)[k - 160] = t4[(L0_TQB + (c * 5 + ty) * 128) / 4 + (k - 160)];
   }
 }
-__global__ __launch_bounds__(256) void k_layer0_rows(const float* __restrict__ tab, const int32_t* __restrict__ lig_v,
-                                                     const float* __restrict__ lig_aux, const int32_t* __restrict__ bond, int B,
-                                                     int NP, int NL, float* __restrict__ l0_P, float* __restrict__ PL,
-                                                     float* __restrict__ l0_qn, float* __restrict__ qlnb, float* __restrict__ PB,
-                                                     float* __restrict__ qb, long atom_f4) {
-  layer0_rows_block(blockIdx.x, tab, lig_v, lig_aux, bond, B, NP, NL, l0_P, PL, l0_qn, qlnb, PB, qb, atom_f4);
-}
+__global__ __launch_bounds__(256) void k_layer0_rows(const Layer0RowsArgs r) { layer0_rows_block(blockIdx.x, r); }
 
 // ------------------------------------------------------------------------------ head of a forward: two launches
 // Everything the first attention layer waits for that only depends on the state the previous reverse step left:
-// k_head_graph -- the kNN graph + edge weights, one wave per centre (the bodies of k_knn and k_edge_weights2, the list
+// k_graph -- the kNN graph + edge weights, one wave per centre (the bodies of k_knn and k_edge_weights2, the list
 // handed over through LDS; x_t is read from the sampler's protein / ligand position buffers, so the launch does not
 // wait for the workspace copy the embedding blocks write); k_head_rows -- the embeddings / context (with the zeroed work
 // counters and the step index) and the layer-0 rows (the bodies of k_embed_all and k_layer0_rows as two block ranges).
 // Outputs bit-identical to the four separate launches.
-struct HeadArgs {
-  // graph
-  int B, NP, NL, K;
-  const float *protein_pos, *lig_pos;
-  int32_t* nbr;
-  float* ew;
-  const float *EW_W1T, *EW_b1, *EW_ln, *EW_w2, *EW_b2;
-  const int32_t *np_real, *nl_real;
-  // embeddings
-  const float* protein_h;
-  const int32_t* lig_v;
-  const float* lig_aux;
-  const float *Wl, *bl;
-  float *h, *xa, *xb;
-  const int32_t* bond;
-  long bond_rows;
-  const float *Wb, *bb;
-  float* hb;
-  int32_t *counters, *advance;
-  int nv;                   // atom classes (columns of the ligand embedding before the two indicators)
-  // layer-0 rows (tab == nullptr: none)
-  const float* tab;
-  float *l0_P, *PL, *l0_qn, *qlnb, *PB, *qb;
-  long atom_f4;
-  int n_graph, n_embed_nodes, n_embed;
-};
+//
+// Block boundary: a refine net with num_blocks > 1 rebuilds the kNN graph and the edge weights from the CURRENT context
+// coordinates before every block but the first (uni_transformer_edge.py:402-427).  That is the same k_graph launch on one
+// [B, N, 3] block of the workspace (w.xa / w.xb, whichever holds x behind the previous block's last layer) instead of the
+// sampler's separate buffers: the two differ in the GraphArgs' base pointers and strides only, so equal coordinates give the
+// same nbr rows and the same e_w bits as the head's launch.  Padding atoms are neither centres nor candidates.
+// All N atoms are candidates again.  The protein-protein distances do not change between blocks, but that is not exploited:
+// a centre's list is ONE selection over protein and ligand candidates in (distance, index) order, so a protein centre near
+// the ligand needs the moved ligand atoms ranked among its protein neighbours anyway (EXPERIMENTS.md).
 // KW: the width of the LDS hand-off srt -- 32 for K <= 32 (the shipped graph), 64 for K <= DD_KNN_MAX
 template <int CAND, int KW>
-__global__ __launch_bounds__(256, 3) void k_head_graph(const HeadArgs a) {
+__global__ __launch_bounds__(256, 3) void k_graph(const GraphArgs a) {
   __shared__ unsigned long long sel[4][64];
   __shared__ int32_t srt[4][KW];
   __shared__ __attribute__((aligned(16))) float lw[512];
@@ -479,60 +436,15 @@ __global__ __launch_bounds__(256, 3) void k_head_graph(const HeadArgs a) {
     if (lane < a.K) a.nbr[(long)centre * a.K + lane] = 0;
     return;
   }
-  const PosView pv{a.protein_pos + (long)b * a.NP * 3, a.lig_pos + (long)b * a.NL * 3, a.NP};
+  const PosView pv = pos_view(a, b);
   knn_wave<CAND>(pv, i, N, a.K, a.nbr + (long)centre * a.K, masked, npb, nlb, sel[w], srt[w]);
   ew_wave(pv, i, a.K, srt[w], a.EW_W1T, lw, a.EW_b2, a.ew + (long)centre * a.K);
 }
 // (a kernel of its own: the copy blocks need many waves per SIMD, the graph blocks ~200 registers per lane)
-__global__ __launch_bounds__(256) void k_head_rows(const HeadArgs a) {
+__global__ __launch_bounds__(256) void k_head_rows(const EmbedArgs e, const Layer0RowsArgs r) {
   const unsigned blk = blockIdx.x;
-  if ((int)blk < a.n_embed) {
-    embed_block(blk, a.protein_h, a.protein_pos, a.lig_pos, a.lig_v, a.lig_aux, a.Wl, a.bl, a.B, a.NP, a.NL, a.h, a.xa, a.xb, a.bond,
-                a.bond_rows, a.Wb, a.bb, a.hb, a.counters, a.n_embed_nodes, a.advance, a.nv);
-    return;
-  }
-  layer0_rows_block(blk - a.n_embed, a.tab, a.lig_v, a.lig_aux, a.bond, a.B, a.NP, a.NL, a.l0_P, a.PL, a.l0_qn, a.qlnb, a.PB, a.qb,
-                    a.atom_f4);
-}
-
-// ------------------------------------------------------------------------------ block boundary: one launch
-// A refine net with num_blocks > 1 rebuilds the kNN graph and the edge weights from the CURRENT context coordinates before
-// every block but the first (uni_transformer_edge.py:402-427).  k_block_graph is k_head_graph on one [B, N, 3] block of the
-// workspace (w.xa / w.xb, whichever holds x behind the previous block's last layer) instead of the sampler's separate
-// protein / ligand buffers: the same knn_wave / ew_wave bodies with the same template arguments, so equal coordinates give
-// the same nbr rows and the same e_w bits as the head's launch.  Padding atoms are neither centres nor candidates.
-// All N atoms are candidates again.  The protein-protein distances do not change between blocks, but that is not exploited:
-// a centre's list is ONE selection over protein and ligand candidates in (distance, index) order, so a protein centre near
-// the ligand needs the moved ligand atoms ranked among its protein neighbours anyway (EXPERIMENTS.md).
-struct BlockGraphArgs {
-  int B, NP, NL, K;
-  const float* x;           // [B, NP + NL, 3]
-  int32_t* nbr;
-  float* ew;
-  const float *EW_W1T, *EW_b1, *EW_ln, *EW_w2, *EW_b2;
-  const int32_t *np_real, *nl_real;
-};
-template <int CAND, int KW>
-__global__ __launch_bounds__(256, 3) void k_block_graph(const BlockGraphArgs a) {
-  __shared__ unsigned long long sel[4][64];
-  __shared__ int32_t srt[4][KW];
-  __shared__ __attribute__((aligned(16))) float lw[512];
-  ew_stage(lw, a.EW_b1, a.EW_ln, a.EW_w2);
-  __syncthreads();                                       // (before any wave leaves)
-  const int N = a.NP + a.NL, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int centre = (int)blockIdx.x * 4 + w;
-  if (centre >= a.B * N) return;
-  const int b = centre / N, i = centre % N;
-  const bool masked = a.nl_real != nullptr;
-  const int npb = masked && a.np_real ? a.np_real[b] : a.NP, nlb = masked ? a.nl_real[b] : a.NL;
-  if (masked && !atom_is_real(i, a.NP, npb, nlb)) {        // a padding atom is no centre: its list is never read
-    if (lane < a.K) a.nbr[(long)centre * a.K + lane] = 0;
-    return;
-  }
-  const float* xb = a.x + (long)b * N * 3;
-  const PosView pv{xb, xb + 3 * (long)a.NP, a.NP};
-  knn_wave<CAND>(pv, i, N, a.K, a.nbr + (long)centre * a.K, masked, npb, nlb, sel[w], srt[w]);
-  ew_wave(pv, i, a.K, srt[w], a.EW_W1T, lw, a.EW_b2, a.ew + (long)centre * a.K);
+  if ((int)blk < e.blocks) embed_block(blk, e);
+  else layer0_rows_block(blk - e.blocks, r);
 }
 
 // --------------------------------------------------------------------------- bond-layer assemble
@@ -682,136 +594,87 @@ int launch_xupdate(const float* x, const float* dxe, const float* dxb, int B, in
   return DD_OK;
 }
 
-int launch_knn(const float* x, int B, int N, int K, int32_t* nbr, hipStream_t st, int NP, const int32_t* np_real,
-               const int32_t* nl_real) {
-  const dim3 grid((B * N + 3) / 4), block(256);
-  const int cand = (N + 63) / 64;
-  if (NP < 0) { NP = N; np_real = nl_real = nullptr; }
-  if (cand <= 2) hipLaunchKernelGGL(k_knn<2>, grid, block, 0, st, x, B, N, K, nbr, NP, np_real, nl_real);
-  else if (cand <= 4) hipLaunchKernelGGL(k_knn<4>, grid, block, 0, st, x, B, N, K, nbr, NP, np_real, nl_real);
-  else if (cand <= 6) hipLaunchKernelGGL(k_knn<6>, grid, block, 0, st, x, B, N, K, nbr, NP, np_real, nl_real);
-  else if (cand <= 11) hipLaunchKernelGGL(k_knn<11>, grid, block, 0, st, x, B, N, K, nbr, NP, np_real, nl_real);
-  else if (cand <= 16) hipLaunchKernelGGL(k_knn<16>, grid, block, 0, st, x, B, N, K, nbr, NP, np_real, nl_real);
-  else hipLaunchKernelGGL(k_knn<DD_N_MAX / 64>, grid, block, 0, st, x, B, N, K, nbr, NP, np_real, nl_real);
+// Candidates per lane are a template argument of the kNN kernels: calls f(std::integral_constant<int, C>) for the first
+// class C of the list with cand <= C (the last one holds every supported size)
+template <int C, int... Rest, class F>
+static void with_cand_class(int cand, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, C>{});
+  else if (cand <= C) f(std::integral_constant<int, C>{});
+  else with_cand_class<Rest...>(cand, f);
+}
+static dim3 graph_grid(const GraphArgs& a) { return dim3((unsigned)((a.B * (a.NP + a.NL) + 3) / 4)); }   // one wave per centre
+
+// (launch_knn / launch_edge_weights: one [B, N, 3] block only; shapes are checked by their callers, the op-level entry
+// points and check_shapes)
+static bool is_block(const GraphArgs& a) {
+  return a.lig == a.prot + 3 * (long)a.NP && a.prot_stride == 3 * (a.NP + a.NL) && a.lig_stride == a.prot_stride;
+}
+int launch_knn(const GraphArgs& a, hipStream_t st) {
+  if (!is_block(a)) return DD_ERR_BAD_ARG;
+  with_cand_class<2, 4, 6, 11, 16, DD_N_MAX / 64>((a.NP + a.NL + 63) / 64, [&](auto c) {
+    hipLaunchKernelGGL(k_knn<decltype(c)::value>, graph_grid(a), dim3(256), 0, st, a);
+  });
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
-int launch_edge_weights(const float* x, const int32_t* nbr, int B, int N, int K, const float* W1T, const float* b1,
-                        const float* ln, const float* w2, const float* b2, float* ew, hipStream_t st, int NP, const int32_t* np_real,
-                        const int32_t* nl_real) {
-  if (NP < 0) { NP = N; np_real = nl_real = nullptr; }
-  hipLaunchKernelGGL(k_edge_weights2, dim3((B * N + 3) / 4), dim3(256), 0, st, x, nbr, B, N, K, W1T, b1, ln, w2, b2, ew, NP, np_real, nl_real);
+int launch_edge_weights(const GraphArgs& a, hipStream_t st) {
+  if (!is_block(a)) return DD_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_edge_weights2, graph_grid(a), dim3(256), 0, st, a);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
-int launch_embed_all(const float* protein_h, const float* protein_pos, const float* lig_pos, const int32_t* lig_v,
-                     const float* lig_aux, const float* Wl, const float* bl, int B, int NP, int NL, float* h, float* xa, float* xb,
-                     const int32_t* bond, long bond_rows, const float* Wb, const float* bb, float* hb, int32_t* counters,
-                     hipStream_t st, int32_t* advance, int nv) {
-  const long nn = (long)B * (NP + NL) * 128, nb = bond_rows * 128;
-  const int node_blocks = (int)((nn + 255) / 256), bond_blocks = (int)((nb + 255) / 256);
-  hipLaunchKernelGGL(k_embed_all, dim3(node_blocks + bond_blocks), dim3(256), 0, st, protein_h, protein_pos, lig_pos, lig_v, lig_aux,
-                     Wl, bl, B, NP, NL, h, xa, xb, bond, bond_rows, Wb, bb, hb, counters, node_blocks, advance, nv);
+int launch_graph(const GraphArgs& a, hipStream_t st) {
+  const int N = a.NP + a.NL;
+  if (!a.lig || (a.NP > 0 && !a.prot) || !a.nbr || !a.ew || a.B <= 0 || a.NP < 0 || a.NL <= 0) return DD_ERR_BAD_ARG;
+  if (a.K <= 0 || a.K > DD_KNN_MAX || a.K > N - 1 || N > DD_N_MAX) return DD_ERR_UNSUPPORTED_SHAPE;
+  with_cand_class<2, 4, 6, 11, 16, DD_N_MAX / 64>((N + 63) / 64, [&](auto c) {
+    constexpr int CAND = decltype(c)::value;
+    if (a.K <= 32) hipLaunchKernelGGL((k_graph<CAND, 32>), graph_grid(a), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_graph<CAND, 64>), graph_grid(a), dim3(256), 0, st, a);
+  });
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
-template <int KW>
-static void launch_head_graph(const HeadArgs& a, int N, dim3 grid, dim3 block, hipStream_t st) {
-  const int cand = (N + 63) / 64;
-  if (cand <= 2) hipLaunchKernelGGL((k_head_graph<2, KW>), grid, block, 0, st, a);
-  else if (cand <= 4) hipLaunchKernelGGL((k_head_graph<4, KW>), grid, block, 0, st, a);
-  else if (cand <= 6) hipLaunchKernelGGL((k_head_graph<6, KW>), grid, block, 0, st, a);
-  else if (cand <= 11) hipLaunchKernelGGL((k_head_graph<11, KW>), grid, block, 0, st, a);
-  else if (cand <= 16) hipLaunchKernelGGL((k_head_graph<16, KW>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_head_graph<DD_N_MAX / 64, KW>), grid, block, 0, st, a);
-}
-int launch_head_all(const float* protein_h, const float* protein_pos, const float* lig_pos, const int32_t* lig_v,
-                    const float* lig_aux, const float* Wl, const float* bl, int B, int NP, int NL, int K, float* h, float* xa, float* xb,
-                    const int32_t* bond, long bond_rows, const float* Wb, const float* bb, float* hb, int32_t* counters,
-                    int32_t* advance, int32_t* nbr, float* ew, const float* EW_W1T, const float* EW_b1, const float* EW_ln,
-                    const float* EW_w2, const float* EW_b2, const int32_t* np_real, const int32_t* nl_real, const float* l0_tables,
-                    float* l0_P, float* PL, float* l0_qn, float* qlnb, float* PB, float* qb, hipStream_t st, int parts, int nv) {
-  if (K > DD_KNN_MAX || (parts & 3) == 0 || (l0_tables != nullptr && nv != DD_NUM_V)) return DD_ERR_UNSUPPORTED_SHAPE;
-  const int N = NP + NL;
-  HeadArgs a;
-  a.B = B; a.NP = NP; a.NL = NL; a.K = K;
-  a.protein_pos = protein_pos; a.lig_pos = lig_pos; a.nbr = nbr; a.ew = ew;
-  a.EW_W1T = EW_W1T; a.EW_b1 = EW_b1; a.EW_ln = EW_ln; a.EW_w2 = EW_w2; a.EW_b2 = EW_b2;
-  a.np_real = np_real; a.nl_real = nl_real;
-  a.protein_h = protein_h; a.lig_v = lig_v; a.lig_aux = lig_aux; a.Wl = Wl; a.bl = bl; a.h = h; a.xa = xa; a.xb = xb;
-  a.bond = bond; a.bond_rows = bond_rows; a.Wb = Wb; a.bb = bb; a.hb = hb; a.counters = counters; a.advance = advance;
-  a.nv = nv;
-  a.tab = l0_tables; a.l0_P = l0_P; a.PL = PL; a.l0_qn = l0_qn; a.qlnb = qlnb; a.PB = PB; a.qb = qb;
-  const long nn = (long)B * N * 128, nb = bond_rows * 128;
-  a.n_embed_nodes = (int)((nn + 255) / 256);
-  a.n_embed = a.n_embed_nodes + (int)((nb + 255) / 256);
-  a.n_graph = (B * N + 3) / 4;
-  a.atom_f4 = (long)B * NL * (160 + 320 + 32 + 32);
-  const long bond_f4 = (long)B * NL * (NL - 1) * (160 + 32);
-  const int n_l0 = l0_tables ? (int)((a.atom_f4 + bond_f4 + 255) / 256) : 0;
-  const dim3 block(256);
-  if (parts & 2) hipLaunchKernelGGL(k_head_rows, dim3((unsigned)(a.n_embed + n_l0)), block, 0, st, a);   // parts: 2 = embedding + layer-0 rows
-  if (parts & 1) {                                                                                        //        1 = graph
-    const dim3 grid((unsigned)a.n_graph);
-    if (K <= 32) launch_head_graph<32>(a, N, grid, block, st);
-    else launch_head_graph<64>(a, N, grid, block, st);
-  }
+int launch_embed(const EmbedArgs& e, hipStream_t st) {
+  hipLaunchKernelGGL(k_embed_all, dim3((unsigned)e.blocks), dim3(256), 0, st, e);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
-template <int KW>
-static void launch_block_graph_kw(const BlockGraphArgs& a, int N, dim3 grid, dim3 block, hipStream_t st) {
-  const int cand = (N + 63) / 64;                          // (the head launch's classes: same CAND for the same N)
-  if (cand <= 2) hipLaunchKernelGGL((k_block_graph<2, KW>), grid, block, 0, st, a);
-  else if (cand <= 4) hipLaunchKernelGGL((k_block_graph<4, KW>), grid, block, 0, st, a);
-  else if (cand <= 6) hipLaunchKernelGGL((k_block_graph<6, KW>), grid, block, 0, st, a);
-  else if (cand <= 11) hipLaunchKernelGGL((k_block_graph<11, KW>), grid, block, 0, st, a);
-  else if (cand <= 16) hipLaunchKernelGGL((k_block_graph<16, KW>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_block_graph<DD_N_MAX / 64, KW>), grid, block, 0, st, a);
-}
-int launch_block_graph(const float* x, int B, int NP, int NL, int K, int32_t* nbr, float* ew, const float* EW_W1T, const float* EW_b1,
-                       const float* EW_ln, const float* EW_w2, const float* EW_b2, const int32_t* np_real, const int32_t* nl_real,
-                       hipStream_t st) {
-  const int N = NP + NL;
-  if (!x || !nbr || !ew || B <= 0 || NP < 0 || NL <= 0) return DD_ERR_BAD_ARG;
-  if (K <= 0 || K > DD_KNN_MAX || K > N - 1 || N > DD_N_MAX) return DD_ERR_UNSUPPORTED_SHAPE;
-  BlockGraphArgs a;
-  a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.x = x; a.nbr = nbr; a.ew = ew;
-  a.EW_W1T = EW_W1T; a.EW_b1 = EW_b1; a.EW_ln = EW_ln; a.EW_w2 = EW_w2; a.EW_b2 = EW_b2;
-  a.np_real = np_real; a.nl_real = nl_real;
-  const dim3 grid((unsigned)((B * N + 3) / 4)), block(256);
-  if (K <= 32) launch_block_graph_kw<32>(a, N, grid, block, st);
-  else launch_block_graph_kw<64>(a, N, grid, block, st);
+int launch_layer0_rows(const Layer0RowsArgs& r, hipStream_t st) {
+  hipLaunchKernelGGL(k_layer0_rows, dim3((unsigned)r.blocks), dim3(256), 0, st, r);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
-int launch_layer0_rows(const float* tables, const int32_t* lig_v, const float* lig_aux, const int32_t* bond, int B, int NP, int NL,
-                       float* l0_P, float* PL, float* l0_qn, float* qlnb, float* PB, float* qb, hipStream_t st) {
-  const long atom_f4 = (long)B * NL * (160 + 320 + 32 + 32), bond_f4 = (long)B * NL * (NL - 1) * (160 + 32);
-  hipLaunchKernelGGL(k_layer0_rows, dim3((unsigned)((atom_f4 + bond_f4 + 255) / 256)), dim3(256), 0, st, tables, lig_v, lig_aux, bond,
-                     B, NP, NL, l0_P, PL, l0_qn, qlnb, PB, qb, atom_f4);
+int launch_head_rows(const EmbedArgs& e, const Layer0RowsArgs* r, hipStream_t st) {
+  if (r != nullptr && e.nv != DD_NUM_V) return DD_ERR_UNSUPPORTED_SHAPE;   // (the tables hold DD_NUM_V classes x arm flag)
+  hipLaunchKernelGGL(k_head_rows, dim3((unsigned)(e.blocks + (r ? r->blocks : 0))), dim3(256), 0, st, e, r ? *r : Layer0RowsArgs{});
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
-int launch_bl_assemble(const float* x, const float* PB, const float* PL, const float* Wgp, int B, int NP, int NL, float* Ek, float* Ev,
-                       float* q1, float* Rk, float* Rv, hipStream_t st, const float* xprev, const float* dxe, const float* dxb,
-                       float* xout, FlagWait fw) {
-  if (Wgp == nullptr) return DD_ERR_BAD_ARG;
-  const long rows = (long)B * NL * (NL - 1);
+int launch_bl_assemble(const AssembleArgs& a, hipStream_t st) {
+  if (a.Wgp == nullptr) return DD_ERR_BAD_ARG;
+  const long rows = (long)a.B * a.NL * (a.NL - 1);
   const long tiles = (rows + 15) / 16;
   const int bpo = (int)((tiles + 3) / 4);                            // blocks per output (4 tiles each)
-  hipLaunchKernelGGL(k_bl_assemble3, dim3((unsigned)(bpo * (q1 ? 5 : 4))), dim3(256), 0, st, x, PB, PL, Wgp, B, NP, NL, Ek, Ev, q1,
-                     Rk, Rv, bpo, xprev, dxe, dxb, xout, fw);
+  hipLaunchKernelGGL(k_bl_assemble3, dim3((unsigned)(bpo * (a.q1 ? 5 : 4))), dim3(256), 0, st, a.x, a.PB, a.PL, a.Wgp, a.B, a.NP, a.NL,
+                     a.Ek, a.Ev, a.q1, a.Rk, a.Rv, bpo, a.xprev, a.dxe, a.dxb, a.xout, a.fw);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
 
 }  // namespace dd
 
+// Op-level graph entry points: a [B, N, 3] tensor is a problem of N "protein" rows (no ligand block, no padding)
+static dd::GraphArgs graph_args(const float* x, int B, int NP, int NL, int K, int32_t* nbr) {
+  dd::GraphArgs a{};
+  a.B = B; a.NP = NP; a.NL = NL; a.K = K; a.nbr = nbr;
+  a.set_block(x);
+  return a;
+}
 extern "C" int dd_knn(const float* x, int B, int N, int K, int32_t* nbr, void* stream) {
   if (!x || !nbr || B <= 0 || N <= 1) return DD_ERR_BAD_ARG;
   if (N > DD_N_MAX || K > DD_KNN_MAX || K > N - 1 || K <= 0) return DD_ERR_UNSUPPORTED_SHAPE;
-  return dd::launch_knn(x, B, N, K, nbr, (hipStream_t)stream);
+  return dd::launch_knn(graph_args(x, B, N, 0, K, nbr), (hipStream_t)stream);
 }
 
 // ... for a padded heterogeneous batch (the sampler's layout: NP + NL rows per sample, the real atoms are the first np_real[b]
@@ -820,7 +683,9 @@ extern "C" int dd_knn_masked(const float* x, int B, int NP, int NL, int K, const
                              void* stream) {
   const int N = NP + NL;
   if (!x || !nbr || !nl_real || B <= 0 || NP < 0 || NL <= 0 || K <= 0 || K > DD_KNN_MAX || K > N - 1 || N > DD_N_MAX) return DD_ERR_BAD_ARG;
-  return dd::launch_knn(x, B, N, K, nbr, (hipStream_t)stream, NP, np_real, nl_real);
+  dd::GraphArgs a = graph_args(x, B, NP, NL, K, nbr);
+  a.np_real = np_real; a.nl_real = nl_real;
+  return dd::launch_knn(a, (hipStream_t)stream);
 }
 
 // ... for a flat PyG batch of different samples (k_knn_csr).  n_max (the largest sample) only picks the chunk size: the
@@ -832,15 +697,10 @@ extern "C" int dd_knn_csr(const float* x, const int32_t* ptr, int B, int n, int 
   if (n == 0 || E == 0) return DD_OK;
   if (!x || !edge_index) return DD_ERR_BAD_ARG;
   const dim3 grid((unsigned)(((long)n + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const int cand = (n_max + 63) / 64;
-#define DD_KNN_CSR(C) hipLaunchKernelGGL(dd::k_knn_csr<C>, grid, block, 0, st, x, ptr, B, n, K, loop, out_off, (long)E, edge_index)
-  if (cand <= 2) DD_KNN_CSR(2);
-  else if (cand <= 4) DD_KNN_CSR(4);
-  else if (cand <= 8) DD_KNN_CSR(8);
-  else if (cand <= 16) DD_KNN_CSR(16);
-  else DD_KNN_CSR(DD_N_MAX / 64);
-#undef DD_KNN_CSR
+  dd::with_cand_class<2, 4, 8, 16, DD_N_MAX / 64>((n_max + 63) / 64, [&](auto c) {
+    hipLaunchKernelGGL(dd::k_knn_csr<decltype(c)::value>, grid, block, 0, (hipStream_t)stream, x, ptr, B, n, K, loop, out_off, (long)E,
+                       edge_index);
+  });
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
@@ -849,7 +709,9 @@ extern "C" int dd_edge_weights(const float* x, const int32_t* nbr, int B, int N,
                                const float* b1, const float* ln, const float* w2, const float* b2, float* ew,
                                void* stream) {
   if (!x || !nbr || !W1T || !b1 || !ln || !w2 || !b2 || !ew) return DD_ERR_BAD_ARG;
-  return dd::launch_edge_weights(x, nbr, B, N, K, W1T, b1, ln, w2, b2, ew, (hipStream_t)stream);
+  dd::GraphArgs a = graph_args(x, B, N, 0, K, const_cast<int32_t*>(nbr));   // (the list is only read here)
+  a.ew = ew; a.EW_W1T = W1T; a.EW_b1 = b1; a.EW_ln = ln; a.EW_w2 = w2; a.EW_b2 = b2;
+  return dd::launch_edge_weights(a, (hipStream_t)stream);
 }
 
 extern "C" int dd_embed_protein(const float* protein_v, int rows, const float* W, const float* b, float* protein_h,

@@ -72,40 +72,79 @@ int launch_gemm128_batch(const GemmArgs* jobs, int njobs, hipStream_t st);
 struct NodeOutArgs { const float* Ae; const float* Ab; const float* h; float* out; const float* blk; int B, NP, NL; };
 int launch_node_out_fc(const NodeOutArgs& a, hipStream_t st);
 
-int launch_embed_all(const float* protein_h, const float* protein_pos, const float* lig_pos, const int32_t* lig_v,
-                     const float* lig_aux, const float* Wl, const float* bl, int B, int NP, int NL, float* h, float* xa, float* xb,
-                     const int32_t* bond, long bond_rows, const float* Wb, const float* bb, float* hb, int32_t* counters,
-                     hipStream_t st, int32_t* advance = nullptr, int nv = DD_NUM_V);
+// ---- head of a forward, block boundaries and the bond-layer assemble (dd_graph.hip); built by dd_api.hip::Fwd
+// One kNN + edge-weight problem: B samples of NP protein + NL ligand atoms (an op-level [B, N, 3] tensor: NP = N, NL = 0).
+struct GraphArgs {
+  int B, NP, NL, K;
+  // positions: the first protein row and the first ligand row of sample 0, each with its per-sample stride in floats --
+  // the sampler's separate buffers (protein_pos, 3 NP) and (lig_pos, 3 NL), or one [B, N, 3] block (set_block)
+  const float* prot; int prot_stride;
+  const float* lig; int lig_stride;
+  int32_t* nbr;            // [B,N,K]
+  float* ew;               // [B,N,K] (launch_knn: unused)
+  const float *EW_W1T, *EW_b1, *EW_ln, *EW_w2, *EW_b2;   // edge-weight MLP (launch_knn: unused)
+  // padded heterogeneous batches: padding atoms are neither centres nor candidates (NULL: dense batch)
+  const int32_t *np_real, *nl_real;
+  void set_block(const float* x) { prot = x; lig = x + 3 * (long)NP; prot_stride = lig_stride = 3 * (NP + NL); }
+};
+int launch_graph(const GraphArgs& a, hipStream_t st);              // kNN + edge weights in one launch, the list handed over through LDS
+// the two halves as launches of their own (edge weights: of the lists in nbr): positions in one [B, N, 3] block only
+int launch_knn(const GraphArgs& a, hipStream_t st);
+int launch_edge_weights(const GraphArgs& a, hipStream_t st);
+
+// Embeddings / context: 256-thread blocks [0, node_blocks) write one float of h each (+ the workspace copies of x_t), blocks
+// [node_blocks, blocks) one float of h_bond; block 0 also zeroes the work counters and advances the step index.
+struct EmbedArgs {
+  int B, NP, NL;
+  int nv;                   // atom classes (columns of the ligand embedding before the two indicators)
+  // inputs: sampler state and embedding weights
+  const float *protein_h, *protein_pos, *lig_pos;
+  const int32_t* lig_v;
+  const float* lig_aux;
+  const int32_t* bond;
+  const float *Wl, *bl, *Wb, *bb;
+  // outputs: h, both copies of x, h_bond
+  float *h, *xa, *xb, *hb;
+  int32_t *counters, *advance;   // (either may be NULL)
+  long bond_rows;           // B NL (NL - 1)
+  int node_blocks, blocks;
+};
+// Layer-0 rows of the ligand atoms / bonds gathered from dd_sampler.l0_tables (see include/decompdiff_hip.h): one thread per
+// float4, the atoms' [0, atom_f4) in front of the bonds'
+constexpr int DD_L0_ATOM_F4 = 160 + 320 + 32 + 32;   // float4 per atom: 640 + 1280 + 128 + 128 floats
+constexpr int DD_L0_BOND_F4 = 160 + 32;              // float4 per bond: 640 + 128 floats
+struct Layer0RowsArgs {
+  int B, NP, NL;
+  const float* tab;
+  const int32_t* lig_v;
+  const float* lig_aux;
+  const int32_t* bond;
+  float *l0_P, *PL, *l0_qn, *qlnb, *PB, *qb;
+  long atom_f4;
+  int blocks;
+};
+int launch_embed(const EmbedArgs& e, hipStream_t st);
+int launch_layer0_rows(const Layer0RowsArgs& r, hipStream_t st);
+int launch_head_rows(const EmbedArgs& e, const Layer0RowsArgs* r /*NULL: no tables*/, hipStream_t st);   // both, one launch
+
+// Host-side arguments of the bond-layer assemble launch (k_bl_assemble3 takes them one by one)
+struct AssembleArgs {
+  const float *x, *PB, *PL, *Wgp;
+  int B, NP, NL;
+  float *Ek, *Ev, *q1, *Rk, *Rv;   // (q1 may be NULL: the query GEMM sums its hidden rows itself)
+  // deferred coordinate update of the previous layer (xprev != NULL): xout = xprev + dxe + dxb on the ligand rows
+  const float *xprev, *dxe, *dxb;
+  float* xout;
+  FlagWait fw;              // PB / PL produced by the layer-tail queue (measurement build)
+};
+int launch_bl_assemble(const AssembleArgs& a, hipStream_t st);
 int launch_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                         float* grad, int accumulate, int norm_B, hipStream_t st);
 int launch_drift_arms_repul(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float max_d, int mode, float* grad,
                             int accumulate, int norm_B, hipStream_t st);
-// (NP, np_real, nl_real: padded heterogeneous batches -- padding atoms are neither centres nor candidates)
+// (nl_real: padded heterogeneous batches -- padding atoms are neither centres nor candidates)
 int launch_drift_clash(const float* lig_pos, const float* offset, const float* full_protein_pos, int B, int NL, int NF,
                        float sigma, float gamma, float* grad, int accumulate, const int32_t* nl_real, hipStream_t st);
-int launch_knn(const float* x, int B, int N, int K, int32_t* nbr, hipStream_t st, int NP = -1, const int32_t* np_real = nullptr,
-               const int32_t* nl_real = nullptr);
-int launch_edge_weights(const float* x, const int32_t* nbr, int B, int N, int K, const float* W1T, const float* b1,
-                        const float* ln, const float* w2, const float* b2, float* ew, hipStream_t st, int NP = -1,
-                        const int32_t* np_real = nullptr, const int32_t* nl_real = nullptr);
-int launch_bl_assemble(const float* x, const float* PB, const float* PL, const float* Wgp, int B, int NP, int NL, float* Ek, float* Ev,
-                       float* q1, float* Rk, float* Rv, hipStream_t st, const float* xprev = nullptr, const float* dxe = nullptr,
-                       const float* dxb = nullptr, float* xout = nullptr, FlagWait fw = FlagWait{nullptr, -1, 0, -1, 0});
-// layer-0 rows of the ligand atoms / bonds gathered from dd_sampler.l0_tables (see include/decompdiff_hip.h)
-int launch_layer0_rows(const float* tables, const int32_t* lig_v, const float* lig_aux, const int32_t* bond, int B, int NP, int NL,
-                       float* l0_P, float* PL, float* l0_qn, float* qlnb, float* PB, float* qb, hipStream_t st);
-// head of a forward: kNN graph + edge weights (parts & 1), embeddings / context + layer-0 rows (parts & 2; l0_tables may be NULL)
-// block boundary of a num_blocks > 1 refine net: kNN graph + edge weights from the workspace's current x (dd_graph.hip)
-int launch_block_graph(const float* x, int B, int NP, int NL, int K, int32_t* nbr, float* ew, const float* EW_W1T, const float* EW_b1,
-                       const float* EW_ln, const float* EW_w2, const float* EW_b2, const int32_t* np_real, const int32_t* nl_real,
-                       hipStream_t st);
-int launch_head_all(const float* protein_h, const float* protein_pos, const float* lig_pos, const int32_t* lig_v,
-                    const float* lig_aux, const float* Wl, const float* bl, int B, int NP, int NL, int K, float* h, float* xa, float* xb,
-                    const int32_t* bond, long bond_rows, const float* Wb, const float* bb, float* hb, int32_t* counters,
-                    int32_t* advance, int32_t* nbr, float* ew, const float* EW_W1T, const float* EW_b1, const float* EW_ln,
-                    const float* EW_w2, const float* EW_b2, const int32_t* np_real, const int32_t* nl_real, const float* l0_tables,
-                    float* l0_P, float* PL, float* l0_qn, float* qlnb, float* PB, float* qb, hipStream_t st, int parts = 3,
-                    int nv = DD_NUM_V);
 int launch_extract_ligand(const float* x, int B, int NP, int NL, float* out, hipStream_t st);
 
 enum { M_NE = 0, M_NB = 1, M_BL = 2, M_PE = 3, M_PB = 4 };

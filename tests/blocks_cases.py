@@ -47,11 +47,12 @@ def _fmt(e):
 
 
 # ------------------------------------------------------------------------------------ frozen coordinates: bit for bit
-def _frozen_pair():
+def _frozen_pair(**over):
     """(2 x 3 model, 1 x 6 model whose layers 3-5 are copies of 0-2), both with the second Linear of every xv MLP zeroed: no
     coordinate ever moves, so the second block's graph is the first block's and the two networks are the same function."""
-    if "frozen" not in _MODELS:
-        cfg2, cfg1 = BF.config(2, 3), BF.config(1, 6)
+    key = ("frozen", tuple(sorted(over.items())))
+    if key not in _MODELS:
+        cfg2, cfg1 = BF.config(2, 3, **over), BF.config(1, 6, **over)
         sd2 = synth.synthetic_state_dict(cfg2, 0)
         for k in sd2:
             if re.search(r"pos_layer_with_(edge|bond)\.xv_func\.net\.3\.(weight|bias)$", k):
@@ -62,17 +63,22 @@ def _frozen_pair():
             if m:
                 sd1[f"refine_net.base_block.{int(m.group(1)) + 3}.{m.group(2)}"] = v.clone()
         assert set(sd1) == set(synth.synthetic_state_dict(cfg1, 0))
-        _MODELS["frozen"] = (_load(cfg2, sd2), _load(cfg1, sd1))
-    return _MODELS["frozen"]
+        _MODELS[key] = (_load(cfg2, sd2), _load(cfg1, sd1))
+    return _MODELS[key]
 
 
-@pytest.mark.parametrize("layout", ["dense", "padded"])
+# (large, large_k48: 142 atoms per sample -- the block-boundary launch in candidate class 4 instead of 2, with the 32-wide and the
+# 64-wide hand-off of the neighbour list: it reproduces the head's lists and edge-weight bits from the workspace's [B, N, 3]
+# block, or the two models differ.  Both sides run the same kernels on the same bits: no kNN-gap condition is needed.)
+@pytest.mark.parametrize("layout", ["dense", "padded", "large", "large_k48"])
 def test_frozen_coordinates_two_blocks_equal_the_unrolled_one_block_model(layout):
-    two, one = _frozen_pair()
+    two, one = _frozen_pair(**(dict(knn=48) if layout == "large_k48" else {}))
     if layout == "dense":
         b = BF.forward_batch("2x3")
-    else:
+    elif layout == "padded":
         b = synth.concat_sampling_batches(BF.ragged_parts(BF.FROZEN_RAGGED))
+    else:
+        b = BF.batch(BF.FROZEN_LARGE, 2, BF.FROZEN_LARGE_SEED)
     a, c = fwd(two, b), fwd(one, b)
     torch.cuda.synchronize()
     x0 = torch.cat([b["init_ligand_pos"]]).to(dev())

@@ -35,6 +35,8 @@ TINY = [(1, 48, (4, 4), 4), (2, 20, (2, 2), 2), (5, 52, (5, 5), 6)]
 RAGGED_SEED, TINY_SEED, RAGGED_CHAIN_SEED = 51, 71, 251
 # frozen coordinates, padded: two samples of different sizes
 FROZEN_RAGGED = [(1, 48, (4, 4), 4), (2, 40, (3, 3), 3)]
+# frozen coordinates, dense, 130 + 12 = 142 atoms per sample: more than 128, the second candidate class of the graph kernel
+FROZEN_LARGE, FROZEN_LARGE_SEED = (4, 130, (4, 4), 4), 83
 # sampling: pocket, samples, noise seed
 SAMPLING = dict(nb=2, L=3, pocket=(1, 48, (4, 4), 4), B=2, seed=321)
 # training: a dense batch and one of two sizes

@@ -12,7 +12,7 @@ import golden_utils as GU
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_CASES = 28
+N_CASES = 30
 
 
 @pytest.fixture(scope="module")

@@ -854,7 +854,7 @@ def test_projections_inside_the_coordinate_launch_are_bit_identical(debug_option
 
 
 def test_two_launch_head_is_bit_identical_to_the_four_launches(debug_options):
-    """Head of a forward: k_head_graph (kNN by radix select + edge weights in one wave per centre, x_t read from the
+    """Head of a forward: k_graph (kNN by radix select + edge weights in one wave per centre, x_t read from the
     sampler's position buffers) beside k_head_rows (embeddings / context / counters + layer-0 rows) against the four
     separate launches (dd_debug_set_option(24, 0)) -- forward and chain bit-identical, dense and padded batches."""
     if not debug_options:

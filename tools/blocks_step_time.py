@@ -4,7 +4,7 @@ on C-small pockets (300 + 30 atoms): reverse-step time of the sampler for a 1 x 
 (production noise, calls of --steps steps timed with HIP events after a warm-up call of the same length, the two models
 alternating), and for a 1 x 2L model -- as many layers and no block boundary -- so that the boundary's own cost shows as the
 difference.  One JSON line per model.  With --forwards N the script instead runs N plain forward passes of the 2 x L model and
-nothing else: the run to put under `rocprofv3 --kernel-trace --stats` for the duration of the boundary launch (k_block_graph).
+nothing else: the run to put under `rocprofv3 --kernel-trace --stats` for the duration of the boundary launch (k_graph on the workspace's x).
 usage: python tools/blocks_step_time.py [--batch 8] [--layers 6] [--steps 1000] [--reps 3] [--forwards 0]"""
 import argparse
 import json
