@@ -6,6 +6,10 @@ reads them as attributes of an EasyDict (utils/misc.py:26-28) and uses
 ``getattr(config, name, default)`` for optional keys (models/decompdiff.py:85-90),
 so any object with these attributes (EasyDict, SimpleNamespace, this class) can be
 handed to :class:`decompdiff_amd.DecompScorePosNet3D`.
+
+Two switches whose other value is supported as well: ``h_node_in_bond_net`` (False: the narrow bond layer, the default of
+the reference's encoder, uni_transformer_edge.py:294 -- an object without the attribute means False) and ``sync_twoup``
+(the ``uni_o2_bond`` encoder stores it and never reads it in ``forward``, so True changes nothing).
 """
 from __future__ import annotations
 

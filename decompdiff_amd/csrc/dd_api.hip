@@ -73,9 +73,24 @@ static Workspace carve(float* base, int B, int NP, int NL, int K) {
 
 static inline int num_v(const dd_sampler* s) { return s->num_v > 0 ? s->num_v : DD_NUM_V; }
 
+// Rows of the ligand projection W_l1, read from the HOST slot table (include/decompdiff_hip.h, slot_off): b_l1 follows W_l1, so
+// their distance is rows * 128 floats -- 1280 rows for the wide bond layer (h_node_in_bond_net: True), 640 for the narrow one
+// (both multiples of the arena's 64-float slot padding, so the difference is exact).  0: another size, or layers that disagree.
+static int l1_rows(const dd_sampler* s) {
+  int rows = 0;
+  for (int l = 0; l < s->num_layers; ++l) {
+    const int64_t* off = s->slot_off + (long)l * DD_NUM_LAYER_SLOTS;
+    const int64_t d = off[DD_b_l1] - off[DD_W_l1];
+    if ((d != 640 * 128 && d != 1280 * 128) || (l > 0 && d != (int64_t)rows * 128)) return 0;
+    rows = (int)(d / 128);
+  }
+  return rows;
+}
+
 static int check_shapes(const dd_sampler* s) {
   if (!s || !s->weights || !s->slot_off || !s->workspace) return DD_ERR_BAD_ARG;
   if (s->B <= 0 || s->NP < 0 || s->NL < 2 || s->K <= 0 || s->num_layers < 1 || s->num_layers > 64) return DD_ERR_BAD_ARG;
+  if (l1_rows(s) == 0) return DD_ERR_BAD_ARG;
   const int N = s->NP + s->NL;
   if (s->NL > DD_NL_MAX || N > DD_N_MAX || s->K > DD_KNN_MAX || s->K > N - 1) return DD_ERR_UNSUPPORTED_SHAPE;
   if (s->num_v != 0 && s->num_v != 8 && s->num_v != 13 && s->num_v != 23) return DD_ERR_UNSUPPORTED_SHAPE;   // utils/transforms.py:138-151
@@ -354,9 +369,16 @@ struct Fwd {
   Workspace w;
   int B, NP, NL, K, N, nE;
   long Eb, hN;
+  // bond-layer width, read once per call (l1_rows; the entry points refuse anything but 640 / 1280 in check_shapes).  Narrow: the
+  // l1 launch forms the 640 node_layer_with_bond columns only -- w.PL keeps its 1280-float row stride and the workspace its
+  // layout, columns [640, 1280) are neither written nor read -- the assemble launch adds no atom rows, and the bond-layer query
+  // MLP's hidden row is PB.q_hb as it stands (no q1 block, no x2_sum epilogue).
+  int plw;
+  bool narrow;
   explicit Fwd(const dd_sampler* s_)
       : s(s_), w(carve(s_->workspace, s_->B, s_->NP, s_->NL, s_->K)), B(s_->B), NP(s_->NP), NL(s_->NL), K(s_->K), N(s_->NP + s_->NL),
-        nE((int)((long)s_->B * s_->NL * (s_->NL - 1))), Eb((long)s_->NL * (s_->NL - 1)), hN((long)(s_->NP + s_->NL) * 128) {}
+        nE((int)((long)s_->B * s_->NL * (s_->NL - 1))), Eb((long)s_->NL * (s_->NL - 1)), hN((long)(s_->NP + s_->NL) * 128),
+        plw(l1_rows(s_)), narrow(plw == 640) {}
   // (l: the step of the forward -- block b, layer l % num_layers of it: the blocks of a refine net share their weights)
   const float* LW(int l, int slot) const { return s->weights + s->slot_off[(long)(l % s->num_layers) * DD_NUM_LAYER_SLOTS + slot]; }
   const float* GW(int slot) const { return s->weights + s->slot_off[(long)s->num_layers * DD_NUM_LAYER_SLOTS + slot]; }
@@ -373,7 +395,7 @@ struct Fwd {
     return gemm_args(s->protein_h, NP, (long)NP * 128, 128, B * NP, LW(0, DD_W_n1), LW(0, DD_b_n1), nullptr, s->l0_P, NP, (long)N * 640, 640, 640, 0);
   }
   GemmArgs l1(int l, const float* h) const {
-    return gemm_args(h + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l1), LW(l, DD_b_l1), nullptr, w.PL, B * NL, 0, 1280, 1280, 0);
+    return gemm_args(h + (long)NP * 128, NL, hN, 128, B * NL, LW(l, DD_W_l1), LW(l, DD_b_l1), nullptr, w.PL, B * NL, 0, 1280, plw, 0);
   }
   GemmArgs b1(int l, int col0 = 0, int ncols = 640) const {
     return gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b1) + col0 * 128, LW(l, DD_b_b1) + col0, nullptr, w.PB + col0, nE, 0, 640, ncols, 0);
@@ -387,11 +409,13 @@ struct Fwd {
   }
   GemmArgs b2(int l) const { return gemm_args(w.hb, nE, 0, 128, nE, LW(l, DD_W_b2), LW(l, DD_b_b2), nullptr, w.PB2, nE, 0, 256, 256, 0); }
   // -- query MLPs, second Linear (LayerNorm + ReLU prologue).  Bond layer: the hidden row is q_hb[bond] + q_hi[destination atom],
-  //    summed while the tile stages its rows (x2_sum), or read from w.q1bl where the assemble launch left the sum
+  //    summed while the tile stages its rows (x2_sum), or read from w.q1bl where the assemble launch left the sum.
+  //    Narrow bond layer: q_hb[bond] alone, read in place whatever x2_sum says
   GemmArgs q_bl(int l, bool x2_sum) const {
-    GemmArgs g = gemm_args(x2_sum ? w.PB + 512 : w.q1bl, nE, 0, x2_sum ? 640 : 128, nE, LW(l, DD_BL_W2q), LW(l, DD_BL_b2q), LW(l, DD_BL_lnq),
+    const bool in_pb = x2_sum || narrow;
+    GemmArgs g = gemm_args(in_pb ? w.PB + 512 : w.q1bl, nE, 0, in_pb ? 640 : 128, nE, LW(l, DD_BL_W2q), LW(l, DD_BL_b2q), LW(l, DD_BL_lnq),
                            w.qb, nE, 0, 128, 128, 0);
-    if (x2_sum) { g.X2 = w.PL + 1152; g.x2_N = NL; g.x2_Eb = (int)Eb; g.x2_NLm1 = NL - 1; g.x2_ld = 1280; }
+    if (x2_sum && !narrow) { g.X2 = w.PL + 1152; g.x2_N = NL; g.x2_Eb = (int)Eb; g.x2_NLm1 = NL - 1; g.x2_ld = 1280; }
     return g;
   }
   GemmArgs q_ne(int l) const {
@@ -544,7 +568,8 @@ struct Fwd {
     r.B = B; r.NP = NP; r.NL = NL;
     r.tab = s->l0_tables; r.lig_v = s->lig_v; r.lig_aux = s->lig_aux; r.bond = s->lig_bond;
     r.l0_P = s->l0_P; r.PL = w.PL; r.l0_qn = s->l0_qn; r.qlnb = w.qlnb; r.PB = w.PB; r.qb = w.qb;
-    r.atom_f4 = (long)B * NL * DD_L0_ATOM_F4;
+    r.pl_width = plw;
+    r.atom_f4 = (long)B * NL * l0_atom_f4(plw);
     r.blocks = (int)((r.atom_f4 + (long)B * Eb * DD_L0_BOND_F4 + 255) / 256);
     return r;
   }
@@ -559,7 +584,8 @@ struct Fwd {
     AssembleArgs a{};
     a.x = x; a.PB = w.PB; a.PL = w.PL; a.Wgp = LW(l, DD_BL_Wgp);
     a.B = B; a.NP = NP; a.NL = NL;
-    a.Ek = w.Ek; a.Ev = w.Ev; a.q1 = q1; a.Rk = w.Rk; a.Rv = w.Rv;
+    a.narrow = narrow;
+    a.Ek = w.Ek; a.Ev = w.Ev; a.q1 = narrow ? nullptr : q1; a.Rk = w.Rk; a.Rv = w.Rv;
     a.dxe = w.dxe; a.dxb = w.dxb;
     a.fw = no_wait();
     return a;
@@ -766,7 +792,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
 #if defined(DD_DEBUG_OPTIONS) && DD_DEBUG_OPTIONS
   if (out_fc && (g_sched >= 5 || g_side_lin)) return DD_ERR_UNSUPPORTED_SHAPE;   // (measurement schedules without the node-output stage)
   if (mo.num_blocks > 1 && (g_sched >= 5 || g_side_lin)) return DD_ERR_UNSUPPORTED_SHAPE;   // (... and without the block boundary)
-  if (fused && !pre_att && g_sched >= 5 && L <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
+  if (fused && !pre_att && !f.narrow && g_sched >= 5 && L <= DD_FLAG_LAYERS && g_q1_in_gemm && g_gemm_ksplit_on() && g_q_in_pos && g_head_fused &&
       g_xup_in_asm && !g_xup_in_pos)
     return forward_tail(f, dc, st, fold, overlap);
 #endif

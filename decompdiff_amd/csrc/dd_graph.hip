@@ -368,22 +368,26 @@ __global__ __launch_bounds__(256) void k_embed_all(const EmbedArgs e) { embed_bl
 // bond e = b*Eb + t*(NL-1) + s' of type ty with destination atom t:  PB[e] = TB[ty] (640), qb[e] = TQB[c(t)][ty].
 constexpr int L0_TN = 0, L0_TL = 16 * 640, L0_TB = L0_TL + 16 * 1280, L0_TQN = L0_TB + 5 * 640, L0_TQL = L0_TQN + 16 * 128,
               L0_TQB = L0_TQL + 16 * 128;
+// PLW: floats of a PL row the model fills -- 1280, or 640 for the narrow bond layer (the node_layer_with_bond blocks; the table
+// rows and the PL rows keep their 1280-float stride, columns [640, 1280) are not copied)
+template <int PLW>
 __device__ __forceinline__ void layer0_rows_block(const unsigned blk, const Layer0RowsArgs& r) {
   const long idx = (long)blk * 256 + threadIdx.x;
   const int NP = r.NP, NL = r.NL, N = NP + NL, Eb = NL * (NL - 1);
   auto combo = [&](long a) { return (r.lig_aux[2 * a + 1] > 0.5f ? 8 : 0) + r.lig_v[a]; };
   const float4* t4 = reinterpret_cast<const float4*>(r.tab);
   if (idx < r.atom_f4) {
-    constexpr int PER = DD_L0_ATOM_F4;
+    constexpr int PER = l0_atom_f4(PLW), K1 = 160 + PLW / 4, K2 = K1 + 32;
+    static_assert(PLW != 1280 || (PER == DD_L0_ATOM_F4 && K1 == 480 && K2 == 512), "wide layout");
     const long a = idx / PER;
     const int k = (int)(idx % PER);
     const int b = (int)(a / NL), i = (int)(a % NL);
     const int c = combo(a);
     const long node = (long)b * N + NP + i;
     if (k < 160) reinterpret_cast<float4*>(r.l0_P + node * 640)[k] = t4[(L0_TN + c * 640) / 4 + k];
-    else if (k < 480) reinterpret_cast<float4*>(r.PL + a * 1280)[k - 160] = t4[(L0_TL + c * 1280) / 4 + (k - 160)];
-    else if (k < 512) reinterpret_cast<float4*>(r.l0_qn + node * 128)[k - 480] = t4[(L0_TQN + c * 128) / 4 + (k - 480)];
-    else reinterpret_cast<float4*>(r.qlnb + a * 128)[k - 512] = t4[(L0_TQL + c * 128) / 4 + (k - 512)];
+    else if (k < K1) reinterpret_cast<float4*>(r.PL + a * 1280)[k - 160] = t4[(L0_TL + c * 1280) / 4 + (k - 160)];
+    else if (k < K2) reinterpret_cast<float4*>(r.l0_qn + node * 128)[k - K1] = t4[(L0_TQN + c * 128) / 4 + (k - K1)];
+    else reinterpret_cast<float4*>(r.qlnb + a * 128)[k - K2] = t4[(L0_TQL + c * 128) / 4 + (k - K2)];
     return;
   }
   constexpr int PERB = DD_L0_BOND_F4;
@@ -400,7 +404,8 @@ __device__ __forceinline__ void layer0_rows_block(const unsigned blk, const Laye
     reinterpret_cast<float4*>(r.qb + e * 128)[k - 160] = t4[(L0_TQB + (c * 5 + ty) * 128) / 4 + (k - 160)];
   }
 }
-__global__ __launch_bounds__(256) void k_layer0_rows(const Layer0RowsArgs r) { layer0_rows_block(blockIdx.x, r); }
+template <int PLW>
+__global__ __launch_bounds__(256) void k_layer0_rows(const Layer0RowsArgs r) { layer0_rows_block<PLW>(blockIdx.x, r); }
 
 // ------------------------------------------------------------------------------ head of a forward: two launches
 // Everything the first attention layer waits for that only depends on the state the previous reverse step left:
@@ -441,10 +446,11 @@ __global__ __launch_bounds__(256, 3) void k_graph(const GraphArgs a) {
   ew_wave(pv, i, a.K, srt[w], a.EW_W1T, lw, a.EW_b2, a.ew + (long)centre * a.K);
 }
 // (a kernel of its own: the copy blocks need many waves per SIMD, the graph blocks ~200 registers per lane)
+template <int PLW>
 __global__ __launch_bounds__(256) void k_head_rows(const EmbedArgs e, const Layer0RowsArgs r) {
   const unsigned blk = blockIdx.x;
   if ((int)blk < e.blocks) embed_block(blk, e);
-  else layer0_rows_block(blk - e.blocks, r);
+  else layer0_rows_block<PLW>(blk - e.blocks, r);
 }
 
 // --------------------------------------------------------------------------- bond-layer assemble
@@ -459,8 +465,13 @@ __global__ __launch_bounds__(256) void k_head_rows(const EmbedArgs e, const Laye
 // (20 Gaussians = 5 k-steps of v_mfma_f32_16x16x4_f32) take the tables as A operands from a channel-permuted LDS image
 // (packing.py BL_Wgp, 40 KB) and the per-lane Gaussians as B; the gathered projection rows enter as the accumulator.
 typedef float f32x4a __attribute__((ext_vector_type(4)));
+//
+// WIDE = false: the narrow bond layer (h_node_in_bond_net: False, uni_transformer_edge.py:147-152) -- its first Linears have no
+// atom columns, so Ek / Ev start from PB.k_hb / PB.v_hb alone, PL is never read, and there is no fifth output block (the query
+// MLP's hidden row is PB.q_hb as it stands).  Adding the wide model's atom rows when they are exact zeros changes no bit.
 // (two waves per SIMD asked for: left alone, the compiler takes 216 VGPRs + 60 AGPRs = one wave per SIMD, i.e. ONE workgroup per
 // CU and 2.1 rounds for the 545 workgroups of a C-small batch; -1.0 % step time, no spills, bit-identical)
+template <bool WIDE>
 __global__ __launch_bounds__(256, 2) void k_bl_assemble3(const float* __restrict__ x, const float* __restrict__ PB,
                                                       const float* __restrict__ PL, const float* __restrict__ Wgp /*[4,20,128]*/,
                                                       int B, int NP, int NL, float* __restrict__ Ek, float* __restrict__ Ev,
@@ -503,10 +514,10 @@ __global__ __launch_bounds__(256, 2) void k_bl_assemble3(const float* __restrict
   const int t = e / (NL - 1), sp = e % (NL - 1);
   const int s = sp + (sp >= t ? 1 : 0);
   const float* pb = PB + e_glob * 640 + 4 * cg;
-  const float* ps = PL + ((long)b * NL + s) * 1280 + 4 * cg;
-  const float* pt = PL + ((long)b * NL + t) * 1280 + 4 * cg;
+  const float* ps = WIDE ? PL + ((long)b * NL + s) * 1280 + 4 * cg : nullptr;
+  const float* pt = WIDE ? PL + ((long)b * NL + t) * 1280 + 4 * cg : nullptr;
   auto ld4 = [](const float* p) { return *reinterpret_cast<const float4*>(p); };
-  if (q == 4) {                                        // q1 = q_hb[e] + q_hi[t]
+  if (WIDE && q == 4) {                                        // q1 = q_hb[e] + q_hi[t]
     if (q1 != nullptr && valid) {
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) {
@@ -521,9 +532,13 @@ __global__ __launch_bounds__(256, 2) void k_bl_assemble3(const float* __restrict
   for (int nt = 0; nt < 8; ++nt) {
     if (q < 2) {
       const float4 a0 = ld4(pb + 256 + 128 * q + 16 * nt);          // k_hb | v_hb
-      const float4 a1 = ld4(ps + 640 + 256 * q + 16 * nt);          // k_hk | v_hk
-      const float4 a2 = ld4(pt + 768 + 256 * q + 16 * nt);          // k_hj | v_hj
-      acc[nt] = f32x4a{(a0.x + a1.x) + a2.x, (a0.y + a1.y) + a2.y, (a0.z + a1.z) + a2.z, (a0.w + a1.w) + a2.w};
+      if constexpr (WIDE) {
+        const float4 a1 = ld4(ps + 640 + 256 * q + 16 * nt);        // k_hk | v_hk
+        const float4 a2 = ld4(pt + 768 + 256 * q + 16 * nt);        // k_hj | v_hj
+        acc[nt] = f32x4a{(a0.x + a1.x) + a2.x, (a0.y + a1.y) + a2.y, (a0.z + a1.z) + a2.z, (a0.w + a1.w) + a2.w};
+      } else {
+        acc[nt] = f32x4a{a0.x, a0.y, a0.z, a0.w};
+      }
     } else {
       acc[nt] = f32x4a{0.f, 0.f, 0.f, 0.f};
     }
@@ -641,13 +656,16 @@ int launch_embed(const EmbedArgs& e, hipStream_t st) {
   return DD_OK;
 }
 int launch_layer0_rows(const Layer0RowsArgs& r, hipStream_t st) {
-  hipLaunchKernelGGL(k_layer0_rows, dim3((unsigned)r.blocks), dim3(256), 0, st, r);
+  if (r.pl_width == 640) hipLaunchKernelGGL(k_layer0_rows<640>, dim3((unsigned)r.blocks), dim3(256), 0, st, r);
+  else hipLaunchKernelGGL(k_layer0_rows<1280>, dim3((unsigned)r.blocks), dim3(256), 0, st, r);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
 int launch_head_rows(const EmbedArgs& e, const Layer0RowsArgs* r, hipStream_t st) {
   if (r != nullptr && e.nv != DD_NUM_V) return DD_ERR_UNSUPPORTED_SHAPE;   // (the tables hold DD_NUM_V classes x arm flag)
-  hipLaunchKernelGGL(k_head_rows, dim3((unsigned)(e.blocks + (r ? r->blocks : 0))), dim3(256), 0, st, e, r ? *r : Layer0RowsArgs{});
+  const dim3 grid((unsigned)(e.blocks + (r ? r->blocks : 0)));
+  if (r != nullptr && r->pl_width == 640) hipLaunchKernelGGL(k_head_rows<640>, grid, dim3(256), 0, st, e, *r);
+  else hipLaunchKernelGGL(k_head_rows<1280>, grid, dim3(256), 0, st, e, r ? *r : Layer0RowsArgs{});
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
@@ -656,8 +674,14 @@ int launch_bl_assemble(const AssembleArgs& a, hipStream_t st) {
   const long rows = (long)a.B * a.NL * (a.NL - 1);
   const long tiles = (rows + 15) / 16;
   const int bpo = (int)((tiles + 3) / 4);                            // blocks per output (4 tiles each)
-  hipLaunchKernelGGL(k_bl_assemble3, dim3((unsigned)(bpo * (a.q1 ? 5 : 4))), dim3(256), 0, st, a.x, a.PB, a.PL, a.Wgp, a.B, a.NP, a.NL,
-                     a.Ek, a.Ev, a.q1, a.Rk, a.Rv, bpo, a.xprev, a.dxe, a.dxb, a.xout, a.fw);
+  if (a.narrow) {                                                    // (no atom rows, no q1 block)
+    if (a.q1 != nullptr) return DD_ERR_BAD_ARG;
+    hipLaunchKernelGGL(k_bl_assemble3<false>, dim3((unsigned)(bpo * 4)), dim3(256), 0, st, a.x, a.PB, nullptr, a.Wgp, a.B, a.NP, a.NL,
+                       a.Ek, a.Ev, nullptr, a.Rk, a.Rv, bpo, a.xprev, a.dxe, a.dxb, a.xout, a.fw);
+  } else {
+    hipLaunchKernelGGL(k_bl_assemble3<true>, dim3((unsigned)(bpo * (a.q1 ? 5 : 4))), dim3(256), 0, st, a.x, a.PB, a.PL, a.Wgp, a.B, a.NP,
+                       a.NL, a.Ek, a.Ev, a.q1, a.Rk, a.Rv, bpo, a.xprev, a.dxe, a.dxb, a.xout, a.fw);
+  }
   DD_CHECK_LAUNCH();
   return DD_OK;
 }

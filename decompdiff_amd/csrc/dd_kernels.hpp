@@ -111,7 +111,8 @@ struct EmbedArgs {
 };
 // Layer-0 rows of the ligand atoms / bonds gathered from dd_sampler.l0_tables (see include/decompdiff_hip.h): one thread per
 // float4, the atoms' [0, atom_f4) in front of the bonds'
-constexpr int DD_L0_ATOM_F4 = 160 + 320 + 32 + 32;   // float4 per atom: 640 + 1280 + 128 + 128 floats
+constexpr int l0_atom_f4(int pl_width) { return 160 + pl_width / 4 + 32 + 32; }   // float4 per atom: 640 + PL row + 128 + 128 floats
+constexpr int DD_L0_ATOM_F4 = l0_atom_f4(1280);
 constexpr int DD_L0_BOND_F4 = 160 + 32;              // float4 per bond: 640 + 128 floats
 struct Layer0RowsArgs {
   int B, NP, NL;
@@ -120,8 +121,9 @@ struct Layer0RowsArgs {
   const float* lig_aux;
   const int32_t* bond;
   float *l0_P, *PL, *l0_qn, *qlnb, *PB, *qb;
-  long atom_f4;
+  long atom_f4;            // B NL l0_atom_f4(pl_width)
   int blocks;
+  int pl_width;            // floats of a PL row gathered: 1280, or 640 for the narrow bond layer (the row stride stays 1280)
 };
 int launch_embed(const EmbedArgs& e, hipStream_t st);
 int launch_layer0_rows(const Layer0RowsArgs& r, hipStream_t st);
@@ -136,6 +138,7 @@ struct AssembleArgs {
   const float *xprev, *dxe, *dxb;
   float* xout;
   FlagWait fw;              // PB / PL produced by the layer-tail queue (measurement build)
+  bool narrow;              // narrow bond layer (h_node_in_bond_net: False): PL is not read, q1 must be NULL
 };
 int launch_bl_assemble(const AssembleArgs& a, hipStream_t st);
 int launch_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,

@@ -104,6 +104,7 @@ class DecompScorePosNet3D(nn.Module):
         self.bond_diffusion = getattr(config, "bond_diffusion", False)
         self.bond_net_type = getattr(config, "bond_net_type", "mlp")
         self.x2h_out_fc = bool(getattr(config, "x2h_out_fc", False))
+        self.h_node_in_bond_net = bool(getattr(config, "h_node_in_bond_net", False))
         self.sample_time_method = getattr(config, "sample_time_method", "symmetric")
         self.loss_pos_type = getattr(config, "loss_pos_type", "mse")
         self.refine_net_type = config.model_type
@@ -182,14 +183,15 @@ class DecompScorePosNet3D(nn.Module):
         need(int(config.num_blocks) >= 1 and 1 <= int(config.num_blocks) * int(config.num_layers) <= 64,
              "1 <= num_blocks and num_blocks * num_layers <= 64")
         need(config.edge_feat_dim == 4 and config.num_r_gaussian == 20, "edge_feat_dim=4, num_r_gaussian=20")
-        need(getattr(config, "h_node_in_bond_net", False), "h_node_in_bond_net=True")
+        # h_node_in_bond_net (uni_transformer_edge.py:147-152; the encoder's default is False): both widths of the bond layer's
+        # first Linears.  sync_twoup: stored by uni_o2_bond and never read in its forward -- accepted, changes nothing.
+        need(getattr(config, "h_node_in_bond_net", False) in (False, True), "h_node_in_bond_net in {False, True}")
         need(config.x2h_out_fc in (False, True) and config.norm and config.act_fn == "relu", "x2h_out_fc in {False, True}, norm, relu")
         need(getattr(config, "num_bond_classes", 1) == 5, "num_bond_classes=5")
         # ligand_atom_mode basic / add_aromatic / full: 8 / 13 / 23 atom classes (utils/transforms.py:15-64,138-151;
         # scripts/sample_diffusion_decomp.py:538-540: feature dim = classes + the 2 arm / scaffold indicators)
         need(num_classes in (8, 13, 23), "num_classes in {8, 13, 23} (ligand_atom_mode basic / add_aromatic / full)")
         need(pdim == 29 and ldim == num_classes + 2, "protein feature dim 29, ligand feature dim num_classes + 2")
-        need(not getattr(config, "sync_twoup", False), "sync_twoup=False")
         need(1 <= config.knn <= 64, "1<=knn<=64")
 
     # ------------------------------------------------------------------------------------------

@@ -11,6 +11,11 @@ first Linear of every edge MLP follow SURVEY.md Appendix C
 * bond_layer kv (437)          : [0:128] h_bond[kj] | [128:148] G(d_kj) | [148:168] G(d_ji) |
                                  [168:181] angle code | [181:309] h[k] | [309:437] h[j]
 * bond_layer q (256)           : [0:128] h_bond[ji] | [128:256] h[i]
+* narrow bond_layer (h_node_in_bond_net: False, the encoder's default, :147-152): the same MLPs without their atom columns --
+  kv (181): [0:128] h_bond[kj] | [128:148] G(d_kj) | [148:168] G(d_ji) | [168:181] angle code;  q (128): h_bond[ji].
+  W_l1 / b_l1 of such a layer hold the five node_layer_with_bond blocks only ([640, 128] / [640]); every other slot has the
+  wide model's shape and takes the same columns.  The library reads the width from the slot table
+  (include/decompdiff_hip.h, slot_off).
 
 Because the first Linear is linear in a concatenation, ``W·[a;b;c] = W_a·a + W_b·b + W_c·c``
 is evaluated as per-node / per-bond projections (dense GEMMs) that the fused attention
@@ -37,7 +42,7 @@ NH = 16
 LAYER_SLOTS = [
     # --- projections on the *old* h / h_bond ---------------------------------------
     "W_n1", "b_n1",          # [640,128] all nodes: NE kd|ks|vd|vs|q1
-    "W_l1", "b_l1",          # [1280,128] ligand nodes: NB kd|ks|vd|vs|q1 , BL k_hk|k_hj|v_hk|v_hj|q_hi
+    "W_l1", "b_l1",          # [1280,128] ligand nodes: NB kd|ks|vd|vs|q1 , BL k_hk|k_hj|v_hk|v_hj|q_hi  (narrow: [640,128], NB only)
     "W_b1", "b_b1",          # [640,128] bond edges: NB ke|ve , BL k_hb|v_hb|q_hb
     # --- node_layer_with_edge (NE) ---------------------------------------------------
     "NE_Ak", "NE_Av",        # [4,21,128] Gaussian/type tables
@@ -133,10 +138,16 @@ def pack_layer(sd: Dict[str, torch.Tensor], prefix: str) -> "OrderedDict[str, to
     out["b_n1"] = torch.cat([k[1], z(H), v[1], z(H), q[1]])
     nk, nv, nq = nb["hk_func"], nb["hv_func"], nb["hq_func"]
     bk, bv, bq = bl["hk_func"], bl["hv_func"], bl["hq_func"]
-    out["W_l1"] = torch.cat([nk[0][:, 128:256], nk[0][:, 256:384], nv[0][:, 128:256], nv[0][:, 256:384], nq[0],
-                             bk[0][:, 181:309], bk[0][:, 309:437], bv[0][:, 181:309], bv[0][:, 309:437],
-                             bq[0][:, 128:256]], 0)
-    out["b_l1"] = torch.cat([nk[1], z(H), nv[1], z(H), nq[1], z(H), z(H), z(H), z(H), z(H)])
+    widths = (bk[0].shape[1], bv[0].shape[1], bq[0].shape[1])
+    if widths not in ((437, 437, 256), (181, 181, 128)):
+        raise ValueError(f"{prefix}.bond_layer: first Linears of hk / hv / hq are 437 / 437 / 256 wide (h_node_in_bond_net: True) "
+                         f"or 181 / 181 / 128 (False), got {widths}")
+    out["W_l1"] = torch.cat([nk[0][:, 128:256], nk[0][:, 256:384], nv[0][:, 128:256], nv[0][:, 256:384], nq[0]], 0)
+    out["b_l1"] = torch.cat([nk[1], z(H), nv[1], z(H), nq[1]])
+    if widths[0] == 437:                                  # (narrow: the bond layer reads no atom rows, the slot ends here)
+        out["W_l1"] = torch.cat([out["W_l1"], bk[0][:, 181:309], bk[0][:, 309:437], bv[0][:, 181:309], bv[0][:, 309:437],
+                                 bq[0][:, 128:256]], 0)
+        out["b_l1"] = torch.cat([out["b_l1"], z(H), z(H), z(H), z(H), z(H)])
     out["W_b1"] = torch.cat([nk[0][:, 0:128], nv[0][:, 0:128], bk[0][:, 0:128], bv[0][:, 0:128], bq[0][:, 0:128]], 0)
     out["b_b1"] = torch.cat([z(H), z(H), bk[1], bv[1], bq[1]])
 
@@ -234,6 +245,9 @@ def kernel_form_layer(out: "OrderedDict[str, torch.Tensor]") -> "OrderedDict[str
         a = g.abs().clamp_min(_GAMMA_FLOOR)
         for (wn, bn, r0) in m["rows"]:
             W, b = o[wn], o[bn]
+            if r0 >= W.shape[0]:                       # narrow bond layer: W_l1 ends behind its NB blocks, nothing to transform
+                assert wn == "W_l1" and W.shape[0] == 5 * H
+                continue
             blk = W[r0:r0 + H]
             W[r0:r0 + H] = (blk - blk.mean(0, keepdim=True)) * s[:, None]
             bb = b[r0:r0 + H]

@@ -317,8 +317,9 @@ def learnable_param_shapes(config, protein_atom_feature_dim=29, ligand_atom_feat
         for f in ("hk_func", "hv_func"):
             mlp(f"{p}.node_layer_with_bond.{f}", 3 * H, H)
         mlp(f"{p}.node_layer_with_bond.hq_func", H, H)
-        kv_in = H + 2 * G + 13 + (2 * H if config.h_node_in_bond_net else 0)
-        q_in = H + (H if config.h_node_in_bond_net else 0)
+        h_node = bool(getattr(config, "h_node_in_bond_net", False))     # (BondUpdateLayer include_h_node, :147-152)
+        kv_in = H + 2 * G + 13 + (2 * H if h_node else 0)
+        q_in = H + (H if h_node else 0)
         for f in ("hk_func", "hv_func"):
             mlp(f"{p}.bond_layer.{f}", kv_in, H)
         mlp(f"{p}.bond_layer.hq_func", q_in, H)

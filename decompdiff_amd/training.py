@@ -558,6 +558,7 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
                            plan).view(-1, NH, 3).mean(1)
 
     out_fc = bool(getattr(cfg, "x2h_out_fc", False))
+    h_node = bool(getattr(cfg, "h_node_in_bond_net", False))
     for blk in range(int(cfg.num_blocks)):
         # ---- graph of a block (uni_transformer_edge.py:402-427): kNN among all atoms of a sample, edge types and edge weights -- built
         #      from the current coordinates at the head of EVERY block (num_blocks > 1: the same num_layers layers run again on it, with
@@ -622,12 +623,27 @@ def network(model, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, 
                     # every triplet (k -> j -> i) term is a per-BOND row: h[k] rides with bond (k -> j) (its source atom), h[j] and the bias
                     # with bond (j -> i) -- two gathers of [Eb, 128] tables per MLP instead of four [E3, 128] ones, and no per-atom
                     # index_add_ of 812 rows per atom in the backward
-                    per_kj = linear128(h_bond, W[:, 0:128]) + linear_feat(gb, W[:, 128:148]) + gather(linear128(h, W[:, 181:309]), S["p_bsrc"])
-                    per_ji = linear_feat(gb, W[:, 148:168]) + P.b(f"{nm_b}.{f_}.net.0") + gather(linear128(h, W[:, 309:437]), S["p_bsrc"])
+                    # (h_node_in_bond_net: False -- the narrow bond layer, :147-152 -- has no atom columns: W is [128, 181])
+                    per_kj = linear128(h_bond, W[:, 0:128]) + linear_feat(gb, W[:, 128:148])
+                    per_ji = linear_feat(gb, W[:, 148:168]) + P.b(f"{nm_b}.{f_}.net.0")
+                    if h_node:
+                        per_kj = per_kj + gather(linear128(h, W[:, 181:309]), S["p_bsrc"])
+                        per_ji = per_ji + gather(linear128(h, W[:, 309:437]), S["p_bsrc"])
                     pre = gather(per_kj, S["p_tkj"]) + gather(per_ji, p_ji) + linear_feat(code, W[:, 168:181])
                     kv.append(P.mlp_tail(f"{nm_b}.{f_}", pre))
                 # hq depends on the (j -> i) bond only: evaluated per bond, gathered per triplet (exact)
-                q_bond = P.mlp(f"{nm_b}.hq_func", torch.cat([h_bond, gather(h, p_bdst)], -1))
+                # Its first Linear is ONE 256-column product over [h_bond[ji] ; h[i]] (a width `linear128` leaves to ATen), and the
+                # float64 gradient tests hold the wide network to that arithmetic.  The narrow bond layer (no atom columns: W is
+                # [128, 128]) evaluates the same product with its atom half zero on both sides, not a 128-column library GEMM: the
+                # two kernels sum in different orders (1.2e-6 apart on equal rows), and a narrow model must give the bits of the
+                # wide model that carries its weights zero-extended.  Cost: Eb x 128 x 128 idle MACs per layer, in training only.
+                if h_node:
+                    q_bond = P.mlp(f"{nm_b}.hq_func", torch.cat([h_bond, gather(h, p_bdst)], -1))
+                else:
+                    Wq = P.w(f"{nm_b}.hq_func.net.0")
+                    q_pre = linear128(torch.cat([h_bond, torch.zeros_like(h_bond)], -1), torch.cat([Wq, torch.zeros_like(Wq)], -1),
+                                      P.b(f"{nm_b}.hq_func.net.0"))
+                    q_bond = P.mlp_tail(f"{nm_b}.hq_func", q_pre)
                 d_hb = attend(q_bond, kv[0], kv[1], p_ji, Eb_tot, real=real_t)
             else:
                 d_hb = torch.zeros_like(h_bond)
@@ -838,8 +854,11 @@ def objective(model, prep: Dict, network_fn=None) -> Dict:
         if len(set(sizes[0])) == 1:
             offset = protein_pos.view(B, sizes[0][0], 3).mean(1)
         else:                                                               # scatter_mean(protein_pos, batch_protein)
+            # (the batch vector is sorted -- check_batch_layout -- so a sample is one row block: summed block by block in a fixed
+            #  order.  An atomic index_add_ here moved the offset, and with it every loss of a ragged batch, in the last bit from
+            #  one call to the next)
             cnt = torch.tensor(sizes[0], dtype=protein_pos.dtype, device=dev).view(B, 1)
-            offset = torch.zeros(B, 3, dtype=protein_pos.dtype, device=dev).index_add_(0, batch_protein, protein_pos) / cnt
+            offset = torch.stack([blk.sum(0) for blk in protein_pos.split(list(sizes[0]))]) / cnt
     elif model.center_pos_mode == "none":
         offset = torch.zeros(B, 3, device=dev)
     else:

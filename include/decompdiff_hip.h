@@ -79,7 +79,14 @@ typedef struct dd_sampler {
   int32_t t_start;                 /* timestep of step 0 (reference: num_timesteps-1) */
   /* model */
   const float* weights;            /* packed arena */
-  const int64_t* slot_off;         /* HOST: offsets (floats) [num_layers*DD_NUM_LAYER_SLOTS + DD_NUM_GLOBAL_SLOTS] */
+  const int64_t* slot_off;         /* HOST: offsets (floats) [num_layers*DD_NUM_LAYER_SLOTS + DD_NUM_GLOBAL_SLOTS].
+                                      The table also says which bond layer the model has (h_node_in_bond_net of the reference's
+                                      configuration): DD_b_l1 follows DD_W_l1, and (slot_off[DD_b_l1] - slot_off[DD_W_l1]) / 128 is
+                                      1280 for the wide bond layer (True: W_l1 = node_layer_with_bond kd|ks|vd|vs|q1 and bond_layer
+                                      k_hk|k_hj|v_hk|v_hj|q_hi) and 640 for the narrow one (False: the node_layer_with_bond blocks
+                                      only; the bond layer's first Linears have no atom columns, and W_b1 holds their h_bond columns
+                                      as before).  Every entry point that runs the network reads it once per call from every layer;
+                                      any other value, or layers that disagree: DD_ERR_BAD_ARG. */
   const float* tab_pos;            /* [3][T]: coefficient of the network's coordinate output, coefficient of x_t, posterior_logvar.
                                       C0: posterior_mean_c0_coef, posterior_mean_ct_coef.  model_mean_type 'noise': the eps -> x0
                                       map folded in, -c0 * sqrt_recipm1_alphas_cumprod and ct + c0 * (sqrt_recip_alphas_cumprod +
@@ -159,7 +166,8 @@ typedef struct dd_sampler {
 
 /* Layout of l0_tables (floats): node projections [16][640], ligand projections [16][1280], bond projections [5][640],
  * node queries [16][128], node-with-bond queries [16][128], bond-layer queries [16 dst combinations][5 types][128].
- * Combination = 8 * (arm flag) + class. */
+ * Combination = 8 * (arm flag) + class.  A model with the narrow bond layer (see slot_off) keeps this layout: of a ligand row
+ * the first 640 floats are used, the rest is unspecified and never gathered. */
 #define DD_L0_TABLE_FLOATS (16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128)
 /* Build the tables: `mini` is a sampler with B = 1, NP = 0, NL = 16, K = 15 whose lig_v[i] = i % 8, lig_aux[i] = (i < 8 ?
  * (1,0) : (0,1)) and lig_bond[dst * 15 + s] = s % 5, with the model's weights and its own workspace; the SAME embedding,
