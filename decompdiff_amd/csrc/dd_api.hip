@@ -754,6 +754,7 @@ struct ModelOpts {
   const dd_bond_head* bh = nullptr;
   const dd_node_out* no = nullptr;
   int num_blocks = 1;
+  const uint64_t* sample_keys = nullptr;   // per-sample noise keys of the *_keyed entry points ([B], device), not part of dd_model_opts
 };
 static int check_blocks(const dd_sampler* s, int num_blocks) {
   if (!s || num_blocks < 1) return DD_ERR_BAD_ARG;
@@ -1166,7 +1167,9 @@ static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled,
 
 // The sampler's part of the step kernels' arguments: atom rows `r`, bond rows `rb`, positions `p`.  The callers add where the
 // head outputs come from (hid / W2 / b2 or logits_in), logits_out, x0 and, with a folded step boundary, counter_bias and x0_*.
-static void fill_step_args(const dd_sampler* s, const DriftGrads& d, StepRowsArgs* r, StepRowsArgs* rb, StepPosArgs* p) {
+// sample_keys: the per-sample noise keys of a keyed chain (the kernels read them at every launch), NULL otherwise.
+static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint64_t* sample_keys, StepRowsArgs* r, StepRowsArgs* rb,
+                           StepPosArgs* p) {
   const int B = s->B, NL = s->NL;
   const long Eb = (long)NL * (NL - 1);
   memset(r, 0, sizeof(*r));
@@ -1174,25 +1177,28 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, StepRowsArg
   r->tab = s->tab_v; r->T = s->T; r->step_counter = s->step_counter;
   r->state = s->lig_v; r->uniforms = s->u_v; r->stream_id = 1;
   r->traj_recon = s->traj_v0; r->traj_prob = s->traj_vt; r->traj_state = s->traj_v;
+  r->sample_keys = sample_keys; r->NL = NL;
   *rb = *r;
   rb->rows = (int)(B * Eb); rb->NC = DD_NUM_B; rb->rows_per_sample = (int)Eb; rb->tab = s->tab_b;
   rb->state = s->lig_bond; rb->uniforms = s->u_b; rb->stream_id = 2;
   rb->traj_recon = nullptr; rb->traj_prob = s->traj_bt; rb->traj_state = s->traj_bond;
+  rb->nl_real = s->nl_real;                              // (keyed bond rows of a padded batch: the sample's own enumeration)
   memset(p, 0, sizeof(*p));
   p->B = B; p->NL = NL; p->T = s->T; p->step_counter = s->step_counter; p->NP = s->NP;
   p->xt = s->lig_pos; p->tab_pos = s->tab_pos; p->tab_score = s->tab_score;
   p->atom_std = s->atom_std; p->offset = s->offset; p->grad_a = d.ga; p->scale_a = s->armsca_scale; p->grad_c = d.gc;
   p->scale_c = s->clash_scale; p->grad_r = d.gr; p->scale_r = s->repul_scale; p->eps = s->eps; p->traj_pos = s->traj_pos;
+  p->sample_keys = sample_keys;
 }
 
-static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr) {
+static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr, const uint64_t* sample_keys = nullptr) {
   const Fwd f(s);
   const Workspace& w = f.w;
   DriftGrads d;
   DD_TRY(launch_drifts(s, w, true, st, &d));
   StepRowsArgs r, rb;
   StepPosArgs p;
-  fill_step_args(s, d, &r, &rb, &p);
+  fill_step_args(s, d, sample_keys, &r, &rb, &p);
   const bool advanced = fold && fold->advance;
   r.counter_bias = rb.counter_bias = p.counter_bias = advanced ? 1 : 0;
   r.hid = w.qn; r.W2 = f.GW(DD_G_VH_W2); r.b2 = f.GW(DD_G_VH_b2); r.logits_out = s->pred_v;
@@ -1219,7 +1225,7 @@ static int reverse_step_from_logits(const dd_sampler* s, const float* logits_v, 
   DD_TRY(launch_drifts(s, w, false, st, &d));
   StepRowsArgs r, rb;
   StepPosArgs p;
-  fill_step_args(s, d, &r, &rb, &p);
+  fill_step_args(s, d, nullptr, &r, &rb, &p);
   r.logits_in = logits_v;
   rb.logits_in = logits_b;
   p.x0 = x0;
@@ -1589,7 +1595,7 @@ static int one_step(const dd_sampler* s, hipStream_t st, const dd::ModelOpts& mo
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
   int rc = dd::forward_impl(s, st, &fold, mo);
   if (rc != DD_OK) return rc;
-  return dd::heads_and_step(s, st, &fold);
+  return dd::heads_and_step(s, st, &fold, mo.sample_keys);
 }
 
 extern "C" int dd_reverse_step(const dd_sampler* s, const float* logits_v, const float* logits_b, const float* x0, void* stream) {
@@ -1613,9 +1619,19 @@ extern "C" int dd_sample_steps_ex2(const dd_sampler* s, const dd_bond_head* bh, 
 }
 
 extern "C" int dd_sample_steps_opts(const dd_sampler* s, const dd_model_opts* opts, int n_steps, void* stream) {
+  return dd_sample_steps_keyed(s, opts, nullptr, n_steps, stream);
+}
+
+// Per-sample noise keys exclude injected noise: a chain draws from one or the other.
+static bool keys_with_injected_noise(const dd_sampler* s, const uint64_t* sample_keys) {
+  return sample_keys != nullptr && s != nullptr && (s->u_v != nullptr || s->u_b != nullptr || s->eps != nullptr);
+}
+
+extern "C" int dd_sample_steps_keyed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, int n_steps, void* stream) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
-  if (!check_step_sampler(s) || n_steps < 0) return DD_ERR_BAD_ARG;
+  if (!check_step_sampler(s) || n_steps < 0 || keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
+  mo.sample_keys = sample_keys;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_steps; ++i) {
     int rc = one_step(s, st, mo);
@@ -1705,9 +1721,16 @@ extern "C" int dd_graph_create_ex2(const dd_sampler* s, const dd_bond_head* bh, 
 }
 
 extern "C" int dd_graph_create_opts(const dd_sampler* s, const dd_model_opts* opts, int steps_per_graph, void* stream, void** graph_out) {
+  return dd_graph_create_keyed(s, opts, nullptr, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_graph_create_keyed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, int steps_per_graph,
+                                     void* stream, void** graph_out) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || !graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
+  if (keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
+  mo.sample_keys = sample_keys;
   hipStream_t st = (hipStream_t)stream;
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   int rc = dd::check_shapes(s);

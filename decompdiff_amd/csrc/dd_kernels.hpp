@@ -217,6 +217,12 @@ struct StepRowsArgs {
   float* traj_recon;       // [n_steps, rows, NC] log_softmax(logits), may be NULL
   float* traj_prob;        // [n_steps, rows, NC] posterior log-probs, may be NULL
   int32_t* traj_state;     // [n_steps, rows] sampled classes, may be NULL
+  // per-sample noise keys (dd_sample_steps_keyed), NULL: the run state's seed and the flat row address the draws.
+  // Not NULL: sample b = row / rows_per_sample draws with key sample_keys[b] at the row of its OWN dense enumeration --
+  // atoms: the index in the sample; bonds: dst * (n - 1) + sp, n = nl_real[b] (padded batches) or NL.
+  const uint64_t* sample_keys;   // [B], read at every launch
+  const int32_t* nl_real;        // [B] real ligand sizes (bond rows of padded batches), or NULL
+  int NL;                        // dense ligand width (bond rows: rows_per_sample = NL * (NL - 1))
 };
 struct StepPosArgs {
   int B, NL, T;
@@ -236,6 +242,7 @@ struct StepPosArgs {
   const float* grad_r; int scale_r;   // arms_repul gradient (may be NULL); the three are added in this order
   const float* eps;         // [n_steps,B*NL,3] or NULL
   float* traj_pos;          // [n_steps,B*NL,3] or NULL
+  const uint64_t* sample_keys;   // [B] per-sample noise keys or NULL: key sample_keys[b], index 3 * i + c inside the sample
 };
 int launch_step_rows(const StepRowsArgs& a, hipStream_t st);
 int launch_step_pos(const StepPosArgs& a, hipStream_t st);

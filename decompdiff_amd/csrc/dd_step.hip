@@ -19,6 +19,8 @@ namespace dd {
 // (row, t, stream) never share a counter.  `t` is the diffusion time index of the step (t_start - steps done), not the
 // step number of the call: a chain resumed with start_step and the same seed continues the noise of the unsplit chain
 // (tests/test_gpu_properties.py) instead of replaying the draws of its first steps.  dd_debug_philox exposes exactly these functions to the statistics test.
+// `seed` and `row` are the run state's seed and the flat row of the batch, or -- keyed chains -- the sample's key and the row of its
+// own enumeration (noise_addr below): the same generator either way.
 template <int NC>
 __device__ __forceinline__ float philox_uniform(uint64_t seed, long row, int step, uint32_t sid, int c) {
   Philox ph(seed);
@@ -51,6 +53,27 @@ __device__ __forceinline__ RunState load_run_state(const int32_t* __restrict__ r
   r.t_start = rs[1];
   r.seed = (uint64_t)(uint32_t)rs[2] | ((uint64_t)(uint32_t)rs[3] << 32);
   return r;
+}
+
+// Where a row's draws come from.  Unkeyed (a.sample_keys == NULL): the run state's seed and the flat row of the batch.  Keyed
+// (dd_sample_steps_keyed): sample b = row / rows_per_sample draws with its own key at the row of its OWN dense enumeration, i.e.
+// what a batch of that sample alone with seed = key draws -- atoms: the index in the sample; bonds of a padded batch: the
+// padded row dst * (NL - 1) + sp is row dst * (n - 1) + sp of the sample's n = nl_real[b] atoms (padding rows keep theirs).
+struct NoiseAddr { uint64_t key; long row; };
+__device__ __forceinline__ NoiseAddr noise_addr(const StepRowsArgs& a, const long row, const uint64_t seed) {
+  if (a.sample_keys == nullptr) return {seed, row};
+  const int b = (int)(row / a.rows_per_sample);
+  int r = (int)(row - (long)b * a.rows_per_sample);
+  if (a.nl_real != nullptr) {
+    const int n = a.nl_real[b], dst = r / (a.NL - 1), sp = r - dst * (a.NL - 1);
+    if (dst < n && sp < n - 1) r = dst * (n - 1) + sp;    // (sp < n - 1 and dst < n: both endpoints are real atoms)
+  }
+  return {a.sample_keys[b], (long)r};
+}
+// ... and a coordinate's: (seed, flat index), or (key of its sample, 3 * i + c inside the sample)
+__device__ __forceinline__ float step_pos_normal(const StepPosArgs& a, const int idx, const int b, const uint64_t seed, const int t) {
+  if (a.sample_keys == nullptr) return philox_normal(seed, idx, t);
+  return philox_normal(a.sample_keys[b], idx - b * a.NL * 3, t);
 }
 
 __device__ __forceinline__ float log_add_exp(float a, float b) {
@@ -120,8 +143,9 @@ __global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) u[c] = a.uniforms[((long)step * a.rows + row) * NC + c];
   } else {
+    const NoiseAddr na = noise_addr(a, row, rs.seed);
 #pragma unroll
-    for (int c = 0; c < NC; ++c) u[c] = philox_uniform<NC>(rs.seed, row, t, a.stream_id, c);
+    for (int c = 0; c < NC; ++c) u[c] = philox_uniform<NC>(na.key, na.row, t, a.stream_id, c);
   }
   int best = 0;
   float bestv = -INFINITY;
@@ -163,7 +187,7 @@ __global__ void k_step_pos(const StepPosArgs a) {
   if (a.eps) {
     e = a.eps[(long)step * n + idx];
   } else {
-    e = philox_normal(rs.seed, idx, t);
+    e = step_pos_normal(a, idx, b, rs.seed, t);
   }
   const float nz = t == 0 ? 0.f : 1.f;
   const float nxt = mean + nz * expf(0.5f * a.tab_pos[2 * a.T + t]) * e * a.atom_std[idx];
@@ -453,7 +477,8 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
   if (a.uniforms) {
     u = a.uniforms[((long)step * a.rows + row) * NC + c];
   } else {
-    u = philox_uniform<NC>(rs.seed, row, t, a.stream_id, c);
+    const NoiseAddr na = noise_addr(a, row, rs.seed);
+    u = philox_uniform<NC>(na.key, na.row, t, a.stream_id, c);
   }
   const float lp = un - ulse;
   const float sc = -logf(-logf(u + 1e-30f) + 1e-30f) + lp;      // Gumbel-argmax (transitions.py:78-84)
@@ -499,7 +524,7 @@ __device__ __forceinline__ void step_pos_elem(const StepPosArgs& a, const int id
   if (a.eps) {
     e = a.eps[(long)step * n + idx];
   } else {
-    e = philox_normal(rs.seed, idx, t);
+    e = step_pos_normal(a, idx, b, rs.seed, t);
   }
   const float nz = t == 0 ? 0.f : 1.f;
   const float nxt = mean + nz * expf(0.5f * a.tab_pos[2 * a.T + t]) * e * a.atom_std[idx];

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import synth
+from .model import sample_keys
 from .pocket_data import PocketData, build_batch
 
 
@@ -44,7 +45,8 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                                    energy_drift_opt=None, per_sample_std_scale=None, noise_fn=None, seed: int = 0,
                                    use_graph: bool = True, prior_mode: str = "ref_prior", num_atoms_mode: str = "ref",
                                    arms_natoms_config=None, scaffold_natoms_config=None, natoms_sampler=None,
-                                   atom_prior_probs=None, bond_prior_probs=None, pool_batches: int = 1) -> Dict[str, list]:
+                                   atom_prior_probs=None, bond_prior_probs=None, pool_batches: int = 1,
+                                   sample_key_seed: Optional[int] = None, first_sample_index: int = 0) -> Dict[str, list]:
     """Sample ``num_samples`` ligands for one pocket in batches of ``batch_size``.
 
     ``pool_batches`` > 1 assembles that many consecutive batches exactly as the reference would (same random draws, same
@@ -60,6 +62,14 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
 
     ``noise_fn(batch_index, n_ligand_atoms, n_bonds, num_steps)`` may return pre-drawn reference-order noise for
     a batch (parity mode); otherwise the device Philox generator is used with ``seed + batch_index``.
+
+    ``sample_key_seed`` (not None): per-sample noise keys instead -- output sample ``g`` of this call draws with
+    ``model.sample_keys(sample_key_seed, first_sample_index + g)`` in every model call (``sample_diffusion(sample_keys=...)``; only
+    for models that take the extra keywords; excludes ``noise_fn``), so the CHAIN of a sample no longer depends on ``batch_size``,
+    ``pool_batches`` or on which process runs it: a shard of a larger job passes its first global sample index.  The keys make
+    the chains reproducible, not this function's initial draws: the initial coordinates, atom and bond types are still drawn
+    from torch's CPU generator in the reference's order, batch by batch, and so still depend on the batching (and a keyed
+    model call draws nothing from that generator).
     """
     out = {k: [] for k in ("pred_pos", "pred_v", "pred_pos_traj", "pred_v_traj", "pred_v0_traj", "pred_vt_traj",
                            "pred_bond_index", "pred_bond_type", "pred_b_traj", "pred_bt_traj", "decomp_mask")}
@@ -87,6 +97,9 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
         noise = noise_fn(i, sum(n_atoms), sum(n * (n - 1) for n in n_atoms), steps) if noise_fn is not None else None
         return batch, n_atoms, noise
 
+    if sample_key_seed is not None and noise_fn is not None:
+        raise ValueError("sample_key_seed excludes noise_fn: a chain draws from one source")
+    n_done = 0                                                             # samples of the earlier model calls
     for i in range(0, num_batch, pool_batches):
         parts = [build(j) for j in range(i, min(num_batch, i + pool_batches))]
         if len(parts) == 1:
@@ -99,6 +112,10 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
         n_bonds = [n * (n - 1) for n in n_atoms]
         dev_batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
         extra = dict(noise=noise, seed=seed + i, use_graph=use_graph) if _accepts_extras(model) else {}
+        if sample_key_seed is not None and extra:
+            first = int(first_sample_index) + n_done
+            extra = dict(use_graph=use_graph, sample_keys=sample_keys(sample_key_seed, range(first, first + n_data)))
+        n_done += n_data
         t1 = time.time()
         r = model.sample_diffusion(num_steps=num_steps, center_pos_mode=center_pos_mode,
                                    energy_drift_opt=energy_drift_opt, **extra, **dev_batch)

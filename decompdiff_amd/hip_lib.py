@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "dd_attn_aggregate_node_masked", "dd_attn_aggregate_pos_masked", "dd_attn_aggregate_node_bwd_masked", "dd_attn_aggregate_pos_bwd_masked",
     "dd_csr_select_scratch_bytes", "dd_csr_select_count", "dd_csr_select_fill",
     "dd_forward_opts", "dd_sample_steps_opts", "dd_sample_steps_graph_opts", "dd_graph_create_opts", "dd_sample_steps_graph_multi_opts",
+    "dd_sample_steps_keyed", "dd_graph_create_keyed",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -190,6 +191,9 @@ def load():
         "dd_sample_steps_graph_opts": [S, POINTER(DDModelOpts), c_int, c_void_p],
         "dd_graph_create_opts": [S, POINTER(DDModelOpts), c_int, c_void_p, POINTER(c_void_p)],
         "dd_sample_steps_graph_multi_opts": [POINTER(S), POINTER(POINTER(DDModelOpts)), c_int, c_int, POINTER(c_void_p)],
+        # (the _opts siblings with the device pointer sample_keys [B] uint64 after opts)
+        "dd_sample_steps_keyed": [S, POINTER(DDModelOpts), c_void_p, c_int, c_void_p],
+        "dd_graph_create_keyed": [S, POINTER(DDModelOpts), c_void_p, c_int, c_void_p, POINTER(c_void_p)],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],

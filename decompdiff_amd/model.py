@@ -74,6 +74,48 @@ def log_sample_categorical(logits: torch.Tensor) -> torch.Tensor:
     return (gumbel + logits).argmax(dim=-1)
 
 
+def sample_keys(seed: int, indices) -> torch.Tensor:
+    """Per-sample noise keys for ``sample_diffusion(sample_keys=...)``: one 64-bit key per global sample index, as an int64 CPU
+    tensor of the shape of ``indices`` (an int, a sequence of ints or an integer tensor; the key's 64 bits, two's complement).
+
+    The function, exactly (all arithmetic on unsigned 64-bit integers, wrapping modulo 2**64)::
+
+        z   = seed + 0x9E3779B97F4A7C15 * (index + 1)
+        z   = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+        z   = (z ^ (z >> 27)) * 0x94D049BB133111EB
+        key = z ^ (z >> 31)
+
+    i.e. output number ``index`` (from 0) of a splitmix64 generator whose state starts at ``seed``.  A job that gives its sample
+    ``g`` the key ``sample_keys(seed, g)`` gets the same chain for that sample under any batch size, sharding or order."""
+    idx = np.asarray(indices.cpu() if torch.is_tensor(indices) else indices)
+    if idx.size and (idx.dtype.kind not in "iu" or int(idx.min()) < 0):
+        raise ValueError("indices must be non-negative integers")
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) + np.uint64(0x9E3779B97F4A7C15) * (idx.astype(np.uint64) + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return torch.from_numpy(np.asarray(z, dtype=np.uint64).astype(np.int64).reshape(idx.shape))
+
+
+def _as_sample_keys(keys, batch_ligand) -> torch.Tensor:
+    """``sample_keys`` of sample_diffusion as an int64 tensor [B] holding the keys' 64 bits: a length-B int64 tensor as it is, a
+    sequence of ints in [0, 2**64) wrapped to two's complement; one key per sample of ``batch_ligand``."""
+    if torch.is_tensor(keys):
+        if keys.dtype != torch.int64 or keys.dim() != 1:
+            raise ValueError("sample_keys must be a one-dimensional int64 tensor or a sequence of ints")
+        out = keys.detach()
+    else:
+        vals = [int(k) for k in keys]
+        if any(not 0 <= k < 2 ** 64 for k in vals):
+            raise ValueError("sample_keys must lie in [0, 2**64)")
+        out = torch.tensor([k - 2 ** 64 if k >= 2 ** 63 else k for k in vals], dtype=torch.int64)
+    B = int(batch_ligand.max().item()) + 1 if batch_ligand.numel() else 0
+    if out.numel() != B:
+        raise ValueError(f"sample_keys must hold one key per sample ({B}), got {out.numel()}")
+    return out
+
+
 def _check_ligand_atom_mask(mask, n_ligand):
     """``ligand_atom_mask`` of forward / sample_diffusion (decompdiff.py:217,560).  The reference's script always passes
     None (scripts/sample_diffusion_decomp.py:340).  An all-True boolean mask is equivalent to None in the reference
@@ -392,7 +434,7 @@ class DecompScorePosNet3D(nn.Module):
                                          kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"].numel(), need_protein=False)
 
     def _sample_heterogeneous(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                              use_graph, start_step=0):
+                              use_graph, start_step=0, sample_keys=None):
         """Samples with different atom counts in one batch (PyG collate, utils/data.py:389-446).  Default: ONE launch
         sequence over the batch padded to its largest pocket / ligand with per-sample real counts (`_sample_padded`).
         Fallbacks to equal-size groups (`_sample_ragged`): DD_RAGGED_MODE=groups, or `batch_layout.fits_padded` says no."""
@@ -401,9 +443,9 @@ class DecompScorePosNet3D(nn.Module):
             layout = self._sampling_layout(kw)
             if BL.fits_padded(layout, self.config.knn):
                 return self._sample_padded(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed,
-                                           keep_traj, use_graph, start_step, layout.n_p, layout.n_l)
+                                           keep_traj, use_graph, start_step, layout.n_p, layout.n_l, sample_keys=sample_keys)
         return self._sample_ragged(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                                   use_graph, start_step=start_step, layout=layout)
+                                   use_graph, start_step=start_step, layout=layout, sample_keys=sample_keys)
 
     def _padded_inputs(self, protein_pos, protein_v, bp, ligand_pos, ligand_v, aux, bl, fc_index, bond_type, batch_ligand_bond,
                        n_p, n_l, center_pos_mode):
@@ -449,7 +491,7 @@ class DecompScorePosNet3D(nn.Module):
         return dict(d=d, offset=offset, masks=masks, n_b=n_b, rows_l=rows_l, rows_b=rows_b, d_l=d_l, d_b=d_b)
 
     def _sample_padded(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, start_step, n_p, n_l):
+                       use_graph, start_step, n_p, n_l, sample_keys=None):
         """Heterogeneous batch as one padded dense batch: every sample's atoms are the first rows of its [NPmax] / [NLmax]
         blocks, the kernels read the real counts from dd_sampler.np_real / nl_real (padding atoms are no kNN candidates,
         own no softmax segment and are no members of one) and the results are gathered back into the caller's flat order.
@@ -495,7 +537,8 @@ class DecompScorePosNet3D(nn.Module):
             raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
         pw = self._packed_weights()
         s, bufs, ent = self._make_sampler(d, pw, num_steps, self.num_timesteps - 1 - int(start_step), pad_noise, keep_traj,
-                                          energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, 0, masks=masks)
+                                          energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, 0, masks=masks,
+                                          sample_keys=sample_keys)             # (the padded batch keeps the caller's sample order)
         chain = dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent)
         self._run_chains([chain], num_steps, use_graph)
         out = self._collect_chain(chain, num_steps, keep_traj, rows_atoms=rows_l, rows_bonds=rows_b)
@@ -503,10 +546,12 @@ class DecompScorePosNet3D(nn.Module):
         return out
 
     def _sample_ragged(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, concurrent=None, start_step=0, split=1, layout=None):
+                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None):
         """One dense chain per group of samples of equal size (`BatchLayout.size_groups`).  ``split`` > 1 additionally cuts
         every group into that many sub-batches (measurement aid, tools/split_bench.py: two concurrent half-batches were
-        measured slower than one chain).  ``layout``: what `_sampling_layout(kw)` gave the caller."""
+        measured slower than one chain).  ``layout``: what `_sampling_layout(kw)` gave the caller.
+        ``sample_keys`` (int64 [B], the caller's sample order): every group gets its members' keys; without keys group ``gi``
+        draws with ``seed + 7919 * gi``."""
         _check_ligand_atom_mask(ligand_atom_mask, kw["batch_ligand"].numel())
         dev = kw["protein_pos"].device
         layout = layout or self._sampling_layout(kw)
@@ -533,7 +578,8 @@ class DecompScorePosNet3D(nn.Module):
                 kw["full_protein_pos"].to(dev)[g.rows_f.to(dev)] if has_full else None,
                 BL.batch_vector(G, g.n_f, dev) if has_full else None, sub_noise,
                 seed + 7919 * gi, keep_traj, B, start_step,        # (the armsca loss is averaged over the whole batch)
-                cache_slot=(g.ids[0] * split) // B)                # (sub-batches of one shape: own cached buffers each)
+                cache_slot=(g.ids[0] * split) // B,                # (sub-batches of one shape: own cached buffers each)
+                sample_keys=None if sample_keys is None else sample_keys[g.ids])
             prepared.append((chain, d_l, d_b, r_l, r_b))
         if concurrent is None:
             # measured on MI355X (tools/ragged_bench.py): with the runtime's default 4 hardware queues the
@@ -687,7 +733,9 @@ class DecompScorePosNet3D(nn.Module):
         return memo[key]
 
     def _make_sampler(self, d, pw, n_steps, t_start, noise, keep_traj, drift, atom_std, offset, decomp_index,
-                      full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0):
+                      full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0, sample_keys=None):
+        """``sample_keys``: int64 [B] (host or device), the per-sample noise keys of this chain in the order of its samples, or None
+        (the chain draws with ``seed``)."""
         lib = hip_lib.load()
         dev = d["protein_pos"].device
         B, NP, NL = d["B"], d["NP"], d["NL"]
@@ -777,6 +825,13 @@ class DecompScorePosNet3D(nn.Module):
         if masks is not None:
             for k in ("np_real", "nl_real", "bl_prefix"):
                 bufs[k].copy_(masks[k])
+        # per-sample noise keys: the buffer belongs to the (cached) entry, its contents to this call -- the step kernels read the
+        # keys at every launch, so the entry's captured graph serves the next chain with other keys
+        if sample_keys is not None:
+            if bufs.get("sample_keys") is None:
+                bufs["sample_keys"] = torch.zeros(B, dtype=torch.int64, device=dev)
+            bufs["sample_keys"].copy_(sample_keys)
+        ent["keyed"] = sample_keys is not None
         for k in ("u_v", "u_b", "eps"):
             bufs[k] = None
         if noise is not None:
@@ -840,7 +895,7 @@ class DecompScorePosNet3D(nn.Module):
         # everything that shapes the captured step graph besides the (cached) pointers
         ent["sig"] = (sm.drift_armsca, sm.armsca_min_d, sm.armsca_max_d, sm.armsca_scale, sm.drift_clash, sm.clash_sigma,
                       sm.clash_gamma, sm.clash_scale, sm.drift_repul, sm.repul_max_d, sm.repul_scale, sm.drift_norm_batch,
-                      int(lib.dd_debug_options_epoch()), bool(use_l0))
+                      int(lib.dd_debug_options_epoch()), bool(use_l0), ent["keyed"])
         if cacheable:
             cache[key] = ent                               # (re-inserted: most recently used last)
             self._evict_chain_cache(self._CACHE_MAX)
@@ -1001,7 +1056,8 @@ class DecompScorePosNet3D(nn.Module):
                          num_steps=None, center_pos_mode=None,
                          energy_drift_opt=None,
                          full_protein_pos=None, full_batch_protein=None,
-                         noise=None, seed=None, keep_traj=True, use_graph=True, start_step=0, _drift_norm_batch=0):
+                         noise=None, seed=None, keep_traj=True, use_graph=True, start_step=0, _drift_norm_batch=0,
+                         sample_keys=None):
         """Reverse diffusion (reference: models/decompdiff.py:552-703), same arguments and return
         keys.  Extra keyword-only knobs (all optional, reference call sites never pass them):
 
@@ -1014,6 +1070,11 @@ class DecompScorePosNet3D(nn.Module):
         * ``start_step`` — resume a chain: the state passed in is x_t / v_t / b_t after ``start_step`` reverse steps,
           i.e. the first step runs at t = num_timesteps - 1 - start_step (``noise`` then holds the draws of the
           remaining ``num_steps`` steps only).
+        * ``sample_keys`` — one 64-bit noise key per sample (a length-B int64 tensor, or a sequence of ints in [0, 2**64);
+          see :func:`sample_keys`): sample b then receives exactly the draws that a call on that sample alone with
+          ``seed=sample_keys[b]`` receives, whatever batch it sits in -- dense, padded or grouped, at any position, with
+          any B -- so its chain is reproducible bit for bit under re-batching, sharding and re-ordering.  Excludes
+          ``noise`` and an explicit ``seed`` (ValueError).
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
@@ -1021,6 +1082,11 @@ class DecompScorePosNet3D(nn.Module):
             raise ValueError(self.model_mean_type)
         if num_steps is None:
             num_steps = self.num_timesteps
+        if sample_keys is not None:
+            if noise is not None or seed is not None:
+                raise ValueError("sample_keys excludes noise= and an explicit seed=: a chain draws from one source")
+            sample_keys = _as_sample_keys(sample_keys, batch_ligand)
+            seed = 0                                             # (not read by a keyed chain; no draw from torch's generator)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         key_t = (protein_pos, batch_protein, batch_ligand, ligand_fc_bond_index, ligand_v_aux)
@@ -1036,12 +1102,12 @@ class DecompScorePosNet3D(nn.Module):
                      init_ligand_fc_bond_type=init_ligand_fc_bond_type, batch_ligand_bond=batch_ligand_bond,
                      full_protein_pos=full_protein_pos, full_batch_protein=full_batch_protein),
                 ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
-                start_step=start_step)
+                start_step=start_step, sample_keys=sample_keys)
         chain = self._prepare_chain(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
                                     batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                                     ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode,
                                     energy_drift_opt, full_protein_pos, full_batch_protein, noise, seed, keep_traj,
-                                    _drift_norm_batch, start_step, static=static)
+                                    _drift_norm_batch, start_step, static=static, sample_keys=sample_keys)
         if static is None and "static" in chain:
             self._static_memo_put(key_t, center_pos_mode, chain["static"])
         tr = self.__dict__.get("_trace")
@@ -1058,7 +1124,7 @@ class DecompScorePosNet3D(nn.Module):
                        batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                        ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode, energy_drift_opt,
                        full_protein_pos, full_batch_protein, noise, seed, keep_traj, drift_norm_batch, start_step=0,
-                       static=None, cache_slot=0):
+                       static=None, cache_slot=0, sample_keys=None):
         """Validate one dense batch, centre it, allocate its state / workspace and fill the ``dd_sampler`` struct.
         ``static``: what an earlier call with the same pocket / batch-vector tensors established (_static_memo_get)."""
         d = self._dense_inputs(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
@@ -1105,7 +1171,8 @@ class DecompScorePosNet3D(nn.Module):
             if center_pos_mode in ("protein", "none") else None
         d["upload_mode"] = center_pos_mode
         s, bufs, ent = self._make_sampler(d, pw, num_steps, t_start, noise, keep_traj, energy_drift_opt, atom_std,
-                                          offset.contiguous(), decomp, fpp, seed, drift_norm_batch, cache_slot=cache_slot)
+                                          offset.contiguous(), decomp, fpp, seed, drift_norm_batch, cache_slot=cache_slot,
+                                          sample_keys=sample_keys)
         return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent,
                     static=dict(layout=(B, NP, NL), offset=offset, protein_pos_centered=d["protein_pos_centered"],
                                 aux_onehot=d["aux_onehot"]))
@@ -1134,10 +1201,7 @@ class DecompScorePosNet3D(nn.Module):
                     if ent.get("graph") is None:
                         if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                             self._drop_cached_graphs()
-                        graph = ctypes.c_void_p()
-                        hip_lib.check(lib.dd_graph_create_opts(ctypes.byref(c["s"]), self._model_opts(), 1, side.cuda_stream,
-                                                              ctypes.byref(graph)), "dd_graph_create")
-                        ent["graph"], ent["graph_sig"] = graph, gsig
+                        ent["graph"], ent["graph_sig"] = self._create_step_graph(c, 1, side.cuda_stream), gsig
                         DecompScorePosNet3D._graph_counter += 1
                         ent["graph_id"] = DecompScorePosNet3D._graph_counter
                     try:
@@ -1150,8 +1214,12 @@ class DecompScorePosNet3D(nn.Module):
             else:
                 with torch.cuda.stream(side):
                     for c in chains:
-                        hip_lib.check(lib.dd_sample_steps_opts(ctypes.byref(c["s"]), self._model_opts(), int(num_steps),
-                                                              hip_lib.stream_ptr(dev)), "dd_sample_steps")
+                        if c["ent"].get("keyed"):
+                            rc = lib.dd_sample_steps_keyed(ctypes.byref(c["s"]), self._model_opts(), hip_lib.ptr(c["bufs"]["sample_keys"]),
+                                                           int(num_steps), hip_lib.stream_ptr(dev))
+                        else:
+                            rc = lib.dd_sample_steps_opts(ctypes.byref(c["s"]), self._model_opts(), int(num_steps), hip_lib.stream_ptr(dev))
+                        hip_lib.check(rc, "dd_sample_steps")
             cur.wait_stream(side)
             return
         if len(chains) > 64:                            # dd_sample_steps_graph_multi takes at most 64 chains
@@ -1162,6 +1230,26 @@ class DecompScorePosNet3D(nn.Module):
         for st in pool:
             st.wait_stream(cur)
         n = len(chains)
+        if any(c["ent"].get("keyed") for c in chains):
+            # keyed chains: dd_sample_steps_graph_multi_* takes no keys -- one step graph per chain on its own stream, replayed
+            # round-robin from this thread; no other graph is alive across their creation and they go away newest first and all
+            # together (see _parked_graphs)
+            self._drop_cached_graphs()
+            graphs = []
+            try:
+                for c, st in zip(chains, pool):
+                    graphs.append(self._create_step_graph(c, 1, st.cuda_stream))
+                for _ in range(int(num_steps)):
+                    for g, st in zip(graphs, pool):
+                        hip_lib.check(lib.dd_graph_launch(g, 1, st.cuda_stream), "dd_graph_launch")
+            finally:
+                for st in pool:
+                    st.synchronize()
+                for g in reversed(graphs):
+                    lib.dd_graph_destroy(g)
+            for st in pool:
+                cur.wait_stream(st)
+            return
         ss = (ctypes.POINTER(hip_lib.DDSampler) * n)(*[ctypes.pointer(c["s"]) for c in chains])
         sts = (ctypes.c_void_p * n)(*[st.cuda_stream for st in pool])
         # (the C entry point captures one graph per chain and destroys them at the end: no other graph may be alive across
@@ -1171,6 +1259,19 @@ class DecompScorePosNet3D(nn.Module):
         hip_lib.check(lib.dd_sample_steps_graph_multi_opts(ss, opts, n, int(num_steps), sts), "dd_sample_steps_graph_multi")
         for st in pool:
             cur.wait_stream(st)
+
+    def _create_step_graph(self, chain, steps_per_graph, stream):
+        """Capture ``steps_per_graph`` reverse steps of a prepared chain on ``stream`` (a raw stream handle) into a new step graph;
+        a keyed chain's kernels read the keys from the entry's own buffer."""
+        lib = hip_lib.load()
+        graph = ctypes.c_void_p()
+        if chain["ent"].get("keyed"):
+            rc = lib.dd_graph_create_keyed(ctypes.byref(chain["s"]), self._model_opts(), hip_lib.ptr(chain["bufs"]["sample_keys"]),
+                                           int(steps_per_graph), stream, ctypes.byref(graph))
+        else:
+            rc = lib.dd_graph_create_opts(ctypes.byref(chain["s"]), self._model_opts(), int(steps_per_graph), stream, ctypes.byref(graph))
+        hip_lib.check(rc, "dd_graph_create")
+        return graph
 
     _TRAJ_KEYS = ("traj_pos", "traj_v", "traj_bond", "traj_v0", "traj_vt", "traj_bt")
 
@@ -1210,10 +1311,7 @@ class DecompScorePosNet3D(nn.Module):
         if ent.get("graph") is None:
             if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
                 self._drop_cached_graphs()                 # (all live graphs, newest first; cached entries re-capture on next use)
-            graph = ctypes.c_void_p()
-            hip_lib.check(lib.dd_graph_create_opts(ctypes.byref(s), self._model_opts(), spg, side.cuda_stream, ctypes.byref(graph)),
-                          "dd_graph_create")
-            ent["graph"], ent["graph_sig"] = graph, gsig
+            ent["graph"], ent["graph_sig"] = self._create_step_graph(chain, spg, side.cuda_stream), gsig
             DecompScorePosNet3D._graph_counter += 1
             ent["graph_id"] = DecompScorePosNet3D._graph_counter
         graph = ent["graph"]                               # (read after priming: never a handle the priming chain destroyed)

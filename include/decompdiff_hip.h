@@ -489,6 +489,27 @@ int dd_graph_create_opts(const dd_sampler* s, const dd_model_opts* opts /*HOST*/
 int dd_sample_steps_graph_multi_opts(const dd_sampler* const* s /*HOST [n]*/, const dd_model_opts* const* opts /*HOST [n]*/, int n,
                                      int n_steps, void* const* streams /*HOST [n]*/);
 
+/* Per-sample noise keys: a sample's production noise independent of the batch it sits in.  The two _opts entry points above
+ * with one more DEVICE pointer, sample_keys [B] uint64.  Sample b then receives exactly the draws that a chain of that sample
+ * alone (B = 1) with dd_sampler.seed = sample_keys[b] receives, at any position of a dense or padded batch of any B:
+ *   atom types   stream 1, Philox key sample_keys[b], counter row i (the atom's index in its sample)
+ *   bond types   stream 2, key sample_keys[b], counter row dst * (n - 1) + sp with sp = src - (src > dst) and n the sample's
+ *                real ligand size (nl_real[b] in a padded batch, NL otherwise): the row of the sample's OWN dst-major bond
+ *                list, not of the padded one.  Rows of padding bonds draw at their padded row (nobody reads them).
+ *   coordinates  stream 7, key sample_keys[b], index 3 * i + c
+ * Philox4x32-10 with counter (row, row >> 32, t, stream | class block << 8) as for dd_sampler.seed; t stays the diffusion time
+ * index, so a chain resumed with another t_start and the same keys continues the unsplit chain's noise.  dd_sampler.seed is
+ * not read.  The keys are read from device memory at every launch (never baked into a graph): a graph from
+ * dd_graph_create_keyed serves every later chain of its shape once other keys are copied into the same buffer, and
+ * dd_graph_launch / dd_graph_destroy take it like any other.
+ *   sample_keys == NULL: exactly dd_sample_steps_opts / dd_graph_create_opts.
+ *   sample_keys together with injected noise (any of s->u_v / u_b / eps): DD_ERR_BAD_ARG.
+ * dd_reverse_step and the dd_sample_steps_graph* / _multi* entry points stay unkeyed.  (New entry points, ABI unchanged.) */
+int dd_sample_steps_keyed(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B]*/,
+                          int n_steps, void* stream);
+int dd_graph_create_keyed(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B]*/,
+                          int steps_per_graph, void* stream, void** graph_out /*HOST*/);
+
 /* Drift guidance gradients at x_t (utils/guidance_funcs.py:24-78), analytic. grad [B,NL,3]. */
 int dd_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                     float* grad, int accumulate, void* stream);
