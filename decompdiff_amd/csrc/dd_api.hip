@@ -755,6 +755,7 @@ struct ModelOpts {
   const dd_node_out* no = nullptr;
   int num_blocks = 1;
   const uint64_t* sample_keys = nullptr;   // per-sample noise keys of the *_keyed entry points ([B], device), not part of dd_model_opts
+  const dd_fixed* fixed = nullptr;         // fixed atoms of the *_fixed entry points (a checked host copy), not part of dd_model_opts
 };
 static int check_blocks(const dd_sampler* s, int num_blocks) {
   if (!s || num_blocks < 1) return DD_ERR_BAD_ARG;
@@ -1168,8 +1169,9 @@ static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled,
 // The sampler's part of the step kernels' arguments: atom rows `r`, bond rows `rb`, positions `p`.  The callers add where the
 // head outputs come from (hid / W2 / b2 or logits_in), logits_out, x0 and, with a folded step boundary, counter_bias and x0_*.
 // sample_keys: the per-sample noise keys of a keyed chain (the kernels read them at every launch), NULL otherwise.
-static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint64_t* sample_keys, StepRowsArgs* r, StepRowsArgs* rb,
-                           StepPosArgs* p) {
+// fixed: the fixed atoms of the chain (device pointers, read at every launch), NULL otherwise.
+static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint64_t* sample_keys, const dd_fixed* fixed, StepRowsArgs* r,
+                           StepRowsArgs* rb, StepPosArgs* p) {
   const int B = s->B, NL = s->NL;
   const long Eb = (long)NL * (NL - 1);
   memset(r, 0, sizeof(*r));
@@ -1178,7 +1180,9 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint6
   r->state = s->lig_v; r->uniforms = s->u_v; r->stream_id = 1;
   r->traj_recon = s->traj_v0; r->traj_prob = s->traj_vt; r->traj_state = s->traj_v;
   r->sample_keys = sample_keys; r->NL = NL;
+  if (fixed) { r->fx_mask = fixed->mask; r->fx_mode = fixed->mode; }
   *rb = *r;
+  if (fixed) { r->fx_val = fixed->v0; rb->fx_val = fixed->b0; rb->fx_bond = 1; }
   rb->rows = (int)(B * Eb); rb->NC = DD_NUM_B; rb->rows_per_sample = (int)Eb; rb->tab = s->tab_b;
   rb->state = s->lig_bond; rb->uniforms = s->u_b; rb->stream_id = 2;
   rb->traj_recon = nullptr; rb->traj_prob = s->traj_bt; rb->traj_state = s->traj_bond;
@@ -1189,16 +1193,18 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint6
   p->atom_std = s->atom_std; p->offset = s->offset; p->grad_a = d.ga; p->scale_a = s->armsca_scale; p->grad_c = d.gc;
   p->scale_c = s->clash_scale; p->grad_r = d.gr; p->scale_r = s->repul_scale; p->eps = s->eps; p->traj_pos = s->traj_pos;
   p->sample_keys = sample_keys;
+  if (fixed) { p->fx_mask = fixed->mask; p->fx_x0c = fixed->x0c; p->fx_cc = fixed->cc; p->fx_tab = fixed->tab; p->fx_mode = fixed->mode; }
 }
 
-static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr, const uint64_t* sample_keys = nullptr) {
+static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr, const uint64_t* sample_keys = nullptr,
+                          const dd_fixed* fixed = nullptr) {
   const Fwd f(s);
   const Workspace& w = f.w;
   DriftGrads d;
   DD_TRY(launch_drifts(s, w, true, st, &d));
   StepRowsArgs r, rb;
   StepPosArgs p;
-  fill_step_args(s, d, sample_keys, &r, &rb, &p);
+  fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p);
   const bool advanced = fold && fold->advance;
   r.counter_bias = rb.counter_bias = p.counter_bias = advanced ? 1 : 0;
   r.hid = w.qn; r.W2 = f.GW(DD_G_VH_W2); r.b2 = f.GW(DD_G_VH_b2); r.logits_out = s->pred_v;
@@ -1225,7 +1231,7 @@ static int reverse_step_from_logits(const dd_sampler* s, const float* logits_v, 
   DD_TRY(launch_drifts(s, w, false, st, &d));
   StepRowsArgs r, rb;
   StepPosArgs p;
-  fill_step_args(s, d, nullptr, &r, &rb, &p);
+  fill_step_args(s, d, nullptr, nullptr, &r, &rb, &p);
   r.logits_in = logits_v;
   rb.logits_in = logits_b;
   p.x0 = x0;
@@ -1234,6 +1240,15 @@ static int reverse_step_from_logits(const dd_sampler* s, const float* logits_v, 
   DD_TRY(launch_step_pos(p, st));
   DD_TRY(launch_advance(s->step_counter, st));
   return DD_OK;
+}
+
+// dd_fixed_init: the held rows' state in front of the first step (dd_step.hip::k_fixed_init)
+static int fixed_init(const dd_sampler* s, const uint64_t* sample_keys, const dd_fixed* fixed, hipStream_t st) {
+  DriftGrads d;
+  StepRowsArgs r, rb;
+  StepPosArgs p;
+  fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p);
+  return launch_fixed_init(rb, r, p, st);
 }
 
 // forward-only head evaluation: logits without sampling (state untouched)
@@ -1595,7 +1610,7 @@ static int one_step(const dd_sampler* s, hipStream_t st, const dd::ModelOpts& mo
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
   int rc = dd::forward_impl(s, st, &fold, mo);
   if (rc != DD_OK) return rc;
-  return dd::heads_and_step(s, st, &fold, mo.sample_keys);
+  return dd::heads_and_step(s, st, &fold, mo.sample_keys, mo.fixed);
 }
 
 extern "C" int dd_reverse_step(const dd_sampler* s, const float* logits_v, const float* logits_b, const float* x0, void* stream) {
@@ -1627,11 +1642,31 @@ static bool keys_with_injected_noise(const dd_sampler* s, const uint64_t* sample
   return sample_keys != nullptr && s != nullptr && (s->u_v != nullptr || s->u_b != nullptr || s->eps != nullptr);
 }
 
+// The caller's dd_fixed as a checked copy (fields beyond its `size` are NULL / 0); NULL stays "no fixed atoms"
+static int read_fixed(const dd_fixed* fixed, dd_fixed* out) {
+  memset(out, 0, sizeof(*out));
+  if (fixed->size < (int32_t)sizeof(int32_t) || fixed->size > 4096) return DD_ERR_BAD_ARG;
+  memcpy(out, fixed, (size_t)fixed->size < sizeof(*out) ? (size_t)fixed->size : sizeof(*out));
+  out->size = (int32_t)sizeof(*out);
+  if (out->mode != DD_FIXED_HOLD && out->mode != DD_FIXED_REPLACE) return DD_ERR_BAD_ARG;
+  if (!out->mask || !out->v0 || !out->b0 || !out->x0c) return DD_ERR_BAD_ARG;
+  if (out->mode == DD_FIXED_REPLACE && (!out->cc || !out->tab)) return DD_ERR_BAD_ARG;
+  return DD_OK;
+}
+
 extern "C" int dd_sample_steps_keyed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, int n_steps, void* stream) {
+  return dd_sample_steps_fixed(s, opts, sample_keys, nullptr, n_steps, stream);
+}
+
+extern "C" int dd_sample_steps_fixed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                                     int n_steps, void* stream) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || n_steps < 0 || keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
+  dd_fixed fx;
+  if (fixed != nullptr && read_fixed(fixed, &fx) != DD_OK) return DD_ERR_BAD_ARG;
   mo.sample_keys = sample_keys;
+  mo.fixed = fixed != nullptr ? &fx : nullptr;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_steps; ++i) {
     int rc = one_step(s, st, mo);
@@ -1726,11 +1761,30 @@ extern "C" int dd_graph_create_opts(const dd_sampler* s, const dd_model_opts* op
 
 extern "C" int dd_graph_create_keyed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, int steps_per_graph,
                                      void* stream, void** graph_out) {
+  return dd_graph_create_fixed(s, opts, sample_keys, nullptr, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_fixed_init(const dd_sampler* s, const uint64_t* sample_keys, const dd_fixed* fixed, void* stream) {
+  if (!check_step_sampler(s) || !fixed || !s->lig_pos || !s->lig_v || !s->lig_bond) return DD_ERR_BAD_ARG;
+  dd_fixed fx;
+  if (read_fixed(fixed, &fx) != DD_OK || keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
+  // replace draws level t_start itself: a chain with injected noise supplies that level, and the level must exist
+  if (fx.mode == DD_FIXED_REPLACE && (s->u_v || s->u_b || s->eps || s->t_start < 0 || s->t_start >= s->T)) return DD_ERR_BAD_ARG;
+  int rc = dd::check_shapes(s);
+  if (rc != DD_OK) return rc;
+  return dd::fixed_init(s, sample_keys, &fx, (hipStream_t)stream);
+}
+
+extern "C" int dd_graph_create_fixed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                                     int steps_per_graph, void* stream, void** graph_out) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || !graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
   if (keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
+  dd_fixed fx;
+  if (fixed != nullptr && read_fixed(fixed, &fx) != DD_OK) return DD_ERR_BAD_ARG;
   mo.sample_keys = sample_keys;
+  mo.fixed = fixed != nullptr ? &fx : nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   int rc = dd::check_shapes(s);

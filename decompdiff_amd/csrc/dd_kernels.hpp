@@ -223,6 +223,12 @@ struct StepRowsArgs {
   const uint64_t* sample_keys;   // [B], read at every launch
   const int32_t* nl_real;        // [B] real ligand sizes (bond rows of padded batches), or NULL
   int NL;                        // dense ligand width (bond rows: rows_per_sample = NL * (NL - 1))
+  // fixed atoms (dd_sample_steps_fixed; include/decompdiff_hip.h), all device pointers read at every launch.  fx_mask == NULL:
+  // nothing is held.  An atom row is held iff its mask byte is set, a bond row (fx_bond) iff both its endpoints' are.
+  const uint8_t* fx_mask;        // [B*NL]
+  const int32_t* fx_val;         // [rows] known clean classes (read at held rows only)
+  int fx_mode;                   // DD_FIXED_HOLD / DD_FIXED_REPLACE
+  int fx_bond;                   // 1: the rows are bond rows dst * (NL - 1) + sp of their sample
 };
 struct StepPosArgs {
   int B, NL, T;
@@ -243,11 +249,20 @@ struct StepPosArgs {
   const float* eps;         // [n_steps,B*NL,3] or NULL
   float* traj_pos;          // [n_steps,B*NL,3] or NULL
   const uint64_t* sample_keys;   // [B] per-sample noise keys or NULL: key sample_keys[b], index 3 * i + c inside the sample
+  // fixed atoms (see StepRowsArgs); fx_mask == NULL: nothing is held
+  const uint8_t* fx_mask;        // [B*NL]
+  const float* fx_x0c;           // [B*NL,3] known clean coordinates, centred
+  const float* fx_cc;            // [B*NL,3] centred prior centres of the atoms' arms (replace mode)
+  const float* fx_tab;           // [2][T] sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod) (replace mode)
+  int fx_mode;
 };
 int launch_step_rows(const StepRowsArgs& a, hipStream_t st);
 int launch_step_pos(const StepPosArgs& a, hipStream_t st);
 int launch_advance(int32_t* ctr, hipStream_t st);
 int launch_reset_run_state(int32_t* rs, int t_start, uint64_t seed, hipStream_t st);
 int launch_step_all(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, hipStream_t st);
+// fixed atoms: hold mode writes the known values into the state, replace mode draws the held rows' level t_start (the run state's)
+// at Philox time t_start + 1; atoms, bonds and coordinates in one launch
+int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, hipStream_t st);
 
 }  // namespace dd

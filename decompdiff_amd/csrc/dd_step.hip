@@ -81,7 +81,31 @@ __device__ __forceinline__ float log_add_exp(float a, float b) {
   return m + logf(expf(a - m) + expf(b - m));
 }
 
-template <int NC>
+// ---- fixed atoms (include/decompdiff_hip.h, dd_fixed).  FIXED instantiations only; the others carry none of this.
+// A held atom row: its mask byte; a held bond row: both endpoints' bytes (row r of a sample: dst = r / (NL - 1),
+// sp = r % (NL - 1), src = sp + (sp >= dst)).  Padding atoms carry 0, so no bond that touches one is held.
+__device__ __forceinline__ bool row_held(const StepRowsArgs& a, const long row) {
+  if (!a.fx_bond) return a.fx_mask[row] != 0;
+  const int b = (int)(row / a.rows_per_sample);
+  const int r = (int)(row - (long)b * a.rows_per_sample);
+  const int dst = r / (a.NL - 1), sp = r - dst * (a.NL - 1), src = sp + (sp >= dst ? 1 : 0);
+  const uint8_t* m = a.fx_mask + (long)b * a.NL;
+  return m[dst] != 0 && m[src] != 0;
+}
+// log q(v_l | v0) of the forward process for class c with the CLEAN one-hot (transitions.py:146-150): the q0 of the step with
+// log(clamp(onehot, 1e-30)) in place of the prediction; lca / l1mca at level l
+__device__ __forceinline__ float fixed_q0(const bool is_v0, const float lca, const float l1mca, const float log_prior) {
+  return log_add_exp((is_v0 ? 0.f : -69.07755278982137f) + lca, l1mca + log_prior);
+}
+__device__ __forceinline__ float gumbel_of(const float u) { return -logf(-logf(u + 1e-30f) + 1e-30f); }
+// x_l = A[l] (x0c - cc) + (S[l] e) std + cc (decompdiff.py:436-455 in the centred frame), every operation rounded on its own: the
+// step, the initial level and every batch layout give the same bits
+__device__ __forceinline__ float fixed_noised_pos(const float A, const float S, const float x0c, const float cc, const float e,
+                                                  const float std) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(A, __fsub_rn(x0c, cc)), __fmul_rn(__fmul_rn(S, e), std)), cc);
+}
+
+template <int NC, bool FIXED>
 __global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -157,8 +181,30 @@ __global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
     if (s > bestv) { bestv = s; best = c; }
     if (a.traj_prob) a.traj_prob[((long)step * a.rows + row) * NC + c] = lp;
   }
+  if constexpr (FIXED) {
+    if (row_held(a, row)) {
+      const int v0 = a.fx_val[row];
+      best = v0;                                          // hold, and the replace step at t = 0
+      if (a.fx_mode == DD_FIXED_REPLACE && t > 0) {
+        bestv = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const float s = gumbel_of(u[c]) + fixed_q0(c == v0, lca, l1mca, log_prior_tab[c]);
+          if (s > bestv) { bestv = s; best = c; }
+        }
+      }
+    }
+  }
   a.state[row] = best;
   if (a.traj_state) a.traj_state[(long)step * a.rows + row] = best;
+}
+
+template <bool FIXED>
+__device__ __forceinline__ void step_pos_elem(const StepPosArgs& a, const int idx, const RunState rs);
+
+// (fixed atoms: the coordinate element of the fused launch as a launch of its own; k_step_pos below stays the unfixed one)
+__global__ void k_step_pos_fixed(const StepPosArgs a) {
+  step_pos_elem<true>(a, blockIdx.x * blockDim.x + threadIdx.x, load_run_state(a.step_counter, a.counter_bias));
 }
 
 __global__ void k_step_pos(const StepPosArgs a) {
@@ -434,7 +480,7 @@ __global__ __launch_bounds__(256) void k_drift_clash(const float* __restrict__ p
 // tried: ~1800 atomics on one address serialise to 45 us).  A row is one wave: the
 // second head Linear uses the whole wave, the per-class posterior / Gumbel arithmetic runs one class per lane with
 // the cross-class sums taken in class order through v_readlane (bit-identical to the serial k_step_rows).
-template <int NC>
+template <int NC, bool FIXED>
 __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, const int lane, const RunState rs) {
   const int step = rs.step, t = rs.t_start - step;
   float2 hv = *reinterpret_cast<const float2*>(a.hid + row * 128 + 2 * lane);
@@ -481,13 +527,24 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
     u = philox_uniform<NC>(na.key, na.row, t, a.stream_id, c);
   }
   const float lp = un - ulse;
-  const float sc = -logf(-logf(u + 1e-30f) + 1e-30f) + lp;      // Gumbel-argmax (transitions.py:78-84)
+  float sc = -logf(-logf(u + 1e-30f) + 1e-30f) + lp;            // Gumbel-argmax (transitions.py:78-84)
+  int v0 = -1;                                                   // FIXED, held row (wave-uniform): its known class
+  if constexpr (FIXED) {
+    if (row_held(a, row)) {
+      v0 = a.fx_val[row];
+      // replace: the row's draw of this step decides the forward sample of the clean class at level t - 1 instead
+      if (a.fx_mode == DD_FIXED_REPLACE && t > 0) sc = gumbel_of(u) + fixed_q0(c == v0, lca, l1mca, log_prior);
+    }
+  }
   int best = 0;
   float bestv = -INFINITY;
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
     const float sk = lane_bcast(sc, k);
     if (sk > bestv) { bestv = sk; best = k; }
+  }
+  if constexpr (FIXED) {
+    if (v0 >= 0 && (a.fx_mode != DD_FIXED_REPLACE || t == 0)) best = v0;
   }
   if (lane < NC) {
     if (a.logits_out) a.logits_out[row * NC + c] = mine;
@@ -500,6 +557,7 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
   }
 }
 
+template <bool FIXED>
 __device__ __forceinline__ void step_pos_elem(const StepPosArgs& a, const int idx, const RunState rs) {
   const int n = a.B * a.NL * 3;
   if (idx >= n) return;
@@ -527,23 +585,30 @@ __device__ __forceinline__ void step_pos_elem(const StepPosArgs& a, const int id
     e = step_pos_normal(a, idx, b, rs.seed, t);
   }
   const float nz = t == 0 ? 0.f : 1.f;
-  const float nxt = mean + nz * expf(0.5f * a.tab_pos[2 * a.T + t]) * e * a.atom_std[idx];
+  float nxt = mean + nz * expf(0.5f * a.tab_pos[2 * a.T + t]) * e * a.atom_std[idx];
+  if constexpr (FIXED) {
+    if (a.fx_mask[atom] != 0) {
+      nxt = a.fx_x0c[idx];                                 // hold, and the replace step at t = 0
+      if (a.fx_mode == DD_FIXED_REPLACE && t > 0)
+        nxt = fixed_noised_pos(a.fx_tab[t - 1], a.fx_tab[a.T + t - 1], nxt, a.fx_cc[idx], e, a.atom_std[idx]);
+    }
+  }
   a.xt[idx] = nxt;
   if (a.traj_pos) a.traj_pos[(long)step * n + idx] = nxt + a.offset[b * 3 + c];
 }
 
-template <int NV>
+template <int NV, bool FIXED>
 __global__ __launch_bounds__(256) void k_step_all(const StepRowsArgs rb, const StepRowsArgs rv, const StepPosArgs p, int nb_b, int nb_v) {
   const int blk = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const RunState rs = load_run_state(rb.step_counter, rb.counter_bias);
   if (blk < nb_b) {
     const long row = (long)blk * 4 + wave;
-    if (row < rb.rows) step_row<DD_NUM_B>(rb, row, lane, rs);
+    if (row < rb.rows) step_row<DD_NUM_B, FIXED>(rb, row, lane, rs);
   } else if (blk < nb_b + nb_v) {
     const long row = (long)(blk - nb_b) * 4 + wave;
-    if (row < rv.rows) step_row<NV>(rv, row, lane, rs);
+    if (row < rv.rows) step_row<NV, FIXED>(rv, row, lane, rs);
   } else {
-    step_pos_elem(p, (blk - nb_b - nb_v) * 256 + threadIdx.x, rs);
+    step_pos_elem<FIXED>(p, (blk - nb_b - nb_v) * 256 + threadIdx.x, rs);
   }
 }
 
@@ -552,9 +617,67 @@ int launch_step_all(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPo
   const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
   const dim3 grid(nb_b + nb_v + nb_p);
   // atom classes: 8 (ligand_atom_mode 'basic'), 13 ('add_aromatic'), 23 ('full') -- utils/transforms.py:15-64,138-151
-  if (rv.NC == 8) hipLaunchKernelGGL(k_step_all<8>, grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-  else if (rv.NC == 13) hipLaunchKernelGGL(k_step_all<13>, grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-  else hipLaunchKernelGGL(k_step_all<23>, grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+  if (p.fx_mask != nullptr) {                              // fixed atoms: instantiations of their own, the others are untouched
+    if (rv.NC == 8) hipLaunchKernelGGL((k_step_all<8, true>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+    else if (rv.NC == 13) hipLaunchKernelGGL((k_step_all<13, true>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+    else hipLaunchKernelGGL((k_step_all<23, true>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+  } else if (rv.NC == 8) hipLaunchKernelGGL((k_step_all<8, false>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+  else if (rv.NC == 13) hipLaunchKernelGGL((k_step_all<13, false>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+  else hipLaunchKernelGGL((k_step_all<23, false>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
+// Fixed atoms, in front of the first step (dd_fixed_init): one thread per bond row, atom row and coordinate.  Hold: the known
+// values.  Replace: level l = t_start of the forward process with the formulas and streams of a step, drawn at Philox time
+// l + 1 -- what the step at time l + 1 would have left.  Free rows are not touched.
+template <int NC>
+__device__ __forceinline__ void fixed_init_row(const StepRowsArgs& a, const long row, const RunState rs) {
+  if (!row_held(a, row)) return;
+  const int v0 = a.fx_val[row];
+  int best = v0;
+  if (a.fx_mode == DD_FIXED_REPLACE) {
+    const int l = rs.t_start;
+    const float lca = a.tab[2 * a.T + l], l1mca = a.tab[3 * a.T + l];
+    const NoiseAddr na = noise_addr(a, row, rs.seed);
+    float bestv = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const float u = philox_uniform<NC>(na.key, na.row, l + 1, a.stream_id, c);
+      const float s = gumbel_of(u) + fixed_q0(c == v0, lca, l1mca, a.tab[4 * a.T + c]);
+      if (s > bestv) { bestv = s; best = c; }
+    }
+  }
+  a.state[row] = best;
+}
+template <int NV>
+__global__ __launch_bounds__(256) void k_fixed_init(const StepRowsArgs rb, const StepRowsArgs rv, const StepPosArgs p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const RunState rs = load_run_state(rb.step_counter, 0);
+  const long n = (long)p.B * p.NL * 3;
+  if (i < rb.rows) {
+    fixed_init_row<DD_NUM_B>(rb, i, rs);
+  } else if (i < (long)rb.rows + rv.rows) {
+    fixed_init_row<NV>(rv, i - rb.rows, rs);
+  } else if (i < (long)rb.rows + rv.rows + n) {
+    const int idx = (int)(i - rb.rows - rv.rows), atom = idx / 3;
+    if (p.fx_mask[atom] == 0) return;
+    float x = p.fx_x0c[idx];
+    if (p.fx_mode == DD_FIXED_REPLACE) {
+      const int l = rs.t_start;
+      const float e = step_pos_normal(p, idx, atom / p.NL, rs.seed, l + 1);
+      x = fixed_noised_pos(p.fx_tab[l], p.fx_tab[p.T + l], x, p.fx_cc[idx], e, p.atom_std[idx]);
+    }
+    p.xt[idx] = x;
+  }
+}
+int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, hipStream_t st) {
+  if (rb.NC != DD_NUM_B || (rv.NC != 8 && rv.NC != 13 && rv.NC != 23) || p.fx_mask == nullptr) return DD_ERR_UNSUPPORTED_SHAPE;
+  const long total = (long)rb.rows + rv.rows + (long)p.B * p.NL * 3;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (rv.NC == 8) hipLaunchKernelGGL(k_fixed_init<8>, grid, dim3(256), 0, st, rb, rv, p);
+  else if (rv.NC == 13) hipLaunchKernelGGL(k_fixed_init<13>, grid, dim3(256), 0, st, rb, rv, p);
+  else hipLaunchKernelGGL(k_fixed_init<23>, grid, dim3(256), 0, st, rb, rv, p);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
@@ -562,17 +685,24 @@ int launch_step_all(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPo
 int launch_step_rows(const StepRowsArgs& a, hipStream_t st) {
   if (a.rows <= 0) return DD_OK;
   dim3 grid((a.rows + 3) / 4);
-  if (a.NC == 8) hipLaunchKernelGGL(k_step_rows<8>, grid, dim3(256), 0, st, a);
-  else if (a.NC == 13) hipLaunchKernelGGL(k_step_rows<13>, grid, dim3(256), 0, st, a);
-  else if (a.NC == 23) hipLaunchKernelGGL(k_step_rows<23>, grid, dim3(256), 0, st, a);
-  else if (a.NC == DD_NUM_B) hipLaunchKernelGGL(k_step_rows<DD_NUM_B>, grid, dim3(256), 0, st, a);
+  if (a.fx_mask != nullptr) {                              // fixed atoms
+    if (a.NC == 8) hipLaunchKernelGGL((k_step_rows<8, true>), grid, dim3(256), 0, st, a);
+    else if (a.NC == 13) hipLaunchKernelGGL((k_step_rows<13, true>), grid, dim3(256), 0, st, a);
+    else if (a.NC == 23) hipLaunchKernelGGL((k_step_rows<23, true>), grid, dim3(256), 0, st, a);
+    else if (a.NC == DD_NUM_B) hipLaunchKernelGGL((k_step_rows<DD_NUM_B, true>), grid, dim3(256), 0, st, a);
+    else return DD_ERR_UNSUPPORTED_SHAPE;
+  } else if (a.NC == 8) hipLaunchKernelGGL((k_step_rows<8, false>), grid, dim3(256), 0, st, a);
+  else if (a.NC == 13) hipLaunchKernelGGL((k_step_rows<13, false>), grid, dim3(256), 0, st, a);
+  else if (a.NC == 23) hipLaunchKernelGGL((k_step_rows<23, false>), grid, dim3(256), 0, st, a);
+  else if (a.NC == DD_NUM_B) hipLaunchKernelGGL((k_step_rows<DD_NUM_B, false>), grid, dim3(256), 0, st, a);
   else return DD_ERR_UNSUPPORTED_SHAPE;
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
 int launch_step_pos(const StepPosArgs& a, hipStream_t st) {
   int n = a.B * a.NL * 3;
-  hipLaunchKernelGGL(k_step_pos, dim3((n + 255) / 256), dim3(256), 0, st, a);
+  if (a.fx_mask != nullptr) hipLaunchKernelGGL(k_step_pos_fixed, dim3((n + 255) / 256), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_step_pos, dim3((n + 255) / 256), dim3(256), 0, st, a);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }

@@ -46,7 +46,8 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                                    use_graph: bool = True, prior_mode: str = "ref_prior", num_atoms_mode: str = "ref",
                                    arms_natoms_config=None, scaffold_natoms_config=None, natoms_sampler=None,
                                    atom_prior_probs=None, bond_prior_probs=None, pool_batches: int = 1,
-                                   sample_key_seed: Optional[int] = None, first_sample_index: int = 0) -> Dict[str, list]:
+                                   sample_key_seed: Optional[int] = None, first_sample_index: int = 0,
+                                   fixed_fn=None, fixed_mode: str = "hold") -> Dict[str, list]:
     """Sample ``num_samples`` ligands for one pocket in batches of ``batch_size``.
 
     ``pool_batches`` > 1 assembles that many consecutive batches exactly as the reference would (same random draws, same
@@ -70,6 +71,13 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     the chains reproducible, not this function's initial draws: the initial coordinates, atom and bond types are still drawn
     from torch's CPU generator in the reference's order, batch by batch, and so still depend on the batching (and a keyed
     model call draws nothing from that generator).
+
+    ``fixed_fn(sample_index, decomp_index_of_sample)`` (not None): conditional generation -- for output sample
+    ``first_sample_index + g`` it returns ``dict(mask [n] bool, pos [n,3], v [n], bond [n*(n-1)])``, the sample's known atoms in
+    the sample's own row order (``decomp_index_of_sample``: its arm ids, -1 = scaffold), or None for nothing held.  The dicts are
+    collated into one flat ``fixed`` per model call (``sample_diffusion(fixed=...)`` with ``mode=fixed_mode``; only for models
+    that take the extra keywords); a size that does not match the sample raises ValueError.  Works with ``pool_batches`` and
+    ``sample_key_seed``; the batches' own draws and order do not change.
     """
     out = {k: [] for k in ("pred_pos", "pred_v", "pred_pos_traj", "pred_v_traj", "pred_v0_traj", "pred_vt_traj",
                            "pred_bond_index", "pred_bond_type", "pred_b_traj", "pred_bt_traj", "decomp_mask")}
@@ -115,6 +123,10 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
         if sample_key_seed is not None and extra:
             first = int(first_sample_index) + n_done
             extra = dict(use_graph=use_graph, sample_keys=sample_keys(sample_key_seed, range(first, first + n_data)))
+        if fixed_fn is not None and extra:
+            fixed = collate_fixed(fixed_fn, int(first_sample_index) + n_done, n_atoms, batch["ligand_decomp_index"], fixed_mode)
+            if fixed is not None:
+                extra["fixed"] = fixed
         n_done += n_data
         t1 = time.time()
         r = model.sample_diffusion(num_steps=num_steps, center_pos_mode=center_pos_mode,
@@ -148,6 +160,32 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
             out["pred_bt_traj"].append(bt_traj[k])
         time_list.append(time.time() - t1)
     out["time_list"] = time_list
+    return out
+
+
+def collate_fixed(fixed_fn, first_index: int, n_atoms: List[int], decomp_index: torch.Tensor, mode: str):
+    """The per-sample dicts of ``fixed_fn`` for the samples ``first_index ...`` of one model call (``n_atoms``: their ligand sizes,
+    ``decomp_index``: the call's flat arm ids) as ONE flat ``fixed`` dict in the call's row order; None if nothing is held."""
+    parts, a0 = [], 0
+    for k, n in enumerate(n_atoms):
+        f = fixed_fn(first_index + k, decomp_index[a0:a0 + n])
+        a0 += n
+        if f is None:
+            f = dict(mask=torch.zeros(n, dtype=torch.bool), pos=torch.zeros(n, 3), v=torch.zeros(n, dtype=torch.long),
+                     bond=torch.zeros(n * (n - 1), dtype=torch.long))
+            parts.append((f, False))
+            continue
+        f = {key: torch.as_tensor(f[key]) for key in ("mask", "pos", "v", "bond")}
+        for key, shape in (("mask", (n,)), ("pos", (n, 3)), ("v", (n,)), ("bond", (n * (n - 1),))):
+            if tuple(f[key].shape) != shape:
+                raise ValueError(f"fixed_fn: sample {first_index + k} has {n} ligand atoms, '{key}' must have shape {shape}, "
+                                 f"got {tuple(f[key].shape)}")
+        parts.append((f, True))
+    if not any(held for _, held in parts):
+        return None
+    out = {key: torch.cat([f[key] for f, _ in parts], 0) for key in ("mask", "pos", "v", "bond")}
+    out["pos"] = out["pos"].to(torch.float32)
+    out["mode"] = mode
     return out
 
 

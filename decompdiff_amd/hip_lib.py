@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "dd_csr_select_scratch_bytes", "dd_csr_select_count", "dd_csr_select_fill",
     "dd_forward_opts", "dd_sample_steps_opts", "dd_sample_steps_graph_opts", "dd_graph_create_opts", "dd_sample_steps_graph_multi_opts",
     "dd_sample_steps_keyed", "dd_graph_create_keyed",
+    "dd_sample_steps_fixed", "dd_graph_create_fixed", "dd_fixed_init",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -101,6 +102,26 @@ def model_opts(bond_head=None, node_out=None, num_blocks=1) -> DDModelOpts:
     if node_out is not None:
         o.node_out = ctypes.pointer(node_out)
     return o
+
+
+FIXED_HOLD, FIXED_REPLACE = 1, 2                       # DD_FIXED_HOLD / DD_FIXED_REPLACE
+FIXED_MODES = {"hold": FIXED_HOLD, "replace": FIXED_REPLACE}
+
+
+class DDFixed(ctypes.Structure):
+    """struct dd_fixed (include/decompdiff_hip.h): the fixed atoms of a chain, handed to the *_fixed entry points; `size` =
+    sizeof of this struct, every other pointer a DEVICE pointer that the kernels read at every launch (see `fixed_struct`)."""
+    _fields_ = [("size", c_int32), ("mode", c_int32), ("mask", c_void_p), ("v0", c_void_p), ("b0", c_void_p), ("x0c", c_void_p),
+                ("cc", c_void_p), ("tab", c_void_p)]
+
+
+def fixed_struct(mode, mask, v0, b0, x0c, cc=None, tab=None) -> DDFixed:
+    """A filled dd_fixed from device tensors (the caller keeps them alive); mode: "hold" / "replace"."""
+    f = DDFixed()
+    f.size, f.mode = ctypes.sizeof(DDFixed), FIXED_MODES[mode]
+    for name, t in (("mask", mask), ("v0", v0), ("b0", b0), ("x0c", x0c), ("cc", cc), ("tab", tab)):
+        setattr(f, name, None if t is None else t.data_ptr())
+    return f
 
 
 L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128      # DD_L0_TABLE_FLOATS
@@ -194,6 +215,10 @@ def load():
         # (the _opts siblings with the device pointer sample_keys [B] uint64 after opts)
         "dd_sample_steps_keyed": [S, POINTER(DDModelOpts), c_void_p, c_int, c_void_p],
         "dd_graph_create_keyed": [S, POINTER(DDModelOpts), c_void_p, c_int, c_void_p, POINTER(c_void_p)],
+        # (the _keyed siblings with the host struct dd_fixed after sample_keys; NULL: exactly the _keyed call)
+        "dd_sample_steps_fixed": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), c_int, c_void_p],
+        "dd_graph_create_fixed": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), c_int, c_void_p, POINTER(c_void_p)],
+        "dd_fixed_init": [S, c_void_p, POINTER(DDFixed), c_void_p],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],

@@ -135,6 +135,76 @@ def _check_ligand_atom_mask(mask, n_ligand):
                        "None or an all-True boolean mask is meaningful")
 
 
+FIXED_MODES = ("hold", "replace")
+
+
+def _as_fixed(fixed, n_ligand, fc_index, bond_type, num_classes, num_bond_classes, noise, start_step, prior_centers,
+              ligand_decomp_batch, ligand_atom_mask, dev):
+    """``fixed`` of sample_diffusion, validated (ValueError) and moved to the device: dict(mode, init, mask bool [n], pos f32 [n,3],
+    v int32 [n], bond int32 [n_bond], cc f32 [n,3] or None -- the prior centre of every atom's arm, replace mode)."""
+    if not isinstance(fixed, dict):
+        raise ValueError("fixed must be None or a dict(mask, pos, v, bond, mode[, init])")
+    unknown = set(fixed) - {"mask", "pos", "v", "bond", "mode", "init"}
+    if unknown or any(k not in fixed for k in ("mask", "pos", "v", "bond")):
+        raise ValueError(f"fixed takes the keys mask, pos, v, bond, mode and init (got {sorted(fixed)})")
+    mode = fixed.get("mode", "hold")
+    if mode not in FIXED_MODES:
+        raise ValueError(f"fixed['mode'] must be one of {FIXED_MODES}, got {mode!r}")
+    if ligand_atom_mask is not None:
+        m = torch.as_tensor(ligand_atom_mask)
+        if not (m.dtype == torch.bool and m.numel() == n_ligand and bool(m.all().item())):
+            raise ValueError("fixed excludes a ligand_atom_mask that masks atoms out: the held atoms are given by fixed['mask']")
+    mask, pos, v, bond = (torch.as_tensor(fixed[k]) for k in ("mask", "pos", "v", "bond"))
+    if mask.dtype != torch.bool:
+        raise ValueError(f"fixed['mask'] must be a bool tensor, got {mask.dtype}")
+    if fc_index is None or bond_type is None:
+        raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
+    n_bond = int(bond_type.numel())
+    for name, t, shape in (("mask", mask, (n_ligand,)), ("pos", pos, (n_ligand, 3)), ("v", v, (n_ligand,)), ("bond", bond, (n_bond,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"fixed['{name}'] must have shape {shape}, got {tuple(t.shape)}")
+    if v.dtype.is_floating_point or bond.dtype.is_floating_point or v.dtype == torch.bool or bond.dtype == torch.bool:
+        raise ValueError("fixed['v'] and fixed['bond'] must be integer class ids")
+    mask_c, v_c, bond_c = mask.cpu(), v.cpu().long(), bond.cpu().long()
+    fc = fc_index.cpu()
+    held_b = mask_c[fc[0]] & mask_c[fc[1]]                   # a bond is held iff both its endpoints are
+    hv, hb = v_c[mask_c], bond_c[held_b]
+    if hv.numel() and (int(hv.min()) < 0 or int(hv.max()) >= num_classes):
+        raise ValueError(f"fixed['v'] holds a class outside [0, {num_classes}) at a held atom")
+    if hb.numel() and (int(hb.min()) < 0 or int(hb.max()) >= num_bond_classes):
+        raise ValueError(f"fixed['bond'] holds a class outside [0, {num_bond_classes}) at a held bond")
+    init, cc = None, None
+    if mode == "replace":
+        need_given = noise is not None or int(start_step) > 0
+        init = fixed.get("init", None if need_given else "draw")
+        if init not in ("draw", "given"):
+            raise ValueError("fixed['init'] must be 'draw' or 'given'" + (
+                " ('given' is required with noise= and with start_step > 0: the held rows of init_ligand_* are the state)"
+                if init is None else f", got {init!r}"))
+        if need_given and init != "given":
+            raise ValueError("fixed['init'] = 'draw' needs the device generator and start_step == 0; with noise= or start_step > 0 "
+                             "pass init='given' and the held rows' state in init_ligand_*")
+        if prior_centers is None or ligand_decomp_batch is None or not torch.is_tensor(prior_centers) or prior_centers.dim() != 2 \
+                or prior_centers.shape[1] != 3 or ligand_decomp_batch.numel() != n_ligand \
+                or (ligand_decomp_batch.numel() and int(ligand_decomp_batch.max()) >= prior_centers.shape[0]):
+            raise ValueError("fixed mode 'replace' needs prior_centers [n_prior,3] and ligand_decomp_batch [n_ligand]: the forward "
+                             "process noises around the arm centres")
+        cc = prior_centers.detach().to(device=dev, dtype=torch.float32)[ligand_decomp_batch.to(dev)].contiguous()
+    elif "init" in fixed and fixed["init"] not in (None, "draw", "given"):
+        raise ValueError(f"fixed['init'] must be 'draw' or 'given', got {fixed['init']!r}")
+    # classes at free rows are never read: zero them so that the int32 copies stay in range whatever the caller left there
+    v_c = torch.where(mask_c, v_c, torch.zeros_like(v_c))
+    bond_c = torch.where(held_b, bond_c, torch.zeros_like(bond_c))
+    return dict(mode=mode, init=init, mask=mask_c.to(dev), pos=pos.detach().to(device=dev, dtype=torch.float32).contiguous(),
+                v=v_c.to(device=dev, dtype=torch.int32), bond=bond_c.to(device=dev, dtype=torch.int32), cc=cc)
+
+
+def _fixed_rows(fx, rows_l, rows_b):
+    """The rows ``rows_l`` (atoms) / ``rows_b`` (bonds) of a validated ``fixed`` (device index tensors): a group's or a sample's share."""
+    return dict(mode=fx["mode"], init=fx["init"], mask=fx["mask"][rows_l], pos=fx["pos"][rows_l], v=fx["v"][rows_l],
+                bond=fx["bond"][rows_b], cc=None if fx["cc"] is None else fx["cc"][rows_l])
+
+
 class DecompScorePosNet3D(nn.Module):
 
     def __init__(self, config, protein_atom_feature_dim, ligand_atom_feature_dim, num_classes,
@@ -282,6 +352,13 @@ class DecompScorePosNet3D(nn.Module):
         elif mode != "C0":
             raise ValueError(mode)
         return torch.stack([c0.float(), ct.float(), self.posterior_logvar.detach().float()]).contiguous()
+
+    def fixed_step_table(self):
+        """The [2][T] fp32 table the step kernels read as ``dd_fixed.tab`` (replace mode): sqrt(alphas_cumprod) and
+        sqrt(1 - alphas_cumprod) of the forward process (decompdiff.py:436-449), composed in float64 from this module's
+        ``alphas_cumprod`` and rounded once."""
+        ac = self.alphas_cumprod.detach().double()
+        return torch.stack([ac.sqrt(), (1.0 - ac).sqrt()]).float().contiguous()
 
     def _predict_x0_from_eps(self, xt, eps, t, batch):
         """x0 from a predicted noise (decompdiff.py:353-356); t [num_graphs], batch [n] on the device of the tables."""
@@ -434,7 +511,7 @@ class DecompScorePosNet3D(nn.Module):
                                          kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"].numel(), need_protein=False)
 
     def _sample_heterogeneous(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                              use_graph, start_step=0, sample_keys=None):
+                              use_graph, start_step=0, sample_keys=None, fixed=None):
         """Samples with different atom counts in one batch (PyG collate, utils/data.py:389-446).  Default: ONE launch
         sequence over the batch padded to its largest pocket / ligand with per-sample real counts (`_sample_padded`).
         Fallbacks to equal-size groups (`_sample_ragged`): DD_RAGGED_MODE=groups, or `batch_layout.fits_padded` says no."""
@@ -443,9 +520,10 @@ class DecompScorePosNet3D(nn.Module):
             layout = self._sampling_layout(kw)
             if BL.fits_padded(layout, self.config.knn):
                 return self._sample_padded(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed,
-                                           keep_traj, use_graph, start_step, layout.n_p, layout.n_l, sample_keys=sample_keys)
+                                           keep_traj, use_graph, start_step, layout.n_p, layout.n_l, sample_keys=sample_keys,
+                                           fixed=fixed)
         return self._sample_ragged(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                                   use_graph, start_step=start_step, layout=layout, sample_keys=sample_keys)
+                                   use_graph, start_step=start_step, layout=layout, sample_keys=sample_keys, fixed=fixed)
 
     def _padded_inputs(self, protein_pos, protein_v, bp, ligand_pos, ligand_v, aux, bl, fc_index, bond_type, batch_ligand_bond,
                        n_p, n_l, center_pos_mode):
@@ -491,7 +569,7 @@ class DecompScorePosNet3D(nn.Module):
         return dict(d=d, offset=offset, masks=masks, n_b=n_b, rows_l=rows_l, rows_b=rows_b, d_l=d_l, d_b=d_b)
 
     def _sample_padded(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, start_step, n_p, n_l, sample_keys=None):
+                       use_graph, start_step, n_p, n_l, sample_keys=None, fixed=None):
         """Heterogeneous batch as one padded dense batch: every sample's atoms are the first rows of its [NPmax] / [NLmax]
         blocks, the kernels read the real counts from dd_sampler.np_real / nl_real (padding atoms are no kNN candidates,
         own no softmax segment and are no members of one) and the results are gathered back into the caller's flat order.
@@ -536,9 +614,18 @@ class DecompScorePosNet3D(nn.Module):
         if num_steps + start_step > self.num_timesteps or start_step < 0:
             raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
         pw = self._packed_weights()
+        fx = None
+        if fixed is not None:                                              # scattered like the inputs; padding rows: not held
+            off_l = offset[kw["batch_ligand"].to(dev)]
+            fx = dict(mode=fixed["mode"], init=fixed["init"],
+                      mask=zeros(B * NL, dtype=torch.uint8).index_copy_(0, d_l, fixed["mask"].to(torch.uint8)),
+                      v0=zeros(B * NL, dtype=torch.int32).index_copy_(0, d_l, fixed["v"]),
+                      b0=zeros(B * Eb, dtype=torch.int32).index_copy_(0, d_b, fixed["bond"]),
+                      x0c=zeros(B * NL, 3).index_copy_(0, d_l, fixed["pos"] - off_l),
+                      cc=None if fixed["cc"] is None else zeros(B * NL, 3).index_copy_(0, d_l, fixed["cc"] - off_l))
         s, bufs, ent = self._make_sampler(d, pw, num_steps, self.num_timesteps - 1 - int(start_step), pad_noise, keep_traj,
                                           energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, 0, masks=masks,
-                                          sample_keys=sample_keys)             # (the padded batch keeps the caller's sample order)
+                                          sample_keys=sample_keys, fixed=fx)   # (the padded batch keeps the caller's sample order)
         chain = dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent)
         self._run_chains([chain], num_steps, use_graph)
         out = self._collect_chain(chain, num_steps, keep_traj, rows_atoms=rows_l, rows_bonds=rows_b)
@@ -546,7 +633,7 @@ class DecompScorePosNet3D(nn.Module):
         return out
 
     def _sample_ragged(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None):
+                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None, fixed=None):
         """One dense chain per group of samples of equal size (`BatchLayout.size_groups`).  ``split`` > 1 additionally cuts
         every group into that many sub-batches (measurement aid, tools/split_bench.py: two concurrent half-batches were
         measured slower than one chain).  ``layout``: what `_sampling_layout(kw)` gave the caller.
@@ -579,7 +666,8 @@ class DecompScorePosNet3D(nn.Module):
                 BL.batch_vector(G, g.n_f, dev) if has_full else None, sub_noise,
                 seed + 7919 * gi, keep_traj, B, start_step,        # (the armsca loss is averaged over the whole batch)
                 cache_slot=(g.ids[0] * split) // B,                # (sub-batches of one shape: own cached buffers each)
-                sample_keys=None if sample_keys is None else sample_keys[g.ids])
+                sample_keys=None if sample_keys is None else sample_keys[g.ids],
+                fixed=None if fixed is None else _fixed_rows(fixed, d_l, d_b))
             prepared.append((chain, d_l, d_b, r_l, r_b))
         if concurrent is None:
             # measured on MI355X (tools/ragged_bench.py): with the runtime's default 4 hardware queues the
@@ -733,9 +821,10 @@ class DecompScorePosNet3D(nn.Module):
         return memo[key]
 
     def _make_sampler(self, d, pw, n_steps, t_start, noise, keep_traj, drift, atom_std, offset, decomp_index,
-                      full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0, sample_keys=None):
+                      full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0, sample_keys=None, fixed=None):
         """``sample_keys``: int64 [B] (host or device), the per-sample noise keys of this chain in the order of its samples, or None
-        (the chain draws with ``seed``)."""
+        (the chain draws with ``seed``).  ``fixed``: the chain's fixed atoms in its dense layout -- dict(mode, init, mask uint8
+        [B*NL], v0 int32 [B*NL], b0 int32 [B*Eb], x0c [B*NL,3] centred, cc [B*NL,3] centred or None) -- or None."""
         lib = hip_lib.load()
         dev = d["protein_pos"].device
         B, NP, NL = d["B"], d["NP"], d["NL"]
@@ -832,6 +921,23 @@ class DecompScorePosNet3D(nn.Module):
                 bufs["sample_keys"] = torch.zeros(B, dtype=torch.int64, device=dev)
             bufs["sample_keys"].copy_(sample_keys)
         ent["keyed"] = sample_keys is not None
+        # fixed atoms: as the keys -- buffers of the entry, contents of this call, read by the kernels at every launch, so one
+        # captured graph serves every mask and every known values of its mode
+        ent["fixed"], ent["fixed_struct"] = None, None
+        if fixed is not None:
+            replace = fixed["mode"] == "replace"
+            for k, shape, dtype in (("mask", (B * NL,), torch.uint8), ("v0", (B * NL,), torch.int32), ("b0", (B * Eb,), torch.int32),
+                                    ("x0c", (B * NL, 3), torch.float32), ("cc", (B * NL, 3), torch.float32)):
+                if k == "cc" and not replace:
+                    continue
+                if bufs.get("fx_" + k) is None:
+                    bufs["fx_" + k] = torch.zeros(shape, dtype=dtype, device=dev)
+                bufs["fx_" + k].copy_(fixed[k].reshape(shape))
+            if replace and pw.get("tab_fixed") is None:
+                pw["tab_fixed"] = self.fixed_step_table().to(dev)
+            ent["fixed"] = fixed["mode"]
+            ent["fixed_struct"] = hip_lib.fixed_struct(fixed["mode"], bufs["fx_mask"], bufs["fx_v0"], bufs["fx_b0"], bufs["fx_x0c"],
+                                                       bufs["fx_cc"] if replace else None, pw["tab_fixed"] if replace else None)
         for k in ("u_v", "u_b", "eps"):
             bufs[k] = None
         if noise is not None:
@@ -890,12 +996,19 @@ class DecompScorePosNet3D(nn.Module):
         if src is not None:
             ent["uploaded"] = [(t, None if t is None else t._version) for t in src]
             ent["uploaded_pw"], ent["uploaded_l0"], ent["uploaded_mode"] = pw, bool(use_l0), d.get("upload_mode")
-        if n_steps > 0:
+        draw_level = fixed is not None and fixed["mode"] == "replace" and fixed["init"] == "draw"
+        if n_steps > 0 or draw_level:                      # (a chain of no steps still prepares its held rows)
             hip_lib.check(lib.dd_sampler_reset(ctypes.byref(sm), hip_lib.stream_ptr(dev)), "dd_sampler_reset")
+        # held rows in front of the first step: hold -- the known values; replace, init 'draw' -- level t_start at Philox time
+        # t_start + 1 ('given': init_ligand_* already holds that level)
+        if fixed is not None and (fixed["mode"] == "hold" or draw_level):
+            keys_ptr = hip_lib.ptr(bufs["sample_keys"]) if sample_keys is not None else None
+            hip_lib.check(lib.dd_fixed_init(ctypes.byref(sm), keys_ptr, ctypes.byref(ent["fixed_struct"]), hip_lib.stream_ptr(dev)),
+                          "dd_fixed_init")
         # everything that shapes the captured step graph besides the (cached) pointers
         ent["sig"] = (sm.drift_armsca, sm.armsca_min_d, sm.armsca_max_d, sm.armsca_scale, sm.drift_clash, sm.clash_sigma,
                       sm.clash_gamma, sm.clash_scale, sm.drift_repul, sm.repul_max_d, sm.repul_scale, sm.drift_norm_batch,
-                      int(lib.dd_debug_options_epoch()), bool(use_l0), ent["keyed"])
+                      int(lib.dd_debug_options_epoch()), bool(use_l0), ent["keyed"], fixed is not None, ent["fixed"])
         if cacheable:
             cache[key] = ent                               # (re-inserted: most recently used last)
             self._evict_chain_cache(self._CACHE_MAX)
@@ -1057,7 +1170,7 @@ class DecompScorePosNet3D(nn.Module):
                          energy_drift_opt=None,
                          full_protein_pos=None, full_batch_protein=None,
                          noise=None, seed=None, keep_traj=True, use_graph=True, start_step=0, _drift_norm_batch=0,
-                         sample_keys=None):
+                         sample_keys=None, fixed=None):
         """Reverse diffusion (reference: models/decompdiff.py:552-703), same arguments and return
         keys.  Extra keyword-only knobs (all optional, reference call sites never pass them):
 
@@ -1075,6 +1188,18 @@ class DecompScorePosNet3D(nn.Module):
           ``seed=sample_keys[b]`` receives, whatever batch it sits in -- dense, padded or grouped, at any position, with
           any B -- so its chain is reproducible bit for bit under re-batching, sharding and re-ordering.  Excludes
           ``noise`` and an explicit ``seed`` (ValueError).
+        * ``fixed`` — conditional generation (EXTENSION; the reference's ``ligand_atom_mask`` hook, decompdiff.py:597,621-622,
+          682-683, cannot run): ``dict(mask bool [n_ligand], pos [n,3], v [n], bond [n_bond], mode="hold" | "replace", init=...)``
+          in the caller's row order.  ``mask`` True = the atom is held at the known ``pos`` / ``v``; a bond is held at ``bond``
+          iff both its endpoints are.  The network and the drift terms see the whole ligand; free rows step exactly as without
+          ``fixed`` with the same draws, and ``v0_traj`` / ``vt_traj`` / ``bt_traj`` stay the network's and the posterior's for
+          every row.  ``hold``: the held rows keep the known values through every step (reported coordinates:
+          ``(known - offset) + offset`` in fp32).  ``replace`` (RePaint): the step at time t leaves the held rows at a fresh
+          forward-process sample of their clean values at level t - 1, drawn with the row's own draws of that step, and the
+          step at t = 0 leaves the clean values; ``init="draw"`` (default without ``noise`` and with ``start_step == 0``) draws
+          their level ``t_start`` on the device first, ``init="given"`` (required with ``noise`` / ``start_step > 0``) takes the
+          held rows of ``init_ligand_*`` as that level.  ``replace`` needs ``prior_centers``.  Bad shapes, dtypes, modes or
+          classes raise ValueError; so does a ``ligand_atom_mask`` that masks atoms out.
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
@@ -1087,6 +1212,10 @@ class DecompScorePosNet3D(nn.Module):
                 raise ValueError("sample_keys excludes noise= and an explicit seed=: a chain draws from one source")
             sample_keys = _as_sample_keys(sample_keys, batch_ligand)
             seed = 0                                             # (not read by a keyed chain; no draw from torch's generator)
+        if fixed is not None:
+            fixed = _as_fixed(fixed, batch_ligand.numel(), ligand_fc_bond_index, init_ligand_fc_bond_type, self.num_classes,
+                              self.num_bond_classes, noise, start_step, prior_centers, ligand_decomp_batch, ligand_atom_mask,
+                              protein_pos.device)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         key_t = (protein_pos, batch_protein, batch_ligand, ligand_fc_bond_index, ligand_v_aux)
@@ -1102,12 +1231,12 @@ class DecompScorePosNet3D(nn.Module):
                      init_ligand_fc_bond_type=init_ligand_fc_bond_type, batch_ligand_bond=batch_ligand_bond,
                      full_protein_pos=full_protein_pos, full_batch_protein=full_batch_protein),
                 ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
-                start_step=start_step, sample_keys=sample_keys)
+                start_step=start_step, sample_keys=sample_keys, fixed=fixed)
         chain = self._prepare_chain(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
                                     batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                                     ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode,
                                     energy_drift_opt, full_protein_pos, full_batch_protein, noise, seed, keep_traj,
-                                    _drift_norm_batch, start_step, static=static, sample_keys=sample_keys)
+                                    _drift_norm_batch, start_step, static=static, sample_keys=sample_keys, fixed=fixed)
         if static is None and "static" in chain:
             self._static_memo_put(key_t, center_pos_mode, chain["static"])
         tr = self.__dict__.get("_trace")
@@ -1124,7 +1253,7 @@ class DecompScorePosNet3D(nn.Module):
                        batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                        ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode, energy_drift_opt,
                        full_protein_pos, full_batch_protein, noise, seed, keep_traj, drift_norm_batch, start_step=0,
-                       static=None, cache_slot=0, sample_keys=None):
+                       static=None, cache_slot=0, sample_keys=None, fixed=None):
         """Validate one dense batch, centre it, allocate its state / workspace and fill the ``dd_sampler`` struct.
         ``static``: what an earlier call with the same pocket / batch-vector tensors established (_static_memo_get)."""
         d = self._dense_inputs(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
@@ -1170,9 +1299,15 @@ class DecompScorePosNet3D(nn.Module):
         d["upload_src"] = (protein_pos, protein_v, ligand_v_aux, full_protein_pos, full_batch_protein) \
             if center_pos_mode in ("protein", "none") else None
         d["upload_mode"] = center_pos_mode
+        fx = None
+        if fixed is not None:                                # centred like the ligand: the same fp32 subtraction per row
+            off_l = offset[:, None, :]
+            fx = dict(mode=fixed["mode"], init=fixed["init"], mask=fixed["mask"].to(torch.uint8), v0=fixed["v"], b0=fixed["bond"],
+                      x0c=(fixed["pos"].view(B, NL, 3) - off_l).contiguous(),
+                      cc=None if fixed["cc"] is None else (fixed["cc"].view(B, NL, 3) - off_l).contiguous())
         s, bufs, ent = self._make_sampler(d, pw, num_steps, t_start, noise, keep_traj, energy_drift_opt, atom_std,
                                           offset.contiguous(), decomp, fpp, seed, drift_norm_batch, cache_slot=cache_slot,
-                                          sample_keys=sample_keys)
+                                          sample_keys=sample_keys, fixed=fx)
         return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent,
                     static=dict(layout=(B, NP, NL), offset=offset, protein_pos_centered=d["protein_pos_centered"],
                                 aux_onehot=d["aux_onehot"]))
@@ -1214,7 +1349,11 @@ class DecompScorePosNet3D(nn.Module):
             else:
                 with torch.cuda.stream(side):
                     for c in chains:
-                        if c["ent"].get("keyed"):
+                        if c["ent"].get("fixed"):
+                            rc = lib.dd_sample_steps_fixed(ctypes.byref(c["s"]), self._model_opts(),
+                                                           hip_lib.ptr(c["bufs"]["sample_keys"]) if c["ent"].get("keyed") else None,
+                                                           ctypes.byref(c["ent"]["fixed_struct"]), int(num_steps), hip_lib.stream_ptr(dev))
+                        elif c["ent"].get("keyed"):
                             rc = lib.dd_sample_steps_keyed(ctypes.byref(c["s"]), self._model_opts(), hip_lib.ptr(c["bufs"]["sample_keys"]),
                                                            int(num_steps), hip_lib.stream_ptr(dev))
                         else:
@@ -1230,8 +1369,8 @@ class DecompScorePosNet3D(nn.Module):
         for st in pool:
             st.wait_stream(cur)
         n = len(chains)
-        if any(c["ent"].get("keyed") for c in chains):
-            # keyed chains: dd_sample_steps_graph_multi_* takes no keys -- one step graph per chain on its own stream, replayed
+        if any(c["ent"].get("keyed") or c["ent"].get("fixed") for c in chains):
+            # keyed chains and chains with fixed atoms: dd_sample_steps_graph_multi_* takes neither -- one step graph per chain on its own stream, replayed
             # round-robin from this thread; no other graph is alive across their creation and they go away newest first and all
             # together (see _parked_graphs)
             self._drop_cached_graphs()
@@ -1265,7 +1404,11 @@ class DecompScorePosNet3D(nn.Module):
         a keyed chain's kernels read the keys from the entry's own buffer."""
         lib = hip_lib.load()
         graph = ctypes.c_void_p()
-        if chain["ent"].get("keyed"):
+        if chain["ent"].get("fixed"):
+            rc = lib.dd_graph_create_fixed(ctypes.byref(chain["s"]), self._model_opts(),
+                                           hip_lib.ptr(chain["bufs"]["sample_keys"]) if chain["ent"].get("keyed") else None,
+                                           ctypes.byref(chain["ent"]["fixed_struct"]), int(steps_per_graph), stream, ctypes.byref(graph))
+        elif chain["ent"].get("keyed"):
             rc = lib.dd_graph_create_keyed(ctypes.byref(chain["s"]), self._model_opts(), hip_lib.ptr(chain["bufs"]["sample_keys"]),
                                            int(steps_per_graph), stream, ctypes.byref(graph))
         else:

@@ -510,6 +510,46 @@ int dd_sample_steps_keyed(const dd_sampler* s, const dd_model_opts* opts /*HOST*
 int dd_graph_create_keyed(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B]*/,
                           int steps_per_graph, void* stream, void** graph_out /*HOST*/);
 
+/* Fixed atoms (EXTENSION; generalises the reference's ligand_atom_mask hook, decompdiff.py:597,621-622,682-683, which its own
+ * loop cannot run): some ligand atoms are KNOWN and are held, or re-noised, at every reverse step while the rest is sampled.
+ * The network and the drift terms always see the whole ligand; pred_*, traj_v0 / traj_vt / traj_bt stay what the network and
+ * the posterior say for every row, and a free row steps exactly as without `fixed`, with the very same draws.
+ *   mask [B*NL] uint8: != 0 -- the atom is held.  A bond row is held iff BOTH its endpoints are: row r of a sample has
+ *     dst = r / (NL - 1), sp = r % (NL - 1), src = sp + (sp >= dst).  Padding atoms of a padded batch must carry 0.
+ *   v0 [B*NL] int32, b0 [B*NL*(NL-1)] int32, x0c [B*NL,3] float: the known clean classes / centred coordinates (x - offset of
+ *     the sample); read at held rows only.
+ *   DD_FIXED_HOLD: every step writes the known values into the state (and the trajectories) of the held rows.
+ *   DD_FIXED_REPLACE (RePaint): the step at time t leaves the held rows at a fresh sample of the forward process at level
+ *     t - 1 (decompdiff.py:436-455, transitions.py:146-150), drawn with the row's OWN draws of that step -- those a free row
+ *     spends on its transition: injected u_v / u_b / eps rows, or Philox (key, row, t, stream) as addressed above --
+ *       x = A[t-1] * (x0c - cc) + (S[t-1] * e) * atom_std + cc       cc [B*NL,3]: centred prior centre of the atom's arm,
+ *                                                                    tab [2][T]: A = sqrt(alphas_cumprod), S = sqrt(1 - A^2)
+ *       class = argmax_c gumbel(u_c) + log_add_exp(log_onehot(v0)_c + log_cumprod[t-1], log_1m_cumprod[t-1] + log_prior_c)
+ *     and the step at t = 0 leaves x0c / v0 / b0 themselves.  "Level l of a held row is drawn at time l + 1", always.
+ *   dd_fixed_init: prepares the state in front of the first step -- HOLD: the known values; REPLACE: level t_start with the
+ *     same formulas and streams at Philox time t_start + 1 (after dd_sampler_reset; no injected noise: DD_ERR_BAD_ARG), so a
+ *     chain split with another t_start continues the unsplit one.  A host that supplies level t_start itself skips the call.
+ * All pointers are DEVICE pointers read at every launch: a graph from dd_graph_create_fixed serves every chain of its shape
+ * and mode, whatever the mask and the known values.  `size` is the caller's sizeof(dd_fixed), as in dd_model_opts.
+ *   fixed == NULL: exactly the _keyed entry point (dd_fixed_init: DD_ERR_BAD_ARG).  A NULL mask / v0 / b0 / x0c, an unknown mode,
+ *   REPLACE without cc / tab: DD_ERR_BAD_ARG before any launch.  dd_reverse_step stays unfixed.  (New entry points, ABI unchanged.) */
+enum { DD_FIXED_HOLD = 1, DD_FIXED_REPLACE = 2 };
+typedef struct dd_fixed {
+  int32_t size;                  /* sizeof(dd_fixed) of the caller */
+  int32_t mode;                  /* DD_FIXED_HOLD / DD_FIXED_REPLACE */
+  const uint8_t* mask;           /* DEVICE [B*NL] */
+  const int32_t* v0;             /* DEVICE [B*NL] */
+  const int32_t* b0;             /* DEVICE [B*NL*(NL-1)] */
+  const float* x0c;              /* DEVICE [B*NL,3] */
+  const float* cc;               /* DEVICE [B*NL,3], REPLACE only */
+  const float* tab;              /* DEVICE [2][T], REPLACE only */
+} dd_fixed;
+int dd_sample_steps_fixed(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B] or NULL*/,
+                          const dd_fixed* fixed /*HOST*/, int n_steps, void* stream);
+int dd_graph_create_fixed(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B] or NULL*/,
+                          const dd_fixed* fixed /*HOST*/, int steps_per_graph, void* stream, void** graph_out /*HOST*/);
+int dd_fixed_init(const dd_sampler* s, const uint64_t* sample_keys /*DEVICE [B] or NULL*/, const dd_fixed* fixed /*HOST*/, void* stream);
+
 /* Drift guidance gradients at x_t (utils/guidance_funcs.py:24-78), analytic. grad [B,NL,3]. */
 int dd_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                     float* grad, int accumulate, void* stream);
