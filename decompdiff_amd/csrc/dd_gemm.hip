@@ -2,8 +2,8 @@
 //
 // Replaces the ATen addmm call sites behind every nn.Linear of the reference's MLPs
 // (models/common.py:85-105) after the first-Linear factorisation (packing.py).  Exact fp32
-// on the matrix cores: v_mfma_f32_32x32x2_f32 is bitwise a k-ordered fmaf chain
-// (cdna_hip_programming.md §3), so results do not depend on scheduling.
+// on the matrix cores: v_mfma_f32_32x32x2_f32 is bitwise an fmaf chain over its two k slots, fed here from the columns
+// (4i, 4i+2) and then (4i+1, 4i+3): an output is the chain over k = 0, 2, 1, 3, 4, 6, 5, 7, ..., whatever the scheduling.
 //
 // Tile: 64 rows x 64 cols per 256-thread workgroup, whole K=128 staged in LDS once
 // (2 x 64 x 130 floats = 66.6 KB -> 2 workgroups/CU); 4 waves as 2x2, one 32x32
@@ -47,25 +47,25 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, const int bx, const
       if (gc < a.ncols) wv[k] = *reinterpret_cast<const float4*>(a.W + (long)gc * 128 + c4);
     }
     // optional LayerNorm+ReLU prologue (MLP hidden activation), on the registers: a row's 128 channels sit in the 32
-    // lanes of a half wave (4 each), so mean / variance are half-wave reductions (4 DPP steps + one permlane swap)
+    // lanes of a half wave (4 each), so mean / variance are half-wave reductions (one permlane swap + 4 DPP steps)
     if (a.ln != nullptr) {
       const int c4 = (tid & 31) * 4;
       const float4 gm = *reinterpret_cast<const float4*>(a.ln + c4);
       const float4 bt = *reinterpret_cast<const float4*>(a.ln + 128 + c4);
-      auto half_sum = [](float v) {
-        v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); v += dpp_mov<0x141>(v); v += dpp_mov<0x140>(v);
-        return swap16_sum(v, v);
+      auto half_sum = [](float v) {                          // (the two 16-lane halves first: the K-split tile's association, bit for bit)
+        v = swap16_sum(v, v); v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); v += dpp_mov<0x141>(v); v += dpp_mov<0x140>(v);
+        return v;
       };
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float mean = half_sum((xv[k].x + xv[k].y) + (xv[k].z + xv[k].w)) * (1.0f / 128.0f);
         const float dx = xv[k].x - mean, dy = xv[k].y - mean, dz = xv[k].z - mean, dw = xv[k].w - mean;
-        const float var = half_sum(fmaf(dx, dx, dy * dy) + fmaf(dz, dz, dw * dw)) * (1.0f / 128.0f);
-        const float rstd = dd_rsqrt(var + 1e-5f);
-        xv[k].x = fmaxf(fmaf(dx * rstd, gm.x, bt.x), 0.f);
-        xv[k].y = fmaxf(fmaf(dy * rstd, gm.y, bt.y), 0.f);
-        xv[k].z = fmaxf(fmaf(dz * rstd, gm.z, bt.z), 0.f);
-        xv[k].w = fmaxf(fmaf(dw * rstd, gm.w, bt.w), 0.f);
+        // (one expression, so that  sum / 128 + eps  contracts to one fma as it does in the K-split tile)
+        const float rstd = dd_rsqrt(half_sum(fmaf(dx, dx, dy * dy) + fmaf(dz, dz, dw * dw)) * (1.0f / 128.0f) + 1e-5f);
+        xv[k].x = relu_nan(fmaf(dx * rstd, gm.x, bt.x));
+        xv[k].y = relu_nan(fmaf(dy * rstd, gm.y, bt.y));
+        xv[k].z = relu_nan(fmaf(dz * rstd, gm.z, bt.z));
+        xv[k].w = relu_nan(fmaf(dw * rstd, gm.w, bt.w));
       }
     }
 #pragma unroll
@@ -487,4 +487,35 @@ extern "C" int dd_gemm128_tn_bias(const float* A, int lda, int M, const float* X
                                   int accumulate, float* bias_out, void* stream) {
   if (!bias_out) return DD_ERR_BAD_ARG;
   return gemm128_tn_impl(A, lda, M, X, ldx, rows, scratch, out, ldo, accumulate, bias_out, stream);
+}
+
+// Test access (include/decompdiff_hip_debug.h): the batched projection launch of the forward (launch_gemm128_batch) from explicit
+// job descriptions.  Everything the tile reads with 16-byte accesses is checked here, before anything is launched.
+extern "C" int dd_debug_gemm128_batch(const dd_gemm_job* jobs, int njobs, void* stream) {
+  if (!jobs || njobs < 1 || njobs > dd::DD_GEMM_BATCH_MAX) return DD_ERR_BAD_ARG;
+  auto misaligned = [](const void* p) { return (reinterpret_cast<size_t>(p) & 15) != 0; };
+  dd::GemmArgs g[dd::DD_GEMM_BATCH_MAX];
+  for (int i = 0; i < njobs; ++i) {
+    const dd_gemm_job& j = jobs[i];
+    if (!j.X || !j.W || !j.Y || j.rows <= 0 || j.ncols <= 0 || j.x_rows_per_b <= 0 || j.y_rows_per_b <= 0) return DD_ERR_BAD_ARG;
+    if (misaligned(j.X) || misaligned(j.W) || misaligned(j.X2) || misaligned(j.ln)) return DD_ERR_BAD_ARG;
+    if ((j.ldx & 3) != 0 || (j.x_stride_b & 3) != 0) return DD_ERR_BAD_ARG;
+    if (j.bias && j.ncols >= 4 && misaligned(j.bias)) return DD_ERR_BAD_ARG;          // (column groups of 4 are read as float4)
+    const bool y_vec = (j.ldy & 3) == 0 && (j.y_stride_b & 3) == 0 && !misaligned(j.Y);
+    if (j.accumulate && j.acc_src && y_vec && misaligned(j.acc_src)) return DD_ERR_BAD_ARG;
+    if (j.X2) {
+      if ((j.x2_ld & 3) != 0) return DD_ERR_BAD_ARG;
+      if (j.x2_Eb > 0) {
+        if (j.x2_N <= 0 || j.x2_NLm1 <= 0 || j.x2_Eb % j.x2_NLm1 != 0 || j.x2_ld <= 0) return DD_ERR_BAD_ARG;
+        if (!dd::g_gemm_ksplit) return DD_ERR_BAD_ARG;                                 // (gemm_tile has the node form only)
+      } else if (j.x2_Eb < 0 || j.x2_NP < 0 || j.x2_N <= j.x2_NP) {
+        return DD_ERR_BAD_ARG;
+      }
+    }
+    g[i] = dd::gemm_args(j.X, j.x_rows_per_b, j.x_stride_b, j.ldx, j.rows, j.W, j.bias, j.ln, j.Y, j.y_rows_per_b, j.y_stride_b, j.ldy,
+                         j.ncols, j.accumulate ? 1 : 0);
+    g[i].acc_src = j.accumulate ? j.acc_src : nullptr;
+    if (j.X2) { g[i].X2 = j.X2; g[i].x2_N = j.x2_N; g[i].x2_NP = j.x2_NP; g[i].x2_Eb = j.x2_Eb; g[i].x2_NLm1 = j.x2_NLm1; g[i].x2_ld = j.x2_ld; }
+  }
+  return dd::launch_gemm128_batch(g, njobs, (hipStream_t)stream);
 }

@@ -9,6 +9,9 @@ namespace dd {
 
 constexpr int GT = 64;        // tile rows / cols
 constexpr int GP = 130;       // LDS row pitch (floats)
+// ReLU of the LayerNorm prologue that keeps a NaN: fmaxf(v, 0.f) is v_max_f32, which returns 0 for a NaN operand -- an input row
+// with a NaN / Inf in it came out as the bias alone, finite, where the reference's relu hands the NaN on
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 
 
 // element offset of logical row r: rows are grouped in batches of rows_per_b (stride_b apart), ld apart inside a
@@ -89,7 +92,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, float* sm /*>= 
 
 // K-split variant for jobs without the LayerNorm prologue: the two 64-wide halves of K go through a 33 KB LDS
 // image (4 workgroups/CU instead of 2); the second half's global loads are in flight while the first half is
-// multiplied.  Same MFMA order per output element as gemm_tile (k ascending), hence bit-identical results.
+// multiplied.  Same MFMA order per output element as gemm_tile (k = 0, 2, 1, 3, 4, 6, ...), hence bit-identical results.
 constexpr int GPH = 66;       // LDS pitch of a K-half tile: (66*row) mod 64 = 2*row -> conflict-free ds_read_b64
 // `ticket` (persistent queue): the workgroup's NEXT ticket is drawn by thread 0 right after the second K-half went to LDS --
 // every load of the wave has been consumed by then, so the returning atomic (which retires in order with loads) stalls
@@ -185,10 +188,10 @@ __device__ __forceinline__ void gemm_tile_ksplit(const GemmArgs& a, const int bx
       return v;
     };
     auto norm4 = [](float4& v, float mean, float rstd, const float4& g, const float4& b) {
-      v.x = fmaxf(fmaf((v.x - mean) * rstd, g.x, b.x), 0.f);
-      v.y = fmaxf(fmaf((v.y - mean) * rstd, g.y, b.y), 0.f);
-      v.z = fmaxf(fmaf((v.z - mean) * rstd, g.z, b.z), 0.f);
-      v.w = fmaxf(fmaf((v.w - mean) * rstd, g.w, b.w), 0.f);
+      v.x = relu_nan(fmaf((v.x - mean) * rstd, g.x, b.x));
+      v.y = relu_nan(fmaf((v.y - mean) * rstd, g.y, b.y));
+      v.z = relu_nan(fmaf((v.z - mean) * rstd, g.z, b.z));
+      v.w = relu_nan(fmaf((v.w - mean) * rstd, g.w, b.w));
     };
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

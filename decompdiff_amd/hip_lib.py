@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
 DEBUG_SYMBOLS = [
     "dd_workspace_view", "dd_workspace_view_opts", "dd_profile_step", "dd_debug_set_clock_buffer", "dd_debug_set_fusion", "dd_debug_set_option",
     "dd_debug_node_split", "dd_debug_node_split_cache_path", "dd_debug_schedule", "dd_debug_philox", "dd_debug_options_epoch", "dd_queue_error",
+    "dd_debug_gemm128_batch",
 ]
 # exported by the measurement build only (-DDD_DEBUG_OPTIONS=1): the tile-queue schedule's sticky error word
 MEASUREMENT_ONLY_SYMBOLS = ("dd_queue_error",)
@@ -130,6 +131,15 @@ L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 12
 class DDWsView(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("h", c_void_p), ("hb", c_void_p), ("ew", c_void_p), ("A", c_void_p),
                 ("nbr", c_void_p), ("Anb", c_void_p), ("lin_in_node", ctypes.c_int32)]
+
+
+class DDGemmJob(ctypes.Structure):
+    """struct dd_gemm_job (include/decompdiff_hip_debug.h): one job of dd_debug_gemm128_batch, device pointers throughout."""
+    _fields_ = [("X", c_void_p), ("x_rows_per_b", c_int), ("x_stride_b", c_long), ("ldx", c_int), ("rows", c_int),
+                ("W", c_void_p), ("bias", c_void_p), ("ln", c_void_p),
+                ("Y", c_void_p), ("y_rows_per_b", c_int), ("y_stride_b", c_long), ("ldy", c_int), ("ncols", c_int),
+                ("accumulate", c_int), ("acc_src", c_void_p),
+                ("X2", c_void_p), ("x2_N", c_int), ("x2_NP", c_int), ("x2_Eb", c_int), ("x2_NLm1", c_int), ("x2_ld", c_int)]
 
 
 PROF_CATS = ["misc", "gemm", "assemble", "attn_NE", "attn_NB", "attn_BL", "attn_PE", "attn_PB", "step", "event_pair"]
@@ -248,6 +258,7 @@ def load():
         "dd_segment_softmax": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
         "dd_debug_philox": [c_uint64, c_int, c_long, c_int, c_void_p, c_void_p],
         "dd_profile_step": [S, c_int, POINTER(c_float), c_void_p],
+        "dd_debug_gemm128_batch": [POINTER(DDGemmJob), c_int, c_void_p],
     }
     restypes = {"dd_workspace_floats": c_size_t, "dd_gemm128_tn_scratch_floats": c_size_t, "dd_ln_relu_scratch_floats": c_size_t,
                 "dd_csr_select_scratch_bytes": c_size_t}

@@ -78,6 +78,27 @@ int dd_workspace_view(const dd_sampler* s, dd_ws_view* out);
  * num_blocks * num_layers of them; opts == NULL: dd_workspace_view). */
 int dd_workspace_view_opts(const dd_sampler* s, const dd_model_opts* opts, dd_ws_view* out);
 
+/* Test aid: ONE batched projection launch (the launch every nn.Linear of the forward goes through) from explicit job
+ * descriptions -- the fields of a dd_gemm128 call per job, plus
+ *   accumulate / acc_src   Y = result + acc_src (NULL: Y itself), same layout as Y
+ *   X2                     second addend of the input rows, added BEFORE the LayerNorm prologue (NULL: none)
+ *     node form (x2_Eb == 0):  X[r] += X2[((r / x2_N) * (x2_N - x2_NP) + r % x2_N - x2_NP) * 128]   for r % x2_N >= x2_NP
+ *     bond form (x2_Eb > 0):   X[r] += X2[((r / x2_Eb) * x2_N + (r % x2_Eb) / x2_NLm1) * x2_ld]
+ * DD_ERR_BAD_ARG, before anything is launched, for what the tile cannot address: njobs outside 1..6; NULL X, W or Y; X, W, X2
+ * or ln not 16-byte aligned; a bias (ncols >= 4) or an acc_src (beside a 16-byte aligned Y with ldy, y_stride_b multiples of 4)
+ * that the 16-byte accesses of the epilogue would read misaligned; ldx, x_stride_b or x2_ld not a multiple of 4; rows, ncols or
+ * rows-per-block <= 0; an X2 description outside  x2_N > x2_NP >= 0  (node form) /  x2_N > 0, x2_NLm1 > 0,
+ * x2_Eb % x2_NLm1 == 0  (bond form); the bond form while the K-split tile is switched off (dd_debug_set_option(1, 0): the
+ * unsplit tile has no such branch). */
+typedef struct dd_gemm_job {
+  const float* X; int x_rows_per_b; long x_stride_b; int ldx; int rows;
+  const float* W; const float* bias; const float* ln;
+  float* Y; int y_rows_per_b; long y_stride_b; int ldy; int ncols;
+  int accumulate; const float* acc_src;
+  const float* X2; int x2_N, x2_NP, x2_Eb, x2_NLm1, x2_ld;
+} dd_gemm_job;
+int dd_debug_gemm128_batch(const dd_gemm_job* jobs, int njobs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
