@@ -756,6 +756,7 @@ struct ModelOpts {
   int num_blocks = 1;
   const uint64_t* sample_keys = nullptr;   // per-sample noise keys of the *_keyed entry points ([B], device), not part of dd_model_opts
   const dd_fixed* fixed = nullptr;         // fixed atoms of the *_fixed entry points (a checked host copy), not part of dd_model_opts
+  const int32_t* epoch = nullptr;          // resampling epoch of the *_resample entry points (a device int, read at every launch)
 };
 static int check_blocks(const dd_sampler* s, int num_blocks) {
   if (!s || num_blocks < 1) return DD_ERR_BAD_ARG;
@@ -1170,8 +1171,9 @@ static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled,
 // head outputs come from (hid / W2 / b2 or logits_in), logits_out, x0 and, with a folded step boundary, counter_bias and x0_*.
 // sample_keys: the per-sample noise keys of a keyed chain (the kernels read them at every launch), NULL otherwise.
 // fixed: the fixed atoms of the chain (device pointers, read at every launch), NULL otherwise.
+// epoch: the resampling epoch of a chain with fixed atoms (a device int, read at every launch), NULL otherwise.
 static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint64_t* sample_keys, const dd_fixed* fixed, StepRowsArgs* r,
-                           StepRowsArgs* rb, StepPosArgs* p) {
+                           StepRowsArgs* rb, StepPosArgs* p, const int32_t* epoch = nullptr) {
   const int B = s->B, NL = s->NL;
   const long Eb = (long)NL * (NL - 1);
   memset(r, 0, sizeof(*r));
@@ -1180,7 +1182,7 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint6
   r->state = s->lig_v; r->uniforms = s->u_v; r->stream_id = 1;
   r->traj_recon = s->traj_v0; r->traj_prob = s->traj_vt; r->traj_state = s->traj_v;
   r->sample_keys = sample_keys; r->NL = NL;
-  if (fixed) { r->fx_mask = fixed->mask; r->fx_mode = fixed->mode; }
+  if (fixed) { r->fx_mask = fixed->mask; r->fx_mode = fixed->mode; r->epoch = epoch; }
   *rb = *r;
   if (fixed) { r->fx_val = fixed->v0; rb->fx_val = fixed->b0; rb->fx_bond = 1; }
   rb->rows = (int)(B * Eb); rb->NC = DD_NUM_B; rb->rows_per_sample = (int)Eb; rb->tab = s->tab_b;
@@ -1193,18 +1195,18 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint6
   p->atom_std = s->atom_std; p->offset = s->offset; p->grad_a = d.ga; p->scale_a = s->armsca_scale; p->grad_c = d.gc;
   p->scale_c = s->clash_scale; p->grad_r = d.gr; p->scale_r = s->repul_scale; p->eps = s->eps; p->traj_pos = s->traj_pos;
   p->sample_keys = sample_keys;
-  if (fixed) { p->fx_mask = fixed->mask; p->fx_x0c = fixed->x0c; p->fx_cc = fixed->cc; p->fx_tab = fixed->tab; p->fx_mode = fixed->mode; }
+  if (fixed) { p->fx_mask = fixed->mask; p->fx_x0c = fixed->x0c; p->fx_cc = fixed->cc; p->fx_tab = fixed->tab; p->fx_mode = fixed->mode; p->epoch = epoch; }
 }
 
 static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr, const uint64_t* sample_keys = nullptr,
-                          const dd_fixed* fixed = nullptr) {
+                          const dd_fixed* fixed = nullptr, const int32_t* epoch = nullptr) {
   const Fwd f(s);
   const Workspace& w = f.w;
   DriftGrads d;
   DD_TRY(launch_drifts(s, w, true, st, &d));
   StepRowsArgs r, rb;
   StepPosArgs p;
-  fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p);
+  fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p, epoch);
   const bool advanced = fold && fold->advance;
   r.counter_bias = rb.counter_bias = p.counter_bias = advanced ? 1 : 0;
   r.hid = w.qn; r.W2 = f.GW(DD_G_VH_W2); r.b2 = f.GW(DD_G_VH_b2); r.logits_out = s->pred_v;
@@ -1249,6 +1251,15 @@ static int fixed_init(const dd_sampler* s, const uint64_t* sample_keys, const dd
   StepPosArgs p;
   fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p);
   return launch_fixed_init(rb, r, p, st);
+}
+
+// dd_resample_jump: the forward jump of the chain's state and the rebase of its run state (dd_step.hip::k_jump)
+static int resample_jump(const dd_sampler* s, const uint64_t* sample_keys, const dd_fixed* fixed, const dd_resample* rsm, hipStream_t st) {
+  DriftGrads d;
+  StepRowsArgs r, rb;
+  StepPosArgs p;
+  fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p, rsm->epoch);
+  return launch_jump(rb, r, p, rsm->tab, rsm->jump_length, rsm->epoch, st);
 }
 
 // forward-only head evaluation: logits without sampling (state untouched)
@@ -1610,7 +1621,7 @@ static int one_step(const dd_sampler* s, hipStream_t st, const dd::ModelOpts& mo
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
   int rc = dd::forward_impl(s, st, &fold, mo);
   if (rc != DD_OK) return rc;
-  return dd::heads_and_step(s, st, &fold, mo.sample_keys, mo.fixed);
+  return dd::heads_and_step(s, st, &fold, mo.sample_keys, mo.fixed, mo.epoch);
 }
 
 extern "C" int dd_reverse_step(const dd_sampler* s, const float* logits_v, const float* logits_b, const float* x0, void* stream) {
@@ -1658,15 +1669,45 @@ extern "C" int dd_sample_steps_keyed(const dd_sampler* s, const dd_model_opts* o
   return dd_sample_steps_fixed(s, opts, sample_keys, nullptr, n_steps, stream);
 }
 
+// The caller's dd_resample as a checked copy: every field is needed, the chain has fixed atoms with centres (a jump noises around
+// them in both modes), draws on the device, and its times fit the 16 bits of the time word below the epoch
+static int read_resample(const dd_resample* rsm, const dd_sampler* s, const dd_fixed* fixed, dd_resample* out) {
+  memset(out, 0, sizeof(*out));
+  if (rsm == nullptr || fixed == nullptr || s == nullptr) return DD_ERR_BAD_ARG;
+  if (rsm->size < (int32_t)sizeof(int32_t) || rsm->size > 4096) return DD_ERR_BAD_ARG;
+  memcpy(out, rsm, (size_t)rsm->size < sizeof(*out) ? (size_t)rsm->size : sizeof(*out));
+  out->size = (int32_t)sizeof(*out);
+  if (out->jump_length < 1 || !out->tab || !out->epoch) return DD_ERR_BAD_ARG;
+  if (s->T < 1 || s->T > 65535 || s->u_v || s->u_b || s->eps) return DD_ERR_BAD_ARG;
+  return DD_OK;
+}
+
+static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                             const dd_resample* rsm, int n_steps, void* stream);
+
 extern "C" int dd_sample_steps_fixed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                                      int n_steps, void* stream) {
+  return sample_steps_impl(s, opts, sample_keys, fixed, nullptr, n_steps, stream);
+}
+
+extern "C" int dd_sample_steps_resample(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                                        const dd_resample* resample, int n_steps, void* stream) {
+  if (!resample) return DD_ERR_BAD_ARG;
+  return sample_steps_impl(s, opts, sample_keys, fixed, resample, n_steps, stream);
+}
+
+static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                             const dd_resample* rsm, int n_steps, void* stream) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || n_steps < 0 || keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
   dd_fixed fx;
   if (fixed != nullptr && read_fixed(fixed, &fx) != DD_OK) return DD_ERR_BAD_ARG;
+  dd_resample rs;
+  if (rsm != nullptr && read_resample(rsm, s, fixed, &rs) != DD_OK) return DD_ERR_BAD_ARG;
   mo.sample_keys = sample_keys;
   mo.fixed = fixed != nullptr ? &fx : nullptr;
+  mo.epoch = rsm != nullptr ? rs.epoch : nullptr;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_steps; ++i) {
     int rc = one_step(s, st, mo);
@@ -1775,16 +1816,52 @@ extern "C" int dd_fixed_init(const dd_sampler* s, const uint64_t* sample_keys, c
   return dd::fixed_init(s, sample_keys, &fx, (hipStream_t)stream);
 }
 
+static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                             const dd_resample* rsm, int steps_per_graph, void* stream, void** graph_out);
+
 extern "C" int dd_graph_create_fixed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                                      int steps_per_graph, void* stream, void** graph_out) {
+  return graph_create_impl(s, opts, sample_keys, fixed, nullptr, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_graph_create_resample(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                                        const dd_resample* resample, int steps_per_graph, void* stream, void** graph_out) {
+  if (!resample) return DD_ERR_BAD_ARG;
+  return graph_create_impl(s, opts, sample_keys, fixed, resample, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_resample_jump(const dd_sampler* s, const uint64_t* sample_keys, const dd_fixed* fixed, const dd_resample* resample,
+                                void* stream) {
+  if (!check_step_sampler(s) || !fixed || !resample || !s->lig_pos || !s->lig_v || !s->lig_bond) return DD_ERR_BAD_ARG;
+  dd_fixed fx;
+  dd_resample rs;
+  if (read_fixed(fixed, &fx) != DD_OK || !fx.cc || read_resample(resample, s, fixed, &rs) != DD_OK) return DD_ERR_BAD_ARG;
+  if (keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
+  int rc = dd::check_shapes(s);
+  if (rc != DD_OK) return rc;
+  return dd::resample_jump(s, sample_keys, &fx, &rs, (hipStream_t)stream);
+}
+
+extern "C" int dd_sampler_reset_resample(const dd_sampler* s, const dd_resample* resample, void* stream) {
+  if (!s || !resample || resample->size < (int32_t)sizeof(dd_resample) || !resample->epoch) return DD_ERR_BAD_ARG;
+  int rc = dd_sampler_reset(s, stream);
+  if (rc != DD_OK) return rc;
+  return dd::launch_reset_epoch(resample->epoch, (hipStream_t)stream);
+}
+
+static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                             const dd_resample* rsm, int steps_per_graph, void* stream, void** graph_out) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || !graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
   if (keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
   dd_fixed fx;
   if (fixed != nullptr && read_fixed(fixed, &fx) != DD_OK) return DD_ERR_BAD_ARG;
+  dd_resample rs;
+  if (rsm != nullptr && read_resample(rsm, s, fixed, &rs) != DD_OK) return DD_ERR_BAD_ARG;
   mo.sample_keys = sample_keys;
   mo.fixed = fixed != nullptr ? &fx : nullptr;
+  mo.epoch = rsm != nullptr ? rs.epoch : nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   int rc = dd::check_shapes(s);

@@ -229,6 +229,9 @@ struct StepRowsArgs {
   const int32_t* fx_val;         // [rows] known clean classes (read at held rows only)
   int fx_mode;                   // DD_FIXED_HOLD / DD_FIXED_REPLACE
   int fx_bond;                   // 1: the rows are bond rows dst * (NL - 1) + sp of their sample
+  // resampling (dd_resample; FIXED instantiations only): the chain's epoch, a device int read at every launch -- the Philox
+  // time word of a step is t + 65536 * epoch.  NULL: epoch 0, today's draws.
+  const int32_t* epoch;
 };
 struct StepPosArgs {
   int B, NL, T;
@@ -255,6 +258,7 @@ struct StepPosArgs {
   const float* fx_cc;            // [B*NL,3] centred prior centres of the atoms' arms (replace mode)
   const float* fx_tab;           // [2][T] sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod) (replace mode)
   int fx_mode;
+  const int32_t* epoch;          // resampling: the chain's epoch (see StepRowsArgs), or NULL
 };
 int launch_step_rows(const StepRowsArgs& a, hipStream_t st);
 int launch_step_pos(const StepPosArgs& a, hipStream_t st);
@@ -264,5 +268,11 @@ int launch_step_all(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPo
 // fixed atoms: hold mode writes the known values into the state, replace mode draws the held rows' level t_start (the run state's)
 // at Philox time t_start + 1; atoms, bonds and coordinates in one launch
 int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, hipStream_t st);
+// resampling: the forward jump q(x_m | x_l), m = l + j, of every row that a jump moves (bond rows, atom rows, coordinates: one
+// launch) with the coefficients jtab [6][T] at m, then a one-thread launch that rebases the run state (t_start += j) and bumps
+// the epoch.  rb / rv / p as for a step of the chain (fixed atoms and the epoch pointer set).
+int launch_jump(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, const float* jtab, int j, int32_t* epoch,
+                hipStream_t st);
+int launch_reset_epoch(int32_t* epoch, hipStream_t st);
 
 }  // namespace dd

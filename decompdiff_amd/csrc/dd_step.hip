@@ -21,6 +21,9 @@ namespace dd {
 // (tests/test_gpu_properties.py) instead of replaying the draws of its first steps.  dd_debug_philox exposes exactly these functions to the statistics test.
 // `seed` and `row` are the run state's seed and the flat row of the batch, or -- keyed chains -- the sample's key and the row of its
 // own enumeration (noise_addr below): the same generator either way.
+// Resampling (dd_resample): a chain that jumps back visits a time again, so the time word of a FIXED step is t + 65536 * epoch
+// (epoch = jumps done so far in the call; epoch 0: the bits above), and the jump that raises the epoch to e draws at
+// (l + j) + 65536 * e on streams of its own: 3 atom types, 4 bond types, 8 coordinates (same class blocks, same row addressing).
 template <int NC>
 __device__ __forceinline__ float philox_uniform(uint64_t seed, long row, int step, uint32_t sid, int c) {
   Philox ph(seed);
@@ -34,10 +37,10 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, long row, int ste
   }
   return u01(bits);
 }
-__device__ __forceinline__ float philox_normal(uint64_t seed, int idx, int step) {
+__device__ __forceinline__ float philox_normal(uint64_t seed, int idx, int step, uint32_t sid = 7u) {
   Philox ph(seed);
   uint32_t r[4];
-  ph.gen((uint32_t)idx, 0u, (uint32_t)step, 7u, r);
+  ph.gen((uint32_t)idx, 0u, (uint32_t)step, sid, r);
   const float u1 = fmaxf(u01(r[0]), 5.9604645e-8f), u2 = u01(r[1]);
   return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
@@ -71,9 +74,14 @@ __device__ __forceinline__ NoiseAddr noise_addr(const StepRowsArgs& a, const lon
   return {a.sample_keys[b], (long)r};
 }
 // ... and a coordinate's: (seed, flat index), or (key of its sample, 3 * i + c inside the sample)
-__device__ __forceinline__ float step_pos_normal(const StepPosArgs& a, const int idx, const int b, const uint64_t seed, const int t) {
-  if (a.sample_keys == nullptr) return philox_normal(seed, idx, t);
-  return philox_normal(a.sample_keys[b], idx - b * a.NL * 3, t);
+__device__ __forceinline__ float step_pos_normal(const StepPosArgs& a, const int idx, const int b, const uint64_t seed, const int t,
+                                                 const uint32_t sid = 7u) {
+  if (a.sample_keys == nullptr) return philox_normal(seed, idx, t, sid);
+  return philox_normal(a.sample_keys[b], idx - b * a.NL * 3, t, sid);
+}
+// the Philox time word of a step at time t (or of a jump to level t) in the chain's current epoch
+__device__ __forceinline__ int epoch_word(const int32_t* __restrict__ epoch, const int t) {
+  return epoch == nullptr ? t : (int)((uint32_t)t + ((uint32_t)*epoch << 16));
 }
 
 __device__ __forceinline__ float log_add_exp(float a, float b) {
@@ -168,8 +176,10 @@ __global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
     for (int c = 0; c < NC; ++c) u[c] = a.uniforms[((long)step * a.rows + row) * NC + c];
   } else {
     const NoiseAddr na = noise_addr(a, row, rs.seed);
+    int tw = t;
+    if constexpr (FIXED) tw = epoch_word(a.epoch, t);
 #pragma unroll
-    for (int c = 0; c < NC; ++c) u[c] = philox_uniform<NC>(na.key, na.row, t, a.stream_id, c);
+    for (int c = 0; c < NC; ++c) u[c] = philox_uniform<NC>(na.key, na.row, tw, a.stream_id, c);
   }
   int best = 0;
   float bestv = -INFINITY;
@@ -524,7 +534,9 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
     u = a.uniforms[((long)step * a.rows + row) * NC + c];
   } else {
     const NoiseAddr na = noise_addr(a, row, rs.seed);
-    u = philox_uniform<NC>(na.key, na.row, t, a.stream_id, c);
+    int tw = t;
+    if constexpr (FIXED) tw = epoch_word(a.epoch, t);
+    u = philox_uniform<NC>(na.key, na.row, tw, a.stream_id, c);
   }
   const float lp = un - ulse;
   float sc = -logf(-logf(u + 1e-30f) + 1e-30f) + lp;            // Gumbel-argmax (transitions.py:78-84)
@@ -582,7 +594,9 @@ __device__ __forceinline__ void step_pos_elem(const StepPosArgs& a, const int id
   if (a.eps) {
     e = a.eps[(long)step * n + idx];
   } else {
-    e = step_pos_normal(a, idx, b, rs.seed, t);
+    int tw = t;
+    if constexpr (FIXED) tw = epoch_word(a.epoch, t);
+    e = step_pos_normal(a, idx, b, rs.seed, tw);
   }
   const float nz = t == 0 ? 0.f : 1.f;
   float nxt = mean + nz * expf(0.5f * a.tab_pos[2 * a.T + t]) * e * a.atom_std[idx];
@@ -682,6 +696,78 @@ int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const Step
   return DD_OK;
 }
 
+// Resampling (include/decompdiff_hip.h, dd_resample): the forward jump q(x_m | x_l) from the chain's current level
+// l = t_start - steps done (the run state's; -1 is the clean level) to m = l + j, for the coordinates, atom rows and bond rows of
+// the batch in one launch.  jtab [6][T] at m: A, S (coordinates), lr / l1mr of the atom and of the bond schedule.  A row is one
+// wave with one class per lane, as in step_row (bond rows dominate: B NL (NL - 1) rows of 5 classes); the cross-class argmax runs
+// in class order through v_readlane with the strict > of the serial loops.  Hold mode leaves the held rows alone; replace mode
+// moves every row (a held row at level m is then a valid forward sample of its clean value).  Draws: time word m + 65536 * e with
+// e = the epoch AFTER this jump, streams 3 / 4 / 8, rows and keys addressed as the step addresses them.
+template <int NC>
+__device__ __forceinline__ void jump_row(const StepRowsArgs& a, const long row, const int lane, const uint64_t seed, const int word,
+                                         const uint32_t sid, const float lr, const float l1mr) {
+  if (a.fx_mode == DD_FIXED_HOLD && row_held(a, row)) return;      // (wave-uniform)
+  const int c = lane < NC ? lane : NC - 1;                         // lanes >= NC shadow the last class (results unused)
+  const int cur = a.state[row];
+  const NoiseAddr na = noise_addr(a, row, seed);
+  const float u = philox_uniform<NC>(na.key, na.row, word, sid, c);
+  const float sc = gumbel_of(u) + log_add_exp((c == cur ? 0.f : -69.07755278982137f) + lr, l1mr + a.tab[4 * a.T + c]);
+  int best = 0;
+  float bestv = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const float sk = lane_bcast(sc, k);
+    if (sk > bestv) { bestv = sk; best = k; }
+  }
+  if (lane == 0) a.state[row] = best;
+}
+template <int NV>
+__global__ __launch_bounds__(256) void k_jump(const StepRowsArgs rb, const StepRowsArgs rv, const StepPosArgs p,
+                                              const float* __restrict__ jtab, const int j, int nb_b, int nb_v) {
+  const int blk = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const RunState rs = load_run_state(rb.step_counter, 0);
+  const int T = p.T;
+  const int m = rs.t_start - rs.step + j;                          // l + j
+  if (m < 0 || m >= T) return;                                     // (the host checks the schedule; never index past the table)
+  const int word = (int)((uint32_t)m + ((uint32_t)(*rb.epoch + 1) << 16));
+  if (blk < nb_b) {
+    const long row = (long)blk * 4 + wave;
+    if (row < rb.rows) jump_row<DD_NUM_B>(rb, row, lane, rs.seed, word, 4u, jtab[4 * T + m], jtab[5 * T + m]);
+  } else if (blk < nb_b + nb_v) {
+    const long row = (long)(blk - nb_b) * 4 + wave;
+    if (row < rv.rows) jump_row<NV>(rv, row, lane, rs.seed, word, 3u, jtab[2 * T + m], jtab[3 * T + m]);
+  } else {
+    const int idx = (blk - nb_b - nb_v) * 256 + threadIdx.x;
+    if (idx >= p.B * p.NL * 3) return;
+    const int atom = idx / 3;
+    if (p.fx_mode == DD_FIXED_HOLD && p.fx_mask[atom] != 0) return;
+    const float e = step_pos_normal(p, idx, atom / p.NL, rs.seed, word, 8u);
+    p.xt[idx] = fixed_noised_pos(jtab[m], jtab[T + m], p.xt[idx], p.fx_cc[idx], e, p.atom_std[idx]);
+  }
+}
+__global__ void k_jump_tail(int32_t* rs, int32_t* epoch, int j) { rs[1] += j; *epoch += 1; }
+__global__ void k_reset_epoch(int32_t* epoch) { *epoch = 0; }
+
+int launch_jump(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, const float* jtab, int j, int32_t* epoch,
+                hipStream_t st) {
+  if (rb.NC != DD_NUM_B || (rv.NC != 8 && rv.NC != 13 && rv.NC != 23)) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (p.fx_mask == nullptr || p.fx_cc == nullptr || jtab == nullptr || epoch == nullptr || rb.epoch != epoch || j < 1) return DD_ERR_BAD_ARG;
+  const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
+  const dim3 grid(nb_b + nb_v + nb_p);
+  if (rv.NC == 8) hipLaunchKernelGGL(k_jump<8>, grid, dim3(256), 0, st, rb, rv, p, jtab, j, nb_b, nb_v);
+  else if (rv.NC == 13) hipLaunchKernelGGL(k_jump<13>, grid, dim3(256), 0, st, rb, rv, p, jtab, j, nb_b, nb_v);
+  else hipLaunchKernelGGL(k_jump<23>, grid, dim3(256), 0, st, rb, rv, p, jtab, j, nb_b, nb_v);
+  DD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_jump_tail, dim3(1), dim3(1), 0, st, const_cast<int32_t*>(rb.step_counter), epoch, j);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+int launch_reset_epoch(int32_t* epoch, hipStream_t st) {
+  hipLaunchKernelGGL(k_reset_epoch, dim3(1), dim3(1), 0, st, epoch);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
 int launch_step_rows(const StepRowsArgs& a, hipStream_t st) {
   if (a.rows <= 0) return DD_OK;
   dim3 grid((a.rows + 3) / 4);
@@ -720,13 +806,21 @@ int launch_advance(int32_t* ctr, hipStream_t st) {
 }  // namespace dd
 
 namespace dd {
+// kind: stream id in the low byte (1 / 3 atom types, 2 / 4 bond types, 7 / 8 coordinates), atom class count in bits 8-15 (0 = 8)
+template <int NC>
+__device__ __forceinline__ void debug_uniforms(uint64_t seed, int step, long rows, uint32_t sid, long i, float* __restrict__ out) {
+  if (i >= rows * NC) return;
+  out[i] = philox_uniform<NC>(seed, i / NC, step, sid, (int)(i % NC));
+}
 __global__ __launch_bounds__(256) void k_debug_philox(uint64_t seed, int step, long rows, int kind, float* __restrict__ out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (kind == 7) { if (i < rows) out[i] = philox_normal(seed, (int)i, step); return; }
-  const int NC = kind == 1 ? DD_NUM_V : DD_NUM_B;
-  if (i >= rows * NC) return;
-  const long row = i / NC; const int c = (int)(i % NC);
-  out[i] = kind == 1 ? philox_uniform<DD_NUM_V>(seed, row, step, 1u, c) : philox_uniform<DD_NUM_B>(seed, row, step, 2u, c);
+  const uint32_t sid = (uint32_t)kind & 0xffu;
+  const int nc = kind >> 8;
+  if (sid == 7u || sid == 8u) { if (i < rows) out[i] = philox_normal(seed, (int)i, step, sid); return; }
+  if (sid == 2u || sid == 4u) debug_uniforms<DD_NUM_B>(seed, step, rows, sid, i, out);
+  else if (nc == 13) debug_uniforms<13>(seed, step, rows, sid, i, out);
+  else if (nc == 23) debug_uniforms<23>(seed, step, rows, sid, i, out);
+  else debug_uniforms<DD_NUM_V>(seed, step, rows, sid, i, out);
 }
 int launch_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                         float* grad, int accumulate, int norm_B, hipStream_t st) {
@@ -778,11 +872,15 @@ extern "C" int dd_drift_clash(const float* lig_pos, const float* offset, const f
                                 (hipStream_t)stream);
 }
 
-// Test aid: the production noise of one step, exactly as the step kernels draw it.  kind 1: uniforms [rows,8] of the
-// atom-type stream, 2: uniforms [rows,5] of the bond-type stream, 7: normals [rows] of the coordinate stream.
+// Test aid: the production noise of one step, exactly as the step kernels draw it.  kind (low byte) 1: uniforms [rows,8] of the
+// atom-type stream, 2: uniforms [rows,5] of the bond-type stream, 7: normals [rows] of the coordinate stream; 3 / 4 / 8: the same
+// three of a resampling jump (`step` is the Philox time word, t + 65536 * epoch).  Bits 8-15 of kind: the atom class count of
+// kinds 1 / 3 (0 or 8, 13, 23 -> [rows, that many]).
 extern "C" int dd_debug_philox(uint64_t seed, int step, long rows, int kind, float* out, void* stream) {
-  if (!out || rows <= 0 || (kind != 1 && kind != 2 && kind != 7)) return DD_ERR_BAD_ARG;
-  const long n = kind == 7 ? rows : rows * (kind == 1 ? DD_NUM_V : DD_NUM_B);
+  const int sid = kind & 0xff, nc = kind >> 8;
+  if (!out || rows <= 0 || kind < 0 || (sid != 1 && sid != 2 && sid != 7 && sid != 3 && sid != 4 && sid != 8)) return DD_ERR_BAD_ARG;
+  if (nc != 0 && ((sid != 1 && sid != 3) || (nc != 8 && nc != 13 && nc != 23))) return DD_ERR_BAD_ARG;
+  const long n = (sid == 7 || sid == 8) ? rows : rows * ((sid == 1 || sid == 3) ? (nc ? nc : DD_NUM_V) : DD_NUM_B);
   hipLaunchKernelGGL(dd::k_debug_philox, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, step, rows, kind, out);
   DD_CHECK_LAUNCH();
   return DD_OK;

@@ -47,7 +47,7 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                                    arms_natoms_config=None, scaffold_natoms_config=None, natoms_sampler=None,
                                    atom_prior_probs=None, bond_prior_probs=None, pool_batches: int = 1,
                                    sample_key_seed: Optional[int] = None, first_sample_index: int = 0,
-                                   fixed_fn=None, fixed_mode: str = "hold") -> Dict[str, list]:
+                                   fixed_fn=None, fixed_mode: str = "hold", resample=None) -> Dict[str, list]:
     """Sample ``num_samples`` ligands for one pocket in batches of ``batch_size``.
 
     ``pool_batches`` > 1 assembles that many consecutive batches exactly as the reference would (same random draws, same
@@ -78,6 +78,10 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     collated into one flat ``fixed`` per model call (``sample_diffusion(fixed=...)`` with ``mode=fixed_mode``; only for models
     that take the extra keywords); a size that does not match the sample raises ValueError.  Works with ``pool_batches`` and
     ``sample_key_seed``; the batches' own draws and order do not change.
+
+    ``resample`` (not None; needs ``fixed_fn``): ``dict(jump_length=j, n_resample=r)``, handed to every model call that holds
+    atoms (``sample_diffusion(resample=...)``, RePaint's jump-back schedule); the trajectories then have one entry per position of
+    ``model.resample_schedule`` instead of one per step.  A model call in which ``fixed_fn`` held nothing runs the plain chain.
     """
     out = {k: [] for k in ("pred_pos", "pred_v", "pred_pos_traj", "pred_v_traj", "pred_v0_traj", "pred_vt_traj",
                            "pred_bond_index", "pred_bond_type", "pred_b_traj", "pred_bt_traj", "decomp_mask")}
@@ -107,6 +111,8 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
 
     if sample_key_seed is not None and noise_fn is not None:
         raise ValueError("sample_key_seed excludes noise_fn: a chain draws from one source")
+    if resample is not None and (fixed_fn is None or noise_fn is not None):
+        raise ValueError("resample needs fixed_fn and excludes noise_fn")
     n_done = 0                                                             # samples of the earlier model calls
     for i in range(0, num_batch, pool_batches):
         parts = [build(j) for j in range(i, min(num_batch, i + pool_batches))]
@@ -127,6 +133,8 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
             fixed = collate_fixed(fixed_fn, int(first_sample_index) + n_done, n_atoms, batch["ligand_decomp_index"], fixed_mode)
             if fixed is not None:
                 extra["fixed"] = fixed
+                if resample is not None:
+                    extra["resample"] = resample
         n_done += n_data
         t1 = time.time()
         r = model.sample_diffusion(num_steps=num_steps, center_pos_mode=center_pos_mode,

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "dd_forward_opts", "dd_sample_steps_opts", "dd_sample_steps_graph_opts", "dd_graph_create_opts", "dd_sample_steps_graph_multi_opts",
     "dd_sample_steps_keyed", "dd_graph_create_keyed",
     "dd_sample_steps_fixed", "dd_graph_create_fixed", "dd_fixed_init",
+    "dd_sample_steps_resample", "dd_graph_create_resample", "dd_resample_jump", "dd_sampler_reset_resample",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -123,6 +124,20 @@ def fixed_struct(mode, mask, v0, b0, x0c, cc=None, tab=None) -> DDFixed:
     for name, t in (("mask", mask), ("v0", v0), ("b0", b0), ("x0c", x0c), ("cc", cc), ("tab", tab)):
         setattr(f, name, None if t is None else t.data_ptr())
     return f
+
+
+class DDResample(ctypes.Structure):
+    """struct dd_resample (include/decompdiff_hip.h): the resampling state of a chain with fixed atoms, handed to the *_resample
+    entry points; `size` = sizeof of this struct, tab / epoch DEVICE pointers read at every launch (see `resample_struct`)."""
+    _fields_ = [("size", c_int32), ("jump_length", c_int32), ("tab", c_void_p), ("epoch", c_void_p)]
+
+
+def resample_struct(jump_length, tab, epoch) -> DDResample:
+    """A filled dd_resample from device tensors (the caller keeps them alive): tab fp32 [6][T], epoch int32 [1]."""
+    r = DDResample()
+    r.size, r.jump_length = ctypes.sizeof(DDResample), int(jump_length)
+    r.tab, r.epoch = tab.data_ptr(), epoch.data_ptr()
+    return r
 
 
 L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128      # DD_L0_TABLE_FLOATS
@@ -229,6 +244,12 @@ def load():
         "dd_sample_steps_fixed": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), c_int, c_void_p],
         "dd_graph_create_fixed": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), c_int, c_void_p, POINTER(c_void_p)],
         "dd_fixed_init": [S, c_void_p, POINTER(DDFixed), c_void_p],
+        # (the _fixed siblings with the host struct dd_resample after fixed; the jump; the reset that also zeroes the epoch)
+        "dd_sample_steps_resample": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), POINTER(DDResample), c_int, c_void_p],
+        "dd_graph_create_resample": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), POINTER(DDResample), c_int, c_void_p,
+                                     POINTER(c_void_p)],
+        "dd_resample_jump": [S, c_void_p, POINTER(DDFixed), POINTER(DDResample), c_void_p],
+        "dd_sampler_reset_resample": [S, POINTER(DDResample), c_void_p],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],

@@ -139,9 +139,10 @@ FIXED_MODES = ("hold", "replace")
 
 
 def _as_fixed(fixed, n_ligand, fc_index, bond_type, num_classes, num_bond_classes, noise, start_step, prior_centers,
-              ligand_decomp_batch, ligand_atom_mask, dev):
+              ligand_decomp_batch, ligand_atom_mask, dev, need_cc=False):
     """``fixed`` of sample_diffusion, validated (ValueError) and moved to the device: dict(mode, init, mask bool [n], pos f32 [n,3],
-    v int32 [n], bond int32 [n_bond], cc f32 [n,3] or None -- the prior centre of every atom's arm, replace mode)."""
+    v int32 [n], bond int32 [n_bond], cc f32 [n,3] or None -- the prior centre of every atom's arm, replace mode and, with
+    ``need_cc`` (resampling: a jump noises around the centres), hold mode)."""
     if not isinstance(fixed, dict):
         raise ValueError("fixed must be None or a dict(mask, pos, v, bond, mode[, init])")
     unknown = set(fixed) - {"mask", "pos", "v", "bond", "mode", "init"}
@@ -184,14 +185,15 @@ def _as_fixed(fixed, n_ligand, fc_index, bond_type, num_classes, num_bond_classe
         if need_given and init != "given":
             raise ValueError("fixed['init'] = 'draw' needs the device generator and start_step == 0; with noise= or start_step > 0 "
                              "pass init='given' and the held rows' state in init_ligand_*")
+    elif "init" in fixed and fixed["init"] not in (None, "draw", "given"):
+        raise ValueError(f"fixed['init'] must be 'draw' or 'given', got {fixed['init']!r}")
+    if mode == "replace" or need_cc:
         if prior_centers is None or ligand_decomp_batch is None or not torch.is_tensor(prior_centers) or prior_centers.dim() != 2 \
                 or prior_centers.shape[1] != 3 or ligand_decomp_batch.numel() != n_ligand \
                 or (ligand_decomp_batch.numel() and int(ligand_decomp_batch.max()) >= prior_centers.shape[0]):
-            raise ValueError("fixed mode 'replace' needs prior_centers [n_prior,3] and ligand_decomp_batch [n_ligand]: the forward "
-                             "process noises around the arm centres")
+            raise ValueError("fixed mode 'replace' (and resample in either mode) needs prior_centers [n_prior,3] and "
+                             "ligand_decomp_batch [n_ligand]: the forward process noises around the arm centres")
         cc = prior_centers.detach().to(device=dev, dtype=torch.float32)[ligand_decomp_batch.to(dev)].contiguous()
-    elif "init" in fixed and fixed["init"] not in (None, "draw", "given"):
-        raise ValueError(f"fixed['init'] must be 'draw' or 'given', got {fixed['init']!r}")
     # classes at free rows are never read: zero them so that the int32 copies stay in range whatever the caller left there
     v_c = torch.where(mask_c, v_c, torch.zeros_like(v_c))
     bond_c = torch.where(held_b, bond_c, torch.zeros_like(bond_c))
@@ -203,6 +205,59 @@ def _fixed_rows(fx, rows_l, rows_b):
     """The rows ``rows_l`` (atoms) / ``rows_b`` (bonds) of a validated ``fixed`` (device index tensors): a group's or a sample's share."""
     return dict(mode=fx["mode"], init=fx["init"], mask=fx["mask"][rows_l], pos=fx["pos"][rows_l], v=fx["v"][rows_l],
                 bond=fx["bond"][rows_b], cc=None if fx["cc"] is None else fx["cc"][rows_l])
+
+
+def resample_schedule(t_hi, t_lo, j, r):
+    """The resampling ("jump-back") schedule of ``sample_diffusion(resample=dict(jump_length=j, n_resample=r))`` over the reverse
+    steps t_hi .. t_lo: a list of ``("step", t)`` and ``("jump", l, l + j)`` in execution order.  Jump points are anchored at the
+    range's last level: every level l in {t_lo - 1, t_lo - 1 + j, ...} with l + j <= t_hi is left r - 1 times by a jump back
+    to l + j.  ``num_steps // j`` jump points, ``num_steps + (r - 1) * j * (num_steps // j)`` steps; r = 1 or j > num_steps: the
+    plain chain."""
+    budget = {l: r - 1 for l in range(t_lo - 1, t_hi - j + 1, j)}
+    ops, t = [], t_hi
+    while t >= t_lo:
+        ops.append(("step", t))
+        l = t - 1
+        if budget.get(l, 0) > 0:
+            budget[l] -= 1
+            ops.append(("jump", l, l + j))
+            t = l + j
+        else:
+            t = l
+    return ops
+
+
+def _as_resample(resample, fixed, noise, num_timesteps, num_steps, start_step):
+    """``resample`` of sample_diffusion, validated (ValueError): dict(j, r, runs, t_traj, n_total) -- ``runs``: [(reverse steps,
+    followed by a jump)] in execution order; ``t_traj``: the int64 times of the n_total positions."""
+    if not isinstance(resample, dict) or set(resample) != {"jump_length", "n_resample"}:
+        raise ValueError("resample must be None or a dict(jump_length=j, n_resample=r)")
+    j, r = resample["jump_length"], resample["n_resample"]
+    if isinstance(j, bool) or isinstance(r, bool) or not isinstance(j, int) or not isinstance(r, int):
+        raise ValueError("resample['jump_length'] and resample['n_resample'] must be ints")
+    if j < 1 or r < 1:
+        raise ValueError("resample needs jump_length >= 1 and n_resample >= 1")
+    if fixed is None:
+        raise ValueError("resample is valid only together with fixed: it re-harmonises the free atoms with the held ones")
+    if noise is not None:
+        raise ValueError("resample excludes noise=: a revisited time draws afresh from the device generator")
+    if num_timesteps > 65535:
+        raise ValueError("resample needs num_timesteps <= 65535 (the epoch shares the Philox time word with t)")
+    t_hi = num_timesteps - 1 - int(start_step)
+    t_lo = t_hi - int(num_steps) + 1
+    if (r - 1) * (int(num_steps) // j) > 65535:
+        raise ValueError("resample: more than 65535 jumps in one call")
+    runs, times, n = [], [], 0
+    for op in resample_schedule(t_hi, t_lo, j, r) if num_steps > 0 else []:
+        if op[0] == "step":
+            times.append(op[1])
+            n += 1
+        else:
+            runs.append((n, True))
+            n = 0
+    if n:
+        runs.append((n, False))
+    return dict(j=j, r=r, runs=runs, t_traj=torch.tensor(times, dtype=torch.int64), n_total=len(times))
 
 
 class DecompScorePosNet3D(nn.Module):
@@ -360,6 +415,29 @@ class DecompScorePosNet3D(nn.Module):
         ac = self.alphas_cumprod.detach().double()
         return torch.stack([ac.sqrt(), (1.0 - ac).sqrt()]).float().contiguous()
 
+    def resample_jump_table(self, jump_length):
+        """The [6][T] fp32 table ``dd_resample.tab`` of the forward jump from level m - j to level m (j = ``jump_length``), indexed
+        by m: A = sqrt(a), S = sqrt(1 - a) with a = alphas_cumprod[m] / alphas_cumprod[m - j] (coordinates), then
+        lr = log_cumprod[m] - log_cumprod[m - j] and l1mr = log(1 - exp(lr)) of the atom-type and of the bond-type schedule; level -1
+        is the clean sample (alphas_cumprod 1, log_cumprod 0).  Composed in float64 from this module's schedule tables and rounded
+        once, like ``fixed_step_table`` (whose rows A, S are this table's at m = j - 1).  Entries m < j - 1 are zeros, never read."""
+        j = int(jump_length)
+        if j < 1:
+            raise ValueError("jump_length must be >= 1")
+        T = int(self.betas.numel())
+        ac = torch.cat([torch.ones(1, dtype=torch.float64), self.alphas_cumprod.detach().double().cpu()])        # [level + 1]
+        lv = torch.cat([torch.zeros(1, dtype=torch.float64), self.atom_type_trans.log_alphas_cumprod_v.detach().double().cpu()])
+        lb = torch.cat([torch.zeros(1, dtype=torch.float64), self.bond_type_trans.log_alphas_cumprod_v.detach().double().cpu()])
+        tab = torch.zeros(6, T, dtype=torch.float64)
+        if j <= T:
+            m = torch.arange(j - 1, T)
+            a = ac[m + 1] / ac[m + 1 - j]
+            tab[0, m], tab[1, m] = a.sqrt(), (1.0 - a).sqrt()
+            for row, lc in ((2, lv), (4, lb)):
+                lr = lc[m + 1] - lc[m + 1 - j]
+                tab[row, m], tab[row + 1, m] = lr, torch.log(1.0 - torch.exp(lr))
+        return tab.float().contiguous()
+
     def _predict_x0_from_eps(self, xt, eps, t, batch):
         """x0 from a predicted noise (decompdiff.py:353-356); t [num_graphs], batch [n] on the device of the tables."""
         return self.sqrt_recip_alphas_cumprod[t][batch].unsqueeze(-1) * xt - \
@@ -511,7 +589,7 @@ class DecompScorePosNet3D(nn.Module):
                                          kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"].numel(), need_protein=False)
 
     def _sample_heterogeneous(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                              use_graph, start_step=0, sample_keys=None, fixed=None):
+                              use_graph, start_step=0, sample_keys=None, fixed=None, resample=None):
         """Samples with different atom counts in one batch (PyG collate, utils/data.py:389-446).  Default: ONE launch
         sequence over the batch padded to its largest pocket / ligand with per-sample real counts (`_sample_padded`).
         Fallbacks to equal-size groups (`_sample_ragged`): DD_RAGGED_MODE=groups, or `batch_layout.fits_padded` says no."""
@@ -521,9 +599,10 @@ class DecompScorePosNet3D(nn.Module):
             if BL.fits_padded(layout, self.config.knn):
                 return self._sample_padded(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed,
                                            keep_traj, use_graph, start_step, layout.n_p, layout.n_l, sample_keys=sample_keys,
-                                           fixed=fixed)
+                                           fixed=fixed, resample=resample)
         return self._sample_ragged(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                                   use_graph, start_step=start_step, layout=layout, sample_keys=sample_keys, fixed=fixed)
+                                   use_graph, start_step=start_step, layout=layout, sample_keys=sample_keys, fixed=fixed,
+                                   resample=resample)
 
     def _padded_inputs(self, protein_pos, protein_v, bp, ligand_pos, ligand_v, aux, bl, fc_index, bond_type, batch_ligand_bond,
                        n_p, n_l, center_pos_mode):
@@ -569,7 +648,7 @@ class DecompScorePosNet3D(nn.Module):
         return dict(d=d, offset=offset, masks=masks, n_b=n_b, rows_l=rows_l, rows_b=rows_b, d_l=d_l, d_b=d_b)
 
     def _sample_padded(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, start_step, n_p, n_l, sample_keys=None, fixed=None):
+                       use_graph, start_step, n_p, n_l, sample_keys=None, fixed=None, resample=None):
         """Heterogeneous batch as one padded dense batch: every sample's atoms are the first rows of its [NPmax] / [NLmax]
         blocks, the kernels read the real counts from dd_sampler.np_real / nl_real (padding atoms are no kNN candidates,
         own no softmax segment and are no members of one) and the results are gathered back into the caller's flat order.
@@ -623,17 +702,18 @@ class DecompScorePosNet3D(nn.Module):
                       b0=zeros(B * Eb, dtype=torch.int32).index_copy_(0, d_b, fixed["bond"]),
                       x0c=zeros(B * NL, 3).index_copy_(0, d_l, fixed["pos"] - off_l),
                       cc=None if fixed["cc"] is None else zeros(B * NL, 3).index_copy_(0, d_l, fixed["cc"] - off_l))
-        s, bufs, ent = self._make_sampler(d, pw, num_steps, self.num_timesteps - 1 - int(start_step), pad_noise, keep_traj,
+        n_pos = num_steps if resample is None else resample["n_total"]
+        s, bufs, ent = self._make_sampler(d, pw, n_pos, self.num_timesteps - 1 - int(start_step), pad_noise, keep_traj,
                                           energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, 0, masks=masks,
-                                          sample_keys=sample_keys, fixed=fx)   # (the padded batch keeps the caller's sample order)
-        chain = dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent)
-        self._run_chains([chain], num_steps, use_graph)
-        out = self._collect_chain(chain, num_steps, keep_traj, rows_atoms=rows_l, rows_bonds=rows_b)
+                                          sample_keys=sample_keys, fixed=fx, resample=resample)   # (the padded batch keeps the caller's sample order)
+        chain = dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent, t_traj=None if resample is None else resample["t_traj"])
+        self._run_chains([chain], n_pos, use_graph)
+        out = self._collect_chain(chain, n_pos, keep_traj, rows_atoms=rows_l, rows_bonds=rows_b)
         self._last = (s, bufs)
         return out
 
     def _sample_ragged(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None, fixed=None):
+                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None, fixed=None, resample=None):
         """One dense chain per group of samples of equal size (`BatchLayout.size_groups`).  ``split`` > 1 additionally cuts
         every group into that many sub-batches (measurement aid, tools/split_bench.py: two concurrent half-batches were
         measured slower than one chain).  ``layout``: what `_sampling_layout(kw)` gave the caller.
@@ -667,21 +747,22 @@ class DecompScorePosNet3D(nn.Module):
                 seed + 7919 * gi, keep_traj, B, start_step,        # (the armsca loss is averaged over the whole batch)
                 cache_slot=(g.ids[0] * split) // B,                # (sub-batches of one shape: own cached buffers each)
                 sample_keys=None if sample_keys is None else sample_keys[g.ids],
-                fixed=None if fixed is None else _fixed_rows(fixed, d_l, d_b))
+                fixed=None if fixed is None else _fixed_rows(fixed, d_l, d_b), resample=resample)
             prepared.append((chain, d_l, d_b, r_l, r_b))
         if concurrent is None:
             # measured on MI355X (tools/ragged_bench.py): with the runtime's default 4 hardware queues the
             # groups' graphs get in each other's way (0.7x); with GPU_MAX_HW_QUEUES=3 running them together gains 1.4x
             concurrent = os.environ.get("DD_RAGGED_CONCURRENT", "0") == "1"
+        n_pos = num_steps if resample is None else resample["n_total"]
         if concurrent:
-            self._run_chains([p[0] for p in prepared], num_steps, use_graph)
+            self._run_chains([p[0] for p in prepared], n_pos, use_graph)
         else:
             for p in prepared:
-                self._run_chains([p[0]], num_steps, use_graph)
+                self._run_chains([p[0]], n_pos, use_graph)
         for chain, d_l, d_b, r_l, r_b in prepared:
-            r = self._collect_chain(chain, num_steps, keep_traj)
+            r = self._collect_chain(chain, n_pos, keep_traj)
             out["pos"][d_l], out["v"][d_l], out["bond"][d_b] = r["pos"], r["v"], r["bond"]
-            if keep_traj and num_steps > 0:
+            if keep_traj and n_pos > 0:
                 for k, rows, n_tot in (("pos_traj", r_l, n_lig), ("v_traj", r_l, n_lig), ("v0_traj", r_l, n_lig),
                                        ("vt_traj", r_l, n_lig), ("bond_traj", r_b, n_bond), ("bt_traj", r_b, n_bond)):
                     st = torch.stack(r[k])                                         # [T, rows of this group, ...]
@@ -692,6 +773,8 @@ class DecompScorePosNet3D(nn.Module):
             out[k] = list(traj[k].unbind(0)) if traj[k] is not None else []
         if all(v is not None for v in traj.values()):
             out["_traj_stacked"] = dict(traj)
+        if resample is not None:
+            out["t_traj"] = resample["t_traj"].clone()
         return out
 
     # ------------------------------------------------------------------------------------------
@@ -821,8 +904,11 @@ class DecompScorePosNet3D(nn.Module):
         return memo[key]
 
     def _make_sampler(self, d, pw, n_steps, t_start, noise, keep_traj, drift, atom_std, offset, decomp_index,
-                      full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0, sample_keys=None, fixed=None):
-        """``sample_keys``: int64 [B] (host or device), the per-sample noise keys of this chain in the order of its samples, or None
+                      full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0, sample_keys=None, fixed=None,
+                      resample=None):
+        """``n_steps``: trajectory positions of the chain (reverse steps; with ``resample`` -- the validated dict of
+        `_as_resample` or None -- the schedule's n_total).
+        ``sample_keys``: int64 [B] (host or device), the per-sample noise keys of this chain in the order of its samples, or None
         (the chain draws with ``seed``).  ``fixed``: the chain's fixed atoms in its dense layout -- dict(mode, init, mask uint8
         [B*NL], v0 int32 [B*NL], b0 int32 [B*Eb], x0c [B*NL,3] centred, cc [B*NL,3] centred or None) -- or None."""
         lib = hip_lib.load()
@@ -926,9 +1012,10 @@ class DecompScorePosNet3D(nn.Module):
         ent["fixed"], ent["fixed_struct"] = None, None
         if fixed is not None:
             replace = fixed["mode"] == "replace"
+            with_cc = replace or resample is not None          # (a jump noises around the centres in hold mode too)
             for k, shape, dtype in (("mask", (B * NL,), torch.uint8), ("v0", (B * NL,), torch.int32), ("b0", (B * Eb,), torch.int32),
                                     ("x0c", (B * NL, 3), torch.float32), ("cc", (B * NL, 3), torch.float32)):
-                if k == "cc" and not replace:
+                if k == "cc" and not with_cc:
                     continue
                 if bufs.get("fx_" + k) is None:
                     bufs["fx_" + k] = torch.zeros(shape, dtype=dtype, device=dev)
@@ -937,7 +1024,18 @@ class DecompScorePosNet3D(nn.Module):
                 pw["tab_fixed"] = self.fixed_step_table().to(dev)
             ent["fixed"] = fixed["mode"]
             ent["fixed_struct"] = hip_lib.fixed_struct(fixed["mode"], bufs["fx_mask"], bufs["fx_v0"], bufs["fx_b0"], bufs["fx_x0c"],
-                                                       bufs["fx_cc"] if replace else None, pw["tab_fixed"] if replace else None)
+                                                       bufs["fx_cc"] if with_cc else None, pw["tab_fixed"] if replace else None)
+        # resampling: the epoch int belongs to the entry and is read at every launch, the jump table to the packed weights (one per
+        # jump length); neither j nor r reaches the captured graph
+        ent["resample"], ent["resample_struct"] = None, None
+        if resample is not None:
+            if bufs.get("epoch") is None:
+                bufs["epoch"] = torch.zeros(1, dtype=torch.int32, device=dev)
+            tabs = pw.setdefault("tab_jump", {})
+            if resample["j"] not in tabs:
+                tabs[resample["j"]] = self.resample_jump_table(resample["j"]).to(dev)
+            ent["resample"] = dict(resample)
+            ent["resample_struct"] = hip_lib.resample_struct(resample["j"], tabs[resample["j"]], bufs["epoch"])
         for k in ("u_v", "u_b", "eps"):
             bufs[k] = None
         if noise is not None:
@@ -997,7 +1095,10 @@ class DecompScorePosNet3D(nn.Module):
             ent["uploaded"] = [(t, None if t is None else t._version) for t in src]
             ent["uploaded_pw"], ent["uploaded_l0"], ent["uploaded_mode"] = pw, bool(use_l0), d.get("upload_mode")
         draw_level = fixed is not None and fixed["mode"] == "replace" and fixed["init"] == "draw"
-        if n_steps > 0 or draw_level:                      # (a chain of no steps still prepares its held rows)
+        if resample is not None:                           # (the epoch starts with the chain)
+            hip_lib.check(lib.dd_sampler_reset_resample(ctypes.byref(sm), ctypes.byref(ent["resample_struct"]), hip_lib.stream_ptr(dev)),
+                          "dd_sampler_reset_resample")
+        elif n_steps > 0 or draw_level:                    # (a chain of no steps still prepares its held rows)
             hip_lib.check(lib.dd_sampler_reset(ctypes.byref(sm), hip_lib.stream_ptr(dev)), "dd_sampler_reset")
         # held rows in front of the first step: hold -- the known values; replace, init 'draw' -- level t_start at Philox time
         # t_start + 1 ('given': init_ligand_* already holds that level)
@@ -1008,7 +1109,8 @@ class DecompScorePosNet3D(nn.Module):
         # everything that shapes the captured step graph besides the (cached) pointers
         ent["sig"] = (sm.drift_armsca, sm.armsca_min_d, sm.armsca_max_d, sm.armsca_scale, sm.drift_clash, sm.clash_sigma,
                       sm.clash_gamma, sm.clash_scale, sm.drift_repul, sm.repul_max_d, sm.repul_scale, sm.drift_norm_batch,
-                      int(lib.dd_debug_options_epoch()), bool(use_l0), ent["keyed"], fixed is not None, ent["fixed"])
+                      int(lib.dd_debug_options_epoch()), bool(use_l0), ent["keyed"], fixed is not None, ent["fixed"],
+                      resample is not None)
         if cacheable:
             cache[key] = ent                               # (re-inserted: most recently used last)
             self._evict_chain_cache(self._CACHE_MAX)
@@ -1170,7 +1272,7 @@ class DecompScorePosNet3D(nn.Module):
                          energy_drift_opt=None,
                          full_protein_pos=None, full_batch_protein=None,
                          noise=None, seed=None, keep_traj=True, use_graph=True, start_step=0, _drift_norm_batch=0,
-                         sample_keys=None, fixed=None):
+                         sample_keys=None, fixed=None, resample=None):
         """Reverse diffusion (reference: models/decompdiff.py:552-703), same arguments and return
         keys.  Extra keyword-only knobs (all optional, reference call sites never pass them):
 
@@ -1200,6 +1302,17 @@ class DecompScorePosNet3D(nn.Module):
           their level ``t_start`` on the device first, ``init="given"`` (required with ``noise`` / ``start_step > 0``) takes the
           held rows of ``init_ligand_*`` as that level.  ``replace`` needs ``prior_centers``.  Bad shapes, dtypes, modes or
           classes raise ValueError; so does a ``ligand_atom_mask`` that masks atoms out.
+        * ``resample`` — RePaint's resampling ("jump-back") schedule, valid only together with ``fixed`` and without ``noise``:
+          ``dict(jump_length=j, n_resample=r)``.  After every j reverse steps (jump points anchored at the call's last level) the
+          WHOLE ligand is diffused forward again by j levels on the device and denoised once more, r passes in all
+          (:func:`resample_schedule` is the contract: ``num_steps + (r - 1) * j * (num_steps // j)`` reverse steps).  In ``replace``
+          mode a jump moves every row, in ``hold`` mode the held atoms and the bonds between them keep their bits; both modes
+          need ``prior_centers``.  A revisited time draws afresh (its Philox time word carries the number of jumps done), with the
+          addressing of ``seed`` / ``sample_keys`` unchanged, so a keyed sample's chain stays independent of its batch.  The
+          trajectories have one entry per reverse step ("position"; jumped states are not recorded) and the result gains
+          ``t_traj``, the int64 times of the positions.  The schedule belongs to the call's range: with ``start_step`` / a
+          shorter ``num_steps`` a split chain is NOT the unsplit one.  ``r = 1`` or ``j > num_steps``: bit for bit the call
+          without ``resample``.  Wrong keys or types, ``j < 1``, ``r < 1``, no ``fixed``, ``noise=``: ValueError.
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
@@ -1212,10 +1325,14 @@ class DecompScorePosNet3D(nn.Module):
                 raise ValueError("sample_keys excludes noise= and an explicit seed=: a chain draws from one source")
             sample_keys = _as_sample_keys(sample_keys, batch_ligand)
             seed = 0                                             # (not read by a keyed chain; no draw from torch's generator)
+        if resample is not None:
+            if start_step < 0 or num_steps + start_step > self.num_timesteps:
+                raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
+            resample = _as_resample(resample, fixed, noise, self.num_timesteps, num_steps, start_step)
         if fixed is not None:
             fixed = _as_fixed(fixed, batch_ligand.numel(), ligand_fc_bond_index, init_ligand_fc_bond_type, self.num_classes,
                               self.num_bond_classes, noise, start_step, prior_centers, ligand_decomp_batch, ligand_atom_mask,
-                              protein_pos.device)
+                              protein_pos.device, need_cc=resample is not None)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         key_t = (protein_pos, batch_protein, batch_ligand, ligand_fc_bond_index, ligand_v_aux)
@@ -1231,19 +1348,21 @@ class DecompScorePosNet3D(nn.Module):
                      init_ligand_fc_bond_type=init_ligand_fc_bond_type, batch_ligand_bond=batch_ligand_bond,
                      full_protein_pos=full_protein_pos, full_batch_protein=full_batch_protein),
                 ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
-                start_step=start_step, sample_keys=sample_keys, fixed=fixed)
+                start_step=start_step, sample_keys=sample_keys, fixed=fixed, resample=resample)
         chain = self._prepare_chain(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
                                     batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                                     ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode,
                                     energy_drift_opt, full_protein_pos, full_batch_protein, noise, seed, keep_traj,
-                                    _drift_norm_batch, start_step, static=static, sample_keys=sample_keys, fixed=fixed)
+                                    _drift_norm_batch, start_step, static=static, sample_keys=sample_keys, fixed=fixed,
+                                    resample=resample)
         if static is None and "static" in chain:
             self._static_memo_put(key_t, center_pos_mode, chain["static"])
         tr = self.__dict__.get("_trace")
         if tr is not None:
             tr.append(("prepared>", time.perf_counter()))
-        self._run_chains([chain], num_steps, use_graph)
-        out = self._collect_chain(chain, num_steps, keep_traj)
+        n_pos = num_steps if resample is None else resample["n_total"]
+        self._run_chains([chain], n_pos, use_graph)
+        out = self._collect_chain(chain, n_pos, keep_traj)
         if tr is not None:
             tr.append(("collected>", time.perf_counter()))
         self._last = (chain["s"], chain["bufs"])
@@ -1253,7 +1372,7 @@ class DecompScorePosNet3D(nn.Module):
                        batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                        ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode, energy_drift_opt,
                        full_protein_pos, full_batch_protein, noise, seed, keep_traj, drift_norm_batch, start_step=0,
-                       static=None, cache_slot=0, sample_keys=None, fixed=None):
+                       static=None, cache_slot=0, sample_keys=None, fixed=None, resample=None):
         """Validate one dense batch, centre it, allocate its state / workspace and fill the ``dd_sampler`` struct.
         ``static``: what an earlier call with the same pocket / batch-vector tensors established (_static_memo_get)."""
         d = self._dense_inputs(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
@@ -1305,15 +1424,55 @@ class DecompScorePosNet3D(nn.Module):
             fx = dict(mode=fixed["mode"], init=fixed["init"], mask=fixed["mask"].to(torch.uint8), v0=fixed["v"], b0=fixed["bond"],
                       x0c=(fixed["pos"].view(B, NL, 3) - off_l).contiguous(),
                       cc=None if fixed["cc"] is None else (fixed["cc"].view(B, NL, 3) - off_l).contiguous())
-        s, bufs, ent = self._make_sampler(d, pw, num_steps, t_start, noise, keep_traj, energy_drift_opt, atom_std,
-                                          offset.contiguous(), decomp, fpp, seed, drift_norm_batch, cache_slot=cache_slot,
-                                          sample_keys=sample_keys, fixed=fx)
-        return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent,
+        s, bufs, ent = self._make_sampler(d, pw, num_steps if resample is None else resample["n_total"], t_start, noise, keep_traj,
+                                          energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, drift_norm_batch,
+                                          cache_slot=cache_slot, sample_keys=sample_keys, fixed=fx, resample=resample)
+        return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent, t_traj=None if resample is None else resample["t_traj"],
                     static=dict(layout=(B, NP, NL), offset=offset, protein_pos_centered=d["protein_pos_centered"],
                                 aux_onehot=d["aux_onehot"]))
 
+    @staticmethod
+    def _chain_runs(chain, num_steps):
+        """[(reverse steps, followed by a jump)] of a prepared chain: the resampling schedule's runs, or one run of ``num_steps``."""
+        rs = chain["ent"].get("resample")
+        return rs["runs"] if rs else ([(int(num_steps), False)] if num_steps > 0 else [])
+
+    @staticmethod
+    def _pieces(runs, piece):
+        """The streamed chain's pieces [(lo, hi, ops)]: positions [lo, hi) of the trajectories and the launches that fill them --
+        replay counts and "jump" -- in order.  Pieces hold at most ``piece`` positions and end on run boundaries (a run that fits no
+        piece is cut), and a jump goes with the run in front of it.  One run without a jump: the plain chain's equal pieces."""
+        pieces, ops, lo, hi = [], [], 0, 0
+        for n, jump in runs:
+            if hi > lo and hi - lo + n > piece:
+                pieces.append((lo, hi, ops))
+                ops, lo = [], hi
+            while n > piece:
+                pieces.append((lo, lo + piece, [piece]))
+                lo = hi = lo + piece
+                n -= piece
+            if n:
+                ops.append(n)
+                hi += n
+            if jump:
+                ops.append("jump")
+            if hi - lo >= piece:
+                pieces.append((lo, hi, ops))
+                ops, lo = [], hi
+        if hi > lo or ops:
+            pieces.append((lo, hi, ops))
+        return pieces
+
+    def _jump(self, chain, stream):
+        """Enqueue the forward jump of a resampled chain (and the rebase of its run state) on ``stream`` (a raw handle)."""
+        ent = chain["ent"]
+        keys = hip_lib.ptr(chain["bufs"]["sample_keys"]) if ent.get("keyed") else None
+        hip_lib.check(hip_lib.load().dd_resample_jump(ctypes.byref(chain["s"]), keys, ctypes.byref(ent["fixed_struct"]),
+                                                      ctypes.byref(ent["resample_struct"]), stream), "dd_resample_jump")
+
     def _run_chains(self, chains, num_steps, use_graph):
-        """Advance every prepared chain by ``num_steps``.  One chain: the captured step graph replayed on a dedicated
+        """Advance every prepared chain by ``num_steps`` (resampled chains: positions -- every chain of a call shares the schedule;
+        the runs of graph replays or eager steps alternate with jump launches on the chain's stream).  One chain: the captured step graph replayed on a dedicated
         stream (the legacy default stream cannot be captured).  Several chains (the equal-size groups of a ragged batch):
         one graph and one stream each, replayed round-robin so the groups overlap on the GPU."""
         lib = hip_lib.load()
@@ -1340,7 +1499,10 @@ class DecompScorePosNet3D(nn.Module):
                         DecompScorePosNet3D._graph_counter += 1
                         ent["graph_id"] = DecompScorePosNet3D._graph_counter
                     try:
-                        hip_lib.check(lib.dd_graph_launch(ent["graph"], int(num_steps), side.cuda_stream), "dd_graph_launch")
+                        for n, jump in self._chain_runs(c, num_steps):
+                            hip_lib.check(lib.dd_graph_launch(ent["graph"], int(n), side.cuda_stream), "dd_graph_launch")
+                            if jump:
+                                self._jump(c, side.cuda_stream)
                     finally:
                         side.synchronize()
                         if not cached:
@@ -1349,7 +1511,16 @@ class DecompScorePosNet3D(nn.Module):
             else:
                 with torch.cuda.stream(side):
                     for c in chains:
-                        if c["ent"].get("fixed"):
+                        if c["ent"].get("resample"):
+                            keys = hip_lib.ptr(c["bufs"]["sample_keys"]) if c["ent"].get("keyed") else None
+                            for n, jump in self._chain_runs(c, num_steps):
+                                hip_lib.check(lib.dd_sample_steps_resample(
+                                    ctypes.byref(c["s"]), self._model_opts(), keys, ctypes.byref(c["ent"]["fixed_struct"]),
+                                    ctypes.byref(c["ent"]["resample_struct"]), int(n), hip_lib.stream_ptr(dev)), "dd_sample_steps_resample")
+                                if jump:
+                                    self._jump(c, hip_lib.stream_ptr(dev))
+                            rc = 0
+                        elif c["ent"].get("fixed"):
                             rc = lib.dd_sample_steps_fixed(ctypes.byref(c["s"]), self._model_opts(),
                                                            hip_lib.ptr(c["bufs"]["sample_keys"]) if c["ent"].get("keyed") else None,
                                                            ctypes.byref(c["ent"]["fixed_struct"]), int(num_steps), hip_lib.stream_ptr(dev))
@@ -1378,9 +1549,13 @@ class DecompScorePosNet3D(nn.Module):
             try:
                 for c, st in zip(chains, pool):
                     graphs.append(self._create_step_graph(c, 1, st.cuda_stream))
-                for _ in range(int(num_steps)):
-                    for g, st in zip(graphs, pool):
-                        hip_lib.check(lib.dd_graph_launch(g, 1, st.cuda_stream), "dd_graph_launch")
+                for n, jump in self._chain_runs(chains[0], num_steps):      # (one call: every chain has the same runs)
+                    for _ in range(int(n)):
+                        for g, st in zip(graphs, pool):
+                            hip_lib.check(lib.dd_graph_launch(g, 1, st.cuda_stream), "dd_graph_launch")
+                    if jump:
+                        for c, st in zip(chains, pool):
+                            self._jump(c, st.cuda_stream)
             finally:
                 for st in pool:
                     st.synchronize()
@@ -1404,7 +1579,12 @@ class DecompScorePosNet3D(nn.Module):
         a keyed chain's kernels read the keys from the entry's own buffer."""
         lib = hip_lib.load()
         graph = ctypes.c_void_p()
-        if chain["ent"].get("fixed"):
+        if chain["ent"].get("resample"):
+            rc = lib.dd_graph_create_resample(ctypes.byref(chain["s"]), self._model_opts(),
+                                              hip_lib.ptr(chain["bufs"]["sample_keys"]) if chain["ent"].get("keyed") else None,
+                                              ctypes.byref(chain["ent"]["fixed_struct"]), ctypes.byref(chain["ent"]["resample_struct"]),
+                                              int(steps_per_graph), stream, ctypes.byref(graph))
+        elif chain["ent"].get("fixed"):
             rc = lib.dd_graph_create_fixed(ctypes.byref(chain["s"]), self._model_opts(),
                                            hip_lib.ptr(chain["bufs"]["sample_keys"]) if chain["ent"].get("keyed") else None,
                                            ctypes.byref(chain["ent"]["fixed_struct"]), int(steps_per_graph), stream, ctypes.byref(graph))
@@ -1418,7 +1598,7 @@ class DecompScorePosNet3D(nn.Module):
 
     _TRAJ_KEYS = ("traj_pos", "traj_v", "traj_bond", "traj_v0", "traj_vt", "traj_bt")
 
-    def _run_chain_streaming(self, chain, num_steps, prime=True):
+    def _run_chain_streaming(self, chain, num_steps, prime=True, runs=None):
         """One chain, trajectories kept: the step graph is replayed in chunks and every finished chunk of the six
         trajectory buffers is drained to the host (device -> pinned staging on a copy stream -> the result tensors,
         with the int32 -> int64 widening in that last host copy) while the GPU is already working on the next chunk,
@@ -1439,7 +1619,9 @@ class DecompScorePosNet3D(nn.Module):
         chunk = int(os.environ.get("DD_TRAJ_CHUNK", "0")) or max(8, min(128, (24 << 20) // max(per_step, 1)))
         side.wait_stream(cur)
         spg = int(os.environ.get("DD_STEPS_PER_GRAPH", "1"))
-        if spg < 1 or num_steps % spg or chunk % spg:
+        if runs is None:
+            runs = self._chain_runs(chain, num_steps)
+        if spg < 1 or num_steps % spg or chunk % spg or ent.get("resample"):      # (resampled chains: runs of any length)
             spg = 1
         gsig = (ent["sig"], spg, side.cuda_stream)
         cached = any(e is ent for e in DecompScorePosNet3D._chain_cache.values())
@@ -1509,13 +1691,17 @@ class DecompScorePosNet3D(nn.Module):
             piece = min(chunk, max(8, -(-num_steps // 3)))
             if spg > 1:
                 piece = max(spg, piece // spg * spg)
-            for c, lo in enumerate(range(0, num_steps, piece)):
-                hi = min(num_steps, lo + piece)
+            pieces = self._pieces(runs, piece)
+            for c, (lo, hi, ops) in enumerate(pieces):
                 mark(f"launch{c}<")
                 if tr is not None and c == 0:              # (trace mode: the device's own clock around every piece)
                     gpu_ev = [torch.cuda.Event(enable_timing=True)]
                     gpu_ev[0].record(side)
-                hip_lib.check(lib.dd_graph_launch(graph, (hi - lo) // spg, side.cuda_stream), "dd_graph_launch")
+                for op in ops:
+                    if op == "jump":
+                        self._jump(chain, side.cuda_stream)
+                    else:
+                        hip_lib.check(lib.dd_graph_launch(graph, op // spg, side.cuda_stream), "dd_graph_launch")
                 mark(f"launch{c}>")
                 ev = torch.cuda.Event(enable_timing=tr is not None)
                 ev.record(side)
@@ -1545,7 +1731,7 @@ class DecompScorePosNet3D(nn.Module):
                 done.record(copy_st)
                 pending.append((lo, hi, c % 2, done))
                 if c == 0 and not dbg & 4:
-                    tail = ((num_steps - 1) // piece) * piece
+                    tail = pieces[-1][0]
                     for k in keys:                     # first touch of the pages the un-hidden last drain writes
                         host["final_np"][k][tail:].fill(0)
                 mark(f"copies{c}>")
@@ -1578,7 +1764,7 @@ class DecompScorePosNet3D(nn.Module):
         if n < 17:
             return False
         state = {k: bufs[k].clone() for k in ("lig_pos", "lig_v", "lig_bond", "step_counter")}
-        self._run_chain_streaming(chain, n, prime=False)
+        self._run_chain_streaming(chain, n, prime=False, runs=[(n, False)])     # (plain steps: no jumps, the epoch stays)
         chain.pop("traj_cpu", None)
         for k, v in state.items():
             bufs[k].copy_(v)
@@ -1613,4 +1799,6 @@ class DecompScorePosNet3D(nn.Module):
         else:
             for k in ("pos_traj", "v_traj", "bond_traj", "v0_traj", "vt_traj", "bt_traj"):
                 out[k] = []
+        if chain.get("t_traj") is not None:                # resampled chains: the time of every position
+            out["t_traj"] = chain["t_traj"].clone()
         return out

@@ -550,6 +550,54 @@ int dd_graph_create_fixed(const dd_sampler* s, const dd_model_opts* opts /*HOST*
                           const dd_fixed* fixed /*HOST*/, int steps_per_graph, void* stream, void** graph_out /*HOST*/);
 int dd_fixed_init(const dd_sampler* s, const uint64_t* sample_keys /*DEVICE [B] or NULL*/, const dd_fixed* fixed /*HOST*/, void* stream);
 
+/* Resampling (EXTENSION; the other half of RePaint beside DD_FIXED_REPLACE): after some reverse steps the whole ligand is diffused
+ * FORWARD again by jump_length levels and denoised once more, so that the free atoms get several passes in which to agree with
+ * the held ones.  The host owns the schedule (decompdiff_amd.resample_schedule: runs of reverse steps with a jump between them);
+ * the library supplies the jump, fresh draws for a revisited time, and step entry points that honour them.
+ *   Levels: a state is at level l in {-1, 0, .., T-1}; the reverse step at time t takes level t to t - 1; level -1 is what the
+ *     step at t = 0 leaves (the clean sample), with alphas_cumprod[-1] = 1 for all three schedules.  The chain's current level is
+ *     l = t_start - steps done of the run state (step_counter).
+ *   dd_resample_jump: the forward transition q(x_m | x_l), m = l + jump_length, in ONE launch over coordinates, atom rows and
+ *     bond rows, coefficients from tab [6][T] at m (rows A, S, lr_v, l1mr_v, lr_b, l1mr_b; composed in float64 by the host and
+ *     rounded once; entries m < jump_length - 1 are never read):
+ *       x' = A * (x - cc) + (S * e) * atom_std + cc        A = sqrt(abar[m] / abar[l]), S = sqrt(1 - abar[m] / abar[l]), cc as in
+ *                                                          dd_fixed (REQUIRED here in both modes), every operation rounded on
+ *                                                          its own; the jump_length-fold composition of decompdiff.py:436-447
+ *       class' = argmax_c gumbel(u_c) + log_add_exp(log_onehot(class)_c + lr, l1mr + log_prior_c)
+ *                                                          lr = log_cumprod[m] - log_cumprod[l], l1mr = log(1 - exp(lr)):
+ *                                                          transitions.py:123-133 composed (exact for any prior)
+ *     DD_FIXED_REPLACE: every row moves (a held row at level m is then a valid forward sample of its clean value).
+ *     DD_FIXED_HOLD: held atoms, and bonds with both endpoints held, keep their bits; every other row moves.  Drift terms play no
+ *     part, and a jumped state is written to no trajectory: trajectory position p is the state after the p-th reverse step of the
+ *     call (steps done keeps counting through jumps).  A one-thread launch behind the jump rebases the run state
+ *     (t_start += jump_length, so the next step runs at time m) and adds 1 to *epoch.  m must be < T (the host's schedule sees to it).
+ *   Fresh draws: *epoch = jumps done so far in the chain.  A reverse step of the _resample entry points draws exactly as
+ *     dd_sample_steps_fixed does, but with Philox counter word 2 = t + 65536 * epoch instead of t (epoch 0: the same bits).  The
+ *     jump that raises the epoch to e draws at word 2 = m + 65536 * e on streams of its own -- 3 atom types, 4 bond types,
+ *     8 coordinates (1, 2, 7 are the step's) -- with rows and keys addressed exactly like the step's: seed and flat row, or
+ *     sample_keys[b] and the row of the sample's own enumeration.  So sample_keys keeps its promise under resampling.
+ *     Needs T <= 65535 and at most 65535 jumps.
+ *   dd_sampler_reset_resample: dd_sampler_reset and *epoch = 0; in front of every chain.
+ * tab and epoch are DEVICE pointers read at every launch; jump_length is an argument of the jump launch only: a graph from
+ * dd_graph_create_resample serves every chain of its shape and mode, whatever the mask, the keys, jump_length and the number of
+ * passes (dd_graph_launch / dd_graph_destroy take it like any other).  `size` is the caller's sizeof(dd_resample).
+ *   resample == NULL, fixed == NULL, jump_length < 1, a NULL tab / epoch, T > 65535, injected noise (s->u_v / u_b / eps), and for
+ *   the jump a dd_fixed without cc: DD_ERR_BAD_ARG before any launch.  (New entry points, ABI unchanged.) */
+typedef struct dd_resample {
+  int32_t size;                  /* sizeof(dd_resample) of the caller */
+  int32_t jump_length;           /* j >= 1 */
+  const float* tab;              /* DEVICE [6][T] */
+  int32_t* epoch;                /* DEVICE [1] */
+} dd_resample;
+int dd_sample_steps_resample(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B] or NULL*/,
+                             const dd_fixed* fixed /*HOST*/, const dd_resample* resample /*HOST*/, int n_steps, void* stream);
+int dd_graph_create_resample(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B] or NULL*/,
+                             const dd_fixed* fixed /*HOST*/, const dd_resample* resample /*HOST*/, int steps_per_graph, void* stream,
+                             void** graph_out /*HOST*/);
+int dd_resample_jump(const dd_sampler* s, const uint64_t* sample_keys /*DEVICE [B] or NULL*/, const dd_fixed* fixed /*HOST*/,
+                     const dd_resample* resample /*HOST*/, void* stream);
+int dd_sampler_reset_resample(const dd_sampler* s, const dd_resample* resample /*HOST*/, void* stream);
+
 /* Drift guidance gradients at x_t (utils/guidance_funcs.py:24-78), analytic. grad [B,NL,3]. */
 int dd_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                     float* grad, int accumulate, void* stream);
