@@ -1253,6 +1253,18 @@ static int fixed_init(const dd_sampler* s, const uint64_t* sample_keys, const dd
   return launch_fixed_init(rb, r, p, st);
 }
 
+// dd_chain_init: the chain's level in front of its first step, every real row (dd_step.hip::k_chain_init)
+static int chain_init(const dd_sampler* s, const uint64_t* sample_keys, const dd_init* in, hipStream_t st) {
+  DriftGrads d;
+  StepRowsArgs r, rb;
+  StepPosArgs p;
+  fill_step_args(s, d, sample_keys, nullptr, &r, &rb, &p);
+  ChainInitArgs ci;
+  ci.mode = in->mode; ci.cc = in->cc; ci.std = in->std; ci.lp_v = in->atom_log_prior; ci.lp_b = in->bond_log_prior;
+  ci.x0c = in->x0c; ci.v0 = in->v0; ci.b0 = in->b0; ci.tab = in->tab; ci.nl_real = s->nl_real;
+  return launch_chain_init(rb, r, p, ci, st);
+}
+
 // dd_resample_jump: the forward jump of the chain's state and the rebase of its run state (dd_step.hip::k_jump)
 static int resample_jump(const dd_sampler* s, const uint64_t* sample_keys, const dd_fixed* fixed, const dd_resample* rsm, hipStream_t st) {
   DriftGrads d;
@@ -1814,6 +1826,30 @@ extern "C" int dd_fixed_init(const dd_sampler* s, const uint64_t* sample_keys, c
   int rc = dd::check_shapes(s);
   if (rc != DD_OK) return rc;
   return dd::fixed_init(s, sample_keys, &fx, (hipStream_t)stream);
+}
+
+// The caller's dd_init as a checked copy (fields beyond its `size` are NULL / 0)
+static int read_init(const dd_init* init, dd_init* out) {
+  memset(out, 0, sizeof(*out));
+  if (init->size < (int32_t)sizeof(int32_t) || init->size > 4096) return DD_ERR_BAD_ARG;
+  memcpy(out, init, (size_t)init->size < sizeof(*out) ? (size_t)init->size : sizeof(*out));
+  out->size = (int32_t)sizeof(*out);
+  if (out->mode != DD_INIT_PRIOR && out->mode != DD_INIT_NOISED) return DD_ERR_BAD_ARG;
+  if (!out->cc || !out->std) return DD_ERR_BAD_ARG;
+  if (out->mode == DD_INIT_NOISED && (!out->x0c || !out->v0 || !out->b0 || !out->tab)) return DD_ERR_BAD_ARG;
+  return DD_OK;
+}
+
+extern "C" int dd_chain_init(const dd_sampler* s, const uint64_t* sample_keys, const dd_init* init, void* stream) {
+  if (!check_step_sampler(s) || !init || !s->lig_pos || !s->lig_v || !s->lig_bond) return DD_ERR_BAD_ARG;
+  dd_init in;
+  if (read_init(init, &in) != DD_OK) return DD_ERR_BAD_ARG;
+  // the level is drawn here: a chain with injected noise supplies its own, and a noised level must exist
+  if (s->u_v || s->u_b || s->eps || s->T < 1) return DD_ERR_BAD_ARG;
+  if (in.mode == DD_INIT_NOISED && (s->t_start < 0 || s->t_start >= s->T)) return DD_ERR_BAD_ARG;
+  int rc = dd::check_shapes(s);
+  if (rc != DD_OK) return rc;
+  return dd::chain_init(s, sample_keys, &in, (hipStream_t)stream);
 }
 
 static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,

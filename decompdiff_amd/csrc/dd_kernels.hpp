@@ -274,5 +274,20 @@ int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const Step
 int launch_jump(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, const float* jtab, int j, int32_t* epoch,
                 hipStream_t st);
 int launch_reset_epoch(int32_t* epoch, hipStream_t st);
+// chain init (dd_init): the chain's level in front of its first step for every real row -- bond rows, atom rows, coordinates: one
+// launch.  rb / rv / p as for a step of the chain (sample_keys set for a keyed chain; no fixed atoms needed).
+struct ChainInitArgs {
+  int mode;                      // DD_INIT_PRIOR / DD_INIT_NOISED
+  const float* cc;               // [B*NL,3] centred centres
+  const float* std;              // [B*NL,3]
+  const float* lp_v;             // [NC] log prior of the atom classes, or NULL: the chain's (tab_v[4 * T + c])
+  const float* lp_b;             // [5] log prior of the bond classes, or NULL: the chain's
+  const float* x0c;              // noised: [B*NL,3] clean centred coordinates
+  const int32_t* v0;             // noised: [B*NL] clean atom classes
+  const int32_t* b0;             // noised: [B*NL*(NL-1)] clean bond classes
+  const float* tab;              // noised: [2][T] sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)
+  const int32_t* nl_real;        // [B] real ligand sizes of a padded batch (atom rows, coordinates), or NULL
+};
+int launch_chain_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, const ChainInitArgs& ci, hipStream_t st);
 
 }  // namespace dd

@@ -24,6 +24,8 @@ namespace dd {
 // Resampling (dd_resample): a chain that jumps back visits a time again, so the time word of a FIXED step is t + 65536 * epoch
 // (epoch = jumps done so far in the call; epoch 0: the bits above), and the jump that raises the epoch to e draws at
 // (l + j) + 65536 * e on streams of its own: 3 atom types, 4 bond types, 8 coordinates (same class blocks, same row addressing).
+// Chain init (dd_init): the chain's first level is drawn at the time word of that level (T, or t_start of a noised init) on streams
+// 5 atom types, 6 bond types, 9 coordinates.
 template <int NC>
 __device__ __forceinline__ float philox_uniform(uint64_t seed, long row, int step, uint32_t sid, int c) {
   Philox ph(seed);
@@ -703,6 +705,18 @@ int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const Step
 // in class order through v_readlane with the strict > of the serial loops.  Hold mode leaves the held rows alone; replace mode
 // moves every row (a held row at level m is then a valid forward sample of its clean value).  Draws: time word m + 65536 * e with
 // e = the epoch AFTER this jump, streams 3 / 4 / 8, rows and keys addressed as the step addresses them.
+// the first class with the largest score of a row that holds one class per lane: class order, strict > (the serial loops' winner)
+template <int NC>
+__device__ __forceinline__ int class_argmax(const float sc) {
+  int best = 0;
+  float bestv = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const float sk = lane_bcast(sc, k);
+    if (sk > bestv) { bestv = sk; best = k; }
+  }
+  return best;
+}
 template <int NC>
 __device__ __forceinline__ void jump_row(const StepRowsArgs& a, const long row, const int lane, const uint64_t seed, const int word,
                                          const uint32_t sid, const float lr, const float l1mr) {
@@ -712,13 +726,7 @@ __device__ __forceinline__ void jump_row(const StepRowsArgs& a, const long row, 
   const NoiseAddr na = noise_addr(a, row, seed);
   const float u = philox_uniform<NC>(na.key, na.row, word, sid, c);
   const float sc = gumbel_of(u) + log_add_exp((c == cur ? 0.f : -69.07755278982137f) + lr, l1mr + a.tab[4 * a.T + c]);
-  int best = 0;
-  float bestv = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    const float sk = lane_bcast(sc, k);
-    if (sk > bestv) { bestv = sk; best = k; }
-  }
+  const int best = class_argmax<NC>(sc);
   if (lane == 0) a.state[row] = best;
 }
 template <int NV>
@@ -768,6 +776,76 @@ int launch_reset_epoch(int32_t* epoch, hipStream_t st) {
   return DD_OK;
 }
 
+// Chain init (include/decompdiff_hip.h, dd_init): the chain's level in front of its first step, drawn for every REAL row of the
+// batch in one launch laid out as k_jump (block ranges over bond rows, atom rows, coordinates; a type row is one wave with one
+// class per lane).  PRIOR: x = cc + (e std), class = argmax gumbel(u_c) + log prior_c, drawn at Philox time T (the level above the
+// first step).  NOISED: level l = t_start (the run state's) of the forward process of a known ligand, with the formulas of the
+// held rows of replace mode (fixed_noised_pos / fixed_q0), drawn at Philox time l.  Streams of their own: 5 atom types, 6 bond
+// types, 9 coordinates -- no counter is shared with a step (1 / 2 / 7), a jump (3 / 4 / 8) or k_fixed_init (a step's streams).
+// Rows and keys are addressed as a step addresses them (noise_addr / step_pos_normal); padding rows of a padded batch -- the
+// rows noise_addr leaves at their padded address -- keep what the host put there.
+__device__ __forceinline__ bool bond_row_real(const StepRowsArgs& a, const long row) {
+  if (a.nl_real == nullptr) return true;
+  const int b = (int)(row / a.rows_per_sample);
+  const int r = (int)(row - (long)b * a.rows_per_sample);
+  const int n = a.nl_real[b], dst = r / (a.NL - 1), sp = r - dst * (a.NL - 1);
+  return dst < n && sp < n - 1;
+}
+template <int NC>
+__device__ __forceinline__ void chain_init_row(const StepRowsArgs& a, const long row, const int lane, const uint64_t seed, const int word,
+                                               const uint32_t sid, const float* __restrict__ lp, const int32_t* __restrict__ v0,
+                                               const float lca, const float l1mca) {
+  const int c = lane < NC ? lane : NC - 1;                         // lanes >= NC shadow the last class (results unused)
+  const NoiseAddr na = noise_addr(a, row, seed);
+  const float u = philox_uniform<NC>(na.key, na.row, word, sid, c);
+  const float log_prior = lp != nullptr ? lp[c] : a.tab[4 * a.T + c];
+  const float sc = gumbel_of(u) + (v0 != nullptr ? fixed_q0(c == v0[row], lca, l1mca, log_prior) : log_prior);
+  const int best = class_argmax<NC>(sc);
+  if (lane == 0) a.state[row] = best;
+}
+template <int NV>
+__global__ __launch_bounds__(256) void k_chain_init(const StepRowsArgs rb, const StepRowsArgs rv, const StepPosArgs p, const ChainInitArgs ci,
+                                                    int nb_b, int nb_v) {
+  const int blk = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const RunState rs = load_run_state(rb.step_counter, 0);
+  const int T = p.T;
+  const bool noised = ci.mode == DD_INIT_NOISED;
+  const int l = noised ? rs.t_start : T;                           // the level drawn = the Philox time word
+  if (noised && (l < 0 || l >= T)) return;                         // (the host checks the level; never index past the tables)
+  if (blk < nb_b) {
+    const long row = (long)blk * 4 + wave;
+    if (row >= rb.rows || !bond_row_real(rb, row)) return;         // (wave-uniform)
+    chain_init_row<DD_NUM_B>(rb, row, lane, rs.seed, l, 6u, ci.lp_b, noised ? ci.b0 : nullptr, noised ? rb.tab[2 * T + l] : 0.f,
+                             noised ? rb.tab[3 * T + l] : 0.f);
+  } else if (blk < nb_b + nb_v) {
+    const long row = (long)(blk - nb_b) * 4 + wave;
+    if (row >= rv.rows) return;
+    if (ci.nl_real != nullptr && (int)(row % p.NL) >= ci.nl_real[row / p.NL]) return;
+    chain_init_row<NV>(rv, row, lane, rs.seed, l, 5u, ci.lp_v, noised ? ci.v0 : nullptr, noised ? rv.tab[2 * T + l] : 0.f,
+                       noised ? rv.tab[3 * T + l] : 0.f);
+  } else {
+    const int idx = (blk - nb_b - nb_v) * 256 + threadIdx.x;
+    if (idx >= p.B * p.NL * 3) return;
+    const int atom = idx / 3, b = atom / p.NL;
+    if (ci.nl_real != nullptr && atom - b * p.NL >= ci.nl_real[b]) return;
+    const float e = step_pos_normal(p, idx, b, rs.seed, l, 9u);
+    const float cc = ci.cc[idx], sd = ci.std[idx];
+    p.xt[idx] = noised ? fixed_noised_pos(ci.tab[l], ci.tab[T + l], ci.x0c[idx], cc, e, sd) : __fadd_rn(cc, __fmul_rn(e, sd));
+  }
+}
+int launch_chain_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, const ChainInitArgs& ci, hipStream_t st) {
+  if (rb.NC != DD_NUM_B || (rv.NC != 8 && rv.NC != 13 && rv.NC != 23)) return DD_ERR_UNSUPPORTED_SHAPE;
+  if ((ci.mode != DD_INIT_PRIOR && ci.mode != DD_INIT_NOISED) || ci.cc == nullptr || ci.std == nullptr) return DD_ERR_BAD_ARG;
+  if (ci.mode == DD_INIT_NOISED && (!ci.x0c || !ci.v0 || !ci.b0 || !ci.tab)) return DD_ERR_BAD_ARG;
+  const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
+  const dim3 grid(nb_b + nb_v + nb_p);
+  if (rv.NC == 8) hipLaunchKernelGGL(k_chain_init<8>, grid, dim3(256), 0, st, rb, rv, p, ci, nb_b, nb_v);
+  else if (rv.NC == 13) hipLaunchKernelGGL(k_chain_init<13>, grid, dim3(256), 0, st, rb, rv, p, ci, nb_b, nb_v);
+  else hipLaunchKernelGGL(k_chain_init<23>, grid, dim3(256), 0, st, rb, rv, p, ci, nb_b, nb_v);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
 int launch_step_rows(const StepRowsArgs& a, hipStream_t st) {
   if (a.rows <= 0) return DD_OK;
   dim3 grid((a.rows + 3) / 4);
@@ -806,7 +884,7 @@ int launch_advance(int32_t* ctr, hipStream_t st) {
 }  // namespace dd
 
 namespace dd {
-// kind: stream id in the low byte (1 / 3 atom types, 2 / 4 bond types, 7 / 8 coordinates), atom class count in bits 8-15 (0 = 8)
+// kind: stream id in the low byte (1 / 3 / 5 atom types, 2 / 4 / 6 bond types, 7 / 8 / 9 coordinates), atom class count in bits 8-15 (0 = 8)
 template <int NC>
 __device__ __forceinline__ void debug_uniforms(uint64_t seed, int step, long rows, uint32_t sid, long i, float* __restrict__ out) {
   if (i >= rows * NC) return;
@@ -816,8 +894,8 @@ __global__ __launch_bounds__(256) void k_debug_philox(uint64_t seed, int step, l
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const uint32_t sid = (uint32_t)kind & 0xffu;
   const int nc = kind >> 8;
-  if (sid == 7u || sid == 8u) { if (i < rows) out[i] = philox_normal(seed, (int)i, step, sid); return; }
-  if (sid == 2u || sid == 4u) debug_uniforms<DD_NUM_B>(seed, step, rows, sid, i, out);
+  if (sid == 7u || sid == 8u || sid == 9u) { if (i < rows) out[i] = philox_normal(seed, (int)i, step, sid); return; }
+  if (sid == 2u || sid == 4u || sid == 6u) debug_uniforms<DD_NUM_B>(seed, step, rows, sid, i, out);
   else if (nc == 13) debug_uniforms<13>(seed, step, rows, sid, i, out);
   else if (nc == 23) debug_uniforms<23>(seed, step, rows, sid, i, out);
   else debug_uniforms<DD_NUM_V>(seed, step, rows, sid, i, out);
@@ -874,13 +952,15 @@ extern "C" int dd_drift_clash(const float* lig_pos, const float* offset, const f
 
 // Test aid: the production noise of one step, exactly as the step kernels draw it.  kind (low byte) 1: uniforms [rows,8] of the
 // atom-type stream, 2: uniforms [rows,5] of the bond-type stream, 7: normals [rows] of the coordinate stream; 3 / 4 / 8: the same
-// three of a resampling jump (`step` is the Philox time word, t + 65536 * epoch).  Bits 8-15 of kind: the atom class count of
-// kinds 1 / 3 (0 or 8, 13, 23 -> [rows, that many]).
+// three of a resampling jump (`step` is the Philox time word, t + 65536 * epoch); 5 / 6 / 9: the same three of the chain init
+// (dd_chain_init; `step` is the level drawn).  Bits 8-15 of kind: the atom class count of kinds 1 / 3 / 5 (0 or 8, 13, 23 ->
+// [rows, that many]).
 extern "C" int dd_debug_philox(uint64_t seed, int step, long rows, int kind, float* out, void* stream) {
   const int sid = kind & 0xff, nc = kind >> 8;
-  if (!out || rows <= 0 || kind < 0 || (sid != 1 && sid != 2 && sid != 7 && sid != 3 && sid != 4 && sid != 8)) return DD_ERR_BAD_ARG;
-  if (nc != 0 && ((sid != 1 && sid != 3) || (nc != 8 && nc != 13 && nc != 23))) return DD_ERR_BAD_ARG;
-  const long n = (sid == 7 || sid == 8) ? rows : rows * ((sid == 1 || sid == 3) ? (nc ? nc : DD_NUM_V) : DD_NUM_B);
+  const bool atoms = sid == 1 || sid == 3 || sid == 5, bonds = sid == 2 || sid == 4 || sid == 6, normals = sid == 7 || sid == 8 || sid == 9;
+  if (!out || rows <= 0 || kind < 0 || !(atoms || bonds || normals)) return DD_ERR_BAD_ARG;
+  if (nc != 0 && (!atoms || (nc != 8 && nc != 13 && nc != 23))) return DD_ERR_BAD_ARG;
+  const long n = normals ? rows : rows * (atoms ? (nc ? nc : DD_NUM_V) : DD_NUM_B);
   hipLaunchKernelGGL(dd::k_debug_philox, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, step, rows, kind, out);
   DD_CHECK_LAUNCH();
   return DD_OK;

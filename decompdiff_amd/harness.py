@@ -47,7 +47,7 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                                    arms_natoms_config=None, scaffold_natoms_config=None, natoms_sampler=None,
                                    atom_prior_probs=None, bond_prior_probs=None, pool_batches: int = 1,
                                    sample_key_seed: Optional[int] = None, first_sample_index: int = 0,
-                                   fixed_fn=None, fixed_mode: str = "hold", resample=None) -> Dict[str, list]:
+                                   fixed_fn=None, fixed_mode: str = "hold", resample=None, init: str = "host") -> Dict[str, list]:
     """Sample ``num_samples`` ligands for one pocket in batches of ``batch_size``.
 
     ``pool_batches`` > 1 assembles that many consecutive batches exactly as the reference would (same random draws, same
@@ -68,9 +68,20 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     ``model.sample_keys(sample_key_seed, first_sample_index + g)`` in every model call (``sample_diffusion(sample_keys=...)``; only
     for models that take the extra keywords; excludes ``noise_fn``), so the CHAIN of a sample no longer depends on ``batch_size``,
     ``pool_batches`` or on which process runs it: a shard of a larger job passes its first global sample index.  The keys make
-    the chains reproducible, not this function's initial draws: the initial coordinates, atom and bond types are still drawn
-    from torch's CPU generator in the reference's order, batch by batch, and so still depend on the batching (and a keyed
-    model call draws nothing from that generator).
+    the chains reproducible, not -- with ``init="host"`` -- this function's initial draws: the initial coordinates, atom and bond
+    types are then still drawn from torch's CPU generator in the reference's order, batch by batch, and so still depend on the
+    batching (and a keyed model call draws nothing from that generator).  ``init="device"`` removes that limitation.
+
+    ``init``: ``"host"`` (default) -- the path above, unchanged.  ``"device"`` (needs ``sample_key_seed``, excludes ``noise_fn``;
+    ValueError otherwise) -- the JOB's contract: output sample ``first_sample_index + g`` is identical under any ``batch_size``,
+    ``pool_batches``, shard or order, in size, initial state, chain, results and all trajectories, so a job can be re-run one
+    sample at a time, resharded, or resumed.  Every sample is assembled ALONE (``build_batch(pocket, 1, ...)`` /
+    ``synth.build_sampling_batch(pocket, 1, ...)``) with torch's and numpy's global generators seeded from that sample's key
+    for the assembly -- so the atom counts of the ``prior`` / ``old`` / ``stat`` modes belong to the sample -- and restored
+    afterwards: the caller's generators end the call in the state they entered it.  A call's samples are collated with
+    ``synth.concat_sampling_batches``, the host-drawn ``init_ligand_*`` are dropped, and the model draws the first state on the
+    device: ``sample_diffusion(init=dict(mode="prior", centers=..., stds=..., atom_prior=atom_prior_probs,
+    bond_prior=bond_prior_probs), sample_keys=...)`` with the centres / stds the assembly drew its coordinates around.
 
     ``fixed_fn(sample_index, decomp_index_of_sample)`` (not None): conditional generation -- for output sample
     ``first_sample_index + g`` it returns ``dict(mask [n] bool, pos [n,3], v [n], bond [n*(n-1)])``, the sample's known atoms in
@@ -90,9 +101,38 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     pool_batches = max(1, int(pool_batches))
     steps = model.num_timesteps if num_steps is None else num_steps
 
+    def assemble_alone(g_local):
+        """init="device": sample ``g_local`` of this call assembled alone under its own key -> (kwargs, [size], init centers, stds)"""
+        key = int(sample_keys(sample_key_seed, int(first_sample_index) + g_local).item()) & 0xFFFFFFFFFFFFFFFF
+        torch.manual_seed(key)
+        np.random.seed([key & 0xFFFFFFFF, key >> 32])
+        if isinstance(pocket, PocketData):
+            drawn = []
+            b, n_atoms, _ = build_batch(pocket, 1, prior_mode=prior_mode, num_atoms_mode=num_atoms_mode,
+                                        num_classes=model.num_classes, num_bond_classes=model.num_bond_classes,
+                                        arms_natoms_config=arms_natoms_config, scaffold_natoms_config=scaffold_natoms_config,
+                                        natoms_sampler=natoms_sampler, atom_prior_probs=atom_prior_probs,
+                                        bond_prior_probs=bond_prior_probs, init_out=drawn)
+            centers, stds = drawn[0]
+        else:
+            scale = None if per_sample_std_scale is None else [per_sample_std_scale[g_local]]
+            b = synth.build_sampling_batch(pocket, 1, num_bond_classes=model.num_bond_classes, num_classes=model.num_classes,
+                                           per_sample_std_scale=scale)
+            n_atoms, centers, stds = [pocket.num_ligand_atoms], b["prior_centers"], b["prior_stds"]
+        return b, n_atoms, centers, stds
+
     def build(i):
-        """batch i as the reference assembles it: (kwargs, ligand sizes, injected noise or None)"""
+        """batch i as the reference assembles it: (kwargs, ligand sizes, injected noise or None, init centers / stds or None)"""
         n_data = batch_size if i < num_batch - 1 else num_samples - batch_size * (num_batch - 1)
+        if init == "device":
+            gen_state = (torch.get_rng_state(), np.random.get_state())
+            try:
+                alone = [assemble_alone(i * batch_size + k) for k in range(n_data)]
+            finally:
+                torch.set_rng_state(gen_state[0])
+                np.random.set_state(gen_state[1])
+            batch = alone[0][0] if n_data == 1 else synth.concat_sampling_batches([a[0] for a in alone])
+            return batch, [a[1][0] for a in alone], None, (torch.cat([a[2] for a in alone], 0), torch.cat([a[3] for a in alone], 0))
         if isinstance(pocket, PocketData):
             batch, n_atoms, _ = build_batch(pocket, n_data, prior_mode=prior_mode, num_atoms_mode=num_atoms_mode,
                                             num_classes=model.num_classes, num_bond_classes=model.num_bond_classes,
@@ -107,8 +147,14 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                                                num_classes=model.num_classes, per_sample_std_scale=scale)
             n_atoms = [pocket.num_ligand_atoms] * n_data
         noise = noise_fn(i, sum(n_atoms), sum(n * (n - 1) for n in n_atoms), steps) if noise_fn is not None else None
-        return batch, n_atoms, noise
+        return batch, n_atoms, noise, None
 
+    if init not in ("host", "device"):
+        raise ValueError(f"init must be 'host' or 'device', got {init!r}")
+    if init == "device" and (sample_key_seed is None or noise_fn is not None):
+        raise ValueError("init='device' needs sample_key_seed and excludes noise_fn: the first state is drawn with the samples' keys")
+    if init == "device" and not _accepts_extras(model):
+        raise ValueError("init='device' needs a model whose sample_diffusion takes sample_keys= and init=")
     if sample_key_seed is not None and noise_fn is not None:
         raise ValueError("sample_key_seed excludes noise_fn: a chain draws from one source")
     if resample is not None and (fixed_fn is None or noise_fn is not None):
@@ -117,18 +163,25 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     for i in range(0, num_batch, pool_batches):
         parts = [build(j) for j in range(i, min(num_batch, i + pool_batches))]
         if len(parts) == 1:
-            batch, n_atoms, noise = parts[0]
+            batch, n_atoms, noise, drawn_around = parts[0]
         else:                                                              # one collated batch (PyG increments re-applied)
             batch = synth.concat_sampling_batches([p[0] for p in parts])
             n_atoms = [n for p in parts for n in p[1]]
             noise = None if parts[0][2] is None else {k: torch.cat([p[2][k] for p in parts], 1) for k in parts[0][2]}
+            drawn_around = None if parts[0][3] is None else tuple(torch.cat([p[3][j] for p in parts], 0) for j in (0, 1))
         n_data = len(n_atoms)
         n_bonds = [n * (n - 1) for n in n_atoms]
+        if init == "device":                                               # (the host-drawn first state is dropped)
+            batch = dict(batch, init_ligand_pos=None, init_ligand_v=None, init_ligand_fc_bond_type=None)
         dev_batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
         extra = dict(noise=noise, seed=seed + i, use_graph=use_graph) if _accepts_extras(model) else {}
         if sample_key_seed is not None and extra:
             first = int(first_sample_index) + n_done
             extra = dict(use_graph=use_graph, sample_keys=sample_keys(sample_key_seed, range(first, first + n_data)))
+            if init == "device":
+                extra["init"] = dict(mode="prior", centers=drawn_around[0], stds=drawn_around[1],
+                                     atom_prior=None if atom_prior_probs is None else torch.as_tensor(np.asarray(atom_prior_probs, np.float32)),
+                                     bond_prior=None if bond_prior_probs is None else torch.as_tensor(np.asarray(bond_prior_probs, np.float32)))
         if fixed_fn is not None and extra:
             fixed = collate_fixed(fixed_fn, int(first_sample_index) + n_done, n_atoms, batch["ligand_decomp_index"], fixed_mode)
             if fixed is not None:

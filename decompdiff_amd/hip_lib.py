@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "dd_sample_steps_keyed", "dd_graph_create_keyed",
     "dd_sample_steps_fixed", "dd_graph_create_fixed", "dd_fixed_init",
     "dd_sample_steps_resample", "dd_graph_create_resample", "dd_resample_jump", "dd_sampler_reset_resample",
+    "dd_chain_init",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -138,6 +139,27 @@ def resample_struct(jump_length, tab, epoch) -> DDResample:
     r.size, r.jump_length = ctypes.sizeof(DDResample), int(jump_length)
     r.tab, r.epoch = tab.data_ptr(), epoch.data_ptr()
     return r
+
+
+INIT_PRIOR, INIT_NOISED = 1, 2                         # DD_INIT_PRIOR / DD_INIT_NOISED
+INIT_MODES = {"prior": INIT_PRIOR, "noised": INIT_NOISED}
+
+
+class DDInit(ctypes.Structure):
+    """struct dd_init (include/decompdiff_hip.h): what dd_chain_init draws the chain's first level from; `size` = sizeof of this
+    struct, every other pointer a DEVICE pointer (see `init_struct`)."""
+    _fields_ = [("size", c_int32), ("mode", c_int32), ("cc", c_void_p), ("std", c_void_p), ("atom_log_prior", c_void_p),
+                ("bond_log_prior", c_void_p), ("x0c", c_void_p), ("v0", c_void_p), ("b0", c_void_p), ("tab", c_void_p)]
+
+
+def init_struct(mode, cc, std, atom_log_prior=None, bond_log_prior=None, x0c=None, v0=None, b0=None, tab=None) -> DDInit:
+    """A filled dd_init from device tensors (the caller keeps them alive); mode: "prior" / "noised"."""
+    f = DDInit()
+    f.size, f.mode = ctypes.sizeof(DDInit), INIT_MODES[mode]
+    for name, t in (("cc", cc), ("std", std), ("atom_log_prior", atom_log_prior), ("bond_log_prior", bond_log_prior), ("x0c", x0c),
+                    ("v0", v0), ("b0", b0), ("tab", tab)):
+        setattr(f, name, None if t is None else t.data_ptr())
+    return f
 
 
 L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128      # DD_L0_TABLE_FLOATS
@@ -250,6 +272,8 @@ def load():
                                      POINTER(c_void_p)],
         "dd_resample_jump": [S, c_void_p, POINTER(DDFixed), POINTER(DDResample), c_void_p],
         "dd_sampler_reset_resample": [S, POINTER(DDResample), c_void_p],
+        # (the chain's first level drawn on the device: sample_keys, the host struct dd_init)
+        "dd_chain_init": [S, c_void_p, POINTER(DDInit), c_void_p],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],

@@ -207,6 +207,86 @@ def _fixed_rows(fx, rows_l, rows_b):
                 bond=fx["bond"][rows_b], cc=None if fx["cc"] is None else fx["cc"][rows_l])
 
 
+INIT_MODES = ("prior", "noised")
+
+
+def _as_init(init, batch_ligand, fc_index, ligand_decomp_batch, prior_centers, prior_stds, given, noise, start_step, num_timesteps,
+             num_classes, num_bond_classes, dev):
+    """``init`` of sample_diffusion, validated (ValueError) and moved to the device: dict(mode, cen f32 [n,3] -- the centre of
+    every atom, uncentred --, std f32 [n,3], atom_lp f32 [num_classes] or None, bond_lp f32 [num_bond_classes] or None and,
+    mode "noised", pos f32 [n,3], v int32 [n], bond int32 [n_bond]).  ``given``: the caller's init_ligand_pos / _v / _fc_bond_type."""
+    if not isinstance(init, dict) or init.get("mode") not in INIT_MODES:
+        raise ValueError(f"init must be None or a dict with mode in {INIT_MODES}")
+    mode = init["mode"]
+    allowed = {"mode", "centers", "stds", "atom_prior", "bond_prior"} | ({"pos", "v", "bond"} if mode == "noised" else set())
+    if set(init) - allowed or (mode == "noised" and any(k not in init for k in ("pos", "v", "bond"))):
+        raise ValueError(f"init mode {mode!r} takes the keys {sorted(allowed)} (got {sorted(init)})")
+    if any(t is not None for t in given):
+        raise ValueError("init draws the chain's first state on the device: init_ligand_pos, init_ligand_v and "
+                         "init_ligand_fc_bond_type must be None")
+    if noise is not None:
+        raise ValueError("init excludes noise=: the first state is drawn by the device generator")
+    if mode == "prior" and int(start_step) != 0:
+        raise ValueError("init mode 'prior' draws the level above the first step: it needs start_step == 0")
+    if mode == "noised" and not 0 <= int(start_step) < num_timesteps:
+        raise ValueError("init mode 'noised' needs 0 <= start_step < num_timesteps (the level num_timesteps - 1 - start_step)")
+    if fc_index is None:
+        raise NotImplementedError("the uni_o2_bond path needs the fully connected ligand bond graph")
+    n, n_bond = int(batch_ligand.numel()), int(fc_index.shape[1])
+    if ligand_decomp_batch is None or ligand_decomp_batch.numel() != n or (n and int(ligand_decomp_batch.min()) < 0):
+        raise ValueError("init needs ligand_decomp_batch [n_ligand]: the centre and std of every atom")
+    n_prior = int(ligand_decomp_batch.max()) + 1 if n else 0
+    per_atom = {}
+    for name, t, what in (("centers", init.get("centers"), prior_centers), ("stds", init.get("stds"), prior_stds)):
+        t = what if t is None else t
+        if t is None:
+            raise ValueError(f"init needs {name} (or prior_{name}): the chain's first level is drawn around the arm centres")
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3 or not t.dtype.is_floating_point or t.shape[0] < n_prior:
+            raise ValueError(f"init['{name}'] must be a float tensor [n_prior,3] with a row for every entry of ligand_decomp_batch")
+        per_atom[name] = t.detach().to(device=dev, dtype=torch.float32)[ligand_decomp_batch.to(dev)].contiguous()
+    log_priors = {}
+    for name, nc in (("atom_prior", num_classes), ("bond_prior", num_bond_classes)):
+        p = init.get(name)
+        if p is None:
+            log_priors[name] = None
+            continue
+        p = torch.as_tensor(p)
+        if tuple(p.shape) != (nc,) or not p.dtype.is_floating_point:
+            raise ValueError(f"init['{name}'] must be a float probability vector of shape ({nc},), got {tuple(p.shape)} {p.dtype}")
+        p = p.detach().cpu().double()
+        if not bool(torch.isfinite(p).all()) or bool((p < 0).any()) or float(p.sum()) <= 0:
+            raise ValueError(f"init['{name}'] must hold finite non-negative probabilities with a positive sum")
+        # (as DiscreteTransition: normalised, log of the clamped probabilities)
+        log_priors[name] = torch.log((p / p.sum()).clamp(min=1e-30)).to(device=dev, dtype=torch.float32).contiguous()
+    out = dict(mode=mode, cen=per_atom["centers"], std=per_atom["stds"], atom_lp=log_priors["atom_prior"],
+               bond_lp=log_priors["bond_prior"], pos=None, v=None, bond=None)
+    if mode == "noised":
+        pos, v, bond = (torch.as_tensor(init[k]) for k in ("pos", "v", "bond"))
+        for name, t, shape in (("pos", pos, (n, 3)), ("v", v, (n,)), ("bond", bond, (n_bond,))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"init['{name}'] must have shape {shape}, got {tuple(t.shape)}")
+        if not pos.dtype.is_floating_point:
+            raise ValueError("init['pos'] must be a float tensor")
+        if v.dtype.is_floating_point or bond.dtype.is_floating_point or v.dtype == torch.bool or bond.dtype == torch.bool:
+            raise ValueError("init['v'] and init['bond'] must be integer class ids")
+        v_c, bond_c = v.detach().cpu().long(), bond.detach().cpu().long()
+        if v_c.numel() and (int(v_c.min()) < 0 or int(v_c.max()) >= num_classes):
+            raise ValueError(f"init['v'] holds a class outside [0, {num_classes})")
+        if bond_c.numel() and (int(bond_c.min()) < 0 or int(bond_c.max()) >= num_bond_classes):
+            raise ValueError(f"init['bond'] holds a class outside [0, {num_bond_classes})")
+        out.update(pos=pos.detach().to(device=dev, dtype=torch.float32).contiguous(), v=v_c.to(device=dev, dtype=torch.int32),
+                   bond=bond_c.to(device=dev, dtype=torch.int32))
+    return out
+
+
+def _init_rows(ini, rows_l, rows_b):
+    """The rows ``rows_l`` (atoms) / ``rows_b`` (bonds) of a validated ``init`` (device index tensors): a group's share."""
+    out = dict(ini, cen=ini["cen"][rows_l], std=ini["std"][rows_l])
+    if ini["mode"] == "noised":
+        out.update(pos=ini["pos"][rows_l], v=ini["v"][rows_l], bond=ini["bond"][rows_b])
+    return out
+
+
 def resample_schedule(t_hi, t_lo, j, r):
     """The resampling ("jump-back") schedule of ``sample_diffusion(resample=dict(jump_length=j, n_resample=r))`` over the reverse
     steps t_hi .. t_lo: a list of ``("step", t)`` and ``("jump", l, l + j)`` in execution order.  Jump points are anchored at the
@@ -589,7 +669,7 @@ class DecompScorePosNet3D(nn.Module):
                                          kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"].numel(), need_protein=False)
 
     def _sample_heterogeneous(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                              use_graph, start_step=0, sample_keys=None, fixed=None, resample=None):
+                              use_graph, start_step=0, sample_keys=None, fixed=None, resample=None, chain_init=None):
         """Samples with different atom counts in one batch (PyG collate, utils/data.py:389-446).  Default: ONE launch
         sequence over the batch padded to its largest pocket / ligand with per-sample real counts (`_sample_padded`).
         Fallbacks to equal-size groups (`_sample_ragged`): DD_RAGGED_MODE=groups, or `batch_layout.fits_padded` says no."""
@@ -599,10 +679,10 @@ class DecompScorePosNet3D(nn.Module):
             if BL.fits_padded(layout, self.config.knn):
                 return self._sample_padded(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed,
                                            keep_traj, use_graph, start_step, layout.n_p, layout.n_l, sample_keys=sample_keys,
-                                           fixed=fixed, resample=resample)
+                                           fixed=fixed, resample=resample, chain_init=chain_init)
         return self._sample_ragged(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
                                    use_graph, start_step=start_step, layout=layout, sample_keys=sample_keys, fixed=fixed,
-                                   resample=resample)
+                                   resample=resample, chain_init=chain_init)
 
     def _padded_inputs(self, protein_pos, protein_v, bp, ligand_pos, ligand_v, aux, bl, fc_index, bond_type, batch_ligand_bond,
                        n_p, n_l, center_pos_mode):
@@ -648,7 +728,7 @@ class DecompScorePosNet3D(nn.Module):
         return dict(d=d, offset=offset, masks=masks, n_b=n_b, rows_l=rows_l, rows_b=rows_b, d_l=d_l, d_b=d_b)
 
     def _sample_padded(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, start_step, n_p, n_l, sample_keys=None, fixed=None, resample=None):
+                       use_graph, start_step, n_p, n_l, sample_keys=None, fixed=None, resample=None, chain_init=None):
         """Heterogeneous batch as one padded dense batch: every sample's atoms are the first rows of its [NPmax] / [NLmax]
         blocks, the kernels read the real counts from dd_sampler.np_real / nl_real (padding atoms are no kNN candidates,
         own no softmax segment and are no members of one) and the results are gathered back into the caller's flat order.
@@ -702,10 +782,19 @@ class DecompScorePosNet3D(nn.Module):
                       b0=zeros(B * Eb, dtype=torch.int32).index_copy_(0, d_b, fixed["bond"]),
                       x0c=zeros(B * NL, 3).index_copy_(0, d_l, fixed["pos"] - off_l),
                       cc=None if fixed["cc"] is None else zeros(B * NL, 3).index_copy_(0, d_l, fixed["cc"] - off_l))
+        ci = None
+        if chain_init is not None:                                         # scattered like the inputs; padding rows are never drawn
+            off_l = offset[kw["batch_ligand"].to(dev)]
+            noised = chain_init["mode"] == "noised"
+            ci = dict(chain_init, cc=zeros(B * NL, 3).index_copy_(0, d_l, chain_init["cen"] - off_l),
+                      std=zeros(B * NL, 3).index_copy_(0, d_l, chain_init["std"]),
+                      x0c=zeros(B * NL, 3).index_copy_(0, d_l, chain_init["pos"] - off_l) if noised else None,
+                      v0=zeros(B * NL, dtype=torch.int32).index_copy_(0, d_l, chain_init["v"]) if noised else None,
+                      b0=zeros(B * Eb, dtype=torch.int32).index_copy_(0, d_b, chain_init["bond"]) if noised else None)
         n_pos = num_steps if resample is None else resample["n_total"]
         s, bufs, ent = self._make_sampler(d, pw, n_pos, self.num_timesteps - 1 - int(start_step), pad_noise, keep_traj,
                                           energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, 0, masks=masks,
-                                          sample_keys=sample_keys, fixed=fx, resample=resample)   # (the padded batch keeps the caller's sample order)
+                                          sample_keys=sample_keys, fixed=fx, resample=resample, chain_init=ci)   # (the padded batch keeps the caller's sample order)
         chain = dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent, t_traj=None if resample is None else resample["t_traj"])
         self._run_chains([chain], n_pos, use_graph)
         out = self._collect_chain(chain, n_pos, keep_traj, rows_atoms=rows_l, rows_bonds=rows_b)
@@ -713,7 +802,8 @@ class DecompScorePosNet3D(nn.Module):
         return out
 
     def _sample_ragged(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None, fixed=None, resample=None):
+                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None, fixed=None, resample=None,
+                       chain_init=None):
         """One dense chain per group of samples of equal size (`BatchLayout.size_groups`).  ``split`` > 1 additionally cuts
         every group into that many sub-batches (measurement aid, tools/split_bench.py: two concurrent half-batches were
         measured slower than one chain).  ``layout``: what `_sampling_layout(kw)` gave the caller.
@@ -747,7 +837,8 @@ class DecompScorePosNet3D(nn.Module):
                 seed + 7919 * gi, keep_traj, B, start_step,        # (the armsca loss is averaged over the whole batch)
                 cache_slot=(g.ids[0] * split) // B,                # (sub-batches of one shape: own cached buffers each)
                 sample_keys=None if sample_keys is None else sample_keys[g.ids],
-                fixed=None if fixed is None else _fixed_rows(fixed, d_l, d_b), resample=resample)
+                fixed=None if fixed is None else _fixed_rows(fixed, d_l, d_b), resample=resample,
+                chain_init=None if chain_init is None else _init_rows(chain_init, d_l, d_b))
             prepared.append((chain, d_l, d_b, r_l, r_b))
         if concurrent is None:
             # measured on MI355X (tools/ragged_bench.py): with the runtime's default 4 hardware queues the
@@ -905,12 +996,15 @@ class DecompScorePosNet3D(nn.Module):
 
     def _make_sampler(self, d, pw, n_steps, t_start, noise, keep_traj, drift, atom_std, offset, decomp_index,
                       full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0, sample_keys=None, fixed=None,
-                      resample=None):
+                      resample=None, chain_init=None):
         """``n_steps``: trajectory positions of the chain (reverse steps; with ``resample`` -- the validated dict of
         `_as_resample` or None -- the schedule's n_total).
         ``sample_keys``: int64 [B] (host or device), the per-sample noise keys of this chain in the order of its samples, or None
         (the chain draws with ``seed``).  ``fixed``: the chain's fixed atoms in its dense layout -- dict(mode, init, mask uint8
-        [B*NL], v0 int32 [B*NL], b0 int32 [B*Eb], x0c [B*NL,3] centred, cc [B*NL,3] centred or None) -- or None."""
+        [B*NL], v0 int32 [B*NL], b0 int32 [B*Eb], x0c [B*NL,3] centred, cc [B*NL,3] centred or None) -- or None.
+        ``chain_init``: what the chain's first level is drawn from (dd_chain_init), in the chain's dense layout -- dict(mode, cc
+        [B*NL,3] centred, std [B*NL,3], atom_lp / bond_lp log priors or None, and, mode "noised", x0c [B*NL,3] centred, v0 int32
+        [B*NL], b0 int32 [B*Eb]) -- or None: d["ligand_pos_centered"] / d["ligand_v"] / d["bond"] are that level."""
         lib = hip_lib.load()
         dev = d["protein_pos"].device
         B, NP, NL = d["B"], d["NP"], d["NL"]
@@ -1036,6 +1130,29 @@ class DecompScorePosNet3D(nn.Module):
                 tabs[resample["j"]] = self.resample_jump_table(resample["j"]).to(dev)
             ent["resample"] = dict(resample)
             ent["resample_struct"] = hip_lib.resample_struct(resample["j"], tabs[resample["j"]], bufs["epoch"])
+        # chain init: as the fixed atoms -- buffers of the entry, contents of this call; the launch is part of the chain's preparation
+        # (below), not of its captured graph
+        ent["init_struct"] = None
+        if chain_init is not None:
+            noised = chain_init["mode"] == "noised"
+            ptrs = {}
+            for k, src_k, shape, dtype in (("cc", "cc", (B * NL, 3), torch.float32), ("std", "std", (B * NL, 3), torch.float32),
+                                           ("lp_v", "atom_lp", (self.num_classes,), torch.float32),
+                                           ("lp_b", "bond_lp", (self.num_bond_classes,), torch.float32),
+                                           ("x0c", "x0c", (B * NL, 3), torch.float32), ("v0", "v0", (B * NL,), torch.int32),
+                                           ("b0", "b0", (B * Eb,), torch.int32)):
+                t = chain_init.get(src_k)
+                if t is None:
+                    ptrs[k] = None
+                    continue
+                if bufs.get("ci_" + k) is None:
+                    bufs["ci_" + k] = torch.zeros(shape, dtype=dtype, device=dev)
+                bufs["ci_" + k].copy_(t.reshape(shape))
+                ptrs[k] = bufs["ci_" + k]
+            if noised and pw.get("tab_fixed") is None:
+                pw["tab_fixed"] = self.fixed_step_table().to(dev)
+            ent["init_struct"] = hip_lib.init_struct(chain_init["mode"], ptrs["cc"], ptrs["std"], ptrs["lp_v"], ptrs["lp_b"], ptrs["x0c"],
+                                                     ptrs["v0"], ptrs["b0"], pw["tab_fixed"] if noised else None)
         for k in ("u_v", "u_b", "eps"):
             bufs[k] = None
         if noise is not None:
@@ -1098,8 +1215,13 @@ class DecompScorePosNet3D(nn.Module):
         if resample is not None:                           # (the epoch starts with the chain)
             hip_lib.check(lib.dd_sampler_reset_resample(ctypes.byref(sm), ctypes.byref(ent["resample_struct"]), hip_lib.stream_ptr(dev)),
                           "dd_sampler_reset_resample")
-        elif n_steps > 0 or draw_level:                    # (a chain of no steps still prepares its held rows)
+        elif n_steps > 0 or draw_level or chain_init is not None:      # (a chain of no steps still prepares its first level / held rows)
             hip_lib.check(lib.dd_sampler_reset(ctypes.byref(sm), hip_lib.stream_ptr(dev)), "dd_sampler_reset")
+        # the chain's first level drawn on the device (every real row), in front of the held rows' preparation
+        if chain_init is not None:
+            keys_ptr = hip_lib.ptr(bufs["sample_keys"]) if sample_keys is not None else None
+            hip_lib.check(lib.dd_chain_init(ctypes.byref(sm), keys_ptr, ctypes.byref(ent["init_struct"]), hip_lib.stream_ptr(dev)),
+                          "dd_chain_init")
         # held rows in front of the first step: hold -- the known values; replace, init 'draw' -- level t_start at Philox time
         # t_start + 1 ('given': init_ligand_* already holds that level)
         if fixed is not None and (fixed["mode"] == "hold" or draw_level):
@@ -1272,7 +1394,7 @@ class DecompScorePosNet3D(nn.Module):
                          energy_drift_opt=None,
                          full_protein_pos=None, full_batch_protein=None,
                          noise=None, seed=None, keep_traj=True, use_graph=True, start_step=0, _drift_norm_batch=0,
-                         sample_keys=None, fixed=None, resample=None):
+                         sample_keys=None, fixed=None, resample=None, init=None):
         """Reverse diffusion (reference: models/decompdiff.py:552-703), same arguments and return
         keys.  Extra keyword-only knobs (all optional, reference call sites never pass them):
 
@@ -1313,6 +1435,23 @@ class DecompScorePosNet3D(nn.Module):
           ``t_traj``, the int64 times of the positions.  The schedule belongs to the call's range: with ``start_step`` / a
           shorter ``num_steps`` a split chain is NOT the unsplit one.  ``r = 1`` or ``j > num_steps``: bit for bit the call
           without ``resample``.  Wrong keys or types, ``j < 1``, ``r < 1``, no ``fixed``, ``noise=``: ValueError.
+        * ``init`` — draw the chain's FIRST state on the device (dd_chain_init) instead of taking it from ``init_ligand_*``, which must
+          then be ``None`` (ValueError otherwise; shapes come from ``batch_ligand`` / ``ligand_fc_bond_index`` /
+          ``ligand_decomp_batch``).  The draws use the chain's own Philox addressing -- ``seed`` and the flat row, or
+          ``sample_keys`` and the row of the sample's own enumeration -- on streams of their own (5 / 6 / 9), so with
+          ``sample_keys`` a sample's starting point is as independent of its batch as its chain: nothing of the sample depends
+          on the batching any more.  ``dict(mode="prior", centers=None, stds=None, atom_prior=None, bond_prior=None)``:
+          coordinates ``centre + e * std`` around the per-atom gather of ``centers`` / ``stds`` [n_prior,3] through
+          ``ligand_decomp_batch`` (default ``prior_centers`` / ``prior_stds``; arguments of their own because the reference's
+          subpocket / stat modes draw the first coordinates around other centres than the chain uses), classes from the
+          probability vectors ``atom_prior`` / ``bond_prior`` (default: the model's transition priors; uniform: the reference's
+          ``log_sample_categorical(zeros)``); needs ``start_step == 0``.  ``dict(mode="noised", pos, v, bond[, centers, stds,
+          atom_prior, bond_prior])`` -- partial diffusion: a KNOWN ligand in the caller's row order is noised by the forward
+          process to level ``num_timesteps - 1 - start_step``, the level the first step expects, and denoised from there; needs
+          ``prior_centers``.  Both exclude ``noise=``.  Composes with ``seed``, ``sample_keys``, ``fixed`` (the held rows are then
+          prepared as always, after the draw; ``fixed['init'] = 'given'`` keeps the drawn level at the held rows), ``resample``,
+          the drift terms, ``use_graph`` and every batch path; a call with ``num_steps=0`` returns the drawn state.  Bad modes,
+          keys, shapes, dtypes, classes or combinations raise ValueError before anything is launched.  ``None``: today's call.
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
@@ -1329,6 +1468,15 @@ class DecompScorePosNet3D(nn.Module):
             if start_step < 0 or num_steps + start_step > self.num_timesteps:
                 raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
             resample = _as_resample(resample, fixed, noise, self.num_timesteps, num_steps, start_step)
+        if init is not None:
+            dev = protein_pos.device
+            init = _as_init(init, batch_ligand, ligand_fc_bond_index, ligand_decomp_batch, prior_centers, prior_stds,
+                            (init_ligand_pos, init_ligand_v, init_ligand_fc_bond_type), noise, start_step, self.num_timesteps,
+                            self.num_classes, self.num_bond_classes, dev)
+            # placeholders of the right shapes: the launch of dd_chain_init overwrites every real row before anything reads it
+            init_ligand_pos = torch.zeros(batch_ligand.numel(), 3, device=dev)
+            init_ligand_v = torch.zeros(batch_ligand.numel(), dtype=torch.long, device=dev)
+            init_ligand_fc_bond_type = torch.zeros(int(ligand_fc_bond_index.shape[1]), dtype=torch.long, device=dev)
         if fixed is not None:
             fixed = _as_fixed(fixed, batch_ligand.numel(), ligand_fc_bond_index, init_ligand_fc_bond_type, self.num_classes,
                               self.num_bond_classes, noise, start_step, prior_centers, ligand_decomp_batch, ligand_atom_mask,
@@ -1348,13 +1496,13 @@ class DecompScorePosNet3D(nn.Module):
                      init_ligand_fc_bond_type=init_ligand_fc_bond_type, batch_ligand_bond=batch_ligand_bond,
                      full_protein_pos=full_protein_pos, full_batch_protein=full_batch_protein),
                 ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
-                start_step=start_step, sample_keys=sample_keys, fixed=fixed, resample=resample)
+                start_step=start_step, sample_keys=sample_keys, fixed=fixed, resample=resample, chain_init=init)
         chain = self._prepare_chain(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
                                     batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                                     ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode,
                                     energy_drift_opt, full_protein_pos, full_batch_protein, noise, seed, keep_traj,
                                     _drift_norm_batch, start_step, static=static, sample_keys=sample_keys, fixed=fixed,
-                                    resample=resample)
+                                    resample=resample, chain_init=init)
         if static is None and "static" in chain:
             self._static_memo_put(key_t, center_pos_mode, chain["static"])
         tr = self.__dict__.get("_trace")
@@ -1372,7 +1520,7 @@ class DecompScorePosNet3D(nn.Module):
                        batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
                        ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode, energy_drift_opt,
                        full_protein_pos, full_batch_protein, noise, seed, keep_traj, drift_norm_batch, start_step=0,
-                       static=None, cache_slot=0, sample_keys=None, fixed=None, resample=None):
+                       static=None, cache_slot=0, sample_keys=None, fixed=None, resample=None, chain_init=None):
         """Validate one dense batch, centre it, allocate its state / workspace and fill the ``dd_sampler`` struct.
         ``static``: what an earlier call with the same pocket / batch-vector tensors established (_static_memo_get)."""
         d = self._dense_inputs(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
@@ -1424,9 +1572,16 @@ class DecompScorePosNet3D(nn.Module):
             fx = dict(mode=fixed["mode"], init=fixed["init"], mask=fixed["mask"].to(torch.uint8), v0=fixed["v"], b0=fixed["bond"],
                       x0c=(fixed["pos"].view(B, NL, 3) - off_l).contiguous(),
                       cc=None if fixed["cc"] is None else (fixed["cc"].view(B, NL, 3) - off_l).contiguous())
+        ci = None
+        if chain_init is not None:                           # centred like the ligand: the same fp32 subtraction per row
+            off_l = offset[:, None, :]
+            noised = chain_init["mode"] == "noised"
+            ci = dict(chain_init, cc=(chain_init["cen"].view(B, NL, 3) - off_l).contiguous(), std=chain_init["std"],
+                      x0c=(chain_init["pos"].view(B, NL, 3) - off_l).contiguous() if noised else None,
+                      v0=chain_init["v"] if noised else None, b0=chain_init["bond"] if noised else None)
         s, bufs, ent = self._make_sampler(d, pw, num_steps if resample is None else resample["n_total"], t_start, noise, keep_traj,
                                           energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, drift_norm_batch,
-                                          cache_slot=cache_slot, sample_keys=sample_keys, fixed=fx, resample=resample)
+                                          cache_slot=cache_slot, sample_keys=sample_keys, fixed=fx, resample=resample, chain_init=ci)
         return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent, t_traj=None if resample is None else resample["t_traj"],
                     static=dict(layout=(B, NP, NL), offset=offset, protein_pos_centered=d["protein_pos_centered"],
                                 aux_onehot=d["aux_onehot"]))

@@ -598,6 +598,43 @@ int dd_resample_jump(const dd_sampler* s, const uint64_t* sample_keys /*DEVICE [
                      const dd_resample* resample /*HOST*/, void* stream);
 int dd_sampler_reset_resample(const dd_sampler* s, const dd_resample* resample /*HOST*/, void* stream);
 
+/* Chain init (EXTENSION): the chain's state in front of its first step, drawn on the device with the chain's own Philox
+ * addressing, so that a keyed sample's STARTING POINT is as independent of its batch as its chain.  One launch (after
+ * dd_sampler_reset, before dd_fixed_init and the first step) writes lig_pos (centred), lig_v and lig_bond of every REAL row;
+ * padding rows of a padded batch (atoms >= nl_real[b], bond rows with such an endpoint) keep what the host put there.
+ *   cc [B*NL,3] / std [B*NL,3]: per-atom centred centre (centre - offset of the sample) and std; they need not be the centres
+ *     and atom_std the steps use.  atom_log_prior [num_v] / bond_log_prior [5]: log prior of the classes, NULL = the prior row
+ *     of the chain's own table (tab_v / tab_b at 4 * T + c).
+ *   DD_INIT_PRIOR: the level above the first step, drawn at Philox time word T:
+ *       x = cc + (e * std)                 class = argmax_c gumbel(u_c) + log_prior_c     (uniform prior: the reference's
+ *                                                                                          log_sample_categorical(zeros))
+ *   DD_INIT_NOISED (partial diffusion): level l = t_start (the run state's) of the forward process of a KNOWN ligand
+ *     x0c [B*NL,3] (centred) / v0 [B*NL] / b0 [B*NL*(NL-1)], drawn at Philox time word l with tab [2][T] as in dd_fixed:
+ *       x = A[l] * (x0c - cc) + (S[l] * e) * std + cc
+ *       class = argmax_c gumbel(u_c) + log_add_exp(log_onehot(v0)_c + log_cumprod[l], log_1m_cumprod[l] + log_prior_c)
+ *     (decompdiff.py:436-455, transitions.py:146-150).  Every operation is rounded on its own; the argmax takes the first
+ *     largest class.
+ *   Draws: streams of their own -- 5 atom types, 6 bond types, 9 coordinates (class blocks as everywhere) -- with rows and keys
+ *     addressed exactly like a step's: dd_sampler.seed and the flat row, or sample_keys[b] and the row of the sample's own
+ *     enumeration.  No counter is shared with a step (1 / 2 / 7), a jump (3 / 4 / 8) or dd_fixed_init.
+ * All pointers are DEVICE pointers; `size` is the caller's sizeof(dd_init).
+ *   init == NULL, an unknown mode, a NULL cc / std, NOISED without x0c / v0 / b0 / tab or with t_start outside [0, T), injected
+ *   noise (s->u_v / u_b / eps): DD_ERR_BAD_ARG before any launch.  (New entry point, ABI unchanged.) */
+enum { DD_INIT_PRIOR = 1, DD_INIT_NOISED = 2 };
+typedef struct dd_init {
+  int32_t size;                  /* sizeof(dd_init) of the caller */
+  int32_t mode;                  /* DD_INIT_PRIOR / DD_INIT_NOISED */
+  const float* cc;               /* DEVICE [B*NL,3] */
+  const float* std;              /* DEVICE [B*NL,3] */
+  const float* atom_log_prior;   /* DEVICE [num_v] or NULL */
+  const float* bond_log_prior;   /* DEVICE [5] or NULL */
+  const float* x0c;              /* DEVICE [B*NL,3], NOISED only */
+  const int32_t* v0;             /* DEVICE [B*NL], NOISED only */
+  const int32_t* b0;             /* DEVICE [B*NL*(NL-1)], NOISED only */
+  const float* tab;              /* DEVICE [2][T], NOISED only */
+} dd_init;
+int dd_chain_init(const dd_sampler* s, const uint64_t* sample_keys /*DEVICE [B] or NULL*/, const dd_init* init /*HOST*/, void* stream);
+
 /* Drift guidance gradients at x_t (utils/guidance_funcs.py:24-78), analytic. grad [B,NL,3]. */
 int dd_drift_armsca(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float min_d, float max_d,
                     float* grad, int accumulate, void* stream);

@@ -63,8 +63,10 @@ int dd_queue_error(const dd_sampler* s, void* stream, int* code);
 /* Test aid: the production (Philox4x32-10) noise of one step exactly as the step kernels draw it -- kind 1: uniforms
  * [rows,8] of the atom-type stream (transitions.py:79 rand_like), 2: uniforms [rows,5] of the bond-type stream,
  * 7: normals [rows] of the coordinate stream (decompdiff.py:680 randn_like).  Kinds 3, 4 and 8: the same three for the streams
- * of a resampling jump (dd_resample_jump).  `step` is Philox counter word 2: the time t, or t + 65536 * epoch of a resampled
- * chain.  Bits 8-15 of kind, kinds 1 and 3 only: the atom class count (0 or 8, 13, 23), e.g. 3 | (13 << 8) -> [rows,13]. */
+ * of a resampling jump (dd_resample_jump).  Kinds 5, 6 and 9: the same three for the streams of the chain init (dd_chain_init):
+ * 5 atom classes, 6 the 5 bond classes, 9 normals.  `step` is Philox counter word 2: the time t, t + 65536 * epoch of a resampled
+ * chain, or the level a chain init draws (T, or t_start of a noised init).  Bits 8-15 of kind, kinds 1, 3 and 5 only: the atom
+ * class count (0 or 8, 13, 23), e.g. 3 | (13 << 8) -> [rows,13]. */
 int dd_debug_philox(uint64_t seed, int step, long rows, int kind, float* out, void* stream);
 
 /* Debug/test access to intermediate buffers of the last dd_forward (pointers into workspace). */
