@@ -12,6 +12,7 @@ results.  Nothing here computes the network on the CPU — CPU tensors raise.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 import time
 from typing import Dict, Optional
@@ -201,12 +202,6 @@ def _as_fixed(fixed, n_ligand, fc_index, bond_type, num_classes, num_bond_classe
                 v=v_c.to(device=dev, dtype=torch.int32), bond=bond_c.to(device=dev, dtype=torch.int32), cc=cc)
 
 
-def _fixed_rows(fx, rows_l, rows_b):
-    """The rows ``rows_l`` (atoms) / ``rows_b`` (bonds) of a validated ``fixed`` (device index tensors): a group's or a sample's share."""
-    return dict(mode=fx["mode"], init=fx["init"], mask=fx["mask"][rows_l], pos=fx["pos"][rows_l], v=fx["v"][rows_l],
-                bond=fx["bond"][rows_b], cc=None if fx["cc"] is None else fx["cc"][rows_l])
-
-
 INIT_MODES = ("prior", "noised")
 
 
@@ -279,14 +274,6 @@ def _as_init(init, batch_ligand, fc_index, ligand_decomp_batch, prior_centers, p
     return out
 
 
-def _init_rows(ini, rows_l, rows_b):
-    """The rows ``rows_l`` (atoms) / ``rows_b`` (bonds) of a validated ``init`` (device index tensors): a group's share."""
-    out = dict(ini, cen=ini["cen"][rows_l], std=ini["std"][rows_l])
-    if ini["mode"] == "noised":
-        out.update(pos=ini["pos"][rows_l], v=ini["v"][rows_l], bond=ini["bond"][rows_b])
-    return out
-
-
 def resample_schedule(t_hi, t_lo, j, r):
     """The resampling ("jump-back") schedule of ``sample_diffusion(resample=dict(jump_length=j, n_resample=r))`` over the reverse
     steps t_hi .. t_lo: a list of ``("step", t)`` and ``("jump", l, l + j)`` in execution order.  Jump points are anchored at the
@@ -338,6 +325,159 @@ def _as_resample(resample, fixed, noise, num_timesteps, num_steps, start_step):
     if n:
         runs.append((n, False))
     return dict(j=j, r=r, runs=runs, t_traj=torch.tensor(times, dtype=torch.int64), n_total=len(times))
+
+
+@dataclasses.dataclass(frozen=True)
+class _Call:
+    """What one sample_diffusion call asks for apart from its batch: built once, after validation, and handed to every batch path
+    (dense, padded, equal-size groups).  ``drift`` is energy_drift_opt; ``sample_keys`` / ``fixed`` / ``resample`` / ``chain_init``
+    are what `_as_sample_keys` / `_as_fixed` / `_as_resample` / `_as_init` returned, in the CALLER's sample and row order
+    (`_chain_rows` lays them into a chain)."""
+    num_timesteps: int
+    num_steps: int
+    start_step: int = 0
+    center_pos_mode: Optional[str] = "protein"
+    drift: Optional[list] = None
+    noise: Optional[dict] = None
+    seed: int = 0
+    keep_traj: bool = True
+    use_graph: bool = True
+    drift_norm_batch: int = 0
+    sample_keys: Optional[torch.Tensor] = None
+    fixed: Optional[dict] = None
+    resample: Optional[dict] = None
+    chain_init: Optional[dict] = None
+
+    def __post_init__(self):
+        if self.start_step < 0 or self.num_steps + self.start_step > self.num_timesteps:
+            raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
+
+    @property
+    def t_start(self):                  # time_seq = reversed(range(T - num_steps, T)), decompdiff.py:575
+        return self.num_timesteps - 1 - int(self.start_step)
+
+    @property
+    def n_pos(self):                    # trajectory positions: the reverse steps the chain runs
+        return self.num_steps if self.resample is None else self.resample["n_total"]
+
+
+class _Placement:
+    """Where the caller's flat ligand-atom rows and bond rows go in ONE chain's dense [B*NL] / [B*Eb] layout.  Taking: a group's
+    chain owns the rows ``rows_l`` / ``rows_b`` (host index tensors) of the call, every other chain owns them all.  Putting: a
+    padded batch scatters its rows to ``put_l`` / ``put_b`` (`BatchLayout.padded_rows()`, of ``n_l`` / ``n_b`` dense rows) over a
+    fill value; every other chain holds them as they are (a reshape: no copy, no launch).  ``sample``: the chain's sample slot of
+    each of its atom rows; ``ids``: the call's samples in the chain's order (None: all); ``n_bonds``: the chain's real bonds."""
+
+    def __init__(self, sample, n_bonds, rows_l=None, rows_b=None, ids=None, put_l=None, put_b=None, n_l=0, n_b=0, dev=None):
+        self.sample, self.n_bonds, self.ids = sample, int(n_bonds), ids
+        self.rows_l, self.rows_b = rows_l, rows_b
+        self.d_l, self.d_b = (None, None) if rows_l is None else (rows_l.to(dev), rows_b.to(dev))     # (the same, on the chain's device)
+        self.put_l, self.put_b, self.n_l, self.n_b = put_l, put_b, n_l, n_b
+
+    def take(self, t, bonds=False, dim=0):
+        rows, d_rows = (self.rows_b, self.d_b) if bonds else (self.rows_l, self.d_l)
+        if rows is None:
+            return t
+        rows = d_rows if t.device == d_rows.device else rows
+        return t[rows] if dim == 0 else t[:, rows]
+
+    def put(self, t, bonds=False, fill=0, dim=0):
+        return self._scatter(t, *((self.put_b, self.n_b) if bonds else (self.put_l, self.n_l)), fill, dim)
+
+    @staticmethod
+    def _scatter(t, rows, n, fill, dim):
+        if rows is None:
+            return t
+        shape = tuple(t.shape[:dim]) + (n,) + tuple(t.shape[dim + 1:])
+        out = torch.full(shape, fill, dtype=t.dtype, device=t.device) if fill else torch.zeros(shape, dtype=t.dtype, device=t.device)
+        return out.index_copy_(dim, rows, t)
+
+    def atoms(self, t, fill=0, dim=0):
+        return self.put(self.take(t, False, dim), False, fill, dim)
+
+    def bonds(self, t, fill=0, dim=0):
+        return self.put(self.take(t, True, dim), True, fill, dim)
+
+
+def _chain_rows(call, place, offset, prior_stds, ligand_decomp_batch, ligand_decomp_index, num_classes, full_protein=(None, None)):
+    """The per-row inputs of ONE chain in its dense layout, as `_make_sampler` consumes them.  From the chain's own batch tensors
+    (``prior_stds`` ... ``full_protein`` = (full_protein_pos, full_batch_protein); put only): ``atom_std`` [B*NL,3], ``decomp`` int32
+    [B*NL] or None, ``fpp`` [B,NF,3] (only with a clash drift, else None).  From the call record (taken, then put): ``keys`` int64 [B]
+    or None; ``noise`` dict(u_v, u_b, eps) or None; ``fx`` -- the fixed atoms, dict(mode, init, mask uint8 [B*NL], v0 int32 [B*NL], b0
+    int32 [B*Eb], x0c [B*NL,3] centred, cc [B*NL,3] centred or None) -- or None; ``ci`` -- what dd_chain_init draws the first level
+    from, dict(mode, cc [B*NL,3] centred, std [B*NL,3], atom_lp / bond_lp or None and, mode "noised", x0c centred, v0, b0) -- or None.
+    Centring is the ligand's own: the fp32 subtraction ``x - offset[row's sample]``.  Padding rows of a padded chain: 0; 0.5 in u_v /
+    u_b; -2 (neither arm nor scaffold) in decomp; 1e6 in fpp (exp(-|p - y|^2 / sigma) underflows to exactly 0: nothing added to any sum)."""
+    dev, B = offset.device, int(offset.shape[0])
+    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
+    out = dict(atom_std=place.put(f32(prior_stds)[ligand_decomp_batch.to(dev)]).contiguous(), decomp=None, fpp=None, noise=None,
+               fx=None, ci=None, keys=call.sample_keys if call.sample_keys is None or place.ids is None else call.sample_keys[place.ids])
+    if ligand_decomp_index is not None:
+        out["decomp"] = place.put(ligand_decomp_index.to(device=dev, dtype=torch.int32), fill=-2).contiguous()
+    if call.drift is not None and any(dr["type"] == "clash" for dr in call.drift):
+        fpos, fbatch = full_protein
+        if fpos is None or fbatch is None:
+            raise ValueError("clash drift needs full_protein_pos / full_batch_protein")
+        if place.put_l is None:
+            nf = fpos.shape[0] // B
+            if fpos.shape[0] % B or not torch.equal(fbatch.to(dev), torch.arange(B, device=dev).repeat_interleave(nf)):
+                raise NotImplementedError("full_protein_pos must hold the same number of atoms per sample")
+            out["fpp"] = f32(fpos).contiguous().view(B, nf, 3)
+        else:
+            n_f = BL.sample_counts(fbatch, B)
+            out["fpp"] = _Placement._scatter(f32(fpos), BL.block_rows(n_f, max(n_f)).to(dev), B * max(n_f), 1.0e6, 0).view(B, max(n_f), 3)
+    if call.noise is not None:
+        n_l, out["noise"] = int(place.sample.numel()), {}
+        for k, bonds, fill, shp in (("u_v", False, 0.5, (call.num_steps, n_l, num_classes)), ("u_b", True, 0.5, (call.num_steps, place.n_bonds, 5)),
+                                    ("eps", False, 0, (call.num_steps, n_l, 3))):
+            t = place.take(call.noise[k], bonds, 1)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"noise['{k}'] must have shape {shp}, got {tuple(t.shape)}")
+            out["noise"][k] = place.put(f32(t), bonds, fill, 1)
+    fixed, ini = call.fixed, call.chain_init
+    if fixed is not None or ini is not None:
+        off_l = offset[place.sample.to(dev)]
+        centred = lambda x: place.put(place.take(x) - off_l).contiguous()
+    if fixed is not None:                                  # (padding rows: not held)
+        out["fx"] = dict(mode=fixed["mode"], init=fixed["init"], mask=place.put(place.take(fixed["mask"]).to(torch.uint8)),
+                         v0=place.atoms(fixed["v"]), b0=place.bonds(fixed["bond"]), x0c=centred(fixed["pos"]),
+                         cc=None if fixed["cc"] is None else centred(fixed["cc"]))
+    if ini is not None:                                    # (padding rows are never drawn)
+        noised = ini["mode"] == "noised"
+        out["ci"] = dict(ini, cc=centred(ini["cen"]), std=place.atoms(ini["std"]), x0c=centred(ini["pos"]) if noised else None,
+                         v0=place.atoms(ini["v"]) if noised else None, b0=place.bonds(ini["bond"]) if noised else None)
+    return out
+
+
+def _drift_fields(drift, has_decomp):
+    """``energy_drift_opt`` as the drift fields of dd_sampler (a term that is not listed: zeros)."""
+    f, seen = dict(drift_armsca=0, armsca_min_d=0.0, armsca_max_d=0.0, armsca_scale=0, drift_clash=0, clash_sigma=0.0, clash_gamma=0.0,
+                   clash_scale=0, drift_repul=0, repul_max_d=0.0, repul_scale=0), []
+    for dr in drift or []:
+        if dr["type"] in seen:                             # one buffer per term: a repeated entry would silently replace the first
+            raise NotImplementedError(f"energy_drift_opt lists '{dr['type']}' twice")
+        seen.append(dr["type"])
+        scale = int(bool(dr.get("scale", False)))
+        if dr["type"] == "armsca_prox":
+            f.update(drift_armsca=1, armsca_min_d=float(dr["min_d"]), armsca_max_d=float(dr["max_d"]), armsca_scale=scale)
+        elif dr["type"] == "clash":
+            f.update(drift_clash=1, clash_sigma=float(dr["sigma"]), clash_gamma=float(dr["gamma"]), clash_scale=scale)
+        elif dr["type"] == "arms_repul":
+            # EXTENSION (SURVEY.md 8f-3): the reference defines the energy (utils/guidance_funcs.py:81-118) but its
+            # sample_diffusion has no branch for it (decompdiff.py:643-675 raises ValueError); wired like armsca_prox
+            # (:648-659): gradient at x_t, optional `scale`.  Defaults = the function's own (max_d 1.9, mode 'min').
+            mode = dr.get("mode", "min")
+            if mode not in ("min", "all"):
+                raise ValueError(mode)                     # (guidance_funcs.py:90)
+            if not has_decomp:
+                raise ValueError("arms_repul drift needs ligand_decomp_index")
+            f.update(drift_repul=1 if mode == "min" else 2, repul_max_d=float(dr.get("max_d", 1.9)), repul_scale=scale)
+        elif dr["type"] in ("center_prox", "mmff_min"):
+            raise NotImplementedError(f"drift '{dr['type']}' is outside the shipped sampling path "
+                                      "(center_prox raises in the reference; mmff_min is RDKit/CPU)")
+        else:
+            raise ValueError(dr["type"])
+    return f
 
 
 class DecompScorePosNet3D(nn.Module):
@@ -668,8 +808,7 @@ class DecompScorePosNet3D(nn.Module):
                                          kw["full_batch_protein"] if has_full else None, kw["batch_ligand_bond"],
                                          kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"].numel(), need_protein=False)
 
-    def _sample_heterogeneous(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                              use_graph, start_step=0, sample_keys=None, fixed=None, resample=None, chain_init=None):
+    def _sample_heterogeneous(self, kw, call):
         """Samples with different atom counts in one batch (PyG collate, utils/data.py:389-446).  Default: ONE launch
         sequence over the batch padded to its largest pocket / ligand with per-sample real counts (`_sample_padded`).
         Fallbacks to equal-size groups (`_sample_ragged`): DD_RAGGED_MODE=groups, or `batch_layout.fits_padded` says no."""
@@ -677,20 +816,16 @@ class DecompScorePosNet3D(nn.Module):
         if os.environ.get("DD_RAGGED_MODE", "padded") != "groups":
             layout = self._sampling_layout(kw)
             if BL.fits_padded(layout, self.config.knn):
-                return self._sample_padded(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed,
-                                           keep_traj, use_graph, start_step, layout.n_p, layout.n_l, sample_keys=sample_keys,
-                                           fixed=fixed, resample=resample, chain_init=chain_init)
-        return self._sample_ragged(kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                                   use_graph, start_step=start_step, layout=layout, sample_keys=sample_keys, fixed=fixed,
-                                   resample=resample, chain_init=chain_init)
+                return self._sample_padded(kw, call, layout)
+        return self._sample_ragged(kw, call, layout=layout)
 
     def _padded_inputs(self, protein_pos, protein_v, bp, ligand_pos, ligand_v, aux, bl, fc_index, bond_type, batch_ligand_bond,
                        n_p, n_l, center_pos_mode):
         """A heterogeneous flat batch validated by `BatchLayout.from_batch` (n_p / n_l: its atoms per sample) as the padded dense
         layout of dd_sampler.np_real / nl_real / bl_prefix (`BatchLayout.padded_rows`); padding rows are zeros.  Shared by the
         padded sampler and the ragged forward.  Returns the dense dict `d` of _make_sampler (positions centred by
-        `center_pos_mode`), the per-sample offset, the masks and the row maps flat row -> padded row (rows_* on the host, d_* on
-        the device)."""
+        `center_pos_mode`), the per-sample offset, the masks, the row maps flat row -> padded row (rows_* on the host, d_* on
+        the device) and the `_Placement` made of them."""
         dev = protein_pos.device
         hip_lib.require_gpu(protein_pos, "protein_pos")
         hip_lib.require_gpu(ligand_pos, "init_ligand_pos")
@@ -725,131 +860,69 @@ class DecompScorePosNet3D(nn.Module):
         prefix = np.concatenate([[0], np.cumsum(n_b)]).astype(np.int32)
         masks = {"np_real": torch.tensor(n_p, dtype=torch.int32), "nl_real": torch.tensor(n_l, dtype=torch.int32),
                  "bl_prefix": torch.from_numpy(prefix)}
-        return dict(d=d, offset=offset, masks=masks, n_b=n_b, rows_l=rows_l, rows_b=rows_b, d_l=d_l, d_b=d_b)
+        return dict(d=d, offset=offset, masks=masks, rows_l=rows_l, rows_b=rows_b, d_l=d_l, d_b=d_b,
+                    place=_Placement(bl, sum(n_b), put_l=d_l, put_b=d_b, n_l=B * NL, n_b=B * Eb))
 
-    def _sample_padded(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, start_step, n_p, n_l, sample_keys=None, fixed=None, resample=None, chain_init=None):
+    def _sample_padded(self, kw, call, layout):
         """Heterogeneous batch as one padded dense batch: every sample's atoms are the first rows of its [NPmax] / [NLmax]
         blocks, the kernels read the real counts from dd_sampler.np_real / nl_real (padding atoms are no kNN candidates,
         own no softmax segment and are no members of one) and the results are gathered back into the caller's flat order.
         Exact: a sample's chain does not depend on its batch, with the one batch-wide quantity of the reference -- the
         armsca loss is averaged over the whole batch (guidance_funcs.py:78) -- unchanged because the batch is whole."""
-        _check_ligand_atom_mask(ligand_atom_mask, kw["batch_ligand"].numel())
+        _check_ligand_atom_mask(kw.get("ligand_atom_mask"), kw["batch_ligand"].numel())
         pad = self._padded_inputs(kw["protein_pos"], kw["protein_v"], kw["batch_protein"], kw["init_ligand_pos"], kw["init_ligand_v"],
                                   kw["ligand_v_aux"], kw["batch_ligand"], kw["ligand_fc_bond_index"], kw["init_ligand_fc_bond_type"],
-                                  kw["batch_ligand_bond"], n_p, n_l, center_pos_mode)
-        d, offset, masks, n_b = pad["d"], pad["offset"], pad["masks"], pad["n_b"]
-        rows_l, rows_b, d_l, d_b = pad["rows_l"], pad["rows_b"], pad["d_l"], pad["d_b"]
-        B, NL = d["B"], d["NL"]
-        Eb = NL * (NL - 1)
-        dev = d["protein_pos"].device
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
-        zeros = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
-        has_full = kw["full_protein_pos"] is not None and kw["full_batch_protein"] is not None
-        atom_std = zeros(B * NL, 3).index_copy_(0, d_l, f32(kw["prior_stds"])[kw["ligand_decomp_batch"].to(dev)])
-        decomp = None
-        if kw["ligand_decomp_index"] is not None:                          # -2: neither arm nor scaffold (padding)
-            decomp = torch.full((B * NL,), -2, dtype=torch.int32, device=dev).index_copy_(
-                0, d_l, kw["ligand_decomp_index"].to(device=dev, dtype=torch.int32))
-        fpp = None
-        if energy_drift_opt is not None and any(dr["type"] == "clash" for dr in energy_drift_opt):
-            if not has_full:
-                raise ValueError("clash drift needs full_protein_pos / full_batch_protein")
-            n_f = BL.sample_counts(kw["full_batch_protein"], B)
-            NF = max(n_f)
-            rows_f = BL.block_rows(n_f, NF).to(dev)
-            # padding far away: exp(-|p - y|^2 / sigma) underflows to exactly 0, so it adds nothing to any sum
-            fpp = torch.full((B * NF, 3), 1.0e6, device=dev).index_copy_(0, rows_f, f32(kw["full_protein_pos"])).view(B, NF, 3)
-        pad_noise = None
-        if noise is not None:
-            n_lig, n_bond = sum(n_l), sum(n_b)
-            for k, shp in (("u_v", (num_steps, n_lig, self.num_classes)), ("u_b", (num_steps, n_bond, 5)), ("eps", (num_steps, n_lig, 3))):
-                if tuple(noise[k].shape) != shp:
-                    raise ValueError(f"noise['{k}'] must have shape {shp}, got {tuple(noise[k].shape)}")
-            pad_noise = {
-                "u_v": torch.full((num_steps, B * NL, self.num_classes), 0.5, device=dev).index_copy_(1, d_l, f32(noise["u_v"])),
-                "u_b": torch.full((num_steps, B * Eb, 5), 0.5, device=dev).index_copy_(1, d_b, f32(noise["u_b"])),
-                "eps": zeros(num_steps, B * NL, 3).index_copy_(1, d_l, f32(noise["eps"]))}
-        if num_steps + start_step > self.num_timesteps or start_step < 0:
-            raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
-        pw = self._packed_weights()
-        fx = None
-        if fixed is not None:                                              # scattered like the inputs; padding rows: not held
-            off_l = offset[kw["batch_ligand"].to(dev)]
-            fx = dict(mode=fixed["mode"], init=fixed["init"],
-                      mask=zeros(B * NL, dtype=torch.uint8).index_copy_(0, d_l, fixed["mask"].to(torch.uint8)),
-                      v0=zeros(B * NL, dtype=torch.int32).index_copy_(0, d_l, fixed["v"]),
-                      b0=zeros(B * Eb, dtype=torch.int32).index_copy_(0, d_b, fixed["bond"]),
-                      x0c=zeros(B * NL, 3).index_copy_(0, d_l, fixed["pos"] - off_l),
-                      cc=None if fixed["cc"] is None else zeros(B * NL, 3).index_copy_(0, d_l, fixed["cc"] - off_l))
-        ci = None
-        if chain_init is not None:                                         # scattered like the inputs; padding rows are never drawn
-            off_l = offset[kw["batch_ligand"].to(dev)]
-            noised = chain_init["mode"] == "noised"
-            ci = dict(chain_init, cc=zeros(B * NL, 3).index_copy_(0, d_l, chain_init["cen"] - off_l),
-                      std=zeros(B * NL, 3).index_copy_(0, d_l, chain_init["std"]),
-                      x0c=zeros(B * NL, 3).index_copy_(0, d_l, chain_init["pos"] - off_l) if noised else None,
-                      v0=zeros(B * NL, dtype=torch.int32).index_copy_(0, d_l, chain_init["v"]) if noised else None,
-                      b0=zeros(B * Eb, dtype=torch.int32).index_copy_(0, d_b, chain_init["bond"]) if noised else None)
-        n_pos = num_steps if resample is None else resample["n_total"]
-        s, bufs, ent = self._make_sampler(d, pw, n_pos, self.num_timesteps - 1 - int(start_step), pad_noise, keep_traj,
-                                          energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, 0, masks=masks,
-                                          sample_keys=sample_keys, fixed=fx, resample=resample, chain_init=ci)   # (the padded batch keeps the caller's sample order)
-        chain = dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent, t_traj=None if resample is None else resample["t_traj"])
-        self._run_chains([chain], n_pos, use_graph)
-        out = self._collect_chain(chain, n_pos, keep_traj, rows_atoms=rows_l, rows_bonds=rows_b)
+                                  kw["batch_ligand_bond"], layout.n_p, layout.n_l, call.center_pos_mode)
+        d, offset = pad["d"], pad["offset"]
+        rows = _chain_rows(call, pad["place"], offset, kw["prior_stds"], kw["ligand_decomp_batch"], kw["ligand_decomp_index"],
+                           self.num_classes, (kw["full_protein_pos"], kw["full_batch_protein"]))
+        s, bufs, ent = self._make_sampler(d, self._packed_weights(), call, rows, offset.contiguous(), masks=pad["masks"])   # (the padded batch keeps the caller's sample order)
+        chain = dict(s=s, bufs=bufs, offset=offset, B=d["B"], NL=d["NL"], dev=d["protein_pos"].device, ent=ent,
+                     t_traj=None if call.resample is None else call.resample["t_traj"])
+        self._run_chains([chain], call.n_pos, call.use_graph)
+        out = self._collect_chain(chain, call.n_pos, call.keep_traj, rows_atoms=pad["rows_l"], rows_bonds=pad["rows_b"])
         self._last = (s, bufs)
         return out
 
-    def _sample_ragged(self, kw, ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj,
-                       use_graph, concurrent=None, start_step=0, split=1, layout=None, sample_keys=None, fixed=None, resample=None,
-                       chain_init=None):
+    def _sample_ragged(self, kw, call, concurrent=None, split=1, layout=None):
         """One dense chain per group of samples of equal size (`BatchLayout.size_groups`).  ``split`` > 1 additionally cuts
         every group into that many sub-batches (measurement aid, tools/split_bench.py: two concurrent half-batches were
         measured slower than one chain).  ``layout``: what `_sampling_layout(kw)` gave the caller.
-        ``sample_keys`` (int64 [B], the caller's sample order): every group gets its members' keys; without keys group ``gi``
-        draws with ``seed + 7919 * gi``."""
-        _check_ligand_atom_mask(ligand_atom_mask, kw["batch_ligand"].numel())
+        With ``call.sample_keys`` (int64 [B], the caller's sample order) every group gets its members' keys; without keys group
+        ``gi`` draws with ``call.seed + 7919 * gi``."""
+        _check_ligand_atom_mask(kw.get("ligand_atom_mask"), kw["batch_ligand"].numel())
         dev = kw["protein_pos"].device
         layout = layout or self._sampling_layout(kw)
         B, has_full = layout.B, max(layout.n_f) > 0
         n_lig, n_bond = sum(layout.n_l), sum(layout.n_b)
+        keep_traj, n_pos = call.keep_traj, call.n_pos
         out = {"pos": torch.empty(n_lig, 3, device=dev), "v": torch.empty(n_lig, dtype=torch.long, device=dev),
                "bond": torch.empty(n_bond, dtype=torch.long, device=dev)}
         traj: Dict[str, Optional[torch.Tensor]] = {k: None for k in ("pos_traj", "v_traj", "bond_traj", "v0_traj", "vt_traj", "bt_traj")}
         prepared = []
         for gi, g in enumerate(layout.size_groups([(b * split) // B for b in range(B)] if split > 1 else ())):
             G, r_l, r_b = len(g.ids), g.rows_l, g.rows_b
-            d_p, d_l, d_pr, d_b = g.rows_p.to(dev), r_l.to(dev), g.rows_pr.to(dev), r_b.to(dev)
             b_p, b_l, fc = self._expected_layout(G, g.n_p, g.n_l, dev)          # (b_l: sample slot of each ligand row)
+            place = _Placement(b_l, len(r_b), rows_l=r_l, rows_b=r_b, ids=g.ids, dev=dev)
+            d_p, d_l, d_pr, d_b = g.rows_p.to(dev), place.d_l, g.rows_pr.to(dev), place.d_b
             old_pr0 = torch.tensor(g.first_pr, device=dev)
-            sub_noise = None
-            if noise is not None:
-                sub_noise = {"u_v": noise["u_v"][:, r_l], "u_b": noise["u_b"][:, r_b], "eps": noise["eps"][:, r_l]}
             chain = self._prepare_chain(
                 kw["protein_pos"][d_p], kw["protein_v"][d_p], b_p, kw["init_ligand_pos"][d_l], kw["init_ligand_v"][d_l],
                 kw["ligand_v_aux"][d_l], b_l, kw["prior_stds"][d_pr],
                 kw["ligand_decomp_batch"].to(dev)[d_l] - old_pr0[b_l] + b_l * g.n_pr,
                 kw["ligand_decomp_index"][d_l] if kw["ligand_decomp_index"] is not None else None, None, fc,
-                kw["init_ligand_fc_bond_type"][d_b], num_steps, center_pos_mode, energy_drift_opt,
-                kw["full_protein_pos"].to(dev)[g.rows_f.to(dev)] if has_full else None,
-                BL.batch_vector(G, g.n_f, dev) if has_full else None, sub_noise,
-                seed + 7919 * gi, keep_traj, B, start_step,        # (the armsca loss is averaged over the whole batch)
+                kw["init_ligand_fc_bond_type"][d_b], kw["full_protein_pos"].to(dev)[g.rows_f.to(dev)] if has_full else None,
+                BL.batch_vector(G, g.n_f, dev) if has_full else None,
+                dataclasses.replace(call, seed=call.seed + 7919 * gi, drift_norm_batch=B),     # (the armsca loss is averaged over the whole batch)
                 cache_slot=(g.ids[0] * split) // B,                # (sub-batches of one shape: own cached buffers each)
-                sample_keys=None if sample_keys is None else sample_keys[g.ids],
-                fixed=None if fixed is None else _fixed_rows(fixed, d_l, d_b), resample=resample,
-                chain_init=None if chain_init is None else _init_rows(chain_init, d_l, d_b))
+                place=place)                                       # (fixed / chain_init / noise / sample_keys: the group's share)
             prepared.append((chain, d_l, d_b, r_l, r_b))
         if concurrent is None:
             # measured on MI355X (tools/ragged_bench.py, DESIGN.md): with the runtime's default 4 hardware queues the
             # groups' graphs get in each other's way (0.7x); with GPU_MAX_HW_QUEUES=3 running them together gains 1.4x
             concurrent = os.environ.get("DD_RAGGED_CONCURRENT", "0") == "1"
-        n_pos = num_steps if resample is None else resample["n_total"]
-        if concurrent:
-            self._run_chains([p[0] for p in prepared], n_pos, use_graph)
-        else:
-            for p in prepared:
-                self._run_chains([p[0]], n_pos, use_graph)
+        for cs in [[p[0] for p in prepared]] if concurrent else [[p[0]] for p in prepared]:
+            self._run_chains(cs, n_pos, call.use_graph)
         for chain, d_l, d_b, r_l, r_b in prepared:
             r = self._collect_chain(chain, n_pos, keep_traj)
             out["pos"][d_l], out["v"][d_l], out["bond"][d_b] = r["pos"], r["v"], r["bond"]
@@ -864,8 +937,8 @@ class DecompScorePosNet3D(nn.Module):
             out[k] = list(traj[k].unbind(0)) if traj[k] is not None else []
         if all(v is not None for v in traj.values()):
             out["_traj_stacked"] = dict(traj)
-        if resample is not None:
-            out["t_traj"] = resample["t_traj"].clone()
+        if call.resample is not None:
+            out["t_traj"] = call.resample["t_traj"].clone()
         return out
 
     # ------------------------------------------------------------------------------------------
@@ -994,97 +1067,120 @@ class DecompScorePosNet3D(nn.Module):
             memo[key] = BL.dense_vectors(B, NP, NL, dev)
         return memo[key]
 
-    def _make_sampler(self, d, pw, n_steps, t_start, noise, keep_traj, drift, atom_std, offset, decomp_index,
-                      full_protein_pos, seed, drift_norm_batch=0, masks=None, cache_slot=0, sample_keys=None, fixed=None,
-                      resample=None, chain_init=None):
-        """``n_steps``: trajectory positions of the chain (reverse steps; with ``resample`` -- the validated dict of
-        `_as_resample` or None -- the schedule's n_total).
-        ``sample_keys``: int64 [B] (host or device), the per-sample noise keys of this chain in the order of its samples, or None
-        (the chain draws with ``seed``).  ``fixed``: the chain's fixed atoms in its dense layout -- dict(mode, init, mask uint8
-        [B*NL], v0 int32 [B*NL], b0 int32 [B*Eb], x0c [B*NL,3] centred, cc [B*NL,3] centred or None) -- or None.
-        ``chain_init``: what the chain's first level is drawn from (dd_chain_init), in the chain's dense layout -- dict(mode, cc
-        [B*NL,3] centred, std [B*NL,3], atom_lp / bond_lp log priors or None, and, mode "noised", x0c [B*NL,3] centred, v0 int32
-        [B*NL], b0 int32 [B*Eb]) -- or None: d["ligand_pos_centered"] / d["ligand_v"] / d["bond"] are that level."""
+    def _make_sampler(self, d, pw, call, rows, offset, masks=None, cache_slot=0):
+        """The prepared chain (dd_sampler, its buffers, its cache entry) of one dense-layout batch ``d`` for the call record ``call``;
+        ``rows``: the chain's per-row inputs (`_chain_rows`); ``masks``: the real counts of a padded batch."""
+        n_pos = call.n_pos
+        cacheable = call.noise is None and n_pos > 0 and self._CACHE_MAX > 0 and os.environ.get("DD_CHAIN_CACHE", "1") != "0"
+        key, ent = self._chain_entry(d, pw, n_pos, call.keep_traj, cacheable, rows["decomp"] is not None,
+                                     0 if rows["fpp"] is None else int(rows["fpp"].shape[1]), masks is not None, cache_slot)
+        upload = self._upload_pocket(ent, d, pw, rows["fpp"], cacheable)
+        self._upload_state(ent, d, rows["atom_std"], offset, rows["decomp"], masks)
+        self._bind_call(ent, d, pw, rows["keys"], rows["fx"], call.resample, rows["ci"])
+        use_l0 = self._fill_sampler(ent, d, pw, call.t_start, call.seed, rows["noise"],
+                                    _drift_fields(call.drift, rows["decomp"] is not None), call.drift_norm_batch, upload)
+        self._start_chain(ent, n_pos, rows["fx"], rows["ci"])
+        # everything that shapes the captured step graph besides the (cached) pointers
+        sm = ent["s"]
+        ent["sig"] = (sm.drift_armsca, sm.armsca_min_d, sm.armsca_max_d, sm.armsca_scale, sm.drift_clash, sm.clash_sigma,
+                      sm.clash_gamma, sm.clash_scale, sm.drift_repul, sm.repul_max_d, sm.repul_scale, sm.drift_norm_batch,
+                      int(hip_lib.load().dd_debug_options_epoch()), use_l0, ent["keyed"], rows["fx"] is not None, ent["fixed"],
+                      call.resample is not None)
+        if cacheable:
+            DecompScorePosNet3D._chain_cache[key] = ent    # (re-inserted: most recently used last)
+            self._evict_chain_cache(self._CACHE_MAX)
+        return sm, ent["bufs"], ent
+
+    def _chain_entry(self, d, pw, n_steps, keep_traj, cacheable, has_decomp=False, NF=0, masked=False, cache_slot=0):
+        """(cache key, entry) of a chain of this shape: taken out of the cache (``cacheable``) or allocated, with the dd_sampler
+        fields that never change.  ``n_steps``: trajectory positions of the chain."""
         lib = hip_lib.load()
         dev = d["protein_pos"].device
         B, NP, NL = d["B"], d["NP"], d["NL"]
         N = NP + NL
         K = min(int(self.config.knn), N - 1)
         Eb = NL * (NL - 1)
-        NF = 0 if full_protein_pos is None else int(full_protein_pos.shape[1])
         arena, offs = pw["arena"], pw["offsets"]
-        cacheable = noise is None and n_steps > 0 and self._CACHE_MAX > 0 and os.environ.get("DD_CHAIN_CACHE", "1") != "0"
         cap = n_steps
         if cacheable and keep_traj:
             # (traj_capacity_hint: a caller that knows the chain length of its later calls -- bench.py's warm-up calls are shorter than its
             #  timed call -- sizes the cached buffers for it, so that call meets the same chain entry and step graph)
             hint = int(getattr(self, "traj_capacity_hint", 0) or 0)
             cap = max(32, 1 << (max(int(n_steps), hint) - 1).bit_length())   # trajectory capacity: 5 and 20 steps share buffers
-        key = (str(dev), B, NP, NL, K, NF, cap if keep_traj else 0, bool(keep_traj), decomp_index is not None, arena.data_ptr(),
-               masks is not None, int(cache_slot), self.bond_net_type, self.x2h_out_fc, int(self.config.num_blocks))     # cache_slot: chains of ONE call that share a shape need separate buffers
-        cache = DecompScorePosNet3D._chain_cache
-        ent = cache.pop(key, None) if cacheable else None
-        if ent is None:
-            z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
-            bufs: Dict[str, Optional[torch.Tensor]] = {}
-            # static inputs (own buffers: a cached graph points at them)
-            bufs["protein_pos"], bufs["protein_h"] = z(B, NP, 3), z(B * NP, H)
-            bufs["lig_aux"], bufs["atom_std"], bufs["offset"] = z(B, NL, 2), z(B * NL, 3), z(B, 3)
-            bufs["decomp_index"] = z(B * NL, dtype=torch.int32) if decomp_index is not None else None
-            bufs["full_protein_pos"] = z(B, NF, 3) if NF else None
-            # state
-            bufs["lig_pos"], bufs["lig_v"], bufs["lig_bond"] = z(B, NL, 3), z(B * NL, dtype=torch.int32), z(B * Eb, dtype=torch.int32)
-            bufs["step_counter"] = z(4, dtype=torch.int32)             # run state: steps done, t_start, seed lo / hi
-            if masks is not None:                                      # padded heterogeneous batch (dd_sampler.np_real ...)
-                bufs["np_real"], bufs["nl_real"] = z(B, dtype=torch.int32), z(B, dtype=torch.int32)
-                bufs["bl_prefix"] = z(B + 1, dtype=torch.int32)
-            bufs["pred_pos"], bufs["pred_v"], bufs["pred_bond"] = z(B * NL, 3), z(B * NL, self.num_classes), z(B * Eb, 5)
-            ws_floats = int(lib.dd_workspace_floats(B, NP, NL, K))
-            bufs["workspace"] = z(ws_floats)
-            if masks is None and self._layer0_tables(pw, dev) is not None:     # layer-0 tables (dd_sampler.l0_*)
-                bufs["l0_P"], bufs["l0_qn"] = z(B * N, 640), z(B * N, 128)
-            if keep_traj and n_steps > 0:
-                bufs["traj_pos"] = z(cap, B * NL, 3)
-                bufs["traj_v"] = z(cap, B * NL, dtype=torch.int32)
-                bufs["traj_bond"] = z(cap, B * Eb, dtype=torch.int32)
-                bufs["traj_v0"] = z(cap, B * NL, self.num_classes)
-                bufs["traj_vt"] = z(cap, B * NL, self.num_classes)
-                bufs["traj_bt"] = z(cap, B * Eb, 5)
-            sm = hip_lib.DDSampler()
-            sm.B, sm.NP, sm.NL, sm.K, sm.NF = B, NP, NL, K, NF
-            sm.num_layers, sm.T = int(self.config.num_layers), int(self.betas.numel())
-            sm.num_v = int(self.num_classes)
-            sm.weights = arena.data_ptr()
-            sm.slot_off = offs.ctypes.data
-            sm.tab_pos, sm.tab_v, sm.tab_b = pw["tab_pos"].data_ptr(), pw["tab_v"].data_ptr(), pw["tab_b"].data_ptr()
-            sm.tab_score = pw["tab_score"].data_ptr()
-            sm.workspace_floats = ws_floats
-            ent = dict(s=sm, bufs=bufs, graph=None, graph_sig=None, dev=dev, pw=pw)
-        sm, bufs = ent["s"], ent["bufs"]
-        # ---- this chain's inputs.  The pocket side (protein coordinates / embedded features, arm indicators, full protein,
-        # layer-0 protein rows) is uploaded once per cached entry and pocket: a later call that passes the SAME tensor objects
-        # with unchanged version counters (the next batch of the pocket, the sampling script's loop) finds them in place --
-        # five launches less in front of the first graph replay.
-        # CONTRACT of the skip: it keys on the identity of the caller's tensors AND their version counters.  Writes that do not bump
-        # the counter (t.data.copy_, set_, another library writing through data_ptr) are invisible to it: after such a write call
-        # model.invalidate_pocket_uploads() or set DD_POCKET_UPLOAD_SKIP=0 (every call then uploads).  The cache entry holds
-        # references to those tensors for as long as it lives (evicted with the chain cache).
+        key = (str(dev), B, NP, NL, K, NF, cap if keep_traj else 0, bool(keep_traj), has_decomp, arena.data_ptr(),
+               masked, int(cache_slot), self.bond_net_type, self.x2h_out_fc, int(self.config.num_blocks))     # cache_slot: chains of ONE call that share a shape need separate buffers
+        ent = DecompScorePosNet3D._chain_cache.pop(key, None) if cacheable else None
+        if ent is not None:
+            return key, ent
+        z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
+        bufs: Dict[str, Optional[torch.Tensor]] = {}
+        # static inputs (own buffers: a cached graph points at them)
+        bufs["protein_pos"], bufs["protein_h"] = z(B, NP, 3), z(B * NP, H)
+        bufs["lig_aux"], bufs["atom_std"], bufs["offset"] = z(B, NL, 2), z(B * NL, 3), z(B, 3)
+        bufs["decomp_index"] = z(B * NL, dtype=torch.int32) if has_decomp else None
+        bufs["full_protein_pos"] = z(B, NF, 3) if NF else None
+        # state
+        bufs["lig_pos"], bufs["lig_v"], bufs["lig_bond"] = z(B, NL, 3), z(B * NL, dtype=torch.int32), z(B * Eb, dtype=torch.int32)
+        bufs["step_counter"] = z(4, dtype=torch.int32)             # run state: steps done, t_start, seed lo / hi
+        if masked:                                                 # padded heterogeneous batch (dd_sampler.np_real ...)
+            bufs["np_real"], bufs["nl_real"] = z(B, dtype=torch.int32), z(B, dtype=torch.int32)
+            bufs["bl_prefix"] = z(B + 1, dtype=torch.int32)
+        bufs["pred_pos"], bufs["pred_v"], bufs["pred_bond"] = z(B * NL, 3), z(B * NL, self.num_classes), z(B * Eb, 5)
+        ws_floats = int(lib.dd_workspace_floats(B, NP, NL, K))
+        bufs["workspace"] = z(ws_floats)
+        if not masked and self._layer0_tables(pw, dev) is not None:        # layer-0 tables (dd_sampler.l0_*)
+            bufs["l0_P"], bufs["l0_qn"] = z(B * N, 640), z(B * N, 128)
+        if keep_traj and n_steps > 0:
+            bufs["traj_pos"] = z(cap, B * NL, 3)
+            bufs["traj_v"] = z(cap, B * NL, dtype=torch.int32)
+            bufs["traj_bond"] = z(cap, B * Eb, dtype=torch.int32)
+            bufs["traj_v0"] = z(cap, B * NL, self.num_classes)
+            bufs["traj_vt"] = z(cap, B * NL, self.num_classes)
+            bufs["traj_bt"] = z(cap, B * Eb, 5)
+        sm = hip_lib.DDSampler()
+        sm.B, sm.NP, sm.NL, sm.K, sm.NF = B, NP, NL, K, NF
+        sm.num_layers, sm.T = int(self.config.num_layers), int(self.betas.numel())
+        sm.num_v = int(self.num_classes)
+        sm.weights = arena.data_ptr()
+        sm.slot_off = offs.ctypes.data
+        sm.tab_pos, sm.tab_v, sm.tab_b = pw["tab_pos"].data_ptr(), pw["tab_v"].data_ptr(), pw["tab_b"].data_ptr()
+        sm.tab_score = pw["tab_score"].data_ptr()
+        sm.workspace_floats = ws_floats
+        return key, dict(s=sm, bufs=bufs, graph=None, graph_sig=None, dev=dev, pw=pw)
+
+    def _upload_pocket(self, ent, d, pw, full_protein_pos, cacheable):
+        """The pocket side of a chain's inputs (protein coordinates / embedded features, arm indicators, full protein,
+        layer-0 protein rows) is uploaded once per cached entry and pocket: a later call that passes the SAME tensor objects
+        with unchanged version counters (the next batch of the pocket, the sampling script's loop) finds them in place --
+        five launches less in front of the first graph replay.
+        CONTRACT of the skip: it keys on the identity of the caller's tensors AND their version counters.  Writes that do not bump
+        the counter (t.data.copy_, set_, another library writing through data_ptr) are invisible to it: after such a write call
+        model.invalidate_pocket_uploads() or set DD_POCKET_UPLOAD_SKIP=0 (every call then uploads).  The cache entry holds
+        references to those tensors for as long as it lives (evicted with the chain cache).
+        Returns (src, pocket_in_place) for `_fill_sampler`, which records the upload once everything is enqueued."""
+        bufs, B, NP = ent["bufs"], d["B"], d["NP"]
         src = d.get("upload_src") if (cacheable and os.environ.get("DD_POCKET_UPLOAD_SKIP", "1") != "0") else None
         pocket_in_place = (src is not None and ent.get("uploaded") is not None and ent.get("uploaded_pw") is pw
                            and ent.get("uploaded_mode") == d.get("upload_mode") and len(src) == len(ent["uploaded"])
                            and all(t is u and (t is None or t._version == ver) for t, (u, ver) in zip(src, ent["uploaded"])))
-        ent["uploaded"] = None                             # (set again below, once everything is enqueued)
-        goff = self._global_offsets(pw)
+        ent["uploaded"] = None
         if not pocket_in_place:
+            arena, goff = pw["arena"], self._global_offsets(pw)
             bufs["protein_pos"].copy_(d["protein_pos_centered"])
-            hip_lib.check(lib.dd_embed_protein(hip_lib.ptr(d["protein_v"].view(B * NP, -1)), B * NP,
-                                               ctypes.c_void_p(arena[goff["W_pemb"]:].data_ptr()),
-                                               ctypes.c_void_p(arena[goff["b_pemb"]:].data_ptr()),
-                                               hip_lib.ptr(bufs["protein_h"]), hip_lib.stream_ptr(dev)), "dd_embed_protein")
+            hip_lib.check(hip_lib.load().dd_embed_protein(hip_lib.ptr(d["protein_v"].view(B * NP, -1)), B * NP,
+                                                          ctypes.c_void_p(arena[goff["W_pemb"]:].data_ptr()),
+                                                          ctypes.c_void_p(arena[goff["b_pemb"]:].data_ptr()),
+                                                          hip_lib.ptr(bufs["protein_h"]), hip_lib.stream_ptr(ent["dev"])), "dd_embed_protein")
             bufs["lig_aux"].copy_(d["ligand_aux"])
-            if NF:
+            if full_protein_pos is not None:
                 bufs["full_protein_pos"].copy_(full_protein_pos)
-        bufs["atom_std"].copy_(atom_std.reshape(B * NL, 3))
+        return src, pocket_in_place
+
+    @staticmethod
+    def _upload_state(ent, d, atom_std, offset, decomp_index, masks):
+        """This chain's ligand side: stds, offset, decomposition, first state and, padded batch, the real counts."""
+        bufs = ent["bufs"]
+        bufs["atom_std"].copy_(atom_std.reshape(-1, 3))
         bufs["offset"].copy_(offset)
         if decomp_index is not None:
             bufs["decomp_index"].copy_(decomp_index.reshape(-1))
@@ -1094,73 +1190,65 @@ class DecompScorePosNet3D(nn.Module):
         if masks is not None:
             for k in ("np_real", "nl_real", "bl_prefix"):
                 bufs[k].copy_(masks[k])
-        # per-sample noise keys: the buffer belongs to the (cached) entry, its contents to this call -- the step kernels read the
-        # keys at every launch, so the entry's captured graph serves the next chain with other keys
-        if sample_keys is not None:
-            if bufs.get("sample_keys") is None:
-                bufs["sample_keys"] = torch.zeros(B, dtype=torch.int64, device=dev)
-            bufs["sample_keys"].copy_(sample_keys)
-        ent["keyed"] = sample_keys is not None
-        # fixed atoms: as the keys -- buffers of the entry, contents of this call, read by the kernels at every launch, so one
-        # captured graph serves every mask and every known values of its mode
-        ent["fixed"], ent["fixed_struct"] = None, None
+
+    def _bind_call(self, ent, d, pw, keys, fixed, resample, chain_init):
+        """The per-call inputs that the kernels read through pointers at every launch -- per-sample noise keys, fixed atoms (fx_*),
+        the resampling epoch, the chain init (ci_*): the buffers belong to the (cached) entry and are created when first needed,
+        their contents to this call, so the entry's captured graph serves the next chain with other keys, masks and known values.
+        ``keys``: int64 [B] (host or device) in the order of the chain's samples, or None (the chain draws with its seed); ``fixed`` /
+        ``chain_init``: the ``fx`` / ``ci`` of `_chain_rows`; ``resample``: the validated dict of `_as_resample`.  Leaves on the entry
+        ``keyed``, ``fixed`` (the mode), ``resample``, the host structs, and ``launch``: the step-launch arguments of this chain."""
+        bufs, dev = ent["bufs"], ent["dev"]
+        A, E = d["B"] * d["NL"], d["B"] * d["NL"] * (d["NL"] - 1)
+        fx, ci = fixed or {}, chain_init or {}
+        replace, noised = fx.get("mode") == "replace", ci.get("mode") == "noised"
+        with_cc = fixed is not None and (replace or resample is not None)      # (a jump noises around the centres in hold mode too)
+        i32, f32, bound = torch.int32, torch.float32, {}
+        for name, src, shape, dtype, wanted in (
+                ("sample_keys", keys, (d["B"],), torch.int64, keys is not None),
+                ("fx_mask", fx.get("mask"), (A,), torch.uint8, fixed is not None), ("fx_v0", fx.get("v0"), (A,), i32, fixed is not None),
+                ("fx_b0", fx.get("b0"), (E,), i32, fixed is not None), ("fx_x0c", fx.get("x0c"), (A, 3), f32, fixed is not None),
+                ("fx_cc", fx.get("cc"), (A, 3), f32, with_cc),
+                ("epoch", None, (1,), i32, resample is not None),          # (zeroed by dd_sampler_reset_resample: it starts with the chain)
+                ("ci_cc", ci.get("cc"), (A, 3), f32, chain_init is not None), ("ci_std", ci.get("std"), (A, 3), f32, chain_init is not None),
+                ("ci_lp_v", ci.get("atom_lp"), (self.num_classes,), f32, ci.get("atom_lp") is not None),
+                ("ci_lp_b", ci.get("bond_lp"), (self.num_bond_classes,), f32, ci.get("bond_lp") is not None),
+                ("ci_x0c", ci.get("x0c"), (A, 3), f32, ci.get("x0c") is not None), ("ci_v0", ci.get("v0"), (A,), i32, ci.get("v0") is not None),
+                ("ci_b0", ci.get("b0"), (E,), i32, ci.get("b0") is not None)):
+            if wanted and bufs.get(name) is None:
+                bufs[name] = torch.zeros(shape, dtype=dtype, device=dev)
+            if wanted and src is not None:
+                bufs[name].copy_(src.reshape(shape))
+            bound[name] = bufs[name] if wanted else None
+        if (replace or noised) and pw.get("tab_fixed") is None:
+            pw["tab_fixed"] = self.fixed_step_table().to(dev)
+        ent["keyed"], ent["fixed"], ent["fixed_struct"] = keys is not None, fx.get("mode"), None
         if fixed is not None:
-            replace = fixed["mode"] == "replace"
-            with_cc = replace or resample is not None          # (a jump noises around the centres in hold mode too)
-            for k, shape, dtype in (("mask", (B * NL,), torch.uint8), ("v0", (B * NL,), torch.int32), ("b0", (B * Eb,), torch.int32),
-                                    ("x0c", (B * NL, 3), torch.float32), ("cc", (B * NL, 3), torch.float32)):
-                if k == "cc" and not with_cc:
-                    continue
-                if bufs.get("fx_" + k) is None:
-                    bufs["fx_" + k] = torch.zeros(shape, dtype=dtype, device=dev)
-                bufs["fx_" + k].copy_(fixed[k].reshape(shape))
-            if replace and pw.get("tab_fixed") is None:
-                pw["tab_fixed"] = self.fixed_step_table().to(dev)
-            ent["fixed"] = fixed["mode"]
-            ent["fixed_struct"] = hip_lib.fixed_struct(fixed["mode"], bufs["fx_mask"], bufs["fx_v0"], bufs["fx_b0"], bufs["fx_x0c"],
-                                                       bufs["fx_cc"] if with_cc else None, pw["tab_fixed"] if replace else None)
-        # resampling: the epoch int belongs to the entry and is read at every launch, the jump table to the packed weights (one per
-        # jump length); neither j nor r reaches the captured graph
+            ent["fixed_struct"] = hip_lib.fixed_struct(fx["mode"], bound["fx_mask"], bound["fx_v0"], bound["fx_b0"], bound["fx_x0c"],
+                                                       bound["fx_cc"], pw["tab_fixed"] if replace else None)
+        # resampling: the jump table belongs to the packed weights (one per jump length); neither j nor r reaches the captured graph
         ent["resample"], ent["resample_struct"] = None, None
         if resample is not None:
-            if bufs.get("epoch") is None:
-                bufs["epoch"] = torch.zeros(1, dtype=torch.int32, device=dev)
             tabs = pw.setdefault("tab_jump", {})
             if resample["j"] not in tabs:
                 tabs[resample["j"]] = self.resample_jump_table(resample["j"]).to(dev)
             ent["resample"] = dict(resample)
-            ent["resample_struct"] = hip_lib.resample_struct(resample["j"], tabs[resample["j"]], bufs["epoch"])
-        # chain init: as the fixed atoms -- buffers of the entry, contents of this call; the launch is part of the chain's preparation
-        # (below), not of its captured graph
+            ent["resample_struct"] = hip_lib.resample_struct(resample["j"], tabs[resample["j"]], bound["epoch"])
+        # chain init: the launch is part of the chain's preparation (_start_chain), not of its captured graph
         ent["init_struct"] = None
         if chain_init is not None:
-            noised = chain_init["mode"] == "noised"
-            ptrs = {}
-            for k, src_k, shape, dtype in (("cc", "cc", (B * NL, 3), torch.float32), ("std", "std", (B * NL, 3), torch.float32),
-                                           ("lp_v", "atom_lp", (self.num_classes,), torch.float32),
-                                           ("lp_b", "bond_lp", (self.num_bond_classes,), torch.float32),
-                                           ("x0c", "x0c", (B * NL, 3), torch.float32), ("v0", "v0", (B * NL,), torch.int32),
-                                           ("b0", "b0", (B * Eb,), torch.int32)):
-                t = chain_init.get(src_k)
-                if t is None:
-                    ptrs[k] = None
-                    continue
-                if bufs.get("ci_" + k) is None:
-                    bufs["ci_" + k] = torch.zeros(shape, dtype=dtype, device=dev)
-                bufs["ci_" + k].copy_(t.reshape(shape))
-                ptrs[k] = bufs["ci_" + k]
-            if noised and pw.get("tab_fixed") is None:
-                pw["tab_fixed"] = self.fixed_step_table().to(dev)
-            ent["init_struct"] = hip_lib.init_struct(chain_init["mode"], ptrs["cc"], ptrs["std"], ptrs["lp_v"], ptrs["lp_b"], ptrs["x0c"],
-                                                     ptrs["v0"], ptrs["b0"], pw["tab_fixed"] if noised else None)
+            ent["init_struct"] = hip_lib.init_struct(ci["mode"], bound["ci_cc"], bound["ci_std"], bound["ci_lp_v"], bound["ci_lp_b"],
+                                                     bound["ci_x0c"], bound["ci_v0"], bound["ci_b0"], pw["tab_fixed"] if noised else None)
+        ref = lambda st: None if st is None else ctypes.byref(st)
+        ent["launch"] = dict(keys=hip_lib.ptr(bound["sample_keys"]), fixed=ref(ent["fixed_struct"]), resample=ref(ent["resample_struct"]))
+
+    def _fill_sampler(self, ent, d, pw, t_start, seed, noise, drift_fields, drift_norm_batch, upload):
+        """The per-call fields of the entry's dd_sampler -- injected noise, layer-0 tables, start time, seed, buffer pointers, drift
+        terms -- and the protein rows of the layer-0 tables; ``upload``: what `_upload_pocket` returned.  Returns "uses the tables"."""
+        sm, bufs, dev = ent["s"], ent["bufs"], ent["dev"]
+        src, pocket_in_place = upload
         for k in ("u_v", "u_b", "eps"):
-            bufs[k] = None
-        if noise is not None:
-            for k, shp in (("u_v", (n_steps, B * NL, self.num_classes)), ("u_b", (n_steps, B * Eb, 5)), ("eps", (n_steps, B * NL, 3))):
-                t = noise[k]
-                if tuple(t.shape) != shp:
-                    raise ValueError(f"noise['{k}'] must have shape {shp}, got {tuple(t.shape)}")
-                bufs[k] = t.to(device=dev, dtype=torch.float32).contiguous()
+            bufs[k] = None if noise is None else noise[k].to(device=dev, dtype=torch.float32).contiguous()
         # layer-0 tables: only for arm / scaffold indicator rows that are exactly (1,0) or (0,1) (d["aux_onehot"])
         use_l0 = bufs.get("l0_P") is not None and bool(d.get("aux_onehot", False))
         sm.l0_tables = self._layer0_tables(pw, dev).data_ptr() if use_l0 else None
@@ -1176,67 +1264,48 @@ class DecompScorePosNet3D(nn.Module):
             if t is not None:
                 assert t.is_contiguous() and t.device == dev, k
             setattr(sm, k, t.data_ptr() if t is not None else None)
-        sm.drift_armsca = sm.drift_clash = sm.armsca_scale = sm.clash_scale = 0
-        sm.drift_repul, sm.repul_max_d, sm.repul_scale = 0, 0.0, 0
-        seen = []
-        for dr in drift or []:
-            if dr["type"] in seen:                         # one buffer per term: a repeated entry would silently replace the first
-                raise NotImplementedError(f"energy_drift_opt lists '{dr['type']}' twice")
-            seen.append(dr["type"])
-            if dr["type"] == "armsca_prox":
-                sm.drift_armsca, sm.armsca_min_d, sm.armsca_max_d = 1, float(dr["min_d"]), float(dr["max_d"])
-                sm.armsca_scale = int(bool(dr.get("scale", False)))
-            elif dr["type"] == "clash":
-                sm.drift_clash, sm.clash_sigma, sm.clash_gamma = 1, float(dr["sigma"]), float(dr["gamma"])
-                sm.clash_scale = int(bool(dr.get("scale", False)))
-            elif dr["type"] == "arms_repul":
-                # EXTENSION: the reference defines the energy (utils/guidance_funcs.py:81-118) but its
-                # sample_diffusion has no branch for it (decompdiff.py:643-675 raises ValueError); wired like armsca_prox
-                # (:648-659): gradient at x_t, optional `scale`.  Defaults = the function's own (max_d 1.9, mode 'min').
-                mode = dr.get("mode", "min")
-                if mode not in ("min", "all"):
-                    raise ValueError(mode)                 # (guidance_funcs.py:90)
-                if decomp_index is None:
-                    raise ValueError("arms_repul drift needs ligand_decomp_index")
-                sm.drift_repul, sm.repul_max_d = (1 if mode == "min" else 2), float(dr.get("max_d", 1.9))
-                sm.repul_scale = int(bool(dr.get("scale", False)))
-            elif dr["type"] in ("center_prox", "mmff_min"):
-                raise NotImplementedError(f"drift '{dr['type']}' is outside the shipped sampling path "
-                                          "(center_prox raises in the reference; mmff_min is RDKit/CPU)")
-            else:
-                raise ValueError(dr["type"])
+        for k, v in drift_fields.items():
+            setattr(sm, k, v)
         sm.drift_norm_batch = int(drift_norm_batch)
         if use_l0 and not (pocket_in_place and ent.get("uploaded_l0")):     # protein rows of the layer-0 tables (this chain's pocket)
-            hip_lib.check(lib.dd_layer0_prepare(ctypes.byref(sm), hip_lib.stream_ptr(dev)), "dd_layer0_prepare")
+            hip_lib.check(hip_lib.load().dd_layer0_prepare(ctypes.byref(sm), hip_lib.stream_ptr(dev)), "dd_layer0_prepare")
         if src is not None:
             ent["uploaded"] = [(t, None if t is None else t._version) for t in src]
             ent["uploaded_pw"], ent["uploaded_l0"], ent["uploaded_mode"] = pw, bool(use_l0), d.get("upload_mode")
+        return bool(use_l0)
+
+    def _start_chain(self, ent, n_steps, fixed, chain_init):
+        """The launches in front of a chain's first step: the reset of its run state, its first level and its held rows."""
+        lib, sm, st, L = hip_lib.load(), ctypes.byref(ent["s"]), hip_lib.stream_ptr(ent["dev"]), ent["launch"]
         draw_level = fixed is not None and fixed["mode"] == "replace" and fixed["init"] == "draw"
-        if resample is not None:                           # (the epoch starts with the chain)
-            hip_lib.check(lib.dd_sampler_reset_resample(ctypes.byref(sm), ctypes.byref(ent["resample_struct"]), hip_lib.stream_ptr(dev)),
-                          "dd_sampler_reset_resample")
+        if L["resample"] is not None:                      # (the epoch starts with the chain)
+            hip_lib.check(lib.dd_sampler_reset_resample(sm, L["resample"], st), "dd_sampler_reset_resample")
         elif n_steps > 0 or draw_level or chain_init is not None:      # (a chain of no steps still prepares its first level / held rows)
-            hip_lib.check(lib.dd_sampler_reset(ctypes.byref(sm), hip_lib.stream_ptr(dev)), "dd_sampler_reset")
+            hip_lib.check(lib.dd_sampler_reset(sm, st), "dd_sampler_reset")
         # the chain's first level drawn on the device (every real row), in front of the held rows' preparation
         if chain_init is not None:
-            keys_ptr = hip_lib.ptr(bufs["sample_keys"]) if sample_keys is not None else None
-            hip_lib.check(lib.dd_chain_init(ctypes.byref(sm), keys_ptr, ctypes.byref(ent["init_struct"]), hip_lib.stream_ptr(dev)),
-                          "dd_chain_init")
+            hip_lib.check(lib.dd_chain_init(sm, L["keys"], ctypes.byref(ent["init_struct"]), st), "dd_chain_init")
         # held rows in front of the first step: hold -- the known values; replace, init 'draw' -- level t_start at Philox time
         # t_start + 1 ('given': init_ligand_* already holds that level)
         if fixed is not None and (fixed["mode"] == "hold" or draw_level):
-            keys_ptr = hip_lib.ptr(bufs["sample_keys"]) if sample_keys is not None else None
-            hip_lib.check(lib.dd_fixed_init(ctypes.byref(sm), keys_ptr, ctypes.byref(ent["fixed_struct"]), hip_lib.stream_ptr(dev)),
-                          "dd_fixed_init")
-        # everything that shapes the captured step graph besides the (cached) pointers
-        ent["sig"] = (sm.drift_armsca, sm.armsca_min_d, sm.armsca_max_d, sm.armsca_scale, sm.drift_clash, sm.clash_sigma,
-                      sm.clash_gamma, sm.clash_scale, sm.drift_repul, sm.repul_max_d, sm.repul_scale, sm.drift_norm_batch,
-                      int(lib.dd_debug_options_epoch()), bool(use_l0), ent["keyed"], fixed is not None, ent["fixed"],
-                      resample is not None)
-        if cacheable:
-            cache[key] = ent                               # (re-inserted: most recently used last)
-            self._evict_chain_cache(self._CACHE_MAX)
-        return sm, bufs, ent
+            hip_lib.check(lib.dd_fixed_init(sm, L["keys"], L["fixed"], st), "dd_fixed_init")
+
+    def _run_forward(self, d, pw, masks=None):
+        """One forward() call on the dense-layout batch ``d``: an entry of its own (never cached), pocket and ligand uploaded,
+        the score network launched; the predictions over the dense [B*NL] / [B*Eb] rows."""
+        dev = d["protein_pos"].device
+        atom_std, offset = torch.ones(d["B"] * d["NL"], 3, device=dev), torch.zeros(d["B"], 3, device=dev)     # (not read by a forward)
+        _, ent = self._chain_entry(d, pw, 0, False, False, masked=masks is not None)
+        upload = self._upload_pocket(ent, d, pw, None, False)
+        self._upload_state(ent, d, atom_std, offset, None, masks)
+        self._fill_sampler(ent, d, pw, 0, 0, None, _drift_fields(None, False), 0, upload)
+        hip_lib.check(hip_lib.load().dd_forward_opts(ctypes.byref(ent["s"]), self._model_opts(pw), hip_lib.stream_ptr(dev)), "dd_forward")
+        _check_queue(ent["s"], dev)
+        self._last, bufs = (ent["s"], ent["bufs"]), ent["bufs"]
+        preds = {"pred_ligand_pos": bufs["pred_pos"], "pred_ligand_v": bufs["pred_v"]}     # ([B*NL,3], [B*NL,num_classes])
+        if self.bond_diffusion:
+            preds["pred_bond"] = bufs["pred_bond"]
+        return preds
 
     def _side_stream(self, dev):
         st = getattr(self, "_stream", None)
@@ -1271,24 +1340,13 @@ class DecompScorePosNet3D(nn.Module):
         dev = protein_pos.device
         layout = BL.BatchLayout.from_batch(batch_protein, batch_ligand, ligand_fc_bond_index=ligand_fc_bond_index.to(dev),
                                            n_bonds=ligand_bond_type.numel())
-        B, n_p, n_l = layout.B, layout.n_p, layout.n_l
+        n_p, n_l = layout.n_p, layout.n_l
         BL.check_size_limits(n_p, n_l)
         if os.environ.get("DD_RAGGED_MODE", "padded") != "groups" and BL.fits_padded(layout, self.config.knn):
             pad = self._padded_inputs(protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, ligand_v_aux, batch_ligand,
                                       ligand_fc_bond_index, ligand_bond_type, None, n_p, n_l, "none")
-            d, d_l, d_b = pad["d"], pad["d_l"], pad["d_b"]
-            NL = d["NL"]
-            pw = self._packed_weights()
-            s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, torch.ones(B * NL, 3, device=dev),
-                                            torch.zeros(B, 3, device=dev), None, None, 0, masks=pad["masks"])
-            hip_lib.check(hip_lib.load().dd_forward_opts(ctypes.byref(s), self._model_opts(pw), hip_lib.stream_ptr(dev)), "dd_forward")
-            _check_queue(s, dev)
-            preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3).index_select(0, d_l),
-                     "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes).index_select(0, d_l)}
-            if self.bond_diffusion:
-                preds["pred_bond"] = bufs["pred_bond"].index_select(0, d_b)
-            self._last = (s, bufs)
-            return preds
+            preds = self._run_forward(pad["d"], self._packed_weights(), masks=pad["masks"])
+            return {k: t.index_select(0, pad["d_b" if k == "pred_bond" else "d_l"]) for k, t in preds.items()}
         # one dense forward per group of equal (protein, ligand) sizes, rows put back in the caller's order
         out = {"pred_ligand_pos": torch.empty(sum(n_l), 3, device=dev), "pred_ligand_v": torch.empty(sum(n_l), self.num_classes, device=dev)}
         if self.bond_diffusion:
@@ -1330,20 +1388,7 @@ class DecompScorePosNet3D(nn.Module):
                                    init_ligand_v_aux, batch_ligand, ligand_fc_bond_index, init_ligand_fc_bond_type,
                                    ligand_atom_mask)
             d["protein_pos_centered"], d["ligand_pos_centered"] = d["protein_pos"], d["ligand_pos"]
-            pw = self._packed_weights()
-            dev = d["protein_pos"].device
-            B, NL = d["B"], d["NL"]
-            dummy3 = torch.ones(B * NL, 3, device=dev)
-            s, bufs, _ = self._make_sampler(d, pw, 0, 0, None, False, None, dummy3,
-                                            torch.zeros(B, 3, device=dev), None, None, 0)
-            hip_lib.check(hip_lib.load().dd_forward_opts(ctypes.byref(s), self._model_opts(pw), hip_lib.stream_ptr(dev)), "dd_forward")
-            _check_queue(s, dev)
-            preds = {"pred_ligand_pos": bufs["pred_pos"].view(B * NL, 3),
-                     "pred_ligand_v": bufs["pred_v"].view(B * NL, self.num_classes)}
-            if self.bond_diffusion:
-                preds["pred_bond"] = bufs["pred_bond"]
-            self._last = (s, bufs)
-            return preds
+            return self._run_forward(d, self._packed_weights())
 
     def train(self, mode: bool = True):
         self.__dict__["_packed"] = None                     # parameters are about to change (or just did)
@@ -1465,8 +1510,6 @@ class DecompScorePosNet3D(nn.Module):
             sample_keys = _as_sample_keys(sample_keys, batch_ligand)
             seed = 0                                             # (not read by a keyed chain; no draw from torch's generator)
         if resample is not None:
-            if start_step < 0 or num_steps + start_step > self.num_timesteps:
-                raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
             resample = _as_resample(resample, fixed, noise, self.num_timesteps, num_steps, start_step)
         if init is not None:
             dev = protein_pos.device
@@ -1485,32 +1528,27 @@ class DecompScorePosNet3D(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         key_t = (protein_pos, batch_protein, batch_ligand, ligand_fc_bond_index, ligand_v_aux)
         static = self._static_memo_get(key_t, center_pos_mode)        # (only dense batches are remembered)
+        call = _Call(self.num_timesteps, num_steps, start_step, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
+                     _drift_norm_batch, sample_keys, fixed, resample, init)
         if static is None and self._is_ragged(batch_protein, batch_ligand):
             return self._sample_heterogeneous(
-                dict(protein_pos=protein_pos, protein_v=protein_v, batch_protein=batch_protein,
-                     protein_group_idx=protein_group_idx, init_ligand_pos=init_ligand_pos, init_ligand_v=init_ligand_v,
-                     ligand_v_aux=ligand_v_aux, batch_ligand=batch_ligand, ligand_group_idx=ligand_group_idx,
-                     prior_centers=prior_centers, prior_stds=prior_stds, prior_num_atoms=prior_num_atoms,
-                     batch_prior=batch_prior, prior_group_idx=prior_group_idx, ligand_decomp_batch=ligand_decomp_batch,
-                     ligand_decomp_index=ligand_decomp_index, ligand_fc_bond_index=ligand_fc_bond_index,
-                     init_ligand_fc_bond_type=init_ligand_fc_bond_type, batch_ligand_bond=batch_ligand_bond,
-                     full_protein_pos=full_protein_pos, full_batch_protein=full_batch_protein),
-                ligand_atom_mask, num_steps, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
-                start_step=start_step, sample_keys=sample_keys, fixed=fixed, resample=resample, chain_init=init)
+                dict(protein_pos=protein_pos, protein_v=protein_v, batch_protein=batch_protein, init_ligand_pos=init_ligand_pos,
+                     init_ligand_v=init_ligand_v, ligand_v_aux=ligand_v_aux, batch_ligand=batch_ligand, prior_stds=prior_stds,
+                     batch_prior=batch_prior, ligand_decomp_batch=ligand_decomp_batch, ligand_decomp_index=ligand_decomp_index,
+                     ligand_fc_bond_index=ligand_fc_bond_index, init_ligand_fc_bond_type=init_ligand_fc_bond_type,
+                     batch_ligand_bond=batch_ligand_bond, full_protein_pos=full_protein_pos, full_batch_protein=full_batch_protein,
+                     ligand_atom_mask=ligand_atom_mask), call)
         chain = self._prepare_chain(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
                                     batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
-                                    ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode,
-                                    energy_drift_opt, full_protein_pos, full_batch_protein, noise, seed, keep_traj,
-                                    _drift_norm_batch, start_step, static=static, sample_keys=sample_keys, fixed=fixed,
-                                    resample=resample, chain_init=init)
+                                    ligand_fc_bond_index, init_ligand_fc_bond_type, full_protein_pos, full_batch_protein, call,
+                                    static=static)
         if static is None and "static" in chain:
             self._static_memo_put(key_t, center_pos_mode, chain["static"])
         tr = self.__dict__.get("_trace")
         if tr is not None:
             tr.append(("prepared>", time.perf_counter()))
-        n_pos = num_steps if resample is None else resample["n_total"]
-        self._run_chains([chain], n_pos, use_graph)
-        out = self._collect_chain(chain, n_pos, keep_traj)
+        self._run_chains([chain], call.n_pos, use_graph)
+        out = self._collect_chain(chain, call.n_pos, keep_traj)
         if tr is not None:
             tr.append(("collected>", time.perf_counter()))
         self._last = (chain["s"], chain["bufs"])
@@ -1518,11 +1556,11 @@ class DecompScorePosNet3D(nn.Module):
 
     def _prepare_chain(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
                        batch_ligand, prior_stds, ligand_decomp_batch, ligand_decomp_index, ligand_atom_mask,
-                       ligand_fc_bond_index, init_ligand_fc_bond_type, num_steps, center_pos_mode, energy_drift_opt,
-                       full_protein_pos, full_batch_protein, noise, seed, keep_traj, drift_norm_batch, start_step=0,
-                       static=None, cache_slot=0, sample_keys=None, fixed=None, resample=None, chain_init=None):
-        """Validate one dense batch, centre it, allocate its state / workspace and fill the ``dd_sampler`` struct.
-        ``static``: what an earlier call with the same pocket / batch-vector tensors established (_static_memo_get)."""
+                       ligand_fc_bond_index, init_ligand_fc_bond_type, full_protein_pos, full_batch_protein, call,
+                       static=None, cache_slot=0, place=None):
+        """Validate one dense batch, centre it, allocate its state / workspace and fill the ``dd_sampler`` struct for the call
+        record ``call``.  ``static``: what an earlier call with the same pocket / batch-vector tensors established
+        (_static_memo_get).  ``place``: which of the call's rows are this chain's (a group of a ragged batch; None: all)."""
         d = self._dense_inputs(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, ligand_v_aux,
                                batch_ligand, ligand_fc_bond_index, init_ligand_fc_bond_type, ligand_atom_mask,
                                layout=None if static is None else static["layout"],
@@ -1532,57 +1570,31 @@ class DecompScorePosNet3D(nn.Module):
         # center_pos (decompdiff.py:20-32): subtract the per-sample protein centroid
         if static is not None:
             offset = static["offset"]
-        elif center_pos_mode == "protein":
+        elif call.center_pos_mode == "protein":
             # scatter_mean(protein_pos, batch_protein, dim=0) (decompdiff.py:25): fp32 accumulation in row order / count --
             # the same arithmetic as the CPU scatter, on the host (B*NP*3 floats), so the offset that is re-added to
             # every output is bit-identical to the reference's
             pp = d["protein_pos"].detach().cpu().reshape(B * NP, 3)
             tot = torch.zeros(B, 3).index_add_(0, torch.arange(B).repeat_interleave(NP), pp)
             offset = (tot / float(max(NP, 1))).to(dev)
-        elif center_pos_mode == "none":
+        elif call.center_pos_mode == "none":
             offset = torch.zeros(B, 3, device=dev)
         else:
-            raise NotImplementedError(center_pos_mode)
+            raise NotImplementedError(call.center_pos_mode)
         d["protein_pos_centered"] = static["protein_pos_centered"] if static is not None else \
             (d["protein_pos"] - offset[:, None, :]).contiguous()
         d["ligand_pos_centered"] = (d["ligand_pos"] - offset[:, None, :]).contiguous()
-        atom_std = prior_stds.to(dev).float()[ligand_decomp_batch.to(dev)].contiguous()           # [B*NL,3]
-        decomp = ligand_decomp_index.to(device=dev, dtype=torch.int32).contiguous() if ligand_decomp_index is not None else None
-        fpp = None
-        if energy_drift_opt is not None and any(dr["type"] == "clash" for dr in energy_drift_opt):
-            if full_protein_pos is None or full_batch_protein is None:
-                raise ValueError("clash drift needs full_protein_pos / full_batch_protein")
-            nf = full_protein_pos.shape[0] // B
-            exp = torch.arange(B, device=dev).repeat_interleave(nf)
-            if full_protein_pos.shape[0] % B or not torch.equal(full_batch_protein.to(dev), exp):
-                raise NotImplementedError("full_protein_pos must hold the same number of atoms per sample")
-            fpp = full_protein_pos.to(dev).float().contiguous().view(B, nf, 3)
-        t_start = self.num_timesteps - 1 - int(start_step)   # time_seq = reversed(range(T - num_steps, T)), decompdiff.py:575
-        if start_step < 0 or num_steps + start_step > self.num_timesteps:
-            raise ValueError("num_steps (+ start_step) exceeds num_timesteps")
+        rows = _chain_rows(call, place or _Placement(batch_ligand, d["bond"].numel()), offset, prior_stds, ligand_decomp_batch,
+                           ligand_decomp_index, self.num_classes, (full_protein_pos, full_batch_protein))
         pw = self._packed_weights()
-        # (what the pocket-side device buffers of a cached entry were filled from: _make_sampler skips the upload if these very
+        # (what the pocket-side device buffers of a cached entry were filled from: _upload_pocket skips the upload if these very
         #  tensors come again unchanged; the centring mode shapes protein_pos_centered / offset)
         d["upload_src"] = (protein_pos, protein_v, ligand_v_aux, full_protein_pos, full_batch_protein) \
-            if center_pos_mode in ("protein", "none") else None
-        d["upload_mode"] = center_pos_mode
-        fx = None
-        if fixed is not None:                                # centred like the ligand: the same fp32 subtraction per row
-            off_l = offset[:, None, :]
-            fx = dict(mode=fixed["mode"], init=fixed["init"], mask=fixed["mask"].to(torch.uint8), v0=fixed["v"], b0=fixed["bond"],
-                      x0c=(fixed["pos"].view(B, NL, 3) - off_l).contiguous(),
-                      cc=None if fixed["cc"] is None else (fixed["cc"].view(B, NL, 3) - off_l).contiguous())
-        ci = None
-        if chain_init is not None:                           # centred like the ligand: the same fp32 subtraction per row
-            off_l = offset[:, None, :]
-            noised = chain_init["mode"] == "noised"
-            ci = dict(chain_init, cc=(chain_init["cen"].view(B, NL, 3) - off_l).contiguous(), std=chain_init["std"],
-                      x0c=(chain_init["pos"].view(B, NL, 3) - off_l).contiguous() if noised else None,
-                      v0=chain_init["v"] if noised else None, b0=chain_init["bond"] if noised else None)
-        s, bufs, ent = self._make_sampler(d, pw, num_steps if resample is None else resample["n_total"], t_start, noise, keep_traj,
-                                          energy_drift_opt, atom_std, offset.contiguous(), decomp, fpp, seed, drift_norm_batch,
-                                          cache_slot=cache_slot, sample_keys=sample_keys, fixed=fx, resample=resample, chain_init=ci)
-        return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent, t_traj=None if resample is None else resample["t_traj"],
+            if call.center_pos_mode in ("protein", "none") else None
+        d["upload_mode"] = call.center_pos_mode
+        s, bufs, ent = self._make_sampler(d, pw, call, rows, offset.contiguous(), cache_slot=cache_slot)
+        return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent,
+                    t_traj=None if call.resample is None else call.resample["t_traj"],
                     static=dict(layout=(B, NP, NL), offset=offset, protein_pos_centered=d["protein_pos_centered"],
                                 aux_onehot=d["aux_onehot"]))
 
@@ -1620,10 +1632,35 @@ class DecompScorePosNet3D(nn.Module):
 
     def _jump(self, chain, stream):
         """Enqueue the forward jump of a resampled chain (and the rebase of its run state) on ``stream`` (a raw handle)."""
-        ent = chain["ent"]
-        keys = hip_lib.ptr(chain["bufs"]["sample_keys"]) if ent.get("keyed") else None
-        hip_lib.check(hip_lib.load().dd_resample_jump(ctypes.byref(chain["s"]), keys, ctypes.byref(ent["fixed_struct"]),
-                                                      ctypes.byref(ent["resample_struct"]), stream), "dd_resample_jump")
+        L = chain["ent"]["launch"]
+        hip_lib.check(hip_lib.load().dd_resample_jump(ctypes.byref(chain["s"]), L["keys"], L["fixed"], L["resample"], stream),
+                      "dd_resample_jump")
+
+    # Step-graph lifetime (see _parked_graphs, _evict_chain_cache): the one place that creates, numbers and parks an entry's graph.
+    @staticmethod
+    def _is_cached(ent):
+        return any(e is ent for e in DecompScorePosNet3D._chain_cache.values())
+
+    def _ensure_step_graph(self, chain, steps_per_graph, stream):
+        """The entry's step graph for (its signature, ``steps_per_graph``, ``stream`` -- a raw handle): kept, or captured (again)."""
+        cls, ent = DecompScorePosNet3D, chain["ent"]
+        gsig = (ent["sig"], steps_per_graph, stream)
+        if ent.get("graph") is not None and ent["graph_sig"] != gsig:      # launch structure changed: capture again
+            self._drop_cached_graphs()
+        if ent.get("graph") is None:
+            if len(cls._parked_graphs) >= cls._PARK_MAX:
+                self._drop_cached_graphs()                 # (all live graphs, newest first; cached entries re-capture on next use)
+            ent["graph"], ent["graph_sig"] = self._create_step_graph(chain, steps_per_graph, stream), gsig
+            cls._graph_counter += 1
+            ent["graph_id"] = cls._graph_counter
+        return ent["graph"]
+
+    @staticmethod
+    def _release_step_graph(ent, cached):
+        """After the run (the streams are idle): a cached entry keeps its graph for the next chain, any other graph is parked."""
+        if not cached:
+            DecompScorePosNet3D._parked_graphs.append({"graph": ent["graph"], "graph_id": ent["graph_id"], "dev": ent["dev"]})
+            ent["graph"] = None
 
     def _run_chains(self, chains, num_steps, use_graph):
         """Advance every prepared chain by ``num_steps`` (resampled chains: positions -- every chain of a call shares the schedule;
@@ -1642,49 +1679,30 @@ class DecompScorePosNet3D(nn.Module):
             if use_graph and num_steps > 0:
                 # (not dd_sample_steps_graph: that entry point creates AND destroys its graph per call -- see _parked_graphs)
                 for c in chains:
-                    ent = c["ent"]
-                    cached = any(e is ent for e in DecompScorePosNet3D._chain_cache.values())
-                    gsig = (ent["sig"], 1, side.cuda_stream)
-                    if ent.get("graph") is not None and ent["graph_sig"] != gsig:
-                        self._drop_cached_graphs()
-                    if ent.get("graph") is None:
-                        if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
-                            self._drop_cached_graphs()
-                        ent["graph"], ent["graph_sig"] = self._create_step_graph(c, 1, side.cuda_stream), gsig
-                        DecompScorePosNet3D._graph_counter += 1
-                        ent["graph_id"] = DecompScorePosNet3D._graph_counter
+                    cached = self._is_cached(c["ent"])
+                    graph = self._ensure_step_graph(c, 1, side.cuda_stream)
                     try:
                         for n, jump in self._chain_runs(c, num_steps):
-                            hip_lib.check(lib.dd_graph_launch(ent["graph"], int(n), side.cuda_stream), "dd_graph_launch")
+                            hip_lib.check(lib.dd_graph_launch(graph, int(n), side.cuda_stream), "dd_graph_launch")
                             if jump:
                                 self._jump(c, side.cuda_stream)
                     finally:
                         side.synchronize()
-                        if not cached:
-                            DecompScorePosNet3D._parked_graphs.append({"graph": ent["graph"], "graph_id": ent["graph_id"], "dev": dev})
-                            ent["graph"] = None
+                        self._release_step_graph(c["ent"], cached)
             else:
+                # (dd_sample_steps_fixed with NULL keys / NULL fixed IS dd_sample_steps_keyed / _opts: in dd_api.hip those only delegate)
                 with torch.cuda.stream(side):
                     for c in chains:
-                        if c["ent"].get("resample"):
-                            keys = hip_lib.ptr(c["bufs"]["sample_keys"]) if c["ent"].get("keyed") else None
-                            for n, jump in self._chain_runs(c, num_steps):
-                                hip_lib.check(lib.dd_sample_steps_resample(
-                                    ctypes.byref(c["s"]), self._model_opts(), keys, ctypes.byref(c["ent"]["fixed_struct"]),
-                                    ctypes.byref(c["ent"]["resample_struct"]), int(n), hip_lib.stream_ptr(dev)), "dd_sample_steps_resample")
-                                if jump:
-                                    self._jump(c, hip_lib.stream_ptr(dev))
-                            rc = 0
-                        elif c["ent"].get("fixed"):
-                            rc = lib.dd_sample_steps_fixed(ctypes.byref(c["s"]), self._model_opts(),
-                                                           hip_lib.ptr(c["bufs"]["sample_keys"]) if c["ent"].get("keyed") else None,
-                                                           ctypes.byref(c["ent"]["fixed_struct"]), int(num_steps), hip_lib.stream_ptr(dev))
-                        elif c["ent"].get("keyed"):
-                            rc = lib.dd_sample_steps_keyed(ctypes.byref(c["s"]), self._model_opts(), hip_lib.ptr(c["bufs"]["sample_keys"]),
-                                                           int(num_steps), hip_lib.stream_ptr(dev))
-                        else:
-                            rc = lib.dd_sample_steps_opts(ctypes.byref(c["s"]), self._model_opts(), int(num_steps), hip_lib.stream_ptr(dev))
-                        hip_lib.check(rc, "dd_sample_steps")
+                        L, sm, st = c["ent"]["launch"], ctypes.byref(c["s"]), hip_lib.stream_ptr(dev)
+                        if L["resample"] is None:
+                            hip_lib.check(lib.dd_sample_steps_fixed(sm, self._model_opts(), L["keys"], L["fixed"], int(num_steps), st),
+                                          "dd_sample_steps")
+                            continue
+                        for n, jump in self._chain_runs(c, num_steps):
+                            hip_lib.check(lib.dd_sample_steps_resample(sm, self._model_opts(), L["keys"], L["fixed"], L["resample"], int(n), st),
+                                          "dd_sample_steps_resample")
+                            if jump:
+                                self._jump(c, st)
             cur.wait_stream(side)
             return
         if len(chains) > 64:                            # dd_sample_steps_graph_multi takes at most 64 chains
@@ -1732,22 +1750,12 @@ class DecompScorePosNet3D(nn.Module):
     def _create_step_graph(self, chain, steps_per_graph, stream):
         """Capture ``steps_per_graph`` reverse steps of a prepared chain on ``stream`` (a raw stream handle) into a new step graph;
         a keyed chain's kernels read the keys from the entry's own buffer."""
-        lib = hip_lib.load()
-        graph = ctypes.c_void_p()
-        if chain["ent"].get("resample"):
-            rc = lib.dd_graph_create_resample(ctypes.byref(chain["s"]), self._model_opts(),
-                                              hip_lib.ptr(chain["bufs"]["sample_keys"]) if chain["ent"].get("keyed") else None,
-                                              ctypes.byref(chain["ent"]["fixed_struct"]), ctypes.byref(chain["ent"]["resample_struct"]),
-                                              int(steps_per_graph), stream, ctypes.byref(graph))
-        elif chain["ent"].get("fixed"):
-            rc = lib.dd_graph_create_fixed(ctypes.byref(chain["s"]), self._model_opts(),
-                                           hip_lib.ptr(chain["bufs"]["sample_keys"]) if chain["ent"].get("keyed") else None,
-                                           ctypes.byref(chain["ent"]["fixed_struct"]), int(steps_per_graph), stream, ctypes.byref(graph))
-        elif chain["ent"].get("keyed"):
-            rc = lib.dd_graph_create_keyed(ctypes.byref(chain["s"]), self._model_opts(), hip_lib.ptr(chain["bufs"]["sample_keys"]),
-                                           int(steps_per_graph), stream, ctypes.byref(graph))
-        else:
-            rc = lib.dd_graph_create_opts(ctypes.byref(chain["s"]), self._model_opts(), int(steps_per_graph), stream, ctypes.byref(graph))
+        lib, L, graph = hip_lib.load(), chain["ent"]["launch"], ctypes.c_void_p()
+        args = (int(steps_per_graph), stream, ctypes.byref(graph))
+        if L["resample"] is not None:
+            rc = lib.dd_graph_create_resample(ctypes.byref(chain["s"]), self._model_opts(), L["keys"], L["fixed"], L["resample"], *args)
+        else:       # (with NULL keys / NULL fixed this IS dd_graph_create_keyed / _opts: those entry points of dd_api.hip only delegate)
+            rc = lib.dd_graph_create_fixed(ctypes.byref(chain["s"]), self._model_opts(), L["keys"], L["fixed"], *args)
         hip_lib.check(rc, "dd_graph_create")
         return graph
 
@@ -1778,23 +1786,14 @@ class DecompScorePosNet3D(nn.Module):
             runs = self._chain_runs(chain, num_steps)
         if spg < 1 or num_steps % spg or chunk % spg or ent.get("resample"):      # (resampled chains: runs of any length)
             spg = 1
-        gsig = (ent["sig"], spg, side.cuda_stream)
-        cached = any(e is ent for e in DecompScorePosNet3D._chain_cache.values())
+        cached = self._is_cached(ent)
         # Priming runs BEFORE this call looks at the cached graph handle: the priming chain goes through this very function
         # and may itself create -- or, if its launch structure differs, destroy and re-create -- the entry's graph.
         if (prime and cached and str(dev) not in DecompScorePosNet3D._primed_devices
                 and os.environ.get("DD_PRIME", "1") != "0"):
             if self._prime_streaming(chain, spg):          # once per process and device (a 100-pocket job creates 100 graphs)
                 DecompScorePosNet3D._primed_devices.add(str(dev))
-        if ent.get("graph") is not None and ent["graph_sig"] != gsig:      # launch structure changed: capture again
-            self._drop_cached_graphs()
-        if ent.get("graph") is None:
-            if len(DecompScorePosNet3D._parked_graphs) >= DecompScorePosNet3D._PARK_MAX:
-                self._drop_cached_graphs()                 # (all live graphs, newest first; cached entries re-capture on next use)
-            ent["graph"], ent["graph_sig"] = self._create_step_graph(chain, spg, side.cuda_stream), gsig
-            DecompScorePosNet3D._graph_counter += 1
-            ent["graph_id"] = DecompScorePosNet3D._graph_counter
-        graph = ent["graph"]                               # (read after priming: never a handle the priming chain destroyed)
+        graph = self._ensure_step_graph(chain, spg, side.cuda_stream)     # (after priming: never a handle the priming chain destroyed)
 
         dbg = int(os.environ.get("DD_TRAJ_DEBUG", "0"))
         widen = {"traj_v": torch.int64, "traj_bond": torch.int64}
@@ -1900,9 +1899,7 @@ class DecompScorePosNet3D(nn.Module):
             if tr is not None:
                 tr.extend((f"[device ms piece {i}: {gpu_ev[i].elapsed_time(gpu_ev[i + 1]):.3f}]", time.perf_counter())
                           for i in range(len(gpu_ev) - 1))
-            if not cached:                                 # (a cached entry keeps its graph for the next chain)
-                DecompScorePosNet3D._parked_graphs.append({"graph": graph, "graph_id": ent.get("graph_id", 0), "dev": dev})
-                ent["graph"] = None
+            self._release_step_graph(ent, cached)
         final = host["final"]
         cur.wait_stream(side)
         chain["traj_cpu"] = final

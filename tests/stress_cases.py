@@ -18,6 +18,7 @@ import torch
 import stress_steps as ST
 import stress_weights as SW
 from decompdiff_amd import DecompScorePosNet3D, hip_lib, shipped_config
+from decompdiff_amd.model import _Call
 from test_gpu_parity import _forward_hip, _sample_hip, dev, maxabs, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -128,8 +129,8 @@ def _one_step(m, bd, xt, t, inp, eps):
         m.num_timesteps = t + 1                    # (the chain then starts at t: test_gpu_parity._sample_hip)
         c = m._prepare_chain(bd["protein_pos"], bd["protein_v"], bd["batch_protein"], bd["init_ligand_pos"], bd["init_ligand_v"],
                              bd["ligand_v_aux"], bd["batch_ligand"], bd["prior_stds"], bd["ligand_decomp_batch"],
-                             bd["ligand_decomp_index"], None, bd["ligand_fc_bond_index"], bd["init_ligand_fc_bond_type"], 1,
-                             "protein", None, None, None, noise, 0, True, 0)
+                             bd["ligand_decomp_index"], None, bd["ligand_fc_bond_index"], bd["init_ligand_fc_bond_type"], None, None,
+                             _Call(m.num_timesteps, 1, noise=noise))
     finally:
         m.num_timesteps = T
     cb = c["bufs"]

@@ -12,6 +12,7 @@ import torch
 
 import golden_utils as GU
 from decompdiff_amd import hip_lib, synth
+from decompdiff_amd.model import _Call
 from test_gpu_parity import POS_TOL, _sample_hip, dev, maxabs, model
 
 pytestmark = pytest.mark.gpu
@@ -551,13 +552,13 @@ def test_same_shape_sub_batches_equal_the_whole_batch():
     kw = {k: (v.to(dev()) if torch.is_tensor(v) else v) for k, v in b.items() if k != "ligand_atom_mask"}
     for concurrent in (False, True):
         for rep in range(2):                                   # second pass: every sub-batch finds its own cache entry
-            part = m._sample_ragged(kw, None, steps, "protein", None, noise, 1, True, True, concurrent=concurrent, split=2)
+            part = m._sample_ragged(kw, _Call(m.num_timesteps, steps, noise=noise, seed=1), concurrent=concurrent, split=2)
             for k in ("pos", "v", "bond"):
                 assert torch.equal(part[k].cpu(), whole[k].cpu()), (concurrent, rep, k)
             assert torch.equal(torch.stack(part["bt_traj"]), torch.stack(whole["bt_traj"]))
     # production noise: the two sub-batches of a call must not share buffers (identical halves would be the symptom)
-    r = m._sample_ragged(kw, None, 5, "protein", None, None, 11, True, True, concurrent=True, split=2)
-    r2 = m._sample_ragged(kw, None, 5, "protein", None, None, 11, True, True, concurrent=False, split=2)   # cached entries re-used
+    r = m._sample_ragged(kw, _Call(m.num_timesteps, 5, seed=11), concurrent=True, split=2)
+    r2 = m._sample_ragged(kw, _Call(m.num_timesteps, 5, seed=11), concurrent=False, split=2)   # cached entries re-used
     nl = r["pos"].shape[0] // 4
     assert torch.isfinite(r["pos"]).all() and not torch.equal(r["pos"][:2 * nl], r["pos"][2 * nl:])
     assert torch.equal(r["pos"], r2["pos"]) and torch.equal(r["bond"], r2["bond"])

@@ -15,6 +15,7 @@ import torch
 import dense_spec as DS
 import golden_utils as GU
 from decompdiff_amd import DecompScorePosNet3D, hip_lib, packing, shipped_config, synth
+from decompdiff_amd.model import _Call
 from oracle import diffusion as OD
 from oracle import model as OM
 
@@ -566,8 +567,8 @@ def test_reverse_step_op_equals_the_loop():
     def chain():
         return m._prepare_chain(b["protein_pos"], b["protein_v"], b["batch_protein"], b["init_ligand_pos"], b["init_ligand_v"],
                                 b["ligand_v_aux"], b["batch_ligand"], b["prior_stds"], b["ligand_decomp_batch"],
-                                b["ligand_decomp_index"], None, b["ligand_fc_bond_index"], b["init_ligand_fc_bond_type"], steps,
-                                "protein", GU.DRIFT, b["full_protein_pos"], b["full_batch_protein"], noise, 0, True, 0)
+                                b["ligand_decomp_index"], None, b["ligand_fc_bond_index"], b["init_ligand_fc_bond_type"],
+                                b["full_protein_pos"], b["full_batch_protein"], _Call(m.num_timesteps, steps, drift=GU.DRIFT, noise=noise))
     st = hip_lib.stream_ptr(dev())
     a = chain()
     hip_lib.check(lib.dd_sample_steps(ctypes.byref(a["s"]), steps, st), "dd_sample_steps")

@@ -18,7 +18,8 @@ def stamp(obj, name):
     def w(*a, **k):
         t0 = time.perf_counter(); r = f(*a, **k); T.append((name, 1e3 * (time.perf_counter() - t0))); return r
     setattr(obj, name, w)
-for n in ("_static_memo_get", "_prepare_chain", "_make_sampler", "_run_chains", "_run_chain_streaming", "_collect_chain", "_packed_weights"):
+for n in ("_static_memo_get", "_prepare_chain", "_make_sampler", "_chain_entry", "_upload_pocket", "_upload_state", "_bind_call", "_fill_sampler",
+          "_start_chain", "_run_chains", "_run_chain_streaming", "_ensure_step_graph", "_collect_chain", "_packed_weights"):
     if hasattr(m, n): stamp(m, n)
 def sample(n, seed):
     return m.sample_diffusion(num_steps=n, center_pos_mode="protein", energy_drift_opt=None, seed=seed, keep_traj=True, use_graph=True, **b)

@@ -4,6 +4,7 @@ usage: python tools/phase_times.py [steps]"""
 import sys, time, ctypes, torch
 sys.path.insert(0, ".")
 from decompdiff_amd import DecompScorePosNet3D, hip_lib, shipped_config, synth
+from decompdiff_amd.model import _Call
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 dev = torch.device("cuda:0"); cfg = shipped_config()
 m = DecompScorePosNet3D(cfg, 29, 10, 8); sd = m.state_dict(); sd.update(synth.synthetic_state_dict(cfg, 0)); m.load_state_dict(sd); m = m.to(dev)
@@ -15,8 +16,7 @@ for rep in range(2):
     t0 = time.perf_counter()
     chain = m._prepare_chain(b["protein_pos"], b["protein_v"], b["batch_protein"], b["init_ligand_pos"], b["init_ligand_v"],
                              b["ligand_v_aux"], b["batch_ligand"], b["prior_stds"], b["ligand_decomp_batch"], b["ligand_decomp_index"],
-                             None, b["ligand_fc_bond_index"], b["init_ligand_fc_bond_type"], steps, "protein", None, None, None,
-                             None, 0, True, 0)
+                             None, b["ligand_fc_bond_index"], b["init_ligand_fc_bond_type"], None, None, _Call(m.num_timesteps, steps))
     sync(); t1 = time.perf_counter()
     m._run_chains([chain], steps, True)
     sync(); t2 = time.perf_counter()
@@ -31,8 +31,8 @@ for bb in (1, 8):
     bx = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in synth.build_sampling_batch(synth.make_pocket_small(0), bb).items()}
     chain = m._prepare_chain(bx["protein_pos"], bx["protein_v"], bx["batch_protein"], bx["init_ligand_pos"], bx["init_ligand_v"],
                              bx["ligand_v_aux"], bx["batch_ligand"], bx["prior_stds"], bx["ligand_decomp_batch"], bx["ligand_decomp_index"],
-                             None, bx["ligand_fc_bond_index"], bx["init_ligand_fc_bond_type"], 1000, "protein", None, None, None,
-                             None, 0, False, 0)
+                             None, bx["ligand_fc_bond_index"], bx["init_ligand_fc_bond_type"], None, None,
+                             _Call(m.num_timesteps, 1000, keep_traj=False))
     st = torch.cuda.Stream(device=dev)
     g = ctypes.c_void_p()
     t0 = time.perf_counter()

@@ -6,6 +6,7 @@ import os as _os; _os.environ.setdefault("DD_HIP_LIB", _os.path.join(_os.path.di
 import os, sys, time, torch
 sys.path.insert(0, ".")
 from decompdiff_amd import DecompScorePosNet3D, hip_lib, shipped_config, synth
+from decompdiff_amd.model import _Call
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 fmode = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 B = int(sys.argv[3]) if len(sys.argv) > 3 else 8
@@ -24,7 +25,7 @@ def run_split(n, k):
         kw.setdefault(key, None)
     kw.setdefault("full_protein_pos", None); kw.setdefault("full_batch_protein", None)
     sync(); t0 = time.perf_counter()
-    r = m._sample_ragged(kw, None, n, "protein", None, None, 1, True, True, concurrent=True, split=k); sync()
+    r = m._sample_ragged(kw, _Call(m.num_timesteps, n, seed=1), concurrent=True, split=k); sync()
     return time.perf_counter() - t0, r
 run_one(5)
 t, r0 = run_one(steps); t, r0 = run_one(steps)
