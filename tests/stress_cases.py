@@ -120,17 +120,18 @@ def test_forward_regime_vs_fp64_oracle(regime, shape, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------ dd_reverse_step at its edges
-def _one_step(m, bd, xt, t, inp, eps):
-    """A fresh chain at t, one dd_reverse_step on the host-made network outputs -> what it wrote, on the CPU."""
+def _one_step(m, bd, xt, t, inp, eps, seed=None):
+    """A fresh chain at t, one dd_reverse_step on the host-made network outputs -> what it wrote, on the CPU.  `seed`: the step
+    draws its own noise on the device with that key (production noise) instead of taking inp's uniforms and `eps`."""
     lib = hip_lib.load()
-    noise = dict(u_v=inp["u_v"][None], u_b=inp["u_b"][None], eps=eps[None])
+    noise = dict(u_v=inp["u_v"][None], u_b=inp["u_b"][None], eps=eps[None]) if seed is None else None
     T = m.num_timesteps
     try:
         m.num_timesteps = t + 1                    # (the chain then starts at t: test_gpu_parity._sample_hip)
         c = m._prepare_chain(bd["protein_pos"], bd["protein_v"], bd["batch_protein"], bd["init_ligand_pos"], bd["init_ligand_v"],
                              bd["ligand_v_aux"], bd["batch_ligand"], bd["prior_stds"], bd["ligand_decomp_batch"],
                              bd["ligand_decomp_index"], None, bd["ligand_fc_bond_index"], bd["init_ligand_fc_bond_type"], None, None,
-                             _Call(m.num_timesteps, 1, noise=noise))
+                             _Call(m.num_timesteps, 1, noise=noise, seed=0 if seed is None else seed))
     finally:
         m.num_timesteps = T
     cb = c["bufs"]
