@@ -18,7 +18,7 @@ namespace dd {
 
 // ---- workspace --------------------------------------------------------------------------------
 struct Workspace {
-  float *xa, *xb, *h, *hb, *ew, *P, *PL, *PB, *P2, *PL2, *PB2, *Ek, *Ev, *Rk, *Rv, *q1bl, *qn, *ql, *ql2, *qlnb, *qb, *A, *Anb, *dxe, *dxb, *ga, *gc, *gr, *h2, *hs;
+  float *xa, *xb, *h, *hb, *ew, *P, *PL, *PB, *P2, *PL2, *PB2, *Ek, *Ev, *Rk, *Rv, *q1bl, *qn, *ql, *ql2, *qlnb, *qb, *A, *Anb, *dxe, *dxb, *ga, *gc, *gr, *gq, *h2, *hs;
   int32_t* nbr;
   int32_t* counters;       // [64] work counters of the persistent attention workgroups (one per layer), zeroed per forward
   size_t total;
@@ -67,6 +67,7 @@ static Workspace carve(float* base, int B, int NP, int NL, int K) {
   w.h2 = w.hs = nullptr;                                 // the shipped schedule never reads them (g_side_lin is the constant 0)
 #endif
   w.counters = reinterpret_cast<int32_t*>(take(DD_NUM_COUNTERS + DD_NUM_FLAGS));   // (+ the layer-tail queue's flag words)
+  w.gq = take((size_t)B * NL * 3);                       // restraint gradient (last: every earlier buffer keeps its offset)
   w.total = off;
   return w;
 }
@@ -757,6 +758,7 @@ struct ModelOpts {
   const uint64_t* sample_keys = nullptr;   // per-sample noise keys of the *_keyed entry points ([B], device), not part of dd_model_opts
   const dd_fixed* fixed = nullptr;         // fixed atoms of the *_fixed entry points (a checked host copy), not part of dd_model_opts
   const int32_t* epoch = nullptr;          // resampling epoch of the *_resample entry points (a device int, read at every launch)
+  const RestraintArgs* restraints = nullptr;   // distance restraints of the *_guided entry points (checked), not part of dd_model_opts
 };
 static int check_blocks(const dd_sampler* s, int num_blocks) {
   if (!s || num_blocks < 1) return DD_ERR_BAD_ARG;
@@ -1137,10 +1139,12 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
   return DD_OK;
 }
 
-// Drift gradients of the enabled guidance terms into w.ga / w.gc / w.gr, evaluated at x_t BEFORE the position update
+// Drift gradients of the enabled guidance terms into w.ga / w.gc / w.gr / w.gq, evaluated at x_t BEFORE the position update
 // (decompdiff.py:638-677); NULL where a term is off.  profiled: the launches count towards dd_profile_step's step category.
-struct DriftGrads { const float *ga = nullptr, *gc = nullptr, *gr = nullptr; };
-static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled, hipStream_t st, DriftGrads* d) {
+// restraints: the chain's distance restraints or NULL; their kernel reads the run state (counter_bias as the step kernels').
+struct DriftGrads { const float *ga = nullptr, *gc = nullptr, *gr = nullptr, *gq = nullptr; int scale_q = 0; };
+static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled, hipStream_t st, DriftGrads* d,
+                         const RestraintArgs* restraints = nullptr, int counter_bias = 0) {
   const int B = s->B, NL = s->NL;
   auto run = [&](auto&& launch) -> int {
     ProfScope prof_scope(DD_PROF_STEP, st, profiled);
@@ -1163,6 +1167,13 @@ static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled,
     DD_TRY(run([&] { return launch_drift_arms_repul(s->lig_pos, s->decomp_index, B, NL, s->repul_max_d, s->drift_repul, w.gr, 0,
                                                     s->drift_norm_batch, st); }));
     d->gr = w.gr;
+  }
+  if (restraints) {
+    RestraintArgs q = *restraints;
+    q.pos = s->lig_pos; q.decomp = s->decomp_index; q.nl_real = s->nl_real; q.step_counter = s->step_counter;
+    q.counter_bias = counter_bias; q.grad = w.gq; q.accumulate = 0; q.dist = nullptr; q.winner = nullptr;
+    DD_TRY(run([&] { return launch_drift_restraint(q, st); }));
+    d->gq = w.gq; d->scale_q = restraints->scale;
   }
   return DD_OK;
 }
@@ -1193,21 +1204,21 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint6
   p->B = B; p->NL = NL; p->T = s->T; p->step_counter = s->step_counter; p->NP = s->NP;
   p->xt = s->lig_pos; p->tab_pos = s->tab_pos; p->tab_score = s->tab_score;
   p->atom_std = s->atom_std; p->offset = s->offset; p->grad_a = d.ga; p->scale_a = s->armsca_scale; p->grad_c = d.gc;
-  p->scale_c = s->clash_scale; p->grad_r = d.gr; p->scale_r = s->repul_scale; p->eps = s->eps; p->traj_pos = s->traj_pos;
+  p->scale_c = s->clash_scale; p->grad_r = d.gr; p->scale_r = s->repul_scale; p->grad_q = d.gq; p->scale_q = d.scale_q; p->eps = s->eps; p->traj_pos = s->traj_pos;
   p->sample_keys = sample_keys;
   if (fixed) { p->fx_mask = fixed->mask; p->fx_x0c = fixed->x0c; p->fx_cc = fixed->cc; p->fx_tab = fixed->tab; p->fx_mode = fixed->mode; p->epoch = epoch; }
 }
 
 static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr, const uint64_t* sample_keys = nullptr,
-                          const dd_fixed* fixed = nullptr, const int32_t* epoch = nullptr) {
+                          const dd_fixed* fixed = nullptr, const int32_t* epoch = nullptr, const RestraintArgs* restraints = nullptr) {
   const Fwd f(s);
   const Workspace& w = f.w;
+  const bool advanced = fold && fold->advance;
   DriftGrads d;
-  DD_TRY(launch_drifts(s, w, true, st, &d));
+  DD_TRY(launch_drifts(s, w, true, st, &d, restraints, advanced ? 1 : 0));
   StepRowsArgs r, rb;
   StepPosArgs p;
   fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p, epoch);
-  const bool advanced = fold && fold->advance;
   r.counter_bias = rb.counter_bias = p.counter_bias = advanced ? 1 : 0;
   r.hid = w.qn; r.W2 = f.GW(DD_G_VH_W2); r.b2 = f.GW(DD_G_VH_b2); r.logits_out = s->pred_v;
   rb.hid = w.qb; rb.W2 = f.GW(DD_G_BH_W2); rb.b2 = f.GW(DD_G_BH_b2); rb.logits_out = s->pred_bond;
@@ -1633,7 +1644,7 @@ static int one_step(const dd_sampler* s, hipStream_t st, const dd::ModelOpts& mo
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
   int rc = dd::forward_impl(s, st, &fold, mo);
   if (rc != DD_OK) return rc;
-  return dd::heads_and_step(s, st, &fold, mo.sample_keys, mo.fixed, mo.epoch);
+  return dd::heads_and_step(s, st, &fold, mo.sample_keys, mo.fixed, mo.epoch, mo.restraints);
 }
 
 extern "C" int dd_reverse_step(const dd_sampler* s, const float* logits_v, const float* logits_b, const float* x0, void* stream) {
@@ -1695,21 +1706,35 @@ static int read_resample(const dd_resample* rsm, const dd_sampler* s, const dd_f
 }
 
 static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
-                             const dd_resample* rsm, int n_steps, void* stream);
+                             const dd_resample* rsm, const dd_restraints* rst, int n_steps, void* stream);
 
 extern "C" int dd_sample_steps_fixed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                                      int n_steps, void* stream) {
-  return sample_steps_impl(s, opts, sample_keys, fixed, nullptr, n_steps, stream);
+  return sample_steps_impl(s, opts, sample_keys, fixed, nullptr, nullptr, n_steps, stream);
 }
 
 extern "C" int dd_sample_steps_resample(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                                         const dd_resample* resample, int n_steps, void* stream) {
   if (!resample) return DD_ERR_BAD_ARG;
-  return sample_steps_impl(s, opts, sample_keys, fixed, resample, n_steps, stream);
+  return dd_sample_steps_guided(s, opts, sample_keys, fixed, resample, nullptr, n_steps, stream);
+}
+
+// The last of the suffix chain: keys, fixed atoms, resampling and distance restraints, each NULL-able
+extern "C" int dd_sample_steps_guided(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                                      const dd_resample* resample, const dd_restraints* restraints, int n_steps, void* stream) {
+  return sample_steps_impl(s, opts, sample_keys, fixed, resample, restraints, n_steps, stream);
+}
+
+// The chain's dd_restraints, checked against the sampler, for the step entry points (NULL stays "no restraints")
+static int read_step_restraints(const dd_restraints* rst, const dd_sampler* s, hipStream_t st, dd::RestraintArgs* out) {
+  if (!s || !s->workspace || !s->lig_pos) return DD_ERR_BAD_ARG;
+  const int rc = dd::read_restraints(rst, s->B, s->NL, s->decomp_index != nullptr, true, st, out);
+  if (rc != DD_OK) return rc;
+  return out->t_min < 0 || out->t_max >= s->T ? DD_ERR_BAD_ARG : DD_OK;
 }
 
 static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
-                             const dd_resample* rsm, int n_steps, void* stream) {
+                             const dd_resample* rsm, const dd_restraints* rst, int n_steps, void* stream) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || n_steps < 0 || keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
@@ -1721,6 +1746,12 @@ static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, con
   mo.fixed = fixed != nullptr ? &fx : nullptr;
   mo.epoch = rsm != nullptr ? rs.epoch : nullptr;
   hipStream_t st = (hipStream_t)stream;
+  dd::RestraintArgs ra;
+  if (rst != nullptr) {
+    const int rrc = read_step_restraints(rst, s, st, &ra);
+    if (rrc != DD_OK) return rrc;
+    mo.restraints = &ra;
+  }
   for (int i = 0; i < n_steps; ++i) {
     int rc = one_step(s, st, mo);
     if (rc != DD_OK) return rc;
@@ -1853,17 +1884,23 @@ extern "C" int dd_chain_init(const dd_sampler* s, const uint64_t* sample_keys, c
 }
 
 static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
-                             const dd_resample* rsm, int steps_per_graph, void* stream, void** graph_out);
+                             const dd_resample* rsm, const dd_restraints* rst, int steps_per_graph, void* stream, void** graph_out);
 
 extern "C" int dd_graph_create_fixed(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                                      int steps_per_graph, void* stream, void** graph_out) {
-  return graph_create_impl(s, opts, sample_keys, fixed, nullptr, steps_per_graph, stream, graph_out);
+  return graph_create_impl(s, opts, sample_keys, fixed, nullptr, nullptr, steps_per_graph, stream, graph_out);
 }
 
 extern "C" int dd_graph_create_resample(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                                         const dd_resample* resample, int steps_per_graph, void* stream, void** graph_out) {
   if (!resample) return DD_ERR_BAD_ARG;
-  return graph_create_impl(s, opts, sample_keys, fixed, resample, steps_per_graph, stream, graph_out);
+  return dd_graph_create_guided(s, opts, sample_keys, fixed, resample, nullptr, steps_per_graph, stream, graph_out);
+}
+
+extern "C" int dd_graph_create_guided(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                                      const dd_resample* resample, const dd_restraints* restraints, int steps_per_graph, void* stream,
+                                      void** graph_out) {
+  return graph_create_impl(s, opts, sample_keys, fixed, resample, restraints, steps_per_graph, stream, graph_out);
 }
 
 extern "C" int dd_resample_jump(const dd_sampler* s, const uint64_t* sample_keys, const dd_fixed* fixed, const dd_resample* resample,
@@ -1886,7 +1923,7 @@ extern "C" int dd_sampler_reset_resample(const dd_sampler* s, const dd_resample*
 }
 
 static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
-                             const dd_resample* rsm, int steps_per_graph, void* stream, void** graph_out) {
+                             const dd_resample* rsm, const dd_restraints* rst, int steps_per_graph, void* stream, void** graph_out) {
   dd::ModelOpts mo;
   if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
   if (!check_step_sampler(s) || !graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
@@ -1902,6 +1939,12 @@ static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, con
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   int rc = dd::check_shapes(s);
   if (rc != DD_OK) return rc;
+  dd::RestraintArgs ra;
+  if (rst != nullptr) {
+    rc = read_step_restraints(rst, s, st, &ra);
+    if (rc != DD_OK) return rc;
+    mo.restraints = &ra;
+  }
   StepGraph* g = new StepGraph();
   rc = capture_steps(s, mo, steps_per_graph, st, &g->graph, &g->exec);
   if (rc != DD_OK) {

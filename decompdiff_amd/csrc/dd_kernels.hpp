@@ -148,6 +148,30 @@ int launch_drift_arms_repul(const float* lig_pos, const int32_t* decomp_index, i
 // (nl_real: padded heterogeneous batches -- padding atoms are neither centres nor candidates)
 int launch_drift_clash(const float* lig_pos, const float* offset, const float* full_protein_pos, int B, int NL, int NF,
                        float sigma, float gamma, float* grad, int accumulate, const int32_t* nl_real, hipStream_t st);
+// Distance restraints (include/decompdiff_hip.h, dd_restraints): gradient of sum_r w_r (relu(min_d_r - d_r) + relu(d_r - max_d_r)),
+// d_r the distance of the point to the explicit atom or to the first nearest member of the group.  Every pointer is a DEVICE
+// pointer read at launch; R bounds what ptr may address.  step_counter != NULL: the term acts only while t_min <= t <= t_max
+// (t = run state's t_start - (steps done - counter_bias)) and writes zeros outside.
+struct RestraintArgs {
+  const float* pos;              // [B*NL,3] centred ligand coordinates
+  const int32_t* decomp;         // [B*NL] arm ids (-1 scaffold, -2 padding) or NULL: arm / scaffold groups are empty
+  const int32_t* nl_real;        // [B] real ligand sizes of a padded batch or NULL
+  int B, NL, R;
+  const int32_t* ptr;            // [B+1] CSR: restraints ptr[b] .. ptr[b+1] belong to sample b
+  const float *point, *min_d, *max_d, *weight;   // [R,3], [R], [R], [R]; points in the frame of pos
+  const int32_t *atom, *group;   // [R] row within the sample or -1: the group (DD_RESTRAINT_ANY, -1 scaffold, >= 0 arm id)
+  const int32_t* step_counter;   // run state [4] or NULL: always active
+  int counter_bias, t_min, t_max;
+  int scale;                     // (host side only: the step multiplies the gradient by tab_score[t])
+  float* grad;                  // [B*NL,3], every row written
+  int accumulate;
+  float* dist;                   // [R] or NULL
+  int32_t* winner;               // [R] row within the sample or -1, or NULL
+};
+int launch_drift_restraint(const RestraintArgs& a, hipStream_t st);
+// the caller's dd_restraints, checked, as the kernel's arguments (pos / decomp / nl_real / step_counter / outputs left to the caller);
+// check_contents: also what only the device arrays say -- copies ptr / atom / group to the host and waits for `st`
+int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, bool check_contents, hipStream_t st, RestraintArgs* out);
 int launch_extract_ligand(const float* x, int B, int NP, int NL, float* out, hipStream_t st);
 
 enum { M_NE = 0, M_NB = 1, M_BL = 2, M_PE = 3, M_PB = 4 };
@@ -248,7 +272,8 @@ struct StepPosArgs {
   const float* offset;      // [B,3]
   const float* grad_a; int scale_a;   // armsca gradient (may be NULL)
   const float* grad_c; int scale_c;   // clash gradient (may be NULL)
-  const float* grad_r; int scale_r;   // arms_repul gradient (may be NULL); the three are added in this order
+  const float* grad_r; int scale_r;   // arms_repul gradient (may be NULL)
+  const float* grad_q; int scale_q;   // restraint gradient (may be NULL); the four are added in this order
   const float* eps;         // [n_steps,B*NL,3] or NULL
   float* traj_pos;          // [n_steps,B*NL,3] or NULL
   const uint64_t* sample_keys;   // [B] per-sample noise keys or NULL: key sample_keys[b], index 3 * i + c inside the sample

@@ -5,9 +5,13 @@
 //                 (ShiftedSoftplus -> Linear, decompdiff.py:194-211), log_softmax, categorical
 //                 posterior q(v_{t-1}|v_t, v0) in log space, Gumbel-argmax sample, trajectories.
 //   k_step_pos    one thread per ligand coordinate: C0 posterior mean, drift, noise.
-//   k_drift_*     gradients of the armsca_prox / clash energies at x_t.
+//   k_drift_*     gradients of the armsca_prox / clash / arms_repul energies at x_t, and of the caller's distance restraints
+//                 (k_drift_restraint, EXTENSION: points in the pocket that an atom or the nearest atom of a group must keep to).
 // The current step index lives in device memory (step_counter) so that one captured hipGraph
 // can be replayed for every step.
+#include <string.h>
+#include <vector>
+
 #include "dd_kernels.hpp"
 
 namespace dd {
@@ -240,6 +244,7 @@ __global__ void k_step_pos(const StepPosArgs a) {
   if (a.grad_a) g += a.scale_a ? a.grad_a[idx] * a.tab_score[t] : a.grad_a[idx];
   if (a.grad_c) g += a.scale_c ? a.grad_c[idx] * a.tab_score[t] : a.grad_c[idx];
   if (a.grad_r) g += a.scale_r ? a.grad_r[idx] * a.tab_score[t] : a.grad_r[idx];
+  if (a.grad_q) g += a.scale_q ? a.grad_q[idx] * a.tab_score[t] : a.grad_q[idx];
   mean -= g;
   float e;
   if (a.eps) {
@@ -485,6 +490,87 @@ __global__ __launch_bounds__(256) void k_drift_clash(const float* __restrict__ p
   }
 }
 
+// ------------------------------------------------------------------------------ drift: restraint
+// E = sum_r w_r (relu(min_d_r - d_r) + relu(d_r - max_d_r)), d_r = |x_w - p_r|, w the explicit atom of restraint r or the FIRST
+// nearest member of its group in row order (include/decompdiff_hip.h, dd_restraints); no division by B or R.  One workgroup per
+// sample, lane = atom: 64 threads (NL <= 64: the reduction stays in registers) or 128 (the two waves' winners meet in LDS, one
+// 8-byte word each: key << 32 | row, double-buffered by the parity of the restraint so that one barrier per restraint is enough).
+// The winning lane adds into its own registers, restraints in ascending order: no atomics, the same bits on every run.  The
+// clamps pass their gradient at equality, a winner at distance 0 gives nothing (as k_drift_armsca), an empty group has distance
+// +inf and winner -1.  Memory-safe for any contents of the restraint arrays: ptr is clamped to [0, R], an atom outside the
+// sample matches no lane.  Outside the time window the gradient rows are zeros; dist / winner are reported either way.
+__global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint(const RestraintArgs a) {
+  __shared__ unsigned long long wk[2][2];
+  const int b = blockIdx.x, l = threadIdx.x, NL = a.NL;
+  int n = a.nl_real ? a.nl_real[b] : NL;
+  n = n < NL ? n : NL;
+  float x = 0.f, y = 0.f, z = 0.f;
+  int my_arm = -2;
+  if (l < n) {
+    const float* p = a.pos + ((long)b * NL + l) * 3;
+    x = p[0]; y = p[1]; z = p[2];
+    if (a.decomp) my_arm = a.decomp[(long)b * NL + l];
+  }
+  bool active = true;
+  if (a.step_counter != nullptr) {
+    const RunState rs = load_run_state(a.step_counter, a.counter_bias);
+    const int t = rs.t_start - rs.step;
+    active = t >= a.t_min && t <= a.t_max;
+  }
+  int r0 = a.ptr[b], r1 = a.ptr[b + 1];
+  r0 = r0 < 0 ? 0 : (r0 > a.R ? a.R : r0);
+  r1 = r1 < r0 ? r0 : (r1 > a.R ? a.R : r1);
+  if (!active && a.dist == nullptr && a.winner == nullptr) r1 = r0;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  for (int r = r0; r < r1; ++r) {                          // (r0, r1: the same in every thread of the workgroup)
+    const int at = a.atom[r], gp = a.group[r];
+    const bool mine = l < n && (at >= 0 ? l == at : (gp == DD_RESTRAINT_ANY || (a.decomp != nullptr && gp >= -1 && my_arm == gp)));
+    const float dx = x - a.point[3 * (long)r], dy = y - a.point[3 * (long)r + 1], dz = z - a.point[3 * (long)r + 2];
+    const float d = mine ? sqrtf(dx * dx + dy * dy + dz * dz) : INFINITY;
+    unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)l;   // d >= 0 (or +inf): bit order = float order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long k2 = (unsigned long long)__shfl_xor((long long)key, off);
+      key = k2 < key ? k2 : key;
+    }
+    if (blockDim.x > 64) {
+      if ((l & 63) == 0) wk[r & 1][l >> 6] = key;
+      __syncthreads();
+      const unsigned long long k0 = wk[r & 1][0], k1 = wk[r & 1][1];
+      key = k1 < k0 ? k1 : k0;
+    }
+    const float best = __uint_as_float((unsigned)(key >> 32));
+    const int win = best < INFINITY || best != best ? (int)(unsigned)(key & 0xffffffffull) : -1;
+    if (l == 0) {
+      if (a.dist) a.dist[r] = best;
+      if (a.winner) a.winner[r] = win;
+    }
+    if (active && l == win) {
+      float coef = 0.f;
+      if (a.min_d[r] - best >= 0.f) coef -= 1.f;
+      if (best - a.max_d[r] >= 0.f) coef += 1.f;
+      coef *= a.weight[r];
+      if (coef != 0.f && best > 0.f) {
+        const float inv = 1.0f / best;
+        gx = __fadd_rn(gx, __fmul_rn(__fmul_rn(coef, dx), inv));
+        gy = __fadd_rn(gy, __fmul_rn(__fmul_rn(coef, dy), inv));
+        gz = __fadd_rn(gz, __fmul_rn(__fmul_rn(coef, dz), inv));
+      }
+    }
+  }
+  if (l < NL) {
+    float* g = a.grad + ((long)b * NL + l) * 3;
+    if (a.accumulate) { g[0] += gx; g[1] += gy; g[2] += gz; }
+    else { g[0] = gx; g[1] = gy; g[2] = gz; }
+  }
+}
+int launch_drift_restraint(const RestraintArgs& a, hipStream_t st) {
+  if (a.B <= 0 || a.NL <= 0 || a.NL > DD_NL_MAX || a.R < 0) return DD_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_drift_restraint, dim3(a.B), dim3(a.NL > 64 ? 128 : 64), 0, st, a);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
+
 
 // ---------------------------------------------------------------------------------- one launch per reverse step
 // Bond rows, atom rows and the coordinate update are independent given the head activations, so they share one
@@ -591,6 +677,7 @@ __device__ __forceinline__ void step_pos_elem(const StepPosArgs& a, const int id
   if (a.grad_a) g += a.scale_a ? a.grad_a[idx] * a.tab_score[t] : a.grad_a[idx];
   if (a.grad_c) g += a.scale_c ? a.grad_c[idx] * a.tab_score[t] : a.grad_c[idx];
   if (a.grad_r) g += a.scale_r ? a.grad_r[idx] * a.tab_score[t] : a.grad_r[idx];
+  if (a.grad_q) g += a.scale_q ? a.grad_q[idx] * a.tab_score[t] : a.grad_q[idx];
   mean -= g;
   float e;
   if (a.eps) {
@@ -948,6 +1035,55 @@ extern "C" int dd_drift_clash(const float* lig_pos, const float* offset, const f
   if (!lig_pos || !offset || !full_protein_pos || !grad || B <= 0 || NL <= 0 || NF <= 0) return DD_ERR_BAD_ARG;
   return dd::launch_drift_clash(lig_pos, offset, full_protein_pos, B, NL, NF, sigma, gamma, grad, accumulate, nullptr,
                                 (hipStream_t)stream);
+}
+
+// The caller's dd_restraints as a checked copy (fields beyond its `size` are NULL / 0) laid into the kernel's arguments.  What the
+// host can see is checked here; check_contents adds what only the device arrays say (a synchronous copy of ptr / atom / group on
+// `st`, for the entry points that are called outside a capture).
+namespace dd {
+int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, bool check_contents, hipStream_t st, RestraintArgs* out) {
+  memset(out, 0, sizeof(*out));
+  if (rs == nullptr || rs->size < (int32_t)sizeof(int32_t) || rs->size > 4096) return DD_ERR_BAD_ARG;
+  dd_restraints r;
+  memset(&r, 0, sizeof(r));
+  memcpy(&r, rs, (size_t)rs->size < sizeof(r) ? (size_t)rs->size : sizeof(r));
+  if (B <= 0 || NL <= 0 || NL > DD_NL_MAX || r.R < 0 || !r.ptr || r.t_min > r.t_max) return DD_ERR_BAD_ARG;
+  if (r.R > 0 && (!r.point || !r.min_d || !r.max_d || !r.weight || !r.atom || !r.group)) return DD_ERR_BAD_ARG;
+  out->B = B; out->NL = NL; out->R = r.R; out->ptr = r.ptr; out->point = r.point; out->min_d = r.min_d; out->max_d = r.max_d;
+  out->weight = r.weight; out->atom = r.atom; out->group = r.group; out->t_min = r.t_min; out->t_max = r.t_max; out->scale = r.scale != 0;
+  if (!check_contents) return DD_OK;
+  std::vector<int32_t> h((size_t)B + 1 + 2 * (size_t)r.R);
+  auto fetch = [&](int32_t* dst, const int32_t* src, size_t n) {         // (n ints to the host, waited for)
+    return n == 0 || (hipMemcpyAsync(dst, src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                      hipStreamSynchronize(st) == hipSuccess);
+  };
+  if (!fetch(h.data(), r.ptr, (size_t)B + 1)) { (void)hipGetLastError(); return DD_ERR_HIP; }
+  if (h[0] != 0 || h[B] != r.R) return DD_ERR_BAD_ARG;                   // (before anything of length R is read)
+  for (int b = 0; b < B; ++b)
+    if (h[b + 1] < h[b]) return DD_ERR_BAD_ARG;
+  if (!fetch(h.data() + B + 1, r.atom, (size_t)r.R) || !fetch(h.data() + B + 1 + r.R, r.group, (size_t)r.R)) {
+    (void)hipGetLastError();
+    return DD_ERR_HIP;
+  }
+  for (int i = 0; i < r.R; ++i) {
+    const int at = h[B + 1 + i], gp = h[B + 1 + r.R + i];
+    if (at < -1 || at >= NL) return DD_ERR_BAD_ARG;
+    if (at == -1 && gp != DD_RESTRAINT_ANY && (gp < -1 || !has_decomp)) return DD_ERR_BAD_ARG;
+  }
+  return DD_OK;
+}
+}  // namespace dd
+
+extern "C" int dd_drift_restraint(const float* lig_pos, const int32_t* decomp_index, const int32_t* nl_real, int B, int NL,
+                                  const dd_restraints* restraints, const int32_t* step_counter, float* grad, int accumulate, float* dist,
+                                  int32_t* winner, void* stream) {
+  if (!lig_pos || !grad || !restraints) return DD_ERR_BAD_ARG;
+  dd::RestraintArgs a;
+  const int rc = dd::read_restraints(restraints, B, NL, decomp_index != nullptr, true, (hipStream_t)stream, &a);
+  if (rc != DD_OK) return rc;
+  a.pos = lig_pos; a.decomp = decomp_index; a.nl_real = nl_real; a.step_counter = step_counter; a.grad = grad;
+  a.accumulate = accumulate; a.dist = dist; a.winner = winner;
+  return dd::launch_drift_restraint(a, (hipStream_t)stream);
 }
 
 // Test aid: the production noise of one step, exactly as the step kernels draw it.  kind (low byte) 1: uniforms [rows,8] of the

@@ -47,7 +47,8 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                                    arms_natoms_config=None, scaffold_natoms_config=None, natoms_sampler=None,
                                    atom_prior_probs=None, bond_prior_probs=None, pool_batches: int = 1,
                                    sample_key_seed: Optional[int] = None, first_sample_index: int = 0,
-                                   fixed_fn=None, fixed_mode: str = "hold", resample=None, init: str = "host") -> Dict[str, list]:
+                                   fixed_fn=None, fixed_mode: str = "hold", resample=None, init: str = "host",
+                                   restraints_fn=None, restraint_opts=None) -> Dict[str, list]:
     """Sample ``num_samples`` ligands for one pocket in batches of ``batch_size``.
 
     ``pool_batches`` > 1 assembles that many consecutive batches exactly as the reference would (same random draws, same
@@ -93,6 +94,13 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     ``resample`` (not None; needs ``fixed_fn``): ``dict(jump_length=j, n_resample=r)``, handed to every model call that holds
     atoms (``sample_diffusion(resample=...)``, RePaint's jump-back schedule); the trajectories then have one entry per position of
     ``model.resample_schedule`` instead of one per step.  A model call in which ``fixed_fn`` held nothing runs the plain chain.
+
+    ``restraints_fn(sample_index, decomp_index_of_sample)`` (not None): distance restraints -- for output sample
+    ``first_sample_index + g`` it returns ``dict(point [r,3], min_d, max_d[, weight, atom, group])`` (``atom``: rows of the SAMPLE's
+    own order, -1 = use ``group``; the rest as the ``restraint`` entry of ``sample_diffusion(energy_drift_opt=...)``), or None.  The
+    dicts are collated into one ``restraint`` entry per model call (`collate_restraints`; ``restraint_opts``: its ``scale`` /
+    ``t_min`` / ``t_max``), appended to ``energy_drift_opt``.  Works with ``pool_batches``, ``sample_key_seed`` and
+    ``init="device"``; the output gains ``restraint_dist`` / ``restraint_atom`` per sample (``restraint_atom``: sample-local row).
     """
     out = {k: [] for k in ("pred_pos", "pred_v", "pred_pos_traj", "pred_v_traj", "pred_v0_traj", "pred_vt_traj",
                            "pred_bond_index", "pred_bond_type", "pred_b_traj", "pred_bt_traj", "decomp_mask")}
@@ -188,10 +196,15 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                 extra["fixed"] = fixed
                 if resample is not None:
                     extra["resample"] = resample
+        drift_opt, rs_entry = energy_drift_opt, None
+        if restraints_fn is not None and extra:
+            rs_entry = collate_restraints(restraints_fn, int(first_sample_index) + n_done, n_atoms, batch["ligand_decomp_index"],
+                                          **(restraint_opts or {}))
+            drift_opt = list(energy_drift_opt or []) + [rs_entry]
         n_done += n_data
         t1 = time.time()
         r = model.sample_diffusion(num_steps=num_steps, center_pos_mode=center_pos_mode,
-                                   energy_drift_opt=energy_drift_opt, **extra, **dev_batch)
+                                   energy_drift_opt=drift_opt, **extra, **dev_batch)
         cum_atoms = np.cumsum([0] + n_atoms)                                   # (:367)
         cum_bonds = np.cumsum([0] + n_bonds)                                   # (:390-393)
         pos = r["pos"].cpu().numpy().astype(np.float64)
@@ -219,6 +232,11 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
             out["pred_vt_traj"].append(vt_traj[k])
             out["pred_b_traj"].append(b_traj[k])
             out["pred_bt_traj"].append(bt_traj[k])
+            if rs_entry is not None:
+                mine = rs_entry["sample"] == k
+                ra = r["restraint_atom"][mine]
+                out.setdefault("restraint_dist", []).append(r["restraint_dist"][mine].numpy())
+                out.setdefault("restraint_atom", []).append(torch.where(ra >= 0, ra - int(a0), ra).numpy())
         time_list.append(time.time() - t1)
     out["time_list"] = time_list
     return out
@@ -248,6 +266,43 @@ def collate_fixed(fixed_fn, first_index: int, n_atoms: List[int], decomp_index: 
     out["pos"] = out["pos"].to(torch.float32)
     out["mode"] = mode
     return out
+
+
+def collate_restraints(restraints_fn, first_index: int, n_atoms: List[int], decomp_index: torch.Tensor, scale=False, t_min=None,
+                       t_max=None):
+    """The per-sample dicts of ``restraints_fn`` for the samples ``first_index ...`` of one model call (``n_atoms``: their ligand
+    sizes, ``decomp_index``: the call's flat arm ids) as ONE ``restraint`` entry of energy_drift_opt: samples numbered by their
+    place in the call, explicit atoms moved from the sample's rows to the call's flat rows.  A sample for which the function
+    returns None has no restraints; a call without any still carries the (empty) entry."""
+    from .model import RESTRAINT_ANY
+    cols = {k: [] for k in ("sample", "point", "min_d", "max_d", "weight", "atom", "group")}
+    a0 = 0
+    for k, n in enumerate(n_atoms):
+        f = restraints_fn(first_index + k, decomp_index[a0:a0 + n])
+        if f is not None:
+            point = torch.as_tensor(f["point"], dtype=torch.float32).reshape(-1, 3)
+            r = int(point.shape[0])
+
+            def col(name, default, dtype):                     # a number for all r restraints, or one value each
+                t = torch.as_tensor(f.get(name, default), dtype=dtype)
+                return t.expand(r) if t.dim() == 0 else t
+            atom = col("atom", -1, torch.long)
+            if tuple(atom.shape) != (r,) or bool((atom < -1).any()) or bool((atom >= n).any()):
+                raise ValueError(f"restraints_fn: sample {first_index + k} has {n} ligand atoms, 'atom' must hold {r} rows in [-1, {n})")
+            cols["sample"].append(torch.full((r,), k, dtype=torch.long))
+            cols["point"].append(point)
+            cols["atom"].append(torch.where(atom >= 0, atom + a0, atom))
+            cols["group"].append(col("group", RESTRAINT_ANY, torch.long))
+            for name, default in (("min_d", None), ("max_d", None), ("weight", 1.0)):
+                if f.get(name, default) is None:
+                    raise ValueError(f"restraints_fn: sample {first_index + k} gives no {name}")
+                cols[name].append(col(name, default, torch.float32))
+            if any(tuple(cols[name][-1].shape) != (r,) for name in ("group", "min_d", "max_d", "weight")):
+                raise ValueError(f"restraints_fn: sample {first_index + k} has {r} points, every other field must be a number or hold {r} values")
+        a0 += n
+    empty = {"sample": torch.long, "point": torch.float32, "atom": torch.long, "group": torch.long}
+    out = {k: (torch.cat(v) if v else torch.zeros((0, 3) if k == "point" else (0,), dtype=empty.get(k, torch.float32))) for k, v in cols.items()}
+    return dict(out, type="restraint", scale=bool(scale), t_min=t_min, t_max=t_max)
 
 
 def _accepts_extras(model) -> bool:

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "dd_sample_steps_fixed", "dd_graph_create_fixed", "dd_fixed_init",
     "dd_sample_steps_resample", "dd_graph_create_resample", "dd_resample_jump", "dd_sampler_reset_resample",
     "dd_chain_init",
+    "dd_drift_restraint", "dd_sample_steps_guided", "dd_graph_create_guided",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -162,6 +163,26 @@ def init_struct(mode, cc, std, atom_log_prior=None, bond_log_prior=None, x0c=Non
     return f
 
 
+RESTRAINT_ANY = -3                                     # DD_RESTRAINT_ANY: every real ligand atom of the sample
+
+
+class DDRestraints(ctypes.Structure):
+    """struct dd_restraints (include/decompdiff_hip.h): the distance restraints of a chain, sorted by sample (CSR ``ptr``); `size` =
+    sizeof of this struct, every pointer a DEVICE pointer that the kernel reads at every launch (see `restraints_struct`)."""
+    _fields_ = [("size", c_int32), ("R", c_int32), ("ptr", c_void_p), ("point", c_void_p), ("min_d", c_void_p), ("max_d", c_void_p),
+                ("weight", c_void_p), ("atom", c_void_p), ("group", c_void_p), ("scale", c_int32), ("t_min", c_int32), ("t_max", c_int32)]
+
+
+def restraints_struct(R, ptr, point, min_d, max_d, weight, atom, group, scale, t_min, t_max) -> DDRestraints:
+    """A filled dd_restraints from device tensors (the caller keeps them alive): ptr int32 [B+1], point fp32 [R,3], min_d / max_d /
+    weight fp32 [R], atom / group int32 [R] (atom: the row within the sample or -1; group: RESTRAINT_ANY, -1 scaffold, >= 0 arm)."""
+    r = DDRestraints()
+    r.size, r.R, r.scale, r.t_min, r.t_max = ctypes.sizeof(DDRestraints), int(R), int(bool(scale)), int(t_min), int(t_max)
+    for name, t in (("ptr", ptr), ("point", point), ("min_d", min_d), ("max_d", max_d), ("weight", weight), ("atom", atom), ("group", group)):
+        setattr(r, name, None if t is None else t.data_ptr())
+    return r
+
+
 L0_TABLE_FLOATS = 16 * 640 + 16 * 1280 + 5 * 640 + 16 * 128 + 16 * 128 + 80 * 128      # DD_L0_TABLE_FLOATS
 
 
@@ -274,6 +295,13 @@ def load():
         "dd_sampler_reset_resample": [S, POINTER(DDResample), c_void_p],
         # (the chain's first level drawn on the device: sample_keys, the host struct dd_init)
         "dd_chain_init": [S, c_void_p, POINTER(DDInit), c_void_p],
+        # (distance restraints: the op-level gradient; the last step pair -- keys, fixed, resample, restraints, each NULL-able)
+        "dd_drift_restraint": [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(DDRestraints), c_void_p, c_void_p, c_int, c_void_p,
+                               c_void_p, c_void_p],
+        "dd_sample_steps_guided": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), POINTER(DDResample), POINTER(DDRestraints), c_int,
+                                   c_void_p],
+        "dd_graph_create_guided": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), POINTER(DDResample), POINTER(DDRestraints), c_int,
+                                   c_void_p, POINTER(c_void_p)],
         "dd_drift_armsca": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_clash": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p],
         "dd_drift_arms_repul": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p],

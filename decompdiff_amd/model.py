@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
+import math
 import os
 import time
 from typing import Dict, Optional
@@ -327,12 +328,121 @@ def _as_resample(resample, fixed, noise, num_timesteps, num_steps, start_step):
     return dict(j=j, r=r, runs=runs, t_traj=torch.tensor(times, dtype=torch.int64), n_total=len(times))
 
 
+RESTRAINT_ANY = hip_lib.RESTRAINT_ANY              # group id "every real ligand atom of the sample" (not an arm id, not -1, not -2)
+_RESTRAINT_KEYS = {"type", "sample", "point", "min_d", "max_d", "weight", "atom", "group", "scale", "t_min", "t_max"}
+
+
+def _split_restraints(energy_drift_opt):
+    """``energy_drift_opt`` as (the entries of the three built-in terms -- what `_drift_fields` takes --, the ``restraint`` entry or
+    None).  The term may be listed once (ValueError)."""
+    if energy_drift_opt is None:
+        return None, None
+    mine = [dr for dr in energy_drift_opt if isinstance(dr, dict) and dr.get("type") == "restraint"]
+    if len(mine) > 1:
+        raise ValueError("energy_drift_opt lists 'restraint' twice: put every restraint into one entry")
+    return [dr for dr in energy_drift_opt if not (isinstance(dr, dict) and dr.get("type") == "restraint")], (mine[0] if mine else None)
+
+
+def _as_restraints(entry, batch_ligand, ligand_decomp_index, num_timesteps):
+    """The ``restraint`` entry of energy_drift_opt, validated (ValueError) into host tensors in the CALLER's restraint order:
+    dict(R, sample int64 [R], point f32 [R,3], min_d / max_d / weight f32 [R], atom int32 [R] -- the row WITHIN the sample, or -1 --,
+    group int32 [R], first int64 [B] -- the first flat ligand row of every sample --, scale, t_min, t_max)."""
+    if not isinstance(entry, dict) or set(entry) - _RESTRAINT_KEYS or "sample" not in entry or "point" not in entry:
+        raise ValueError(f"a restraint entry takes the keys {sorted(_RESTRAINT_KEYS)} and needs sample and point")
+    bl = batch_ligand.detach().cpu().long()
+    n = int(bl.numel())
+    B = int(bl.max()) + 1 if n else 0
+    counts = torch.bincount(bl, minlength=B) if n else torch.zeros(0, dtype=torch.long)
+    first = torch.cumsum(counts, 0) - counts
+    if n and not torch.equal(bl, torch.arange(B).repeat_interleave(counts)):
+        raise ValueError("restraints need batch_ligand sorted by sample")
+
+    def ints(name, t, shape):
+        t = torch.as_tensor(t)
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex or tuple(t.shape) != shape:
+            raise ValueError(f"restraint['{name}'] must be an integer tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+        return t.detach().cpu().long()
+
+    sample = torch.as_tensor(entry["sample"])
+    if sample.dim() != 1:
+        raise ValueError("restraint['sample'] must be one-dimensional: the sample of every restraint")
+    R = int(sample.numel())
+    sample = ints("sample", sample, (R,))
+    if R and (int(sample.min()) < 0 or int(sample.max()) >= B):
+        raise ValueError(f"restraint['sample'] must lie in [0, {B})")
+    point = torch.as_tensor(entry["point"])
+    if not point.dtype.is_floating_point or tuple(point.shape) != (R, 3):
+        raise ValueError(f"restraint['point'] must be a float tensor of shape ({R}, 3), got {point.dtype} {tuple(point.shape)}")
+    point = point.detach().cpu().to(torch.float32)
+    if not bool(torch.isfinite(point).all()):
+        raise ValueError("restraint['point'] must be finite")
+    per = {}
+    for name, default in (("min_d", None), ("max_d", None), ("weight", 1.0)):
+        v = entry.get(name, default)
+        if v is None:
+            raise ValueError(f"a restraint entry needs {name}")
+        v = torch.as_tensor(v)
+        if v.dtype == torch.bool or v.dtype.is_complex or tuple(v.shape) not in ((), (R,)):
+            raise ValueError(f"restraint['{name}'] must be a number or a tensor of shape ({R},), got {tuple(v.shape)}")
+        per[name] = v.detach().cpu().to(torch.float32).expand(R).contiguous()
+    if bool(torch.isnan(per["min_d"]).any() | torch.isinf(per["min_d"]).any() | (per["min_d"] < 0).any()):
+        raise ValueError("restraint['min_d'] must be finite and >= 0")
+    if bool(torch.isnan(per["max_d"]).any() | (per["max_d"] == -math.inf).any() | (per["min_d"] > per["max_d"]).any()):
+        raise ValueError("restraint needs min_d <= max_d (max_d may be +inf)")
+    if not bool(torch.isfinite(per["weight"]).all()) or bool((per["weight"] < 0).any()):
+        raise ValueError("restraint['weight'] must be finite and >= 0")
+    atom = entry.get("atom")
+    atom = torch.full((R,), -1, dtype=torch.long) if atom is None else ints("atom", atom, (R,))
+    explicit = atom >= 0
+    if bool((atom < -1).any()) or bool((atom >= n).any()) or not torch.equal(bl[atom[explicit]], sample[explicit]):
+        raise ValueError("restraint['atom'] must be -1 (use group) or a flat ligand row of the restraint's own sample")
+    group = entry.get("group")
+    group = torch.full((R,), RESTRAINT_ANY, dtype=torch.long) if group is None else ints("group", group, (R,))
+    grp = group[~explicit]
+    if bool(((grp < -1) & (grp != RESTRAINT_ANY)).any()):
+        raise ValueError("restraint['group'] must be RESTRAINT_ANY, -1 (scaffold) or an arm id >= 0")
+    if ligand_decomp_index is None and bool((grp != RESTRAINT_ANY).any()):
+        raise ValueError("a scaffold / arm restraint needs ligand_decomp_index")
+    group = torch.where(explicit, torch.full_like(group, RESTRAINT_ANY), group)      # (not read for an explicit atom)
+    T = int(num_timesteps)
+    t_min, t_max = entry.get("t_min"), entry.get("t_max")
+    t_min, t_max = 0 if t_min is None else t_min, T - 1 if t_max is None else t_max
+    if any(isinstance(t, bool) or not isinstance(t, int) for t in (t_min, t_max)) or not 0 <= t_min <= t_max <= T - 1:
+        raise ValueError(f"restraint needs ints 0 <= t_min <= t_max <= {T - 1}")
+    scale = entry.get("scale", False)
+    if not isinstance(scale, (bool, int)):
+        raise ValueError("restraint['scale'] must be a bool")
+    local = torch.where(explicit, atom - first[sample], atom) if R else atom
+    return dict(R=R, sample=sample, point=point, min_d=per["min_d"], max_d=per["max_d"], weight=per["weight"],
+                atom=local.to(torch.int32), group=group.to(torch.int32), first=first, scale=bool(scale), t_min=int(t_min), t_max=int(t_max))
+
+
+def _place_restraints(rs, ids, B, offset):
+    """The call's restraints ``rs`` (`_as_restraints`) as ONE chain's share, sorted by the chain's sample slot -- a stable sort: the
+    caller's order within a sample -- with the CSR ``ptr`` [B+1] rebuilt.  ``ids``: the call's samples in the chain's order (None:
+    all, in order); ``offset`` [B,3]: the chain's offsets, points are centred as the ligand is (the fp32 ``p - offset[slot]``).
+    ``order``: the caller's restraint index of every row (the way back).  ``atom`` stays the row within the sample: the explicit
+    atom of a padded chain sits at padded row ``slot * NL + atom``, that of a group's chain at ``slot * n + atom``."""
+    slot_of = torch.arange(B) if ids is None else torch.full((int(rs["first"].numel()),), -1, dtype=torch.long).index_put_(
+        (torch.as_tensor(list(ids), dtype=torch.long),), torch.arange(len(ids)))
+    slot = slot_of[rs["sample"]] if rs["R"] else torch.zeros(0, dtype=torch.long)
+    keep = (slot >= 0).nonzero()[:, 0]
+    order = keep[torch.sort(slot[keep], stable=True).indices]
+    slot = slot[order]
+    ptr = torch.zeros(B + 1, dtype=torch.int32)
+    ptr[1:] = torch.cumsum(torch.bincount(slot, minlength=B), 0).to(torch.int32)
+    point = rs["point"][order].to(offset.device) - offset.detach().to(torch.float32)[slot.to(offset.device)]
+    return dict(R=int(order.numel()), order=order, slot=slot, ptr=ptr, point=point.contiguous(), min_d=rs["min_d"][order],
+                max_d=rs["max_d"][order], weight=rs["weight"][order], atom=rs["atom"][order], group=rs["group"][order],
+                first=rs["first"][rs["sample"][order]], scale=rs["scale"], t_min=rs["t_min"], t_max=rs["t_max"])
+
+
 @dataclasses.dataclass(frozen=True)
 class _Call:
     """What one sample_diffusion call asks for apart from its batch: built once, after validation, and handed to every batch path
-    (dense, padded, equal-size groups).  ``drift`` is energy_drift_opt; ``sample_keys`` / ``fixed`` / ``resample`` / ``chain_init``
-    are what `_as_sample_keys` / `_as_fixed` / `_as_resample` / `_as_init` returned, in the CALLER's sample and row order
-    (`_chain_rows` lays them into a chain)."""
+    (dense, padded, equal-size groups).  ``drift`` is energy_drift_opt without its ``restraint`` entry; ``sample_keys`` / ``fixed`` /
+    ``resample`` / ``chain_init`` / ``restraints`` are what `_as_sample_keys` / `_as_fixed` / `_as_resample` / `_as_init` /
+    `_as_restraints` returned, in the CALLER's sample, row and restraint order (`_chain_rows` lays them into a chain)."""
     num_timesteps: int
     num_steps: int
     start_step: int = 0
@@ -347,6 +457,7 @@ class _Call:
     fixed: Optional[dict] = None
     resample: Optional[dict] = None
     chain_init: Optional[dict] = None
+    restraints: Optional[dict] = None
 
     def __post_init__(self):
         if self.start_step < 0 or self.num_steps + self.start_step > self.num_timesteps:
@@ -405,13 +516,15 @@ def _chain_rows(call, place, offset, prior_stds, ligand_decomp_batch, ligand_dec
     [B*NL] or None, ``fpp`` [B,NF,3] (only with a clash drift, else None).  From the call record (taken, then put): ``keys`` int64 [B]
     or None; ``noise`` dict(u_v, u_b, eps) or None; ``fx`` -- the fixed atoms, dict(mode, init, mask uint8 [B*NL], v0 int32 [B*NL], b0
     int32 [B*Eb], x0c [B*NL,3] centred, cc [B*NL,3] centred or None) -- or None; ``ci`` -- what dd_chain_init draws the first level
-    from, dict(mode, cc [B*NL,3] centred, std [B*NL,3], atom_lp / bond_lp or None and, mode "noised", x0c centred, v0, b0) -- or None.
+    from, dict(mode, cc [B*NL,3] centred, std [B*NL,3], atom_lp / bond_lp or None and, mode "noised", x0c centred, v0, b0) -- or None;
+    ``rs`` -- the chain's share of the distance restraints (`_place_restraints`: sorted by sample slot, points centred) -- or None.
     Centring is the ligand's own: the fp32 subtraction ``x - offset[row's sample]``.  Padding rows of a padded chain: 0; 0.5 in u_v /
     u_b; -2 (neither arm nor scaffold) in decomp; 1e6 in fpp (exp(-|p - y|^2 / sigma) underflows to exactly 0: nothing added to any sum)."""
     dev, B = offset.device, int(offset.shape[0])
     f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
     out = dict(atom_std=place.put(f32(prior_stds)[ligand_decomp_batch.to(dev)]).contiguous(), decomp=None, fpp=None, noise=None,
-               fx=None, ci=None, keys=call.sample_keys if call.sample_keys is None or place.ids is None else call.sample_keys[place.ids])
+               fx=None, ci=None, rs=None if call.restraints is None else _place_restraints(call.restraints, place.ids, B, offset),
+               keys=call.sample_keys if call.sample_keys is None or place.ids is None else call.sample_keys[place.ids])
     if ligand_decomp_index is not None:
         out["decomp"] = place.put(ligand_decomp_index.to(device=dev, dtype=torch.int32), fill=-2).contiguous()
     if call.drift is not None and any(dr["type"] == "clash" for dr in call.drift):
@@ -881,6 +994,7 @@ class DecompScorePosNet3D(nn.Module):
                      t_traj=None if call.resample is None else call.resample["t_traj"])
         self._run_chains([chain], call.n_pos, call.use_graph)
         out = self._collect_chain(chain, call.n_pos, call.keep_traj, rows_atoms=pad["rows_l"], rows_bonds=pad["rows_b"])
+        self._restraint_results(call, [chain], out)
         self._last = (s, bufs)
         return out
 
@@ -939,6 +1053,7 @@ class DecompScorePosNet3D(nn.Module):
             out["_traj_stacked"] = dict(traj)
         if call.resample is not None:
             out["t_traj"] = call.resample["t_traj"].clone()
+        self._restraint_results(call, [p[0] for p in prepared], out)
         return out
 
     # ------------------------------------------------------------------------------------------
@@ -1076,7 +1191,7 @@ class DecompScorePosNet3D(nn.Module):
                                      0 if rows["fpp"] is None else int(rows["fpp"].shape[1]), masks is not None, cache_slot)
         upload = self._upload_pocket(ent, d, pw, rows["fpp"], cacheable)
         self._upload_state(ent, d, rows["atom_std"], offset, rows["decomp"], masks)
-        self._bind_call(ent, d, pw, rows["keys"], rows["fx"], call.resample, rows["ci"])
+        self._bind_call(ent, d, pw, rows["keys"], rows["fx"], call.resample, rows["ci"], rows["rs"])
         use_l0 = self._fill_sampler(ent, d, pw, call.t_start, call.seed, rows["noise"],
                                     _drift_fields(call.drift, rows["decomp"] is not None), call.drift_norm_batch, upload)
         self._start_chain(ent, n_pos, rows["fx"], rows["ci"])
@@ -1085,7 +1200,7 @@ class DecompScorePosNet3D(nn.Module):
         ent["sig"] = (sm.drift_armsca, sm.armsca_min_d, sm.armsca_max_d, sm.armsca_scale, sm.drift_clash, sm.clash_sigma,
                       sm.clash_gamma, sm.clash_scale, sm.drift_repul, sm.repul_max_d, sm.repul_scale, sm.drift_norm_batch,
                       int(hip_lib.load().dd_debug_options_epoch()), use_l0, ent["keyed"], rows["fx"] is not None, ent["fixed"],
-                      call.resample is not None)
+                      call.resample is not None, ent["restraint_sig"])
         if cacheable:
             DecompScorePosNet3D._chain_cache[key] = ent    # (re-inserted: most recently used last)
             self._evict_chain_cache(self._CACHE_MAX)
@@ -1191,13 +1306,14 @@ class DecompScorePosNet3D(nn.Module):
             for k in ("np_real", "nl_real", "bl_prefix"):
                 bufs[k].copy_(masks[k])
 
-    def _bind_call(self, ent, d, pw, keys, fixed, resample, chain_init):
+    def _bind_call(self, ent, d, pw, keys, fixed, resample, chain_init, restraints=None):
         """The per-call inputs that the kernels read through pointers at every launch -- per-sample noise keys, fixed atoms (fx_*),
         the resampling epoch, the chain init (ci_*): the buffers belong to the (cached) entry and are created when first needed,
         their contents to this call, so the entry's captured graph serves the next chain with other keys, masks and known values.
         ``keys``: int64 [B] (host or device) in the order of the chain's samples, or None (the chain draws with its seed); ``fixed`` /
-        ``chain_init``: the ``fx`` / ``ci`` of `_chain_rows`; ``resample``: the validated dict of `_as_resample`.  Leaves on the entry
-        ``keyed``, ``fixed`` (the mode), ``resample``, the host structs, and ``launch``: the step-launch arguments of this chain."""
+        ``chain_init``: the ``fx`` / ``ci`` of `_chain_rows`; ``resample``: the validated dict of `_as_resample`; ``restraints``: the
+        ``rs`` of `_chain_rows`.  Leaves on the entry ``keyed``, ``fixed`` (the mode), ``resample``, ``restraints``, the host structs,
+        and ``launch``: the step-launch arguments of this chain."""
         bufs, dev = ent["bufs"], ent["dev"]
         A, E = d["B"] * d["NL"], d["B"] * d["NL"] * (d["NL"] - 1)
         fx, ci = fixed or {}, chain_init or {}
@@ -1239,8 +1355,33 @@ class DecompScorePosNet3D(nn.Module):
         if chain_init is not None:
             ent["init_struct"] = hip_lib.init_struct(ci["mode"], bound["ci_cc"], bound["ci_std"], bound["ci_lp_v"], bound["ci_lp_b"],
                                                      bound["ci_x0c"], bound["ci_v0"], bound["ci_b0"], pw["tab_fixed"] if noised else None)
+        # distance restraints: the arrays hold a CAPACITY of entries (a power of two, at least 8) that the captured graph's launch
+        # carries as R; the call's R entries come first and weight-0 entries of the last sample fill the rest (they add nothing)
+        ent["restraints"], ent["restraints_struct"], ent["restraint_sig"] = None, None, None
+        if restraints is not None:
+            rs, nB = restraints, d["B"]
+            cap = max(8, 1 << max(rs["R"] - 1, 0).bit_length(), int(bufs["rs_weight"].numel()) if bufs.get("rs_weight") is not None else 0)
+            if bufs.get("rs_weight") is None or int(bufs["rs_weight"].numel()) != cap:
+                z = lambda *shape, dtype=f32: torch.zeros(*shape, dtype=dtype, device=dev)
+                bufs.update(rs_ptr=z(nB + 1, dtype=i32), rs_point=z(cap, 3), rs_min_d=z(cap), rs_max_d=z(cap), rs_weight=z(cap),
+                            rs_atom=z(cap, dtype=i32), rs_group=z(cap, dtype=i32), rs_dist=z(cap), rs_winner=z(cap, dtype=i32),
+                            rs_grad=z(A, 3))
+            pad = cap - rs["R"]
+            ptr = rs["ptr"].clone()
+            ptr[nB] = cap
+            fill = lambda t, v: torch.cat([t.to(dev), torch.full((pad,) + tuple(t.shape[1:]), v, dtype=t.dtype, device=dev)])
+            for name, t, v in (("rs_point", rs["point"], 0.0), ("rs_min_d", rs["min_d"], 0.0), ("rs_max_d", rs["max_d"], math.inf),
+                               ("rs_weight", rs["weight"], 0.0), ("rs_atom", rs["atom"], -1), ("rs_group", rs["group"], RESTRAINT_ANY)):
+                bufs[name].copy_(fill(t, v))
+            bufs["rs_ptr"].copy_(ptr)
+            ent["restraints"] = rs
+            ent["restraints_struct"] = hip_lib.restraints_struct(cap, *(bufs[k] for k in ("rs_ptr", "rs_point", "rs_min_d", "rs_max_d",
+                                                                                        "rs_weight", "rs_atom", "rs_group")),
+                                                                 rs["scale"], rs["t_min"], rs["t_max"])
+            ent["restraint_sig"] = (cap, rs["scale"], rs["t_min"], rs["t_max"])
         ref = lambda st: None if st is None else ctypes.byref(st)
-        ent["launch"] = dict(keys=hip_lib.ptr(bound["sample_keys"]), fixed=ref(ent["fixed_struct"]), resample=ref(ent["resample_struct"]))
+        ent["launch"] = dict(keys=hip_lib.ptr(bound["sample_keys"]), fixed=ref(ent["fixed_struct"]), resample=ref(ent["resample_struct"]),
+                             restraints=ref(ent["restraints_struct"]))
 
     def _fill_sampler(self, ent, d, pw, t_start, seed, noise, drift_fields, drift_norm_batch, upload):
         """The per-call fields of the entry's dd_sampler -- injected noise, layer-0 tables, start time, seed, buffer pointers, drift
@@ -1497,6 +1638,19 @@ class DecompScorePosNet3D(nn.Module):
           prepared as always, after the draw; ``fixed['init'] = 'given'`` keeps the drawn level at the held rows), ``resample``,
           the drift terms, ``use_graph`` and every batch path; a call with ``num_steps=0`` returns the drawn state.  Bad modes,
           keys, shapes, dtypes, classes or combinations raise ValueError before anything is launched.  ``None``: today's call.
+        * ``energy_drift_opt`` may list, once, a fourth term with the caller's own geometry (EXTENSION):
+          ``dict(type="restraint", sample=[R], point=[R,3], min_d=, max_d=, weight=1.0, atom=None|[R], group=None|[R], scale=False,
+          t_min=None, t_max=None)`` -- restraint r asks that an atom of sample ``sample[r]`` stays ``min_d .. max_d`` (scalars or
+          [R]; ``min_d`` may be 0, ``max_d`` +inf) from ``point[r]`` (the frame of ``protein_pos``): the ligand atom ``atom[r]`` (a
+          flat row of the caller's order), or, where ``atom[r] == -1`` (``atom=None``: everywhere), the nearest member of
+          ``group[r]`` -- ``RESTRAINT_ANY`` (default: every atom of the sample), -1 (scaffold) or an arm id.  Energy
+          ``sum_r weight_r (relu(min_d_r - d_r) + relu(d_r - max_d_r))`` with no division by B or R, so a sample's gradient does
+          not depend on its batch; the step subtracts its gradient at x_t (times ``pos_score_coef[t]`` with ``scale``) next to the
+          other terms while ``t_min <= t <= t_max`` (default: always).  Composes with every batch path, ``sample_keys``, ``fixed``
+          (held atoms count as targets), ``resample``, ``init``, ``start_step`` and ``use_graph``; R = 0 is legal.  The result
+          gains ``restraint_dist`` [R] and ``restraint_atom`` [R] (the flat row of the atom that counts, or -1: an empty group)
+          of the final state.  Bad keys, shapes, dtypes, non-finite values, ``min_d > max_d``, an ``atom`` of another sample, a
+          scaffold / arm group without ``ligand_decomp_index``, the term listed twice: ValueError before anything is launched.
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
@@ -1524,12 +1678,15 @@ class DecompScorePosNet3D(nn.Module):
             fixed = _as_fixed(fixed, batch_ligand.numel(), ligand_fc_bond_index, init_ligand_fc_bond_type, self.num_classes,
                               self.num_bond_classes, noise, start_step, prior_centers, ligand_decomp_batch, ligand_atom_mask,
                               protein_pos.device, need_cc=resample is not None)
+        energy_drift_opt, restraints = _split_restraints(energy_drift_opt)
+        if restraints is not None:
+            restraints = _as_restraints(restraints, batch_ligand, ligand_decomp_index, self.num_timesteps)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         key_t = (protein_pos, batch_protein, batch_ligand, ligand_fc_bond_index, ligand_v_aux)
         static = self._static_memo_get(key_t, center_pos_mode)        # (only dense batches are remembered)
         call = _Call(self.num_timesteps, num_steps, start_step, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
-                     _drift_norm_batch, sample_keys, fixed, resample, init)
+                     _drift_norm_batch, sample_keys, fixed, resample, init, restraints)
         if static is None and self._is_ragged(batch_protein, batch_ligand):
             return self._sample_heterogeneous(
                 dict(protein_pos=protein_pos, protein_v=protein_v, batch_protein=batch_protein, init_ligand_pos=init_ligand_pos,
@@ -1549,6 +1706,7 @@ class DecompScorePosNet3D(nn.Module):
             tr.append(("prepared>", time.perf_counter()))
         self._run_chains([chain], call.n_pos, use_graph)
         out = self._collect_chain(chain, call.n_pos, keep_traj)
+        self._restraint_results(call, [chain], out)
         if tr is not None:
             tr.append(("collected>", time.perf_counter()))
         self._last = (chain["s"], chain["bufs"])
@@ -1690,17 +1848,14 @@ class DecompScorePosNet3D(nn.Module):
                         side.synchronize()
                         self._release_step_graph(c["ent"], cached)
             else:
-                # (dd_sample_steps_fixed with NULL keys / NULL fixed IS dd_sample_steps_keyed / _opts: in dd_api.hip those only delegate)
+                # (dd_sample_steps_guided with NULL keys / fixed / resample / restraints IS dd_sample_steps_opts: in dd_api.hip the
+                #  whole suffix chain only delegates to it)
                 with torch.cuda.stream(side):
                     for c in chains:
                         L, sm, st = c["ent"]["launch"], ctypes.byref(c["s"]), hip_lib.stream_ptr(dev)
-                        if L["resample"] is None:
-                            hip_lib.check(lib.dd_sample_steps_fixed(sm, self._model_opts(), L["keys"], L["fixed"], int(num_steps), st),
-                                          "dd_sample_steps")
-                            continue
                         for n, jump in self._chain_runs(c, num_steps):
-                            hip_lib.check(lib.dd_sample_steps_resample(sm, self._model_opts(), L["keys"], L["fixed"], L["resample"], int(n), st),
-                                          "dd_sample_steps_resample")
+                            hip_lib.check(self._step_entry(lib, "dd_sample_steps", L)(sm, self._model_opts(), *self._step_extras(lib, L),
+                                                                                       int(n), st), "dd_sample_steps_guided")
                             if jump:
                                 self._jump(c, st)
             cur.wait_stream(side)
@@ -1713,8 +1868,8 @@ class DecompScorePosNet3D(nn.Module):
         for st in pool:
             st.wait_stream(cur)
         n = len(chains)
-        if any(c["ent"].get("keyed") or c["ent"].get("fixed") for c in chains):
-            # keyed chains and chains with fixed atoms: dd_sample_steps_graph_multi_* takes neither -- one step graph per chain on its own stream, replayed
+        if any(c["ent"].get("keyed") or c["ent"].get("fixed") or c["ent"].get("restraints") for c in chains):
+            # keyed chains, chains with fixed atoms or restraints: dd_sample_steps_graph_multi_* takes none of them -- one step graph per chain on its own stream, replayed
             # round-robin from this thread; no other graph is alive across their creation and they go away newest first and all
             # together (see _parked_graphs)
             self._drop_cached_graphs()
@@ -1747,15 +1902,28 @@ class DecompScorePosNet3D(nn.Module):
         for st in pool:
             cur.wait_stream(st)
 
+    @staticmethod
+    def _step_entry(lib, stem, L):
+        """``stem`` + "_guided", the one step pair this file calls.  A build from before that pair, loaded with DD_IGNORE_ABI=1 by the
+        A/B tools (tools/ab_builds.py), serves chains without restraints through the pair it forwards from."""
+        if hasattr(lib, stem + "_guided") or L["restraints"] is not None:
+            return getattr(lib, stem + "_guided")
+        return getattr(lib, stem + ("_resample" if L["resample"] is not None else "_fixed"))
+
+    @staticmethod
+    def _step_extras(lib, L):
+        """The NULL-able arguments between ``opts`` and the step count of the entry point `_step_entry` chose."""
+        if hasattr(lib, "dd_graph_create_guided") or L["restraints"] is not None:
+            return L["keys"], L["fixed"], L["resample"], L["restraints"]
+        return (L["keys"], L["fixed"]) + ((L["resample"],) if L["resample"] is not None else ())
+
     def _create_step_graph(self, chain, steps_per_graph, stream):
         """Capture ``steps_per_graph`` reverse steps of a prepared chain on ``stream`` (a raw stream handle) into a new step graph;
         a keyed chain's kernels read the keys from the entry's own buffer."""
         lib, L, graph = hip_lib.load(), chain["ent"]["launch"], ctypes.c_void_p()
         args = (int(steps_per_graph), stream, ctypes.byref(graph))
-        if L["resample"] is not None:
-            rc = lib.dd_graph_create_resample(ctypes.byref(chain["s"]), self._model_opts(), L["keys"], L["fixed"], L["resample"], *args)
-        else:       # (with NULL keys / NULL fixed this IS dd_graph_create_keyed / _opts: those entry points of dd_api.hip only delegate)
-            rc = lib.dd_graph_create_fixed(ctypes.byref(chain["s"]), self._model_opts(), L["keys"], L["fixed"], *args)
+        # (with NULL keys / fixed / resample / restraints this IS dd_graph_create_opts: the suffix chain of dd_api.hip only delegates)
+        rc = self._step_entry(lib, "dd_graph_create", L)(ctypes.byref(chain["s"]), self._model_opts(), *self._step_extras(lib, L), *args)
         hip_lib.check(rc, "dd_graph_create")
         return graph
 
@@ -1922,6 +2090,26 @@ class DecompScorePosNet3D(nn.Module):
             bufs[k].copy_(v)
         torch.cuda.synchronize(chain["dev"])
         return True
+
+    @staticmethod
+    def _restraint_results(call, chains, out):
+        """``restraint_dist`` [R] / ``restraint_atom`` [R] (the caller's flat ligand row of the atom that counts, or -1) of a call with a
+        ``restraint`` entry, in the caller's restraint order: ONE dd_drift_restraint launch per chain on its final state."""
+        if call.restraints is None:
+            return
+        lib, R = hip_lib.load(), call.restraints["R"]
+        dist, atom = torch.full((R,), math.inf), torch.full((R,), -1, dtype=torch.long)
+        for c in chains:
+            ent, bufs, dev = c["ent"], c["bufs"], c["dev"]
+            rs = ent["restraints"]
+            hip_lib.check(lib.dd_drift_restraint(hip_lib.ptr(bufs["lig_pos"]), hip_lib.ptr(bufs.get("decomp_index")), hip_lib.ptr(bufs.get("nl_real")),
+                                                 c["B"], c["NL"], ctypes.byref(ent["restraints_struct"]), None, hip_lib.ptr(bufs["rs_grad"]), 0,
+                                                 hip_lib.ptr(bufs["rs_dist"]), hip_lib.ptr(bufs["rs_winner"]), hip_lib.stream_ptr(dev)),
+                          "dd_drift_restraint")
+            win = bufs["rs_winner"][:rs["R"]].cpu().long()
+            dist[rs["order"]] = bufs["rs_dist"][:rs["R"]].cpu()
+            atom[rs["order"]] = torch.where(win >= 0, rs["first"] + win, win)
+        out["restraint_dist"], out["restraint_atom"] = dist, atom
 
     def _collect_chain(self, chain, num_steps, keep_traj, rows_atoms=None, rows_bonds=None):
         """Result dict of a finished chain.  rows_atoms / rows_bonds (padded batches): the rows of the dense [B*NL] /

@@ -646,6 +646,57 @@ int dd_drift_clash(const float* lig_pos, const float* offset, const float* full_
 int dd_drift_arms_repul(const float* lig_pos, const int32_t* decomp_index, int B, int NL, float max_d, int mode, float* grad,
                         int accumulate, void* stream);
 
+/* Distance restraints (EXTENSION; a fourth drift term with caller-supplied geometry -- pharmacophore points): restraint r belongs
+ * to ONE sample and asks that an atom of it stays min_d_r .. max_d_r from the point p_r (min_d may be 0, max_d +inf), weight w_r >= 0:
+ *     d_r = | x_w - p_r |      w = the explicit atom atom[r] (its row within the sample, 0 .. NL-1), or, atom[r] == -1, the FIRST
+ *                              nearest member in row order (strict <) of the group group[r]: DD_RESTRAINT_ANY -- every real atom of
+ *                              the sample (decomp_index is not read) --, -1 -- the scaffold (decomp_index == -1) --, a >= 0 -- arm a
+ *     E   = sum_r  w_r * ( max(min_d_r - d_r, 0) + max(d_r - max_d_r, 0) )
+ * No division by the batch size or by R: a sample's gradient does not depend on its batch.  The gradient is torch.autograd.grad(E, x):
+ * the clamps pass theirs at exact equality with a bound (min_d == max_d == d: the two cancel), d == 0 gives nothing (finite), an
+ * empty group -- an arm the sample does not have, every group but ANY without decomp_index -- gives nothing (distance +inf,
+ * winner -1).  Padding atoms of a padded batch (row >= nl_real[b]) are never eligible.  Points are in the frame of lig_pos (the
+ * host subtracts the sample's offset).  Restraints arrive sorted by sample: ptr [B+1] with ptr[0] == 0 and ptr[B] == R.
+ *   dd_drift_restraint: grad [B*NL,3] (+)= dE/dx, every row written (zeros where nothing acts); optional dist [R] and winner [R]
+ *     (row within the sample, or -1).  step_counter != NULL (a dd_sampler's run state): the term acts only while
+ *     t_min <= t <= t_max, t the run state's current time, and writes zeros outside; dist / winner are reported either way.
+ *     One workgroup per sample, no atomics: the same bits on every run.
+ *   dd_sample_steps_guided / dd_graph_create_guided: the reverse steps of the _resample entry points with every extra NULL-able
+ *     -- sample_keys, fixed, resample (needs fixed), restraints -- and the last of the suffix chain: the _resample pair forwards
+ *     here.  The step subtracts the restraint gradient at x_t, times tab_score[t] when `scale`, from the posterior mean next to
+ *     the other drift terms, inside the window only; held atoms take part as targets and their own motion is overwritten by the
+ *     hold; a resampling jump and the chain init take no drift.  Every restraint pointer is a DEVICE pointer read at every launch:
+ *     one graph serves any restraint values and any split of the R entries over the samples.  R, scale, t_min and t_max are
+ *     arguments of the launches, so a graph keeps those of its creation (a host that varies the count pads to a capacity with
+ *     weight-0 entries).  The gradient lives in the workspace (dd_workspace_floats grew by B*NL*3 floats, rounded up).
+ *   `size` is the caller's sizeof(dd_restraints).  DD_ERR_BAD_ARG before any launch: NL > 128, R < 0, a NULL ptr (or, R > 0, any
+ *   other NULL array), t_min > t_max, and -- read back from the device with one synchronous copy on `stream` -- a ptr that does
+ *   not start at 0, rise monotonically and end at R, an atom outside [-1, NL), a group below -1 other than DD_RESTRAINT_ANY, an
+ *   arm / scaffold group without decomp_index.  dd_reverse_step stays without restraints.  (New entry points, ABI unchanged.) */
+enum { DD_RESTRAINT_ANY = -3 };  /* not an arm id (>= 0), not the scaffold (-1), not the padding mark of padded chains (-2) */
+typedef struct dd_restraints {
+  int32_t size;                  /* sizeof(dd_restraints) of the caller */
+  int32_t R;                     /* restraints in the arrays */
+  const int32_t* ptr;            /* DEVICE [B+1] */
+  const float* point;            /* DEVICE [R,3] */
+  const float* min_d;            /* DEVICE [R] */
+  const float* max_d;            /* DEVICE [R] */
+  const float* weight;           /* DEVICE [R] */
+  const int32_t* atom;           /* DEVICE [R] */
+  const int32_t* group;          /* DEVICE [R] */
+  int32_t scale;                 /* != 0: the step multiplies the gradient by tab_score[t] */
+  int32_t t_min, t_max;          /* the window, inclusive (0 and T - 1: always) */
+} dd_restraints;
+int dd_drift_restraint(const float* lig_pos, const int32_t* decomp_index /*or NULL*/, const int32_t* nl_real /*or NULL*/, int B, int NL,
+                       const dd_restraints* restraints /*HOST*/, const int32_t* step_counter /*DEVICE [4] or NULL*/, float* grad,
+                       int accumulate, float* dist /*or NULL*/, int32_t* winner /*or NULL*/, void* stream);
+int dd_sample_steps_guided(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B] or NULL*/,
+                           const dd_fixed* fixed /*HOST or NULL*/, const dd_resample* resample /*HOST or NULL*/,
+                           const dd_restraints* restraints /*HOST or NULL*/, int n_steps, void* stream);
+int dd_graph_create_guided(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B] or NULL*/,
+                           const dd_fixed* fixed /*HOST or NULL*/, const dd_resample* resample /*HOST or NULL*/,
+                           const dd_restraints* restraints /*HOST or NULL*/, int steps_per_graph, void* stream, void** graph_out /*HOST*/);
+
 /* Build flags of the loaded library: bit 0 = measurement build (-DDD_DEBUG_OPTIONS=1: alternative launch schedules behind
  * dd_debug_set_option, see decompdiff_hip_debug.h), bit 1 = -DDD_EXACT_MATH=1 (correctly rounded 1/sqrt and softmax
  * division).  0 for the default library. */
