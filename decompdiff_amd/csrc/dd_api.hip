@@ -758,7 +758,7 @@ struct ModelOpts {
   const uint64_t* sample_keys = nullptr;   // per-sample noise keys of the *_keyed entry points ([B], device), not part of dd_model_opts
   const dd_fixed* fixed = nullptr;         // fixed atoms of the *_fixed entry points (a checked host copy), not part of dd_model_opts
   const int32_t* epoch = nullptr;          // resampling epoch of the *_resample entry points (a device int, read at every launch)
-  const RestraintArgs* restraints = nullptr;   // distance restraints of the *_guided entry points (checked), not part of dd_model_opts
+  const Restraint2Args* restraints = nullptr;  // distance restraints of the *_guided entry points (checked), not part of dd_model_opts
 };
 static int check_blocks(const dd_sampler* s, int num_blocks) {
   if (!s || num_blocks < 1) return DD_ERR_BAD_ARG;
@@ -1144,7 +1144,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
 // restraints: the chain's distance restraints or NULL; their kernel reads the run state (counter_bias as the step kernels').
 struct DriftGrads { const float *ga = nullptr, *gc = nullptr, *gr = nullptr, *gq = nullptr; int scale_q = 0; };
 static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled, hipStream_t st, DriftGrads* d,
-                         const RestraintArgs* restraints = nullptr, int counter_bias = 0) {
+                         const Restraint2Args* restraints = nullptr, int counter_bias = 0) {
   const int B = s->B, NL = s->NL;
   auto run = [&](auto&& launch) -> int {
     ProfScope prof_scope(DD_PROF_STEP, st, profiled);
@@ -1169,11 +1169,17 @@ static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled,
     d->gr = w.gr;
   }
   if (restraints) {
-    RestraintArgs q = *restraints;
+    RestraintArgs q = restraints->o;
     q.pos = s->lig_pos; q.decomp = s->decomp_index; q.nl_real = s->nl_real; q.step_counter = s->step_counter;
     q.counter_bias = counter_bias; q.grad = w.gq; q.accumulate = 0; q.dist = nullptr; q.winner = nullptr;
-    DD_TRY(run([&] { return launch_drift_restraint(q, st); }));
-    d->gq = w.gq; d->scale_q = restraints->scale;
+    if (restraints->general) {                             // (typed / pair / harmonic / trajectories: the sampler's own atom classes)
+      Restraint2Args g = *restraints;
+      g.o = q; g.lig_v = s->lig_v; g.winner2 = nullptr;
+      DD_TRY(run([&] { return launch_drift_restraint2(g, st); }));
+    } else {
+      DD_TRY(run([&] { return launch_drift_restraint(q, st); }));
+    }
+    d->gq = w.gq; d->scale_q = restraints->o.scale;
   }
   return DD_OK;
 }
@@ -1210,7 +1216,7 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint6
 }
 
 static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr, const uint64_t* sample_keys = nullptr,
-                          const dd_fixed* fixed = nullptr, const int32_t* epoch = nullptr, const RestraintArgs* restraints = nullptr) {
+                          const dd_fixed* fixed = nullptr, const int32_t* epoch = nullptr, const Restraint2Args* restraints = nullptr) {
   const Fwd f(s);
   const Workspace& w = f.w;
   const bool advanced = fold && fold->advance;
@@ -1726,11 +1732,11 @@ extern "C" int dd_sample_steps_guided(const dd_sampler* s, const dd_model_opts* 
 }
 
 // The chain's dd_restraints, checked against the sampler, for the step entry points (NULL stays "no restraints")
-static int read_step_restraints(const dd_restraints* rst, const dd_sampler* s, hipStream_t st, dd::RestraintArgs* out) {
+static int read_step_restraints(const dd_restraints* rst, const dd_sampler* s, hipStream_t st, dd::Restraint2Args* out) {
   if (!s || !s->workspace || !s->lig_pos) return DD_ERR_BAD_ARG;
-  const int rc = dd::read_restraints(rst, s->B, s->NL, s->decomp_index != nullptr, true, st, out);
+  const int rc = dd::read_restraints2(rst, s->B, s->NL, s->decomp_index != nullptr, s->lig_v != nullptr, true, st, out);
   if (rc != DD_OK) return rc;
-  return out->t_min < 0 || out->t_max >= s->T ? DD_ERR_BAD_ARG : DD_OK;
+  return out->o.t_min < 0 || out->o.t_max >= s->T ? DD_ERR_BAD_ARG : DD_OK;
 }
 
 static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
@@ -1746,7 +1752,7 @@ static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, con
   mo.fixed = fixed != nullptr ? &fx : nullptr;
   mo.epoch = rsm != nullptr ? rs.epoch : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  dd::RestraintArgs ra;
+  dd::Restraint2Args ra;
   if (rst != nullptr) {
     const int rrc = read_step_restraints(rst, s, st, &ra);
     if (rrc != DD_OK) return rrc;
@@ -1939,7 +1945,7 @@ static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, con
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   int rc = dd::check_shapes(s);
   if (rc != DD_OK) return rc;
-  dd::RestraintArgs ra;
+  dd::Restraint2Args ra;
   if (rst != nullptr) {
     rc = read_step_restraints(rst, s, st, &ra);
     if (rc != DD_OK) return rc;

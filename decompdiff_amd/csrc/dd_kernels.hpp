@@ -172,6 +172,24 @@ int launch_drift_restraint(const RestraintArgs& a, hipStream_t st);
 // the caller's dd_restraints, checked, as the kernel's arguments (pos / decomp / nl_real / step_counter / outputs left to the caller);
 // check_contents: also what only the device arrays say -- copies ptr / atom / group to the host and waits for `st`
 int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, bool check_contents, hipStream_t st, RestraintArgs* out);
+// The general form (dd_restraints' trailing fields): class masks over the current atom classes, ligand-ligand pairs, harmonic hinges
+// and per-step rows of dist / winner(s).  `o` is what k_drift_restraint takes, unchanged; `general`: the caller's struct carries a
+// non-NULL trailing array -- launch k_drift_restraint2 --, else everything below is NULL and `o` goes to k_drift_restraint.
+struct Restraint2Args {
+  RestraintArgs o;
+  bool general;
+  const int32_t* lig_v;          // [B*NL] current atom classes or NULL (then cls / cls2 are NULL too)
+  const uint32_t *cls, *cls2;    // [R] class masks (bit c = class c) or NULL: untyped
+  const int32_t *pair, *atom2, *group2, *form;   // [R] each or NULL: no pairs / no explicit second atom / no second group / linear
+  int32_t* winner2;              // [R] the j of a pair (row within the sample) or -1, or NULL
+  float* dist_traj;              // [traj_positions, R] or NULL; row = the run state's step
+  int32_t *winner_traj, *winner2_traj;
+  int traj_positions;
+};
+int launch_drift_restraint2(const Restraint2Args& a, hipStream_t st);
+// read_restraints, then the trailing fields: has_v -- the caller has atom classes for cls / cls2
+int read_restraints2(const dd_restraints* rs, int B, int NL, bool has_decomp, bool has_v, bool check_contents, hipStream_t st,
+                     Restraint2Args* out);
 int launch_extract_ligand(const float* x, int B, int NP, int NL, float* out, hipStream_t st);
 
 enum { M_NE = 0, M_NB = 1, M_BL = 2, M_PE = 3, M_PB = 4 };

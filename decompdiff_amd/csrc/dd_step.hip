@@ -571,6 +571,145 @@ int launch_drift_restraint(const RestraintArgs& a, hipStream_t st) {
   return DD_OK;
 }
 
+// The general restraint kernel (include/decompdiff_hip.h, "the general form"): the launch shape, the reductions and, for a linear
+// untyped point restraint, the arithmetic of k_drift_restraint operation for operation; on top of it class masks over the CURRENT
+// atom classes, pair restraints between two ligand atoms, the harmonic hinge and one trajectory row per step.  The sample's
+// coordinates, class bits and arm ids are staged in LDS once (128 x 5 words); a pair restraint has lane i (a member of set 1) scan
+// the members j != i of set 2 in ascending order under strict <, then the workgroup reduces dist_bits << 32 | i << 8 | j, whose
+// minimum is the first nearest pair in (i, j) order.  Both winning lanes add the SAME rounded products into their own registers
+// (+ on i, - on j), restraints in ascending order: no atomics, the same bits on every run.  Memory-safe for any array contents:
+// ptr is clamped, an atom outside the sample matches no lane and no j, a class id outside [0, 32) has no bit.
+__device__ __forceinline__ bool restraint_member(int row, int n, int at, int gp, int arm, bool has_decomp, bool typed, unsigned cbit,
+                                                 unsigned mask) {
+  return row < n && (at >= 0 ? row == at : (gp == DD_RESTRAINT_ANY || (has_decomp && gp >= -1 && arm == gp))) &&
+         (!typed || (cbit & mask) != 0u);
+}
+__global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint2(const Restraint2Args q) {
+  __shared__ unsigned long long wk[2][2];
+  __shared__ float sx[DD_NL_MAX], sy[DD_NL_MAX], sz[DD_NL_MAX];
+  __shared__ unsigned sbit[DD_NL_MAX];
+  __shared__ int sarm[DD_NL_MAX];
+  const RestraintArgs& a = q.o;
+  const int b = blockIdx.x, l = threadIdx.x, NL = a.NL;
+  int n = a.nl_real ? a.nl_real[b] : NL;
+  n = n < NL ? n : NL;
+  float x = 0.f, y = 0.f, z = 0.f;
+  int my_arm = -2;
+  unsigned my_bit = 0u;
+  if (l < n) {
+    const float* p = a.pos + ((long)b * NL + l) * 3;
+    x = p[0]; y = p[1]; z = p[2];
+    if (a.decomp) my_arm = a.decomp[(long)b * NL + l];
+    if (q.lig_v) {
+      const int c = q.lig_v[(long)b * NL + l];
+      my_bit = c >= 0 && c < 32 ? 1u << c : 0u;
+    }
+  }
+  sx[l] = x; sy[l] = y; sz[l] = z; sbit[l] = my_bit; sarm[l] = my_arm;       // (blockDim.x <= DD_NL_MAX)
+  __syncthreads();
+  bool active = true;
+  int trow = -1;
+  if (a.step_counter != nullptr) {
+    const RunState rs = load_run_state(a.step_counter, a.counter_bias);
+    const int t = rs.t_start - rs.step;
+    active = t >= a.t_min && t <= a.t_max;
+    if (rs.step >= 0 && rs.step < q.traj_positions) trow = rs.step;
+  }
+  const bool traj = trow >= 0 && (q.dist_traj != nullptr || q.winner_traj != nullptr || q.winner2_traj != nullptr);
+  int r0 = a.ptr[b], r1 = a.ptr[b + 1];
+  r0 = r0 < 0 ? 0 : (r0 > a.R ? a.R : r0);
+  r1 = r1 < r0 ? r0 : (r1 > a.R ? a.R : r1);
+  if (!active && !traj && a.dist == nullptr && a.winner == nullptr && q.winner2 == nullptr) r1 = r0;
+  const bool has_decomp = a.decomp != nullptr;
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  for (int r = r0; r < r1; ++r) {                          // (r0, r1: the same in every thread of the workgroup)
+    const int at = a.atom[r], gp = a.group[r];
+    const bool mine = restraint_member(l, n, at, gp, my_arm, has_decomp, q.cls != nullptr, my_bit, q.cls ? q.cls[r] : 0u);
+    const bool is_pair = q.pair != nullptr && q.pair[r] != 0;
+    float dx, dy, dz, d = INFINITY;
+    unsigned long long key;
+    if (!is_pair) {
+      dx = x - a.point[3 * (long)r]; dy = y - a.point[3 * (long)r + 1]; dz = z - a.point[3 * (long)r + 2];
+      d = mine ? sqrtf(dx * dx + dy * dy + dz * dz) : INFINITY;
+      key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)l;   // d >= 0 (or +inf): bit order = float order
+    } else {
+      const int at2 = q.atom2 ? q.atom2[r] : -1, gp2 = q.group2 ? q.group2[r] : DD_RESTRAINT_NONE;
+      const bool typed2 = q.cls2 != nullptr;
+      const unsigned m2 = typed2 ? q.cls2[r] : 0u;
+      int j0 = 0, j1 = n, bj = 0;
+      if (at2 >= 0) { j0 = at2 < n ? at2 : n; j1 = at2 < n ? at2 + 1 : n; }   // (an explicit second atom: one candidate)
+      if (mine) {
+        for (int j = j0; j < j1; ++j) {
+          if (j == l || !restraint_member(j, n, at2, gp2, sarm[j], has_decomp, typed2, sbit[j], m2)) continue;
+          const float ex = x - sx[j], ey = y - sy[j], ez = z - sz[j];
+          const float dj = sqrtf(ex * ex + ey * ey + ez * ez);
+          if (dj < d) { d = dj; bj = j; }
+        }
+      }
+      key = ((unsigned long long)__float_as_uint(d) << 32) | ((unsigned)l << 8) | (unsigned)bj;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long k2 = (unsigned long long)__shfl_xor((long long)key, off);
+      key = k2 < key ? k2 : key;
+    }
+    if (blockDim.x > 64) {
+      if ((l & 63) == 0) wk[r & 1][l >> 6] = key;
+      __syncthreads();
+      const unsigned long long k0 = wk[r & 1][0], k1 = wk[r & 1][1];
+      key = k1 < k0 ? k1 : k0;
+    }
+    const float best = __uint_as_float((unsigned)(key >> 32));
+    const bool found = best < INFINITY || best != best;
+    const unsigned low = (unsigned)(key & 0xffffffffull);
+    const int win = found ? (int)(is_pair ? low >> 8 : low) : -1;
+    const int win2 = found && is_pair ? (int)(low & 0xffu) : -1;
+    if (l == 0) {
+      if (a.dist) a.dist[r] = best;
+      if (a.winner) a.winner[r] = win;
+      if (q.winner2) q.winner2[r] = win2;
+      if (traj) {
+        const long o = (long)trow * a.R + r;
+        if (q.dist_traj) q.dist_traj[o] = best;
+        if (q.winner_traj) q.winner_traj[o] = win;
+        if (q.winner2_traj) q.winner2_traj[o] = win2;
+      }
+    }
+    if (active && found && (l == win || l == win2)) {
+      const float w = a.weight[r];
+      float coef = 0.f;
+      if (q.form != nullptr && q.form[r] != 0) {
+        const float lo = a.min_d[r] - best, hi = best - a.max_d[r];
+        if (lo > 0.f) coef -= 2.f * w * lo;
+        if (hi > 0.f) coef += 2.f * w * hi;
+      } else {
+        if (a.min_d[r] - best >= 0.f) coef -= 1.f;
+        if (best - a.max_d[r] >= 0.f) coef += 1.f;
+        coef *= w;
+      }
+      if (coef != 0.f && best > 0.f) {
+        const float inv = 1.0f / best;
+        if (is_pair) {                                       // (both ends form the same three products from LDS: exactly opposite)
+          dx = sx[win] - sx[win2]; dy = sy[win] - sy[win2]; dz = sz[win] - sz[win2];
+        }
+        const float tx = __fmul_rn(__fmul_rn(coef, dx), inv), ty = __fmul_rn(__fmul_rn(coef, dy), inv), tz = __fmul_rn(__fmul_rn(coef, dz), inv);
+        if (l == win) { gx = __fadd_rn(gx, tx); gy = __fadd_rn(gy, ty); gz = __fadd_rn(gz, tz); }
+        else { gx = __fadd_rn(gx, -tx); gy = __fadd_rn(gy, -ty); gz = __fadd_rn(gz, -tz); }
+      }
+    }
+  }
+  if (l < NL) {
+    float* g = a.grad + ((long)b * NL + l) * 3;
+    if (a.accumulate) { g[0] += gx; g[1] += gy; g[2] += gz; }
+    else { g[0] = gx; g[1] = gy; g[2] = gz; }
+  }
+}
+int launch_drift_restraint2(const Restraint2Args& a, hipStream_t st) {
+  if (a.o.B <= 0 || a.o.NL <= 0 || a.o.NL > DD_NL_MAX || a.o.R < 0) return DD_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_drift_restraint2, dim3(a.o.B), dim3(a.o.NL > 64 ? 128 : 64), 0, st, a);
+  DD_CHECK_LAUNCH();
+  return DD_OK;
+}
 
 // ---------------------------------------------------------------------------------- one launch per reverse step
 // Bond rows, atom rows and the coordinate update are independent given the head activations, so they share one
@@ -1074,6 +1213,73 @@ int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, boo
 }
 }  // namespace dd
 
+// The trailing fields of the caller's dd_restraints (NULL / 0 where its `size` ends before them) behind read_restraints' checks.
+namespace dd {
+// does the caller's struct (checked by read_restraints: size >= 4) carry a non-NULL trailing array or trajectory pointer?
+static bool carries_general(const dd_restraints* rs) {
+  dd_restraints r;
+  memset(&r, 0, sizeof(r));
+  memcpy(&r, rs, (size_t)rs->size < sizeof(r) ? (size_t)rs->size : sizeof(r));
+  return r.cls || r.cls2 || r.pair || r.atom2 || r.group2 || r.form || r.dist_traj || r.winner_traj || r.winner2_traj;
+}
+int read_restraints2(const dd_restraints* rs, int B, int NL, bool has_decomp, bool has_v, bool check_contents, hipStream_t st,
+                     Restraint2Args* out) {
+  memset(out, 0, sizeof(*out));
+  const int rc = read_restraints(rs, B, NL, has_decomp, check_contents, st, &out->o);
+  if (rc != DD_OK) return rc;
+  dd_restraints r;
+  memset(&r, 0, sizeof(r));
+  memcpy(&r, rs, (size_t)rs->size < sizeof(r) ? (size_t)rs->size : sizeof(r));
+  const bool traj = r.dist_traj || r.winner_traj || r.winner2_traj;
+  out->general = carries_general(rs);
+  if (!out->general) return DD_OK;
+  if ((r.cls || r.cls2) && !has_v) return DD_ERR_BAD_ARG;
+  if (r.pair && !r.atom2 && !r.group2) return DD_ERR_BAD_ARG;
+  if (traj && r.traj_positions <= 0) return DD_ERR_BAD_ARG;
+  out->cls = r.cls; out->cls2 = r.cls2; out->pair = r.pair; out->atom2 = r.atom2; out->group2 = r.group2; out->form = r.form;
+  out->dist_traj = r.dist_traj; out->winner_traj = r.winner_traj; out->winner2_traj = r.winner2_traj;
+  out->traj_positions = traj ? r.traj_positions : 0;
+  if (!check_contents || r.R == 0) return DD_OK;
+  const size_t R = (size_t)r.R;
+  std::vector<int32_t> h(4 * R, 0);
+  int32_t *pr = h.data(), *a2 = pr + R, *g2 = a2 + R, *fm = g2 + R;
+  for (size_t i = 0; i < R; ++i) { a2[i] = -1; g2[i] = DD_RESTRAINT_NONE; }
+  const int32_t* src[4] = {r.pair, r.atom2, r.group2, r.form};
+  bool copied = true;
+  for (int k = 0; k < 4; ++k)
+    if (src[k] != nullptr) copied = copied && hipMemcpyAsync(h.data() + k * R, src[k], sizeof(int32_t) * R, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (!copied || hipStreamSynchronize(st) != hipSuccess) {              // (one wait for the copies that were issued)
+    (void)hipGetLastError();
+    return DD_ERR_HIP;
+  }
+  for (size_t i = 0; i < R; ++i) {
+    if (fm[i] != 0 && fm[i] != 1) return DD_ERR_BAD_ARG;
+    if (a2[i] < -1 || a2[i] >= NL) return DD_ERR_BAD_ARG;
+    if (pr[i] != 0 && a2[i] == -1 && g2[i] != DD_RESTRAINT_ANY && (g2[i] < -1 || !has_decomp)) return DD_ERR_BAD_ARG;
+  }
+  return DD_OK;
+}
+}  // namespace dd
+
+extern "C" int dd_drift_restraint2(const float* lig_pos, const int32_t* lig_v, const int32_t* decomp_index, const int32_t* nl_real, int B,
+                                   int NL, const dd_restraints* restraints, const int32_t* step_counter, float* grad, int accumulate,
+                                   float* dist, int32_t* winner, int32_t* winner2, void* stream) {
+  if (!lig_pos || !grad || !restraints) return DD_ERR_BAD_ARG;
+  dd::Restraint2Args a;
+  const int rc = dd::read_restraints2(restraints, B, NL, decomp_index != nullptr, lig_v != nullptr, true, (hipStream_t)stream, &a);
+  if (rc != DD_OK) return rc;
+  a.o.pos = lig_pos; a.o.decomp = decomp_index; a.o.nl_real = nl_real; a.o.step_counter = step_counter; a.o.grad = grad;
+  a.o.accumulate = accumulate; a.o.dist = dist; a.o.winner = winner;
+  a.lig_v = lig_v; a.winner2 = winner2;
+  if (a.general) return dd::launch_drift_restraint2(a, (hipStream_t)stream);
+  if (winner2 != nullptr && a.o.R > 0 &&                                 // (the point kernel knows no second winner: all -1)
+      hipMemsetAsync(winner2, 0xff, sizeof(int32_t) * (size_t)a.o.R, (hipStream_t)stream) != hipSuccess) {
+    (void)hipGetLastError();
+    return DD_ERR_HIP;
+  }
+  return dd::launch_drift_restraint(a.o, (hipStream_t)stream);
+}
+
 extern "C" int dd_drift_restraint(const float* lig_pos, const int32_t* decomp_index, const int32_t* nl_real, int B, int NL,
                                   const dd_restraints* restraints, const int32_t* step_counter, float* grad, int accumulate, float* dist,
                                   int32_t* winner, void* stream) {
@@ -1081,6 +1287,7 @@ extern "C" int dd_drift_restraint(const float* lig_pos, const int32_t* decomp_in
   dd::RestraintArgs a;
   const int rc = dd::read_restraints(restraints, B, NL, decomp_index != nullptr, true, (hipStream_t)stream, &a);
   if (rc != DD_OK) return rc;
+  if (dd::carries_general(restraints)) return DD_ERR_BAD_ARG;            // (the general form has its own entry point)
   a.pos = lig_pos; a.decomp = decomp_index; a.nl_real = nl_real; a.step_counter = step_counter; a.grad = grad;
   a.accumulate = accumulate; a.dist = dist; a.winner = winner;
   return dd::launch_drift_restraint(a, (hipStream_t)stream);

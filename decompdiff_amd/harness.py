@@ -101,6 +101,9 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     dicts are collated into one ``restraint`` entry per model call (`collate_restraints`; ``restraint_opts``: its ``scale`` /
     ``t_min`` / ``t_max``), appended to ``energy_drift_opt``.  Works with ``pool_batches``, ``sample_key_seed`` and
     ``init="device"``; the output gains ``restraint_dist`` / ``restraint_atom`` per sample (``restraint_atom``: sample-local row).
+    The dict may carry the general form's keys -- ``classes`` / ``classes2``, ``atom2`` (sample rows) / ``group2``, ``form`` -- and
+    ``restraint_opts`` its ``traj``; the output then also has ``restraint_atom2`` (-1 off the pairs) and, with ``traj``,
+    ``restraint_dist_traj`` / ``restraint_atom_traj`` / ``restraint_atom2_traj`` [positions, r] per sample.
     """
     out = {k: [] for k in ("pred_pos", "pred_v", "pred_pos_traj", "pred_v_traj", "pred_v0_traj", "pred_vt_traj",
                            "pred_bond_index", "pred_bond_type", "pred_b_traj", "pred_bt_traj", "decomp_mask")}
@@ -237,7 +240,19 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                 ra = r["restraint_atom"][mine]
                 out.setdefault("restraint_dist", []).append(r["restraint_dist"][mine].numpy())
                 out.setdefault("restraint_atom", []).append(torch.where(ra >= 0, ra - int(a0), ra).numpy())
+                # (the general form; second atoms are reported for every sample as soon as any call of the job has a pair -- filled
+                #  in below --, so that a sample's output does not depend on its batch)
+                for key in ("restraint_atom2",) + (("restraint_dist_traj", "restraint_atom_traj", "restraint_atom2_traj") if rs_entry.get("traj") else ()):
+                    part = r[key][..., mine] if key in r else None
+                    if part is not None and key != "restraint_dist_traj":
+                        part = torch.where(part >= 0, part - int(a0), part)
+                    out.setdefault(key, []).append(None if part is None else part.numpy())
         time_list.append(time.time() - t1)
+    for key, like in (("restraint_atom2", "restraint_atom"), ("restraint_atom2_traj", "restraint_atom_traj")):
+        if key in out and all(v is None for v in out[key]):
+            del out[key]
+        elif key in out:
+            out[key] = [np.full_like(out[like][g], -1) if v is None else v for g, v in enumerate(out[key])]
     out["time_list"] = time_list
     return out
 
@@ -269,19 +284,31 @@ def collate_fixed(fixed_fn, first_index: int, n_atoms: List[int], decomp_index: 
 
 
 def collate_restraints(restraints_fn, first_index: int, n_atoms: List[int], decomp_index: torch.Tensor, scale=False, t_min=None,
-                       t_max=None):
+                       t_max=None, traj=False):
     """The per-sample dicts of ``restraints_fn`` for the samples ``first_index ...`` of one model call (``n_atoms``: their ligand
     sizes, ``decomp_index``: the call's flat arm ids) as ONE ``restraint`` entry of energy_drift_opt: samples numbered by their
     place in the call, explicit atoms moved from the sample's rows to the call's flat rows.  A sample for which the function
-    returns None has no restraints; a call without any still carries the (empty) entry."""
-    from .model import RESTRAINT_ANY
+    returns None has no restraints; a call without any still carries the (empty) entry.  The general form's keys pass through when
+    any sample gives one: ``atom2`` like ``atom`` (sample rows -> flat rows), ``group2`` (a number, or one value each with
+    RESTRAINT_NONE / None for "no second endpoint"), ``classes`` / ``classes2`` (a bool tensor [r, num_classes] or r entries of
+    None | class ids), ``form`` (a name or r names); ``point`` may be left out by a sample whose restraints are all pairs."""
+    from .model import RESTRAINT_ANY, RESTRAINT_NONE
     cols = {k: [] for k in ("sample", "point", "min_d", "max_d", "weight", "atom", "group")}
+    extra = {k: [] for k in ("atom2", "group2", "classes", "classes2", "form")}
+    used = set()
     a0 = 0
     for k, n in enumerate(n_atoms):
         f = restraints_fn(first_index + k, decomp_index[a0:a0 + n])
         if f is not None:
-            point = torch.as_tensor(f["point"], dtype=torch.float32).reshape(-1, 3)
+            if f.get("point") is None:                        # (pairs only: the count comes from the second endpoint)
+                second = f.get("atom2") if f.get("atom2") is not None else f.get("group2")
+                if second is None or torch.as_tensor(second).dim() != 1:
+                    raise ValueError(f"restraints_fn: sample {first_index + k} gives no point and no atom2 / group2 of one value per restraint")
+                point = torch.zeros(len(second), 3)
+            else:
+                point = torch.as_tensor(f["point"], dtype=torch.float32).reshape(-1, 3)
             r = int(point.shape[0])
+            used |= {key for key in extra if f.get(key) is not None}
 
             def col(name, default, dtype):                     # a number for all r restraints, or one value each
                 t = torch.as_tensor(f.get(name, default), dtype=dtype)
@@ -293,6 +320,25 @@ def collate_restraints(restraints_fn, first_index: int, n_atoms: List[int], deco
             cols["point"].append(point)
             cols["atom"].append(torch.where(atom >= 0, atom + a0, atom))
             cols["group"].append(col("group", RESTRAINT_ANY, torch.long))
+            atom2 = col("atom2", -1, torch.long)
+            if tuple(atom2.shape) != (r,) or bool((atom2 < -1).any()) or bool((atom2 >= n).any()):
+                raise ValueError(f"restraints_fn: sample {first_index + k} has {n} ligand atoms, 'atom2' must hold {r} rows in [-1, {n})")
+            extra["atom2"].append(torch.where(atom2 >= 0, atom2 + a0, atom2))
+            g2 = f.get("group2")
+            if g2 is not None and not torch.is_tensor(g2) and not isinstance(g2, int):
+                g2 = [RESTRAINT_NONE if g is None else g for g in g2]
+            g2 = torch.as_tensor(RESTRAINT_NONE if g2 is None else g2, dtype=torch.long)
+            extra["group2"].append(g2.expand(r) if g2.dim() == 0 else g2)
+            for name in ("classes", "classes2"):
+                c = f.get(name)
+                if torch.is_tensor(c) and c.dtype == torch.bool and c.dim() == 2:
+                    c = [row.nonzero()[:, 0].tolist() for row in c]
+                c = [None] * r if c is None else list(c)
+                extra[name].append(c)
+            form = f.get("form", "linear")
+            extra["form"].append([form] * r if isinstance(form, str) else list(form))
+            if any(len(extra[name][-1]) != r for name in extra):
+                raise ValueError(f"restraints_fn: sample {first_index + k} has {r} restraints, every general field must be one value or hold {r}")
             for name, default in (("min_d", None), ("max_d", None), ("weight", 1.0)):
                 if f.get(name, default) is None:
                     raise ValueError(f"restraints_fn: sample {first_index + k} gives no {name}")
@@ -302,7 +348,13 @@ def collate_restraints(restraints_fn, first_index: int, n_atoms: List[int], deco
         a0 += n
     empty = {"sample": torch.long, "point": torch.float32, "atom": torch.long, "group": torch.long}
     out = {k: (torch.cat(v) if v else torch.zeros((0, 3) if k == "point" else (0,), dtype=empty.get(k, torch.float32))) for k, v in cols.items()}
-    return dict(out, type="restraint", scale=bool(scale), t_min=t_min, t_max=t_max)
+    out = dict(out, type="restraint", scale=bool(scale), t_min=t_min, t_max=t_max)
+    for key in sorted(used):                                   # (an entry no sample gave a general key to stays a point entry)
+        parts = extra[key]
+        out[key] = torch.cat(parts) if key in ("atom2", "group2") and parts else [v for part in parts for v in part]
+    if traj:
+        out["traj"] = True
+    return out
 
 
 def _accepts_extras(model) -> bool:

@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = [
     "dd_sample_steps_fixed", "dd_graph_create_fixed", "dd_fixed_init",
     "dd_sample_steps_resample", "dd_graph_create_resample", "dd_resample_jump", "dd_sampler_reset_resample",
     "dd_chain_init",
-    "dd_drift_restraint", "dd_sample_steps_guided", "dd_graph_create_guided",
+    "dd_drift_restraint", "dd_drift_restraint2", "dd_sample_steps_guided", "dd_graph_create_guided",
 ]
 # measurement / profiling / test access: include/decompdiff_hip_debug.h (same library, not part of the boundary)
 DEBUG_SYMBOLS = [
@@ -164,21 +164,35 @@ def init_struct(mode, cc, std, atom_log_prior=None, bond_log_prior=None, x0c=Non
 
 
 RESTRAINT_ANY = -3                                     # DD_RESTRAINT_ANY: every real ligand atom of the sample
+RESTRAINT_NONE = -4                                    # DD_RESTRAINT_NONE: group2 of a row without a second endpoint
 
 
 class DDRestraints(ctypes.Structure):
     """struct dd_restraints (include/decompdiff_hip.h): the distance restraints of a chain, sorted by sample (CSR ``ptr``); `size` =
     sizeof of this struct, every pointer a DEVICE pointer that the kernel reads at every launch (see `restraints_struct`)."""
     _fields_ = [("size", c_int32), ("R", c_int32), ("ptr", c_void_p), ("point", c_void_p), ("min_d", c_void_p), ("max_d", c_void_p),
-                ("weight", c_void_p), ("atom", c_void_p), ("group", c_void_p), ("scale", c_int32), ("t_min", c_int32), ("t_max", c_int32)]
+                ("weight", c_void_p), ("atom", c_void_p), ("group", c_void_p), ("scale", c_int32), ("t_min", c_int32), ("t_max", c_int32),
+                # the general form (trailing, every one NULL-able): typed atoms, pairs, the harmonic hinge, per-step rows
+                ("cls", c_void_p), ("cls2", c_void_p), ("pair", c_void_p), ("atom2", c_void_p), ("group2", c_void_p), ("form", c_void_p),
+                ("dist_traj", c_void_p), ("winner_traj", c_void_p), ("winner2_traj", c_void_p), ("traj_positions", c_int32)]
 
 
-def restraints_struct(R, ptr, point, min_d, max_d, weight, atom, group, scale, t_min, t_max) -> DDRestraints:
+RESTRAINT_GENERAL_FIELDS = ("cls", "cls2", "pair", "atom2", "group2", "form", "dist_traj", "winner_traj", "winner2_traj")
+
+
+def restraints_struct(R, ptr, point, min_d, max_d, weight, atom, group, scale, t_min, t_max, traj_positions=0, **general) -> DDRestraints:
     """A filled dd_restraints from device tensors (the caller keeps them alive): ptr int32 [B+1], point fp32 [R,3], min_d / max_d /
-    weight fp32 [R], atom / group int32 [R] (atom: the row within the sample or -1; group: RESTRAINT_ANY, -1 scaffold, >= 0 arm)."""
+    weight fp32 [R], atom / group int32 [R] (atom: the row within the sample or -1; group: RESTRAINT_ANY, -1 scaffold, >= 0 arm).
+    ``general`` -- any of RESTRAINT_GENERAL_FIELDS: cls / cls2 (class masks, int32 or uint32 [R]), pair / atom2 / group2 / form int32
+    [R], dist_traj fp32 and winner_traj / winner2_traj int32 [traj_positions, R] -- sends the launches to the general kernel; left
+    out (or None) they stay NULL and the struct is the one the point kernel serves."""
+    if set(general) - set(RESTRAINT_GENERAL_FIELDS):
+        raise TypeError(f"restraints_struct: unknown fields {sorted(set(general) - set(RESTRAINT_GENERAL_FIELDS))}")
     r = DDRestraints()
     r.size, r.R, r.scale, r.t_min, r.t_max = ctypes.sizeof(DDRestraints), int(R), int(bool(scale)), int(t_min), int(t_max)
-    for name, t in (("ptr", ptr), ("point", point), ("min_d", min_d), ("max_d", max_d), ("weight", weight), ("atom", atom), ("group", group)):
+    r.traj_positions = int(traj_positions)
+    for name, t in (("ptr", ptr), ("point", point), ("min_d", min_d), ("max_d", max_d), ("weight", weight), ("atom", atom),
+                    ("group", group)) + tuple(general.items()):
         setattr(r, name, None if t is None else t.data_ptr())
     return r
 
@@ -298,6 +312,8 @@ def load():
         # (distance restraints: the op-level gradient; the last step pair -- keys, fixed, resample, restraints, each NULL-able)
         "dd_drift_restraint": [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(DDRestraints), c_void_p, c_void_p, c_int, c_void_p,
                                c_void_p, c_void_p],
+        "dd_drift_restraint2": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(DDRestraints), c_void_p, c_void_p, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p],
         "dd_sample_steps_guided": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), POINTER(DDResample), POINTER(DDRestraints), c_int,
                                    c_void_p],
         "dd_graph_create_guided": [S, POINTER(DDModelOpts), c_void_p, POINTER(DDFixed), POINTER(DDResample), POINTER(DDRestraints), c_int,

@@ -329,7 +329,11 @@ def _as_resample(resample, fixed, noise, num_timesteps, num_steps, start_step):
 
 
 RESTRAINT_ANY = hip_lib.RESTRAINT_ANY              # group id "every real ligand atom of the sample" (not an arm id, not -1, not -2)
-_RESTRAINT_KEYS = {"type", "sample", "point", "min_d", "max_d", "weight", "atom", "group", "scale", "t_min", "t_max"}
+RESTRAINT_NONE = hip_lib.RESTRAINT_NONE            # ``group2`` of a row without a second endpoint (no arm id, not -1, -2 or -3)
+_RESTRAINT_KEYS = {"type", "sample", "point", "min_d", "max_d", "weight", "atom", "group", "scale", "t_min", "t_max",
+                   "classes", "classes2", "atom2", "group2", "form", "traj"}
+_RESTRAINT_FORMS = {"linear": 0, "harmonic": 1}
+_ALL_CLASSES = 0xFFFFFFFF                          # the class mask of an untyped endpoint
 
 
 def _split_restraints(energy_drift_opt):
@@ -343,11 +347,47 @@ def _split_restraints(energy_drift_opt):
     return [dr for dr in energy_drift_opt if not (isinstance(dr, dict) and dr.get("type") == "restraint")], (mine[0] if mine else None)
 
 
-def _as_restraints(entry, batch_ligand, ligand_decomp_index, num_timesteps):
+def _class_masks(name, v, R, num_classes):
+    """``classes`` / ``classes2`` of a restraint entry -- None, a bool tensor [R, num_classes], or R entries of None | class ids --
+    as int64 [R] bit masks (bit c = class c; None: every bit), or None where the key is not given."""
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        if v.dtype != torch.bool or tuple(v.shape) != (R, num_classes):
+            raise ValueError(f"restraint['{name}'] must be a bool tensor of shape ({R}, {num_classes}) or a list, got {v.dtype} {tuple(v.shape)}")
+        rows = [r.nonzero()[:, 0].tolist() for r in v.detach().cpu()]
+    else:
+        try:
+            rows = list(v)
+        except TypeError:
+            raise ValueError(f"restraint['{name}'] must be None, a bool tensor or a list of {R} class sets") from None
+        if len(rows) != R:
+            raise ValueError(f"restraint['{name}'] must hold {R} entries, got {len(rows)}")
+    masks = []
+    for ids in rows:
+        if ids is None:
+            masks.append(_ALL_CLASSES)
+            continue
+        try:
+            ids = [i for i in (ids.tolist() if torch.is_tensor(ids) else ids)]
+        except TypeError:
+            raise ValueError(f"restraint['{name}']: a class set is None or an iterable of class ids") from None
+        if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < num_classes for i in ids):
+            raise ValueError(f"restraint['{name}']: class ids must be ints in [0, {num_classes})")
+        if not ids:
+            raise ValueError(f"restraint['{name}']: an empty class set matches nothing (use a weight of 0 instead)")
+        masks.append(sum(1 << i for i in set(ids)))
+    return torch.tensor(masks, dtype=torch.long).reshape(R)
+
+
+def _as_restraints(entry, batch_ligand, ligand_decomp_index, num_timesteps, num_classes=32):
     """The ``restraint`` entry of energy_drift_opt, validated (ValueError) into host tensors in the CALLER's restraint order:
     dict(R, sample int64 [R], point f32 [R,3], min_d / max_d / weight f32 [R], atom int32 [R] -- the row WITHIN the sample, or -1 --,
-    group int32 [R], first int64 [B] -- the first flat ligand row of every sample --, scale, t_min, t_max)."""
-    if not isinstance(entry, dict) or set(entry) - _RESTRAINT_KEYS or "sample" not in entry or "point" not in entry:
+    group int32 [R], first int64 [B] -- the first flat ligand row of every sample --, scale, t_min, t_max) and the general form:
+    cls / cls2 int64 [R] class masks or None (key not given), pair bool [R], atom2 int32 [R] (row within the sample or -1), group2
+    int32 [R] (RESTRAINT_NONE off the pairs), form int32 [R], traj, general -- does the entry use anything the point kernel lacks."""
+    if not isinstance(entry, dict) or set(entry) - _RESTRAINT_KEYS or "sample" not in entry or \
+            ("point" not in entry and "atom2" not in entry and "group2" not in entry):
         raise ValueError(f"a restraint entry takes the keys {sorted(_RESTRAINT_KEYS)} and needs sample and point")
     bl = batch_ligand.detach().cpu().long()
     n = int(bl.numel())
@@ -370,6 +410,24 @@ def _as_restraints(entry, batch_ligand, ligand_decomp_index, num_timesteps):
     sample = ints("sample", sample, (R,))
     if R and (int(sample.min()) < 0 or int(sample.max()) >= B):
         raise ValueError(f"restraint['sample'] must lie in [0, {B})")
+    if not 1 <= int(num_classes) <= 32:
+        raise ValueError("restraint class masks hold 32 classes")
+    # the second endpoint: a restraint is a pair iff its atom2 >= 0 or its group2 is given
+    atom2 = entry.get("atom2")
+    atom2 = torch.full((R,), -1, dtype=torch.long) if atom2 is None else ints("atom2", atom2, (R,))
+    group2 = entry.get("group2")
+    if group2 is not None and not torch.is_tensor(group2):
+        try:
+            group2 = [RESTRAINT_NONE if g is None else g for g in group2]
+        except TypeError:
+            raise ValueError(f"restraint['group2'] must be None, an integer tensor of shape ({R},) or a list") from None
+    group2 = torch.full((R,), RESTRAINT_NONE, dtype=torch.long) if group2 is None else ints("group2", group2, (R,))
+    explicit2 = atom2 >= 0
+    pair = explicit2 | (group2 != RESTRAINT_NONE)
+    if entry.get("point") is None:
+        if not bool(pair.all()):
+            raise ValueError("restraint['point'] may be None only when every restraint is a pair (atom2 / group2): a pair without a second endpoint")
+        entry = dict(entry, point=torch.zeros(R, 3))
     point = torch.as_tensor(entry["point"])
     if not point.dtype.is_floating_point or tuple(point.shape) != (R, 3):
         raise ValueError(f"restraint['point'] must be a float tensor of shape ({R}, 3), got {point.dtype} {tuple(point.shape)}")
@@ -404,6 +462,26 @@ def _as_restraints(entry, batch_ligand, ligand_decomp_index, num_timesteps):
     if ligand_decomp_index is None and bool((grp != RESTRAINT_ANY).any()):
         raise ValueError("a scaffold / arm restraint needs ligand_decomp_index")
     group = torch.where(explicit, torch.full_like(group, RESTRAINT_ANY), group)      # (not read for an explicit atom)
+    if bool((atom2 < -1).any()) or bool((atom2 >= n).any()) or not torch.equal(bl[atom2[explicit2]], sample[explicit2]):
+        raise ValueError("restraint['atom2'] must be -1 or a flat ligand row of the restraint's own sample")
+    if bool((explicit & explicit2 & (atom == atom2)).any()):
+        raise ValueError("restraint['atom2'] must differ from restraint['atom']: a pair needs two atoms")
+    grp2 = group2[pair & ~explicit2]
+    if bool(((grp2 < -1) & (grp2 != RESTRAINT_ANY)).any()):
+        raise ValueError("restraint['group2'] must be RESTRAINT_ANY, -1 (scaffold), an arm id >= 0 or RESTRAINT_NONE (no second endpoint)")
+    if ligand_decomp_index is None and bool((grp2 != RESTRAINT_ANY).any()):
+        raise ValueError("a scaffold / arm group2 needs ligand_decomp_index")
+    group2 = torch.where(explicit2, torch.full_like(group2, RESTRAINT_ANY), group2)  # (not read for an explicit atom)
+    group2 = torch.where(pair, group2, torch.full_like(group2, RESTRAINT_NONE))
+    cls, cls2 = (_class_masks(k, entry.get(k), R, int(num_classes)) for k in ("classes", "classes2"))
+    form = entry.get("form", "linear")
+    forms = [form] * R if isinstance(form, str) else (list(form) if isinstance(form, (list, tuple)) else None)
+    if forms is None or len(forms) != R or any(not isinstance(f, str) or f not in _RESTRAINT_FORMS for f in forms):
+        raise ValueError(f"restraint['form'] must be one of {sorted(_RESTRAINT_FORMS)} or a list of {R} of them")
+    form = torch.tensor([_RESTRAINT_FORMS[f] for f in forms], dtype=torch.int32).reshape(R)
+    traj = entry.get("traj", False)
+    if not isinstance(traj, bool):
+        raise ValueError("restraint['traj'] must be a bool")
     T = int(num_timesteps)
     t_min, t_max = entry.get("t_min"), entry.get("t_max")
     t_min, t_max = 0 if t_min is None else t_min, T - 1 if t_max is None else t_max
@@ -413,16 +491,21 @@ def _as_restraints(entry, batch_ligand, ligand_decomp_index, num_timesteps):
     if not isinstance(scale, (bool, int)):
         raise ValueError("restraint['scale'] must be a bool")
     local = torch.where(explicit, atom - first[sample], atom) if R else atom
+    local2 = torch.where(explicit2, atom2 - first[sample], atom2) if R else atom2
+    general = cls is not None or cls2 is not None or bool(pair.any()) or bool(form.any()) or traj
     return dict(R=R, sample=sample, point=point, min_d=per["min_d"], max_d=per["max_d"], weight=per["weight"],
-                atom=local.to(torch.int32), group=group.to(torch.int32), first=first, scale=bool(scale), t_min=int(t_min), t_max=int(t_max))
+                atom=local.to(torch.int32), group=group.to(torch.int32), first=first, scale=bool(scale), t_min=int(t_min), t_max=int(t_max),
+                cls=cls, cls2=cls2, pair=pair, atom2=local2.to(torch.int32), group2=group2.to(torch.int32), form=form, traj=traj,
+                general=general)
 
 
 def _place_restraints(rs, ids, B, offset):
     """The call's restraints ``rs`` (`_as_restraints`) as ONE chain's share, sorted by the chain's sample slot -- a stable sort: the
     caller's order within a sample -- with the CSR ``ptr`` [B+1] rebuilt.  ``ids``: the call's samples in the chain's order (None:
     all, in order); ``offset`` [B,3]: the chain's offsets, points are centred as the ligand is (the fp32 ``p - offset[slot]``).
-    ``order``: the caller's restraint index of every row (the way back).  ``atom`` stays the row within the sample: the explicit
-    atom of a padded chain sits at padded row ``slot * NL + atom``, that of a group's chain at ``slot * n + atom``."""
+    ``order``: the caller's restraint index of every row (the way back).  ``atom`` / ``atom2`` stay the row within the sample: the
+    explicit atom of a padded chain sits at padded row ``slot * NL + atom``, that of a group's chain at ``slot * n + atom``.  The
+    general form's arrays travel with their restraint; an entry written before it (no ``general`` key) is a point entry."""
     slot_of = torch.arange(B) if ids is None else torch.full((int(rs["first"].numel()),), -1, dtype=torch.long).index_put_(
         (torch.as_tensor(list(ids), dtype=torch.long),), torch.arange(len(ids)))
     slot = slot_of[rs["sample"]] if rs["R"] else torch.zeros(0, dtype=torch.long)
@@ -432,9 +515,16 @@ def _place_restraints(rs, ids, B, offset):
     ptr = torch.zeros(B + 1, dtype=torch.int32)
     ptr[1:] = torch.cumsum(torch.bincount(slot, minlength=B), 0).to(torch.int32)
     point = rs["point"][order].to(offset.device) - offset.detach().to(torch.float32)[slot.to(offset.device)]
-    return dict(R=int(order.numel()), order=order, slot=slot, ptr=ptr, point=point.contiguous(), min_d=rs["min_d"][order],
-                max_d=rs["max_d"][order], weight=rs["weight"][order], atom=rs["atom"][order], group=rs["group"][order],
-                first=rs["first"][rs["sample"][order]], scale=rs["scale"], t_min=rs["t_min"], t_max=rs["t_max"])
+    out = dict(R=int(order.numel()), order=order, slot=slot, ptr=ptr, point=point.contiguous(), min_d=rs["min_d"][order],
+               max_d=rs["max_d"][order], weight=rs["weight"][order], atom=rs["atom"][order], group=rs["group"][order],
+               first=rs["first"][rs["sample"][order]], scale=rs["scale"], t_min=rs["t_min"], t_max=rs["t_max"],
+               general=bool(rs.get("general", False)), traj=bool(rs.get("traj", False)))
+    if out["general"]:
+        for k in ("pair", "atom2", "group2", "form"):
+            out[k] = rs[k][order]
+        for k in ("cls", "cls2"):
+            out[k] = torch.full((out["R"],), _ALL_CLASSES, dtype=torch.long) if rs[k] is None else rs[k][order]
+    return out
 
 
 @dataclasses.dataclass(frozen=True)
@@ -1191,7 +1281,7 @@ class DecompScorePosNet3D(nn.Module):
                                      0 if rows["fpp"] is None else int(rows["fpp"].shape[1]), masks is not None, cache_slot)
         upload = self._upload_pocket(ent, d, pw, rows["fpp"], cacheable)
         self._upload_state(ent, d, rows["atom_std"], offset, rows["decomp"], masks)
-        self._bind_call(ent, d, pw, rows["keys"], rows["fx"], call.resample, rows["ci"], rows["rs"])
+        self._bind_call(ent, d, pw, rows["keys"], rows["fx"], call.resample, rows["ci"], rows["rs"], n_pos)
         use_l0 = self._fill_sampler(ent, d, pw, call.t_start, call.seed, rows["noise"],
                                     _drift_fields(call.drift, rows["decomp"] is not None), call.drift_norm_batch, upload)
         self._start_chain(ent, n_pos, rows["fx"], rows["ci"])
@@ -1306,13 +1396,13 @@ class DecompScorePosNet3D(nn.Module):
             for k in ("np_real", "nl_real", "bl_prefix"):
                 bufs[k].copy_(masks[k])
 
-    def _bind_call(self, ent, d, pw, keys, fixed, resample, chain_init, restraints=None):
+    def _bind_call(self, ent, d, pw, keys, fixed, resample, chain_init, restraints=None, n_pos=0):
         """The per-call inputs that the kernels read through pointers at every launch -- per-sample noise keys, fixed atoms (fx_*),
         the resampling epoch, the chain init (ci_*): the buffers belong to the (cached) entry and are created when first needed,
         their contents to this call, so the entry's captured graph serves the next chain with other keys, masks and known values.
         ``keys``: int64 [B] (host or device) in the order of the chain's samples, or None (the chain draws with its seed); ``fixed`` /
         ``chain_init``: the ``fx`` / ``ci`` of `_chain_rows`; ``resample``: the validated dict of `_as_resample`; ``restraints``: the
-        ``rs`` of `_chain_rows`.  Leaves on the entry ``keyed``, ``fixed`` (the mode), ``resample``, ``restraints``, the host structs,
+        ``rs`` of `_chain_rows`; ``n_pos``: the chain's positions (the rows of the restraint trajectories).  Leaves on the entry ``keyed``, ``fixed`` (the mode), ``resample``, ``restraints``, the host structs,
         and ``launch``: the step-launch arguments of this chain."""
         bufs, dev = ent["bufs"], ent["dev"]
         A, E = d["B"] * d["NL"], d["B"] * d["NL"] * (d["NL"] - 1)
@@ -1374,11 +1464,34 @@ class DecompScorePosNet3D(nn.Module):
                                ("rs_weight", rs["weight"], 0.0), ("rs_atom", rs["atom"], -1), ("rs_group", rs["group"], RESTRAINT_ANY)):
                 bufs[name].copy_(fill(t, v))
             bufs["rs_ptr"].copy_(ptr)
+            # the general form (typed / pair / harmonic / trajectories): its arrays are laid out the same way and ALL handed over, so
+            # that one graph serves any values; an entry without it hands none over and is served by the point kernel as before
+            general, rows = {}, 0
+            if rs["general"]:
+                if bufs.get("rs_pair") is None or int(bufs["rs_pair"].numel()) != cap:
+                    zi = lambda: torch.zeros(cap, dtype=i32, device=dev)
+                    bufs.update(rs_cls=zi(), rs_cls2=zi(), rs_pair=zi(), rs_atom2=zi(), rs_group2=zi(), rs_form=zi(), rs_winner2=zi())
+                as_bits = lambda m: torch.where(m >= 2 ** 31, m - 2 ** 32, m).to(i32)      # (a 32-bit mask in an int32 tensor)
+                for name, t, v in (("rs_cls", as_bits(rs["cls"]), -1), ("rs_cls2", as_bits(rs["cls2"]), -1), ("rs_pair", rs["pair"].to(i32), 0),
+                                   ("rs_atom2", rs["atom2"], -1), ("rs_group2", rs["group2"], hip_lib.RESTRAINT_NONE), ("rs_form", rs["form"], 0)):
+                    bufs[name].copy_(fill(t, v))
+                general = dict(cls=bufs["rs_cls"], cls2=bufs["rs_cls2"], pair=bufs["rs_pair"], atom2=bufs["rs_atom2"],
+                               group2=bufs["rs_group2"], form=bufs["rs_form"])
+                if rs["traj"]:
+                    have = bufs.get("rs_dist_traj")
+                    if have is None or int(have.shape[1]) != cap or int(have.shape[0]) < max(int(n_pos), 1):
+                        rows = max(int(n_pos), 1)
+                        bufs.update(rs_dist_traj=torch.zeros(rows, cap, dtype=f32, device=dev),
+                                    rs_winner_traj=torch.zeros(rows, cap, dtype=i32, device=dev),
+                                    rs_winner2_traj=torch.zeros(rows, cap, dtype=i32, device=dev))
+                    rows = int(bufs["rs_dist_traj"].shape[0])
+                    general.update(dist_traj=bufs["rs_dist_traj"], winner_traj=bufs["rs_winner_traj"], winner2_traj=bufs["rs_winner2_traj"])
             ent["restraints"] = rs
             ent["restraints_struct"] = hip_lib.restraints_struct(cap, *(bufs[k] for k in ("rs_ptr", "rs_point", "rs_min_d", "rs_max_d",
                                                                                         "rs_weight", "rs_atom", "rs_group")),
-                                                                 rs["scale"], rs["t_min"], rs["t_max"])
-            ent["restraint_sig"] = (cap, rs["scale"], rs["t_min"], rs["t_max"])
+                                                                 rs["scale"], rs["t_min"], rs["t_max"], traj_positions=rows, **general)
+            # (what the captured launch carries by value, and which kernel it is: "general" / the trajectory rows, 0 = none)
+            ent["restraint_sig"] = (cap, rs["scale"], rs["t_min"], rs["t_max"], "general" if rs["general"] else "point", rows)
         ref = lambda st: None if st is None else ctypes.byref(st)
         ent["launch"] = dict(keys=hip_lib.ptr(bound["sample_keys"]), fixed=ref(ent["fixed_struct"]), resample=ref(ent["resample_struct"]),
                              restraints=ref(ent["restraints_struct"]))
@@ -1651,6 +1764,19 @@ class DecompScorePosNet3D(nn.Module):
           gains ``restraint_dist`` [R] and ``restraint_atom`` [R] (the flat row of the atom that counts, or -1: an empty group)
           of the final state.  Bad keys, shapes, dtypes, non-finite values, ``min_d > max_d``, an ``atom`` of another sample, a
           scaffold / arm group without ``ligand_decomp_index``, the term listed twice: ValueError before anything is launched.
+          Optional keys of the same entry (the general form; an entry without them runs the point kernel, bit for bit as before):
+          ``classes`` / ``classes2`` -- None, a bool tensor [R, num_classes], or R entries of None | class ids: the endpoint's
+          candidates are those whose CURRENT atom class (the chain's ``v_t``) is in the set, an explicit atom included;
+          ``atom2`` / ``group2`` -- as ``atom`` / ``group``: restraint r is a PAIR restraint iff ``atom2[r] >= 0`` or ``group2[r]``
+          is given (``RESTRAINT_NONE`` or None in a list: no second endpoint), its distance that of the nearest pair (i, j), i != j,
+          of the two candidate sets (first in (i, j) order), the gradient +c u on i and -c u on j; ``point`` may then be None;
+          ``form`` -- ``"linear"`` (default) | ``"harmonic"`` (``weight (relu(min_d - d)^2 + relu(d - max_d)^2)``), or R of them;
+          ``traj=True`` -- the result gains ``restraint_dist_traj`` [n_pos, R] and ``restraint_atom_traj`` [n_pos, R] (with pairs
+          also ``restraint_atom2_traj``): entry p holds the distance and winner(s) at the state (x_t, v_t) that the step of
+          position p took its gradient from, window open or not, whatever ``keep_traj`` says.  With pairs the result gains
+          ``restraint_atom2`` [R] (-1 for a point restraint or an empty pair).  Class ids outside ``[0, num_classes)``, an empty
+          class set, ``atom2`` of another sample or equal to ``atom``, a pair without a second endpoint, an arm / scaffold
+          ``group2`` without ``ligand_decomp_index``, an unknown ``form``, a non-bool ``traj``: ValueError.
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
@@ -1680,7 +1806,7 @@ class DecompScorePosNet3D(nn.Module):
                               protein_pos.device, need_cc=resample is not None)
         energy_drift_opt, restraints = _split_restraints(energy_drift_opt)
         if restraints is not None:
-            restraints = _as_restraints(restraints, batch_ligand, ligand_decomp_index, self.num_timesteps)
+            restraints = _as_restraints(restraints, batch_ligand, ligand_decomp_index, self.num_timesteps, self.num_classes)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         key_t = (protein_pos, batch_protein, batch_ligand, ligand_fc_bond_index, ligand_v_aux)
@@ -2097,19 +2223,40 @@ class DecompScorePosNet3D(nn.Module):
         ``restraint`` entry, in the caller's restraint order: ONE dd_drift_restraint launch per chain on its final state."""
         if call.restraints is None:
             return
-        lib, R = hip_lib.load(), call.restraints["R"]
-        dist, atom = torch.full((R,), math.inf), torch.full((R,), -1, dtype=torch.long)
+        lib, R, n_pos = hip_lib.load(), call.restraints["R"], call.n_pos
+        general, traj = bool(call.restraints.get("general")), bool(call.restraints.get("traj"))
+        pairs = general and bool(call.restraints["pair"].any())
+        dist, atom, atom2 = torch.full((R,), math.inf), torch.full((R,), -1, dtype=torch.long), torch.full((R,), -1, dtype=torch.long)
+        dist_t, atom_t, atom2_t = (torch.full((n_pos, R), math.inf), torch.full((n_pos, R), -1, dtype=torch.long),
+                                   torch.full((n_pos, R), -1, dtype=torch.long))
         for c in chains:
             ent, bufs, dev = c["ent"], c["bufs"], c["dev"]
             rs = ent["restraints"]
-            hip_lib.check(lib.dd_drift_restraint(hip_lib.ptr(bufs["lig_pos"]), hip_lib.ptr(bufs.get("decomp_index")), hip_lib.ptr(bufs.get("nl_real")),
-                                                 c["B"], c["NL"], ctypes.byref(ent["restraints_struct"]), None, hip_lib.ptr(bufs["rs_grad"]), 0,
-                                                 hip_lib.ptr(bufs["rs_dist"]), hip_lib.ptr(bufs["rs_winner"]), hip_lib.stream_ptr(dev)),
-                          "dd_drift_restraint")
-            win = bufs["rs_winner"][:rs["R"]].cpu().long()
+            flat = lambda w: torch.where(w >= 0, rs["first"] + w, w)          # (rows within the sample -> the caller's flat rows)
+            if not general:
+                hip_lib.check(lib.dd_drift_restraint(hip_lib.ptr(bufs["lig_pos"]), hip_lib.ptr(bufs.get("decomp_index")), hip_lib.ptr(bufs.get("nl_real")),
+                                                     c["B"], c["NL"], ctypes.byref(ent["restraints_struct"]), None, hip_lib.ptr(bufs["rs_grad"]), 0,
+                                                     hip_lib.ptr(bufs["rs_dist"]), hip_lib.ptr(bufs["rs_winner"]), hip_lib.stream_ptr(dev)),
+                              "dd_drift_restraint")
+            else:                                                           # (no run state: the trajectory rows stay as the chain left them)
+                hip_lib.check(lib.dd_drift_restraint2(hip_lib.ptr(bufs["lig_pos"]), hip_lib.ptr(bufs["lig_v"]), hip_lib.ptr(bufs.get("decomp_index")),
+                                                      hip_lib.ptr(bufs.get("nl_real")), c["B"], c["NL"], ctypes.byref(ent["restraints_struct"]), None,
+                                                      hip_lib.ptr(bufs["rs_grad"]), 0, hip_lib.ptr(bufs["rs_dist"]), hip_lib.ptr(bufs["rs_winner"]),
+                                                      hip_lib.ptr(bufs["rs_winner2"]), hip_lib.stream_ptr(dev)), "dd_drift_restraint2")
+                atom2[rs["order"]] = flat(bufs["rs_winner2"][:rs["R"]].cpu().long())
             dist[rs["order"]] = bufs["rs_dist"][:rs["R"]].cpu()
-            atom[rs["order"]] = torch.where(win >= 0, rs["first"] + win, win)
+            atom[rs["order"]] = flat(bufs["rs_winner"][:rs["R"]].cpu().long())
+            if traj and n_pos > 0:
+                dist_t[:, rs["order"]] = bufs["rs_dist_traj"][:n_pos, :rs["R"]].cpu()
+                atom_t[:, rs["order"]] = flat(bufs["rs_winner_traj"][:n_pos, :rs["R"]].cpu().long())
+                atom2_t[:, rs["order"]] = flat(bufs["rs_winner2_traj"][:n_pos, :rs["R"]].cpu().long())
         out["restraint_dist"], out["restraint_atom"] = dist, atom
+        if pairs:
+            out["restraint_atom2"] = atom2
+        if traj:
+            out["restraint_dist_traj"], out["restraint_atom_traj"] = dist_t, atom_t
+            if pairs:
+                out["restraint_atom2_traj"] = atom2_t
 
     def _collect_chain(self, chain, num_steps, keep_traj, rows_atoms=None, rows_bonds=None):
         """Result dict of a finished chain.  rows_atoms / rows_bonds (padded batches): the rows of the dense [B*NL] /

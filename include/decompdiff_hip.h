@@ -672,8 +672,37 @@ int dd_drift_arms_repul(const float* lig_pos, const int32_t* decomp_index, int B
  *   `size` is the caller's sizeof(dd_restraints).  DD_ERR_BAD_ARG before any launch: NL > 128, R < 0, a NULL ptr (or, R > 0, any
  *   other NULL array), t_min > t_max, and -- read back from the device with one synchronous copy on `stream` -- a ptr that does
  *   not start at 0, rise monotonically and end at R, an atom outside [-1, NL), a group below -1 other than DD_RESTRAINT_ANY, an
- *   arm / scaffold group without decomp_index.  dd_reverse_step stays without restraints.  (New entry points, ABI unchanged.) */
+ *   arm / scaffold group without decomp_index.  dd_reverse_step stays without restraints.  (New entry points, ABI unchanged.)
+ *
+ * The general form (typed atoms, ligand-ligand pairs, harmonic hinges, per-step distances) rides on the trailing fields of
+ * dd_restraints, every one a NULL-able DEVICE pointer.  A struct whose `size` ends before them, or that leaves them all NULL,
+ * is served by the kernel described above, bit for bit; any non-NULL one sends the launch to the general kernel.
+ *   Endpoints: restraint r has endpoint 1 -- atom[r] / group[r], filtered by the class set cls[r] -- and, where pair[r] != 0,
+ *     endpoint 2 -- atom2[r] / group2[r] / cls2[r]; without a pair its other end is point[r] as above.
+ *   Candidates: an endpoint's candidates are the explicit atom or the real atoms of the group (never a padding row).  A class set
+ *     is a 32-bit mask (bit c = class c; NULL array: untyped) and keeps the candidates whose CURRENT class lig_v[row] is in it:
+ *     an explicit atom of another class is an empty set, a class id outside [0, 32) matches nothing.
+ *   Point restraint: as above over the filtered set (first nearest in row order; empty: +inf, winner -1, no gradient).
+ *   Pair restraint: the winner is the pair (i, j), i in set 1, j in set 2, i != j, that minimises d = |x_i - x_j|; ties go to the
+ *     first in (i, then j) row order under strict <.  With u = (x_i - x_j) / d the gradient +c u goes on row i and -c u on row j,
+ *     c the hinge coefficient of the form in force; d == 0 gives nothing; an empty set, or two sets that are the same single
+ *     atom, give +inf / -1 / -1 and nothing.  point[r] of a pair is not read.
+ *   Form: form[r] == 0 (or a NULL array), linear: w (relu(min_d - d) + relu(d - max_d)), c = -w / +w;  form[r] == 1, harmonic:
+ *     w (relu(min_d - d)^2 + relu(d - max_d)^2), c = -2 w (min_d - d) below the window, 2 w (d - max_d) above it.  No division
+ *     by B or R in either.  scale, t_min / t_max and weight >= 0 keep their meaning.
+ *   Held atoms (dd_fixed) are candidates; the hold overwrites their own motion: of a pair with one held end only the free end moves.
+ *   Trajectories: with a run state, every launch writes row `step` (steps done) of dist_traj / winner_traj / winner2_traj
+ *     [traj_positions, R] -- the distance and winner(s) at the state the step of that position takes its gradient from --,
+ *     window open or not; nothing is written at step >= traj_positions or without a run state.
+ *   dd_drift_restraint2: dd_drift_restraint with the atom classes lig_v (NULL: untyped only) and winner2 [R] (the j of a pair; -1
+ *     for a point restraint or an empty pair).  dd_sample_steps_guided / dd_graph_create_guided pass the sampler's own lig_v.
+ *   One workgroup per sample, no atomics: the same bits on every run, and a sample's rows do not depend on its batch.
+ *   DD_ERR_BAD_ARG before any launch, beyond the list above: pair without atom2 and group2; for a pair row an atom2 outside
+ *   [-1, NL), or, atom2 == -1, a group2 that is neither DD_RESTRAINT_ANY nor >= -1 (DD_RESTRAINT_NONE included), or an arm /
+ *   scaffold group2 without decomp_index; a form outside {0, 1}; cls / cls2 with a NULL lig_v; trajectory pointers with
+ *   traj_positions <= 0.  dd_drift_restraint itself refuses a struct that carries any of the trailing arrays. */
 enum { DD_RESTRAINT_ANY = -3 };  /* not an arm id (>= 0), not the scaffold (-1), not the padding mark of padded chains (-2) */
+enum { DD_RESTRAINT_NONE = -4 }; /* group2 of a row without a second endpoint: matches no atom */
 typedef struct dd_restraints {
   int32_t size;                  /* sizeof(dd_restraints) of the caller */
   int32_t R;                     /* restraints in the arrays */
@@ -686,10 +715,25 @@ typedef struct dd_restraints {
   const int32_t* group;          /* DEVICE [R] */
   int32_t scale;                 /* != 0: the step multiplies the gradient by tab_score[t] */
   int32_t t_min, t_max;          /* the window, inclusive (0 and T - 1: always) */
+  /* the general form: every field below may be NULL / 0, and a caller's smaller `size` reads as that */
+  const uint32_t* cls;           /* DEVICE [R] class mask of endpoint 1 */
+  const uint32_t* cls2;          /* DEVICE [R] class mask of endpoint 2 */
+  const int32_t* pair;           /* DEVICE [R] != 0: a pair restraint */
+  const int32_t* atom2;          /* DEVICE [R] */
+  const int32_t* group2;         /* DEVICE [R] */
+  const int32_t* form;           /* DEVICE [R] 0 linear, 1 harmonic */
+  float* dist_traj;              /* DEVICE [traj_positions, R] */
+  int32_t* winner_traj;          /* DEVICE [traj_positions, R] row within the sample or -1 */
+  int32_t* winner2_traj;         /* DEVICE [traj_positions, R] */
+  int32_t traj_positions;        /* rows of the trajectory buffers */
 } dd_restraints;
 int dd_drift_restraint(const float* lig_pos, const int32_t* decomp_index /*or NULL*/, const int32_t* nl_real /*or NULL*/, int B, int NL,
                        const dd_restraints* restraints /*HOST*/, const int32_t* step_counter /*DEVICE [4] or NULL*/, float* grad,
                        int accumulate, float* dist /*or NULL*/, int32_t* winner /*or NULL*/, void* stream);
+int dd_drift_restraint2(const float* lig_pos, const int32_t* lig_v /*int32 [B*NL] or NULL: untyped only*/, const int32_t* decomp_index /*or NULL*/,
+                        const int32_t* nl_real /*or NULL*/, int B, int NL, const dd_restraints* restraints /*HOST*/,
+                        const int32_t* step_counter /*DEVICE [4] or NULL*/, float* grad, int accumulate, float* dist /*or NULL*/,
+                        int32_t* winner /*or NULL*/, int32_t* winner2 /*or NULL*/, void* stream);
 int dd_sample_steps_guided(const dd_sampler* s, const dd_model_opts* opts /*HOST*/, const uint64_t* sample_keys /*DEVICE [B] or NULL*/,
                            const dd_fixed* fixed /*HOST or NULL*/, const dd_resample* resample /*HOST or NULL*/,
                            const dd_restraints* restraints /*HOST or NULL*/, int n_steps, void* stream);
