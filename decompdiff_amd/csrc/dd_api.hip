@@ -755,10 +755,16 @@ struct ModelOpts {
   const dd_bond_head* bh = nullptr;
   const dd_node_out* no = nullptr;
   int num_blocks = 1;
-  const uint64_t* sample_keys = nullptr;   // per-sample noise keys of the *_keyed entry points ([B], device), not part of dd_model_opts
-  const dd_fixed* fixed = nullptr;         // fixed atoms of the *_fixed entry points (a checked host copy), not part of dd_model_opts
-  const int32_t* epoch = nullptr;          // resampling epoch of the *_resample entry points (a device int, read at every launch)
-  const Restraint2Args* restraints = nullptr;  // distance restraints of the *_guided entry points (checked), not part of dd_model_opts
+};
+// What a chain's reverse steps take beyond the model: the arguments of the *_keyed / *_fixed / *_resample / *_guided entry points,
+// checked and held by value (read_step_extras)
+struct StepExtras {
+  const uint64_t* sample_keys = nullptr;   // per-sample noise keys ([B], device, read at every launch) or NULL
+  bool has_fixed = false;
+  dd_fixed fixed = {};                     // has_fixed: the fixed atoms (device pointers, read at every launch)
+  const int32_t* epoch = nullptr;          // resampling epoch (a device int, read at every launch) or NULL
+  bool has_restraints = false;
+  RestraintArgs restraints = {};           // has_restraints: the distance restraints
 };
 static int check_blocks(const dd_sampler* s, int num_blocks) {
   if (!s || num_blocks < 1) return DD_ERR_BAD_ARG;
@@ -1144,7 +1150,7 @@ static int forward_impl(const dd_sampler* s, hipStream_t st, StepFold* fold = nu
 // restraints: the chain's distance restraints or NULL; their kernel reads the run state (counter_bias as the step kernels').
 struct DriftGrads { const float *ga = nullptr, *gc = nullptr, *gr = nullptr, *gq = nullptr; int scale_q = 0; };
 static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled, hipStream_t st, DriftGrads* d,
-                         const Restraint2Args* restraints = nullptr, int counter_bias = 0) {
+                         const RestraintArgs* restraints = nullptr, int counter_bias = 0) {
   const int B = s->B, NL = s->NL;
   auto run = [&](auto&& launch) -> int {
     ProfScope prof_scope(DD_PROF_STEP, st, profiled);
@@ -1169,17 +1175,12 @@ static int launch_drifts(const dd_sampler* s, const Workspace& w, bool profiled,
     d->gr = w.gr;
   }
   if (restraints) {
-    RestraintArgs q = restraints->o;
+    RestraintArgs q = *restraints;
     q.pos = s->lig_pos; q.decomp = s->decomp_index; q.nl_real = s->nl_real; q.step_counter = s->step_counter;
     q.counter_bias = counter_bias; q.grad = w.gq; q.accumulate = 0; q.dist = nullptr; q.winner = nullptr;
-    if (restraints->general) {                             // (typed / pair / harmonic / trajectories: the sampler's own atom classes)
-      Restraint2Args g = *restraints;
-      g.o = q; g.lig_v = s->lig_v; g.winner2 = nullptr;
-      DD_TRY(run([&] { return launch_drift_restraint2(g, st); }));
-    } else {
-      DD_TRY(run([&] { return launch_drift_restraint(q, st); }));
-    }
-    d->gq = w.gq; d->scale_q = restraints->o.scale;
+    q.lig_v = s->lig_v; q.winner2 = nullptr;               // (typed restraints: the sampler's own atom classes)
+    DD_TRY(run([&] { return launch_drift_restraint(q, st); }));
+    d->gq = w.gq; d->scale_q = q.scale;
   }
   return DD_OK;
 }
@@ -1215,16 +1216,15 @@ static void fill_step_args(const dd_sampler* s, const DriftGrads& d, const uint6
   if (fixed) { p->fx_mask = fixed->mask; p->fx_x0c = fixed->x0c; p->fx_cc = fixed->cc; p->fx_tab = fixed->tab; p->fx_mode = fixed->mode; p->epoch = epoch; }
 }
 
-static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold = nullptr, const uint64_t* sample_keys = nullptr,
-                          const dd_fixed* fixed = nullptr, const int32_t* epoch = nullptr, const Restraint2Args* restraints = nullptr) {
+static int heads_and_step(const dd_sampler* s, hipStream_t st, const StepFold* fold, const StepExtras& x) {
   const Fwd f(s);
   const Workspace& w = f.w;
   const bool advanced = fold && fold->advance;
   DriftGrads d;
-  DD_TRY(launch_drifts(s, w, true, st, &d, restraints, advanced ? 1 : 0));
+  DD_TRY(launch_drifts(s, w, true, st, &d, x.has_restraints ? &x.restraints : nullptr, advanced ? 1 : 0));
   StepRowsArgs r, rb;
   StepPosArgs p;
-  fill_step_args(s, d, sample_keys, fixed, &r, &rb, &p, epoch);
+  fill_step_args(s, d, x.sample_keys, x.has_fixed ? &x.fixed : nullptr, &r, &rb, &p, x.epoch);
   r.counter_bias = rb.counter_bias = p.counter_bias = advanced ? 1 : 0;
   r.hid = w.qn; r.W2 = f.GW(DD_G_VH_W2); r.b2 = f.GW(DD_G_VH_b2); r.logits_out = s->pred_v;
   rb.hid = w.qb; rb.W2 = f.GW(DD_G_BH_W2); rb.b2 = f.GW(DD_G_BH_b2); rb.logits_out = s->pred_bond;
@@ -1645,12 +1645,13 @@ static bool check_step_sampler(const dd_sampler* s) {
   return s && s->step_counter && s->tab_pos && s->tab_v && s->tab_b && s->atom_std && s->offset && s->pred_pos;
 }
 
-static int one_step(const dd_sampler* s, hipStream_t st, const dd::ModelOpts& mo = dd::ModelOpts()) {
+static int one_step(const dd_sampler* s, hipStream_t st, const dd::ModelOpts& mo = dd::ModelOpts(),
+                    const dd::StepExtras& x = dd::StepExtras()) {
   dd::StepFold fold;
   fold.advance = fold.fold_tail = dd::g_step_fold != 0;
   int rc = dd::forward_impl(s, st, &fold, mo);
   if (rc != DD_OK) return rc;
-  return dd::heads_and_step(s, st, &fold, mo.sample_keys, mo.fixed, mo.epoch, mo.restraints);
+  return dd::heads_and_step(s, st, &fold, x);
 }
 
 extern "C" int dd_reverse_step(const dd_sampler* s, const float* logits_v, const float* logits_b, const float* x0, void* stream) {
@@ -1684,10 +1685,7 @@ static bool keys_with_injected_noise(const dd_sampler* s, const uint64_t* sample
 
 // The caller's dd_fixed as a checked copy (fields beyond its `size` are NULL / 0); NULL stays "no fixed atoms"
 static int read_fixed(const dd_fixed* fixed, dd_fixed* out) {
-  memset(out, 0, sizeof(*out));
-  if (fixed->size < (int32_t)sizeof(int32_t) || fixed->size > 4096) return DD_ERR_BAD_ARG;
-  memcpy(out, fixed, (size_t)fixed->size < sizeof(*out) ? (size_t)fixed->size : sizeof(*out));
-  out->size = (int32_t)sizeof(*out);
+  if (!dd::read_sized(fixed, out)) return DD_ERR_BAD_ARG;
   if (out->mode != DD_FIXED_HOLD && out->mode != DD_FIXED_REPLACE) return DD_ERR_BAD_ARG;
   if (!out->mask || !out->v0 || !out->b0 || !out->x0c) return DD_ERR_BAD_ARG;
   if (out->mode == DD_FIXED_REPLACE && (!out->cc || !out->tab)) return DD_ERR_BAD_ARG;
@@ -1701,11 +1699,7 @@ extern "C" int dd_sample_steps_keyed(const dd_sampler* s, const dd_model_opts* o
 // The caller's dd_resample as a checked copy: every field is needed, the chain has fixed atoms with centres (a jump noises around
 // them in both modes), draws on the device, and its times fit the 16 bits of the time word below the epoch
 static int read_resample(const dd_resample* rsm, const dd_sampler* s, const dd_fixed* fixed, dd_resample* out) {
-  memset(out, 0, sizeof(*out));
-  if (rsm == nullptr || fixed == nullptr || s == nullptr) return DD_ERR_BAD_ARG;
-  if (rsm->size < (int32_t)sizeof(int32_t) || rsm->size > 4096) return DD_ERR_BAD_ARG;
-  memcpy(out, rsm, (size_t)rsm->size < sizeof(*out) ? (size_t)rsm->size : sizeof(*out));
-  out->size = (int32_t)sizeof(*out);
+  if (!dd::read_sized(rsm, out) || fixed == nullptr || s == nullptr) return DD_ERR_BAD_ARG;
   if (out->jump_length < 1 || !out->tab || !out->epoch) return DD_ERR_BAD_ARG;
   if (s->T < 1 || s->T > 65535 || s->u_v || s->u_b || s->eps) return DD_ERR_BAD_ARG;
   return DD_OK;
@@ -1731,38 +1725,45 @@ extern "C" int dd_sample_steps_guided(const dd_sampler* s, const dd_model_opts* 
   return sample_steps_impl(s, opts, sample_keys, fixed, resample, restraints, n_steps, stream);
 }
 
-// The chain's dd_restraints, checked against the sampler, for the step entry points (NULL stays "no restraints")
-static int read_step_restraints(const dd_restraints* rst, const dd_sampler* s, hipStream_t st, dd::Restraint2Args* out) {
-  if (!s || !s->workspace || !s->lig_pos) return DD_ERR_BAD_ARG;
-  const int rc = dd::read_restraints2(rst, s->B, s->NL, s->decomp_index != nullptr, s->lig_v != nullptr, true, st, out);
+// What the step entry points take beside their step count, read and checked in one place, each of the last four NULL-able: the
+// model against the sampler, the keys (a keyed chain draws on the device), the fixed atoms, the resampling schedule (it needs fixed
+// atoms) and the restraints (checked against the sampler; their arrays are fetched on `st` and waited for).  capture: a graph is
+// about to be captured from `st`, which must then be a real stream, and an unsupported shape is reported before the restraints
+// are fetched -- the eager loop learns of one in its first forward.
+static int read_step_extras(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
+                            const dd_resample* rsm, const dd_restraints* rst, hipStream_t st, bool capture, dd::ModelOpts* mo,
+                            dd::StepExtras* x) {
+  *x = dd::StepExtras();
+  if (read_model_opts(opts, mo) != DD_OK || check_model(s, *mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
+  if (!check_step_sampler(s) || keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
+  if (fixed != nullptr && read_fixed(fixed, &x->fixed) != DD_OK) return DD_ERR_BAD_ARG;
+  dd_resample rs;
+  if (rsm != nullptr && read_resample(rsm, s, fixed, &rs) != DD_OK) return DD_ERR_BAD_ARG;
+  x->sample_keys = sample_keys;
+  x->has_fixed = fixed != nullptr;
+  x->epoch = rsm != nullptr ? rs.epoch : nullptr;
+  if (capture) {
+    if (st == nullptr) return DD_ERR_BAD_ARG;    // the legacy default stream cannot be captured
+    const int rc = dd::check_shapes(s);
+    if (rc != DD_OK) return rc;
+  }
+  if (rst == nullptr) return DD_OK;
+  if (!s->workspace || !s->lig_pos) return DD_ERR_BAD_ARG;
+  const int rc = dd::read_restraints(rst, s->B, s->NL, s->decomp_index != nullptr, s->lig_v != nullptr, true, st, &x->restraints);
   if (rc != DD_OK) return rc;
-  return out->o.t_min < 0 || out->o.t_max >= s->T ? DD_ERR_BAD_ARG : DD_OK;
+  x->has_restraints = true;
+  return x->restraints.t_min < 0 || x->restraints.t_max >= s->T ? DD_ERR_BAD_ARG : DD_OK;
 }
 
 static int sample_steps_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                              const dd_resample* rsm, const dd_restraints* rst, int n_steps, void* stream) {
-  dd::ModelOpts mo;
-  if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
-  if (!check_step_sampler(s) || n_steps < 0 || keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
-  dd_fixed fx;
-  if (fixed != nullptr && read_fixed(fixed, &fx) != DD_OK) return DD_ERR_BAD_ARG;
-  dd_resample rs;
-  if (rsm != nullptr && read_resample(rsm, s, fixed, &rs) != DD_OK) return DD_ERR_BAD_ARG;
-  mo.sample_keys = sample_keys;
-  mo.fixed = fixed != nullptr ? &fx : nullptr;
-  mo.epoch = rsm != nullptr ? rs.epoch : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  dd::Restraint2Args ra;
-  if (rst != nullptr) {
-    const int rrc = read_step_restraints(rst, s, st, &ra);
-    if (rrc != DD_OK) return rrc;
-    mo.restraints = &ra;
-  }
-  for (int i = 0; i < n_steps; ++i) {
-    int rc = one_step(s, st, mo);
-    if (rc != DD_OK) return rc;
-  }
-  return DD_OK;
+  dd::ModelOpts mo;
+  dd::StepExtras x;
+  if (n_steps < 0) return DD_ERR_BAD_ARG;
+  int rc = read_step_extras(s, opts, sample_keys, fixed, rsm, rst, st, false, &mo, &x);
+  for (int i = 0; i < n_steps && rc == DD_OK; ++i) rc = one_step(s, st, mo, x);
+  return rc;
 }
 
 extern "C" int dd_sample_steps_graph(const dd_sampler* s, int n_steps, void* stream) {
@@ -1776,8 +1777,8 @@ extern "C" int dd_sample_steps_graph_ex(const dd_sampler* s, const dd_bond_head*
 // `steps` reverse steps of `s` captured from `st` into a graph and instantiated.  Measures the node split of the shape first
 // (eager passes), then holds the capture mutex while the stream captures: the side stream / events of the device are shared.
 // On any failure nothing is left behind: what was made is destroyed, *graph / *exec are NULL and the sticky HIP error is cleared.
-static int capture_steps(const dd_sampler* s, const dd::ModelOpts& mo, int steps, hipStream_t st, hipGraph_t* graph,
-                         hipGraphExec_t* exec) {
+static int capture_steps(const dd_sampler* s, const dd::ModelOpts& mo, const dd::StepExtras& x, int steps, hipStream_t st,
+                         hipGraph_t* graph, hipGraphExec_t* exec) {
   *graph = nullptr;
   *exec = nullptr;
   int rc = autotune_node_split(s, mo.num_blocks, st);
@@ -1788,7 +1789,7 @@ static int capture_steps(const dd_sampler* s, const dd::ModelOpts& mo, int steps
       (void)hipGetLastError();                     // do not leave a sticky error behind for the caller
       return DD_ERR_HIP;
     }
-    for (int i = 0; i < steps && rc == DD_OK; ++i) rc = one_step(s, st, mo);
+    for (int i = 0; i < steps && rc == DD_OK; ++i) rc = one_step(s, st, mo, x);
     if (hipStreamEndCapture(st, graph) != hipSuccess || !*graph) rc = rc != DD_OK ? rc : DD_ERR_HIP;
   }
   if (rc == DD_OK && hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) rc = DD_ERR_HIP;
@@ -1817,7 +1818,7 @@ extern "C" int dd_sample_steps_graph_opts(const dd_sampler* s, const dd_model_op
   if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  rc = capture_steps(s, mo, 1, st, &graph, &exec);
+  rc = capture_steps(s, mo, dd::StepExtras(), 1, st, &graph, &exec);
   if (rc != DD_OK) return rc;
   for (int i = 0; i < n_steps; ++i) {
     if (hipGraphLaunch(exec, st) != hipSuccess) { rc = DD_ERR_HIP; break; }
@@ -1867,10 +1868,7 @@ extern "C" int dd_fixed_init(const dd_sampler* s, const uint64_t* sample_keys, c
 
 // The caller's dd_init as a checked copy (fields beyond its `size` are NULL / 0)
 static int read_init(const dd_init* init, dd_init* out) {
-  memset(out, 0, sizeof(*out));
-  if (init->size < (int32_t)sizeof(int32_t) || init->size > 4096) return DD_ERR_BAD_ARG;
-  memcpy(out, init, (size_t)init->size < sizeof(*out) ? (size_t)init->size : sizeof(*out));
-  out->size = (int32_t)sizeof(*out);
+  if (!dd::read_sized(init, out)) return DD_ERR_BAD_ARG;
   if (out->mode != DD_INIT_PRIOR && out->mode != DD_INIT_NOISED) return DD_ERR_BAD_ARG;
   if (!out->cc || !out->std) return DD_ERR_BAD_ARG;
   if (out->mode == DD_INIT_NOISED && (!out->x0c || !out->v0 || !out->b0 || !out->tab)) return DD_ERR_BAD_ARG;
@@ -1930,29 +1928,14 @@ extern "C" int dd_sampler_reset_resample(const dd_sampler* s, const dd_resample*
 
 static int graph_create_impl(const dd_sampler* s, const dd_model_opts* opts, const uint64_t* sample_keys, const dd_fixed* fixed,
                              const dd_resample* rsm, const dd_restraints* rst, int steps_per_graph, void* stream, void** graph_out) {
-  dd::ModelOpts mo;
-  if (read_model_opts(opts, &mo) != DD_OK || check_model(s, mo) == DD_ERR_BAD_ARG) return DD_ERR_BAD_ARG;
-  if (!check_step_sampler(s) || !graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
-  if (keys_with_injected_noise(s, sample_keys)) return DD_ERR_BAD_ARG;
-  dd_fixed fx;
-  if (fixed != nullptr && read_fixed(fixed, &fx) != DD_OK) return DD_ERR_BAD_ARG;
-  dd_resample rs;
-  if (rsm != nullptr && read_resample(rsm, s, fixed, &rs) != DD_OK) return DD_ERR_BAD_ARG;
-  mo.sample_keys = sample_keys;
-  mo.fixed = fixed != nullptr ? &fx : nullptr;
-  mo.epoch = rsm != nullptr ? rs.epoch : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  if (st == nullptr) return DD_ERR_BAD_ARG;      // the legacy default stream cannot be captured
-  int rc = dd::check_shapes(s);
+  dd::ModelOpts mo;
+  dd::StepExtras x;
+  if (!graph_out || steps_per_graph < 1 || steps_per_graph > 64) return DD_ERR_BAD_ARG;
+  int rc = read_step_extras(s, opts, sample_keys, fixed, rsm, rst, st, true, &mo, &x);
   if (rc != DD_OK) return rc;
-  dd::Restraint2Args ra;
-  if (rst != nullptr) {
-    rc = read_step_restraints(rst, s, st, &ra);
-    if (rc != DD_OK) return rc;
-    mo.restraints = &ra;
-  }
   StepGraph* g = new StepGraph();
-  rc = capture_steps(s, mo, steps_per_graph, st, &g->graph, &g->exec);
+  rc = capture_steps(s, mo, x, steps_per_graph, st, &g->graph, &g->exec);
   if (rc != DD_OK) {
     delete g;
     return rc;
@@ -2020,7 +2003,7 @@ extern "C" int dd_sample_steps_graph_multi_opts(const dd_sampler* const* ss, con
   // the side streams / events used inside a step are shared, which is fine: they only shape each graph while it
   // is being captured, one chain at a time; the replays below do not touch them
   for (int i = 0; i < n && rc == DD_OK; ++i)
-    rc = capture_steps(ss[i], mos[i], 1, (hipStream_t)streams[i], &graph[i], &exec[i]);
+    rc = capture_steps(ss[i], mos[i], dd::StepExtras(), 1, (hipStream_t)streams[i], &graph[i], &exec[i]);
   if (rc == DD_OK) {
     static const int threaded = [] { const char* e = getenv("DD_MULTI_THREADS"); return e ? atoi(e) : 1; }();
     if (threaded) {

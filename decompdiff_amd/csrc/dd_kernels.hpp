@@ -1,8 +1,22 @@
 // Kernel argument structs and launcher prototypes shared by the translation units.
 #pragma once
+#include <string.h>
+
 #include "dd_common.hpp"
 
 namespace dd {
+
+// A checked copy of a caller's `size`-prefixed struct (include/decompdiff_hip.h: dd_fixed, dd_resample, dd_init, dd_restraints):
+// fields beyond the caller's `size` read as NULL / 0, so a caller built against a shorter struct keeps working; the copy's `size`
+// is the full one.  false (and all zeros): NULL, or a size outside [4, 4096].
+template <class T>
+inline bool read_sized(const T* in, T* out) {
+  memset(out, 0, sizeof(T));
+  if (in == nullptr || in->size < (int32_t)sizeof(int32_t) || in->size > 4096) return false;
+  memcpy(out, in, (size_t)in->size < sizeof(T) ? (size_t)in->size : sizeof(T));
+  out->size = (int32_t)sizeof(T);
+  return true;
+}
 
 struct FlagWait { const int32_t* flags; int idx0, n0, idx1, n1; };       // up to two counters (idx < 0: none)
 inline FlagWait no_wait() { return FlagWait{nullptr, -1, 0, -1, 0}; }
@@ -167,16 +181,9 @@ struct RestraintArgs {
   int accumulate;
   float* dist;                   // [R] or NULL
   int32_t* winner;               // [R] row within the sample or -1, or NULL
-};
-int launch_drift_restraint(const RestraintArgs& a, hipStream_t st);
-// the caller's dd_restraints, checked, as the kernel's arguments (pos / decomp / nl_real / step_counter / outputs left to the caller);
-// check_contents: also what only the device arrays say -- copies ptr / atom / group to the host and waits for `st`
-int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, bool check_contents, hipStream_t st, RestraintArgs* out);
-// The general form (dd_restraints' trailing fields): class masks over the current atom classes, ligand-ligand pairs, harmonic hinges
-// and per-step rows of dist / winner(s).  `o` is what k_drift_restraint takes, unchanged; `general`: the caller's struct carries a
-// non-NULL trailing array -- launch k_drift_restraint2 --, else everything below is NULL and `o` goes to k_drift_restraint.
-struct Restraint2Args {
-  RestraintArgs o;
+  // The general form (dd_restraints' trailing fields): class masks over the current atom classes, ligand-ligand pairs, harmonic
+  // hinges and per-step rows of dist / winner(s).  `general`: the caller's struct carries a non-NULL trailing array -- the launch
+  // takes k_drift_restraint<true> --, else everything below is NULL / 0 and the point instantiation reads none of it.
   bool general;
   const int32_t* lig_v;          // [B*NL] current atom classes or NULL (then cls / cls2 are NULL too)
   const uint32_t *cls, *cls2;    // [R] class masks (bit c = class c) or NULL: untyped
@@ -186,10 +193,12 @@ struct Restraint2Args {
   int32_t *winner_traj, *winner2_traj;
   int traj_positions;
 };
-int launch_drift_restraint2(const Restraint2Args& a, hipStream_t st);
-// read_restraints, then the trailing fields: has_v -- the caller has atom classes for cls / cls2
-int read_restraints2(const dd_restraints* rs, int B, int NL, bool has_decomp, bool has_v, bool check_contents, hipStream_t st,
-                     Restraint2Args* out);
+int launch_drift_restraint(const RestraintArgs& a, hipStream_t st);   // (picks the instantiation from a.general)
+// the caller's dd_restraints, checked, as the kernel's arguments (pos / decomp / nl_real / lig_v / step_counter / outputs left to the
+// caller); has_v: the caller has atom classes for cls / cls2; check_contents: also what only the device arrays say -- copies
+// ptr / atom / group (and pair / atom2 / group2 / form) to the host and waits for `st`
+int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, bool has_v, bool check_contents, hipStream_t st,
+                    RestraintArgs* out);
 int launch_extract_ligand(const float* x, int B, int NP, int NL, float* out, hipStream_t st);
 
 enum { M_NE = 0, M_NB = 1, M_BL = 2, M_PE = 3, M_PB = 4 };
@@ -244,7 +253,8 @@ int launch_xupdate(const float* x, const float* dxe, const float* dxb, int B, in
 
 struct StepRowsArgs {
   const float* hid;        // [rows,128] first Linear of the head (pre-activation incl. bias)
-  const float* logits_in;  // [rows,NC] head outputs supplied by the host instead of hid / W2 / b2 (k_step_rows only), or NULL
+  const float* logits_in;  // [rows,NC] head outputs supplied by the host instead of hid / W2 / b2 (dd_reverse_step: k_step_rows of a
+                           // chain without fixed atoms reads them; k_step_all never does), or NULL
   const float* W2;         // [NC,128]
   const float* b2;         // [NC]
   int rows, NC, rows_per_sample;

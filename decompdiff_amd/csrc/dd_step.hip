@@ -1,15 +1,20 @@
 // Reverse-diffusion step kernels (models/decompdiff.py:601-689, models/transitions.py:65-161)
 // and drift guidance with analytic gradients (utils/guidance_funcs.py:24-78).
 //
-//   k_step_rows   one wave per ligand atom / per bond row: type head second Linear
-//                 (ShiftedSoftplus -> Linear, decompdiff.py:194-211), log_softmax, categorical
-//                 posterior q(v_{t-1}|v_t, v0) in log space, Gumbel-argmax sample, trajectories.
-//   k_step_pos    one thread per ligand coordinate: C0 posterior mean, drift, noise.
-//   k_drift_*     gradients of the armsca_prox / clash / arms_repul energies at x_t, and of the caller's distance restraints
-//                 (k_drift_restraint, EXTENSION: points in the pocket that an atom or the nearest atom of a group must keep to).
+//   step_row       one wave per ligand atom / per bond row: type head second Linear
+//                  (ShiftedSoftplus -> Linear, decompdiff.py:194-211), log_softmax, categorical
+//                  posterior q(v_{t-1}|v_t, v0) in log space, Gumbel-argmax sample, trajectories.
+//   step_pos_elem  one thread per ligand coordinate: C0 posterior mean, drift, noise.
+//   k_step_all     both in one launch per step (block ranges); k_step_rows / k_step_pos: each as a launch of its own
+//                  (dd_reverse_step, where the host supplies the logits, and the measurement build).
+//   forward_row    one wave per row: a class drawn from the forward process or the prior (k_jump, k_chain_init).
+//   k_drift_*      gradients of the armsca_prox / clash / arms_repul energies at x_t, and of the caller's distance restraints
+//                  (k_drift_restraint, EXTENSION: points in the pocket that an atom or the nearest atom of a group must keep to;
+//                  its GENERAL instantiation adds typed atoms, ligand pairs, the harmonic form and per-step rows).
 // The current step index lives in device memory (step_counter) so that one captured hipGraph
 // can be replayed for every step.
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 #include "dd_kernels.hpp"
@@ -112,150 +117,23 @@ __device__ __forceinline__ float fixed_q0(const bool is_v0, const float lca, con
   return log_add_exp((is_v0 ? 0.f : -69.07755278982137f) + lca, l1mca + log_prior);
 }
 __device__ __forceinline__ float gumbel_of(const float u) { return -logf(-logf(u + 1e-30f) + 1e-30f); }
+// the first class with the largest score of a row that holds one class per lane: class order, strict > (a serial loop's winner)
+template <int NC>
+__device__ __forceinline__ int class_argmax(const float sc) {
+  int best = 0;
+  float bestv = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const float sk = lane_bcast(sc, k);
+    if (sk > bestv) { bestv = sk; best = k; }
+  }
+  return best;
+}
 // x_l = A[l] (x0c - cc) + (S[l] e) std + cc (decompdiff.py:436-455 in the centred frame), every operation rounded on its own: the
 // step, the initial level and every batch layout give the same bits
 __device__ __forceinline__ float fixed_noised_pos(const float A, const float S, const float x0c, const float cc, const float e,
                                                   const float std) {
   return __fadd_rn(__fadd_rn(__fmul_rn(A, __fsub_rn(x0c, cc)), __fmul_rn(__fmul_rn(S, e), std)), cc);
-}
-
-template <int NC, bool FIXED>
-__global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= a.rows) return;
-  const RunState rs = load_run_state(a.step_counter, a.counter_bias);
-  const int step = rs.step, t = rs.t_start - step;
-  // ShiftedSoftplus (common.py:66-72): softplus(x) - log 2, torch threshold 20
-  float logit[NC];
-  if (a.logits_in != nullptr) {                          // dd_reverse_step: the host supplies the head outputs
-#pragma unroll
-    for (int c = 0; c < NC; ++c) logit[c] = a.logits_in[row * NC + c];
-  } else {
-    float2 hv = *reinterpret_cast<const float2*>(a.hid + row * 128 + 2 * lane);
-    hv.x = (hv.x > 20.f ? hv.x : log1pf(expf(hv.x))) - 0.6931471805599453f;
-    hv.y = (hv.y > 20.f ? hv.y : log1pf(expf(hv.y))) - 0.6931471805599453f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const float2 w = *reinterpret_cast<const float2*>(a.W2 + c * 128 + 2 * lane);
-      logit[c] = wave_sum(fmaf(hv.y, w.y, hv.x * w.x)) + a.b2[c];
-    }
-  }
-  if (lane != 0) return;
-  // log_softmax
-  float mx = logit[0];
-#pragma unroll
-  for (int c = 1; c < NC; ++c) mx = fmaxf(mx, logit[c]);
-  float se = 0.f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) se += expf(logit[c] - mx);
-  // (x - max) - log(sum), as torch's log_softmax: x - (max + log(sum)) rounds the sum at the size of the logits, which costs the
-  //  leading class half an ulp of max (1.2e-4 at logits of a few thousand) and carries into the posterior
-  const float lsum = logf(se);
-  const int tm1 = t - 1 < 0 ? 0 : t - 1;
-  const float la_t = a.tab[t], l1ma_t = a.tab[a.T + t];
-  const float lca = a.tab[2 * a.T + tm1], l1mca = a.tab[3 * a.T + tm1];
-  const float* log_prior_tab = a.tab + 4 * a.T;         // [NC] log prior (uniform: -log NC), DiscreteTransition.prior_probs
-  const int cur = a.state[row];
-  float un[NC];
-  float umax = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const float log_prior = log_prior_tab[c];
-    const float lv0 = (logit[c] - mx) - lsum;
-    const float lvt = (c == cur) ? 0.f : -69.07755278982137f;    // log(clamp(onehot, 1e-30))
-    const float q0 = log_add_exp(lv0 + lca, l1mca + log_prior);  // q(v_{t-1} | v0)
-    const float q1 = log_add_exp(lvt + la_t, l1ma_t + log_prior); // q(v_t | v_{t-1})
-    un[c] = q0 + q1;
-    umax = fmaxf(umax, un[c]);
-    if (a.logits_out) a.logits_out[row * NC + c] = logit[c];
-    if (a.traj_recon) a.traj_recon[((long)step * a.rows + row) * NC + c] = lv0;
-  }
-  float us = 0.f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) us += expf(un[c] - umax);
-  const float ulse = umax + logf(us);
-  // Gumbel-argmax (transitions.py:78-84)
-  float u[NC];
-  if (a.uniforms) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) u[c] = a.uniforms[((long)step * a.rows + row) * NC + c];
-  } else {
-    const NoiseAddr na = noise_addr(a, row, rs.seed);
-    int tw = t;
-    if constexpr (FIXED) tw = epoch_word(a.epoch, t);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) u[c] = philox_uniform<NC>(na.key, na.row, tw, a.stream_id, c);
-  }
-  int best = 0;
-  float bestv = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const float lp = un[c] - ulse;
-    const float g = -logf(-logf(u[c] + 1e-30f) + 1e-30f);
-    const float s = g + lp;
-    if (s > bestv) { bestv = s; best = c; }
-    if (a.traj_prob) a.traj_prob[((long)step * a.rows + row) * NC + c] = lp;
-  }
-  if constexpr (FIXED) {
-    if (row_held(a, row)) {
-      const int v0 = a.fx_val[row];
-      best = v0;                                          // hold, and the replace step at t = 0
-      if (a.fx_mode == DD_FIXED_REPLACE && t > 0) {
-        bestv = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const float s = gumbel_of(u[c]) + fixed_q0(c == v0, lca, l1mca, log_prior_tab[c]);
-          if (s > bestv) { bestv = s; best = c; }
-        }
-      }
-    }
-  }
-  a.state[row] = best;
-  if (a.traj_state) a.traj_state[(long)step * a.rows + row] = best;
-}
-
-template <bool FIXED>
-__device__ __forceinline__ void step_pos_elem(const StepPosArgs& a, const int idx, const RunState rs);
-
-// (fixed atoms: the coordinate element of the fused launch as a launch of its own; k_step_pos below stays the unfixed one)
-__global__ void k_step_pos_fixed(const StepPosArgs a) {
-  step_pos_elem<true>(a, blockIdx.x * blockDim.x + threadIdx.x, load_run_state(a.step_counter, a.counter_bias));
-}
-
-__global__ void k_step_pos(const StepPosArgs a) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = a.B * a.NL * 3;
-  if (idx >= n) return;
-  const RunState rs = load_run_state(a.step_counter, a.counter_bias);
-  const int step = rs.step, t = rs.t_start - step;
-  const int atom = idx / 3, c = idx % 3, b = atom / a.NL;
-  const float xt = a.xt[idx];
-  float x0;
-  if (a.x0_prev != nullptr) {
-    const int r = idx % (a.NL * 3);
-    x0 = a.x0_prev[((long)b * (a.NP + a.NL) + a.NP) * 3 + r] + a.x0_dxe[idx] + a.x0_dxb[idx];
-    a.x0_out[idx] = x0;
-  } else {
-    x0 = a.x0[idx];
-  }
-  float mean = a.tab_pos[t] * x0 + a.tab_pos[a.T + t] * xt;
-  float g = 0.f;
-  if (a.grad_a) g += a.scale_a ? a.grad_a[idx] * a.tab_score[t] : a.grad_a[idx];
-  if (a.grad_c) g += a.scale_c ? a.grad_c[idx] * a.tab_score[t] : a.grad_c[idx];
-  if (a.grad_r) g += a.scale_r ? a.grad_r[idx] * a.tab_score[t] : a.grad_r[idx];
-  if (a.grad_q) g += a.scale_q ? a.grad_q[idx] * a.tab_score[t] : a.grad_q[idx];
-  mean -= g;
-  float e;
-  if (a.eps) {
-    e = a.eps[(long)step * n + idx];
-  } else {
-    e = step_pos_normal(a, idx, b, rs.seed, t);
-  }
-  const float nz = t == 0 ? 0.f : 1.f;
-  const float nxt = mean + nz * expf(0.5f * a.tab_pos[2 * a.T + t]) * e * a.atom_std[idx];
-  a.xt[idx] = nxt;
-  if (a.traj_pos) a.traj_pos[(long)step * n + idx] = nxt + a.offset[b * 3 + c];
 }
 
 __global__ void k_advance(int32_t* step_counter) { *step_counter += 1; }
@@ -499,97 +377,29 @@ __global__ __launch_bounds__(256) void k_drift_clash(const float* __restrict__ p
 // clamps pass their gradient at equality, a winner at distance 0 gives nothing (as k_drift_armsca), an empty group has distance
 // +inf and winner -1.  Memory-safe for any contents of the restraint arrays: ptr is clamped to [0, R], an atom outside the
 // sample matches no lane.  Outside the time window the gradient rows are zeros; dist / winner are reported either way.
-__global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint(const RestraintArgs a) {
-  __shared__ unsigned long long wk[2][2];
-  const int b = blockIdx.x, l = threadIdx.x, NL = a.NL;
-  int n = a.nl_real ? a.nl_real[b] : NL;
-  n = n < NL ? n : NL;
-  float x = 0.f, y = 0.f, z = 0.f;
-  int my_arm = -2;
-  if (l < n) {
-    const float* p = a.pos + ((long)b * NL + l) * 3;
-    x = p[0]; y = p[1]; z = p[2];
-    if (a.decomp) my_arm = a.decomp[(long)b * NL + l];
-  }
-  bool active = true;
-  if (a.step_counter != nullptr) {
-    const RunState rs = load_run_state(a.step_counter, a.counter_bias);
-    const int t = rs.t_start - rs.step;
-    active = t >= a.t_min && t <= a.t_max;
-  }
-  int r0 = a.ptr[b], r1 = a.ptr[b + 1];
-  r0 = r0 < 0 ? 0 : (r0 > a.R ? a.R : r0);
-  r1 = r1 < r0 ? r0 : (r1 > a.R ? a.R : r1);
-  if (!active && a.dist == nullptr && a.winner == nullptr) r1 = r0;
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-  for (int r = r0; r < r1; ++r) {                          // (r0, r1: the same in every thread of the workgroup)
-    const int at = a.atom[r], gp = a.group[r];
-    const bool mine = l < n && (at >= 0 ? l == at : (gp == DD_RESTRAINT_ANY || (a.decomp != nullptr && gp >= -1 && my_arm == gp)));
-    const float dx = x - a.point[3 * (long)r], dy = y - a.point[3 * (long)r + 1], dz = z - a.point[3 * (long)r + 2];
-    const float d = mine ? sqrtf(dx * dx + dy * dy + dz * dz) : INFINITY;
-    unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)l;   // d >= 0 (or +inf): bit order = float order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long k2 = (unsigned long long)__shfl_xor((long long)key, off);
-      key = k2 < key ? k2 : key;
-    }
-    if (blockDim.x > 64) {
-      if ((l & 63) == 0) wk[r & 1][l >> 6] = key;
-      __syncthreads();
-      const unsigned long long k0 = wk[r & 1][0], k1 = wk[r & 1][1];
-      key = k1 < k0 ? k1 : k0;
-    }
-    const float best = __uint_as_float((unsigned)(key >> 32));
-    const int win = best < INFINITY || best != best ? (int)(unsigned)(key & 0xffffffffull) : -1;
-    if (l == 0) {
-      if (a.dist) a.dist[r] = best;
-      if (a.winner) a.winner[r] = win;
-    }
-    if (active && l == win) {
-      float coef = 0.f;
-      if (a.min_d[r] - best >= 0.f) coef -= 1.f;
-      if (best - a.max_d[r] >= 0.f) coef += 1.f;
-      coef *= a.weight[r];
-      if (coef != 0.f && best > 0.f) {
-        const float inv = 1.0f / best;
-        gx = __fadd_rn(gx, __fmul_rn(__fmul_rn(coef, dx), inv));
-        gy = __fadd_rn(gy, __fmul_rn(__fmul_rn(coef, dy), inv));
-        gz = __fadd_rn(gz, __fmul_rn(__fmul_rn(coef, dz), inv));
-      }
-    }
-  }
-  if (l < NL) {
-    float* g = a.grad + ((long)b * NL + l) * 3;
-    if (a.accumulate) { g[0] += gx; g[1] += gy; g[2] += gz; }
-    else { g[0] = gx; g[1] = gy; g[2] = gz; }
-  }
-}
-int launch_drift_restraint(const RestraintArgs& a, hipStream_t st) {
-  if (a.B <= 0 || a.NL <= 0 || a.NL > DD_NL_MAX || a.R < 0) return DD_ERR_BAD_ARG;
-  hipLaunchKernelGGL(k_drift_restraint, dim3(a.B), dim3(a.NL > 64 ? 128 : 64), 0, st, a);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
-}
-
-// The general restraint kernel (include/decompdiff_hip.h, "the general form"): the launch shape, the reductions and, for a linear
-// untyped point restraint, the arithmetic of k_drift_restraint operation for operation; on top of it class masks over the CURRENT
-// atom classes, pair restraints between two ligand atoms, the harmonic hinge and one trajectory row per step.  The sample's
-// coordinates, class bits and arm ids are staged in LDS once (128 x 5 words); a pair restraint has lane i (a member of set 1) scan
-// the members j != i of set 2 in ascending order under strict <, then the workgroup reduces dist_bits << 32 | i << 8 | j, whose
-// minimum is the first nearest pair in (i, j) order.  Both winning lanes add the SAME rounded products into their own registers
-// (+ on i, - on j), restraints in ascending order: no atomics, the same bits on every run.  Memory-safe for any array contents:
-// ptr is clamped, an atom outside the sample matches no lane and no j, a class id outside [0, 32) has no bit.
+//
+// GENERAL (include/decompdiff_hip.h, "the general form"; the caller's struct carries a trailing array): on top of that class masks
+// over the CURRENT atom classes, pair restraints between two ligand atoms, the harmonic hinge and one trajectory row per step; a
+// linear untyped point restraint keeps the arithmetic above operation for operation.  The sample's coordinates, class bits and arm
+// ids are staged in LDS once (128 x 5 words); a pair restraint has lane i (a member of set 1) scan the members j != i of set 2 in
+// ascending order under strict <, then the workgroup reduces dist_bits << 32 | i << 8 | j, whose minimum is the first nearest pair
+// in (i, j) order.  Both winning lanes add the SAME rounded products into their own registers (+ on i, - on j).  Memory-safe for
+// any array contents: an atom outside the sample matches no j either, a class id outside [0, 32) has no bit.  The point
+// instantiation carries none of this: no staging, no class, pair, form or trajectory code.
 __device__ __forceinline__ bool restraint_member(int row, int n, int at, int gp, int arm, bool has_decomp, bool typed, unsigned cbit,
                                                  unsigned mask) {
   return row < n && (at >= 0 ? row == at : (gp == DD_RESTRAINT_ANY || (has_decomp && gp >= -1 && arm == gp))) &&
          (!typed || (cbit & mask) != 0u);
 }
-__global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint2(const Restraint2Args q) {
+template <bool GENERAL>
+__global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint(const RestraintArgs g) {
+  // One struct under two names: `g.` reads the general form's fields, `a.` the point form's.  Reading both through one name
+  // is the same program, but the compiler then orders the GENERAL instantiation's scalar code differently (8 instructions more).
+  const RestraintArgs& a = g;
   __shared__ unsigned long long wk[2][2];
-  __shared__ float sx[DD_NL_MAX], sy[DD_NL_MAX], sz[DD_NL_MAX];
+  __shared__ float sx[DD_NL_MAX], sy[DD_NL_MAX], sz[DD_NL_MAX];              // (these five: GENERAL only)
   __shared__ unsigned sbit[DD_NL_MAX];
   __shared__ int sarm[DD_NL_MAX];
-  const RestraintArgs& a = q.o;
   const int b = blockIdx.x, l = threadIdx.x, NL = a.NL;
   int n = a.nl_real ? a.nl_real[b] : NL;
   n = n < NL ? n : NL;
@@ -600,42 +410,53 @@ __global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint2(const Restraint2
     const float* p = a.pos + ((long)b * NL + l) * 3;
     x = p[0]; y = p[1]; z = p[2];
     if (a.decomp) my_arm = a.decomp[(long)b * NL + l];
-    if (q.lig_v) {
-      const int c = q.lig_v[(long)b * NL + l];
-      my_bit = c >= 0 && c < 32 ? 1u << c : 0u;
+    if constexpr (GENERAL) {
+      if (g.lig_v) {
+        const int c = g.lig_v[(long)b * NL + l];
+        my_bit = c >= 0 && c < 32 ? 1u << c : 0u;
+      }
     }
   }
-  sx[l] = x; sy[l] = y; sz[l] = z; sbit[l] = my_bit; sarm[l] = my_arm;       // (blockDim.x <= DD_NL_MAX)
-  __syncthreads();
+  if constexpr (GENERAL) {
+    sx[l] = x; sy[l] = y; sz[l] = z; sbit[l] = my_bit; sarm[l] = my_arm;     // (blockDim.x <= DD_NL_MAX)
+    __syncthreads();
+  }
   bool active = true;
   int trow = -1;
   if (a.step_counter != nullptr) {
     const RunState rs = load_run_state(a.step_counter, a.counter_bias);
     const int t = rs.t_start - rs.step;
     active = t >= a.t_min && t <= a.t_max;
-    if (rs.step >= 0 && rs.step < q.traj_positions) trow = rs.step;
+    if constexpr (GENERAL) {
+      if (rs.step >= 0 && rs.step < g.traj_positions) trow = rs.step;
+    }
   }
-  const bool traj = trow >= 0 && (q.dist_traj != nullptr || q.winner_traj != nullptr || q.winner2_traj != nullptr);
+  const bool traj = GENERAL ? trow >= 0 && (g.dist_traj != nullptr || g.winner_traj != nullptr || g.winner2_traj != nullptr) : false;
   int r0 = a.ptr[b], r1 = a.ptr[b + 1];
   r0 = r0 < 0 ? 0 : (r0 > a.R ? a.R : r0);
   r1 = r1 < r0 ? r0 : (r1 > a.R ? a.R : r1);
-  if (!active && !traj && a.dist == nullptr && a.winner == nullptr && q.winner2 == nullptr) r1 = r0;
+  if constexpr (GENERAL) {                                 // (inactive and nothing to report: no restraint is visited)
+    if (!active && !traj && a.dist == nullptr && a.winner == nullptr && g.winner2 == nullptr) r1 = r0;
+  } else {
+    if (!active && a.dist == nullptr && a.winner == nullptr) r1 = r0;
+  }
   const bool has_decomp = a.decomp != nullptr;
   float gx = 0.f, gy = 0.f, gz = 0.f;
   for (int r = r0; r < r1; ++r) {                          // (r0, r1: the same in every thread of the workgroup)
     const int at = a.atom[r], gp = a.group[r];
-    const bool mine = restraint_member(l, n, at, gp, my_arm, has_decomp, q.cls != nullptr, my_bit, q.cls ? q.cls[r] : 0u);
-    const bool is_pair = q.pair != nullptr && q.pair[r] != 0;
+    const bool mine = GENERAL ? restraint_member(l, n, at, gp, my_arm, has_decomp, g.cls != nullptr, my_bit, g.cls ? g.cls[r] : 0u)
+                              : l < n && (at >= 0 ? l == at : (gp == DD_RESTRAINT_ANY || (a.decomp != nullptr && gp >= -1 && my_arm == gp)));
+    const bool is_pair = GENERAL ? g.pair != nullptr && g.pair[r] != 0 : false;
     float dx, dy, dz, d = INFINITY;
     unsigned long long key;
     if (!is_pair) {
       dx = x - a.point[3 * (long)r]; dy = y - a.point[3 * (long)r + 1]; dz = z - a.point[3 * (long)r + 2];
       d = mine ? sqrtf(dx * dx + dy * dy + dz * dz) : INFINITY;
       key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)l;   // d >= 0 (or +inf): bit order = float order
-    } else {
-      const int at2 = q.atom2 ? q.atom2[r] : -1, gp2 = q.group2 ? q.group2[r] : DD_RESTRAINT_NONE;
-      const bool typed2 = q.cls2 != nullptr;
-      const unsigned m2 = typed2 ? q.cls2[r] : 0u;
+    } else if constexpr (GENERAL) {
+      const int at2 = g.atom2 ? g.atom2[r] : -1, gp2 = g.group2 ? g.group2[r] : DD_RESTRAINT_NONE;
+      const bool typed2 = g.cls2 != nullptr;
+      const unsigned m2 = typed2 ? g.cls2[r] : 0u;
       int j0 = 0, j1 = n, bj = 0;
       if (at2 >= 0) { j0 = at2 < n ? at2 : n; j1 = at2 < n ? at2 + 1 : n; }   // (an explicit second atom: one candidate)
       if (mine) {
@@ -667,30 +488,40 @@ __global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint2(const Restraint2
     if (l == 0) {
       if (a.dist) a.dist[r] = best;
       if (a.winner) a.winner[r] = win;
-      if (q.winner2) q.winner2[r] = win2;
-      if (traj) {
-        const long o = (long)trow * a.R + r;
-        if (q.dist_traj) q.dist_traj[o] = best;
-        if (q.winner_traj) q.winner_traj[o] = win;
-        if (q.winner2_traj) q.winner2_traj[o] = win2;
+      if constexpr (GENERAL) {
+        if (g.winner2) g.winner2[r] = win2;
+        if (traj) {
+          const long o = (long)trow * a.R + r;
+          if (g.dist_traj) g.dist_traj[o] = best;
+          if (g.winner_traj) g.winner_traj[o] = win;
+          if (g.winner2_traj) g.winner2_traj[o] = win2;
+        }
       }
     }
-    if (active && found && (l == win || l == win2)) {
-      const float w = a.weight[r];
+    if (active && (GENERAL ? found && (l == win || l == win2) : l == win)) {
       float coef = 0.f;
-      if (q.form != nullptr && q.form[r] != 0) {
-        const float lo = a.min_d[r] - best, hi = best - a.max_d[r];
-        if (lo > 0.f) coef -= 2.f * w * lo;
-        if (hi > 0.f) coef += 2.f * w * hi;
+      if constexpr (GENERAL) {
+        const float w = a.weight[r];
+        if (g.form != nullptr && g.form[r] != 0) {
+          const float lo = a.min_d[r] - best, hi = best - a.max_d[r];
+          if (lo > 0.f) coef -= 2.f * w * lo;
+          if (hi > 0.f) coef += 2.f * w * hi;
+        } else {
+          if (a.min_d[r] - best >= 0.f) coef -= 1.f;
+          if (best - a.max_d[r] >= 0.f) coef += 1.f;
+          coef *= w;
+        }
       } else {
         if (a.min_d[r] - best >= 0.f) coef -= 1.f;
         if (best - a.max_d[r] >= 0.f) coef += 1.f;
-        coef *= w;
+        coef *= a.weight[r];
       }
       if (coef != 0.f && best > 0.f) {
         const float inv = 1.0f / best;
-        if (is_pair) {                                       // (both ends form the same three products from LDS: exactly opposite)
-          dx = sx[win] - sx[win2]; dy = sy[win] - sy[win2]; dz = sz[win] - sz[win2];
+        if constexpr (GENERAL) {
+          if (is_pair) {                                     // (both ends form the same three products from LDS: exactly opposite)
+            dx = sx[win] - sx[win2]; dy = sy[win] - sy[win2]; dz = sz[win] - sz[win2];
+          }
         }
         const float tx = __fmul_rn(__fmul_rn(coef, dx), inv), ty = __fmul_rn(__fmul_rn(coef, dy), inv), tz = __fmul_rn(__fmul_rn(coef, dz), inv);
         if (l == win) { gx = __fadd_rn(gx, tx); gy = __fadd_rn(gy, ty); gz = __fadd_rn(gz, tz); }
@@ -704,9 +535,11 @@ __global__ __launch_bounds__(DD_NL_MAX) void k_drift_restraint2(const Restraint2
     else { g[0] = gx; g[1] = gy; g[2] = gz; }
   }
 }
-int launch_drift_restraint2(const Restraint2Args& a, hipStream_t st) {
-  if (a.o.B <= 0 || a.o.NL <= 0 || a.o.NL > DD_NL_MAX || a.o.R < 0) return DD_ERR_BAD_ARG;
-  hipLaunchKernelGGL(k_drift_restraint2, dim3(a.o.B), dim3(a.o.NL > 64 ? 128 : 64), 0, st, a);
+int launch_drift_restraint(const RestraintArgs& a, hipStream_t st) {
+  if (a.B <= 0 || a.NL <= 0 || a.NL > DD_NL_MAX || a.R < 0) return DD_ERR_BAD_ARG;
+  const dim3 grid(a.B), block(a.NL > 64 ? 128 : 64);
+  if (a.general) hipLaunchKernelGGL(k_drift_restraint<true>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(k_drift_restraint<false>, grid, block, 0, st, a);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
@@ -716,18 +549,25 @@ int launch_drift_restraint2(const Restraint2Args& a, hipStream_t st) {
 // launch (block ranges); the step counter is advanced by a 1-thread launch behind it (a last-block ticket was
 // tried: ~1800 atomics on one address serialise to 45 us).  A row is one wave: the
 // second head Linear uses the whole wave, the per-class posterior / Gumbel arithmetic runs one class per lane with
-// the cross-class sums taken in class order through v_readlane (bit-identical to the serial k_step_rows).
-template <int NC, bool FIXED>
+// the cross-class sums taken in class order through v_readlane (the sums of a serial loop over the classes, bit for bit).
+// LOGITS_IN (dd_reverse_step): the host supplies the head outputs in a.logits_in; hid / W2 / b2 are not read.
+template <int NC, bool FIXED, bool LOGITS_IN = false>
 __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, const int lane, const RunState rs) {
   const int step = rs.step, t = rs.t_start - step;
-  float2 hv = *reinterpret_cast<const float2*>(a.hid + row * 128 + 2 * lane);
-  hv.x = (hv.x > 20.f ? hv.x : log1pf(expf(hv.x))) - 0.6931471805599453f;
-  hv.y = (hv.y > 20.f ? hv.y : log1pf(expf(hv.y))) - 0.6931471805599453f;
   float logit[NC];
+  if constexpr (LOGITS_IN) {
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const float2 w = *reinterpret_cast<const float2*>(a.W2 + c * 128 + 2 * lane);
-    logit[c] = wave_sum(fmaf(hv.y, w.y, hv.x * w.x)) + a.b2[c];
+    for (int c = 0; c < NC; ++c) logit[c] = a.logits_in[row * NC + c];
+  } else {
+    // ShiftedSoftplus (common.py:66-72): softplus(x) - log 2, torch threshold 20
+    float2 hv = *reinterpret_cast<const float2*>(a.hid + row * 128 + 2 * lane);
+    hv.x = (hv.x > 20.f ? hv.x : log1pf(expf(hv.x))) - 0.6931471805599453f;
+    hv.y = (hv.y > 20.f ? hv.y : log1pf(expf(hv.y))) - 0.6931471805599453f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const float2 w = *reinterpret_cast<const float2*>(a.W2 + c * 128 + 2 * lane);
+      logit[c] = wave_sum(fmaf(hv.y, w.y, hv.x * w.x)) + a.b2[c];
+    }
   }
   const int c = lane < NC ? lane : NC - 1;               // lanes >= NC shadow the last class (results unused)
   float mine = logit[0], mx = logit[0];
@@ -737,7 +577,9 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
   float se = 0.f;
 #pragma unroll
   for (int k = 0; k < NC; ++k) se += lane_bcast(e, k);
-  const float lsum = logf(se);                            // (log_softmax as (x - max) - log(sum): see k_step_rows)
+  // (x - max) - log(sum), as torch's log_softmax: x - (max + log(sum)) rounds the sum at the size of the logits, which costs the
+  //  leading class half an ulp of max (1.2e-4 at logits of a few thousand) and carries into the posterior
+  const float lsum = logf(se);
   const int tm1 = t - 1 < 0 ? 0 : t - 1;
   const float la_t = a.tab[t], l1ma_t = a.tab[a.T + t];
   const float lca = a.tab[2 * a.T + tm1], l1mca = a.tab[3 * a.T + tm1];
@@ -766,7 +608,7 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
     u = philox_uniform<NC>(na.key, na.row, tw, a.stream_id, c);
   }
   const float lp = un - ulse;
-  float sc = -logf(-logf(u + 1e-30f) + 1e-30f) + lp;            // Gumbel-argmax (transitions.py:78-84)
+  float sc = gumbel_of(u) + lp;                                  // Gumbel-argmax (transitions.py:78-84)
   int v0 = -1;                                                   // FIXED, held row (wave-uniform): its known class
   if constexpr (FIXED) {
     if (row_held(a, row)) {
@@ -775,7 +617,7 @@ __device__ __forceinline__ void step_row(const StepRowsArgs& a, const long row, 
       if (a.fx_mode == DD_FIXED_REPLACE && t > 0) sc = gumbel_of(u) + fixed_q0(c == v0, lca, l1mca, log_prior);
     }
   }
-  int best = 0;
+  int best = 0;                                                  // (class_argmax, written out: the call schedules k_step_all anew)
   float bestv = -INFINITY;
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
@@ -854,20 +696,48 @@ __global__ __launch_bounds__(256) void k_step_all(const StepRowsArgs rb, const S
   }
 }
 
+// The same two as launches of their own: dd_reverse_step, whose logits come from the host (unfixed chains only), and the
+// measurement build's unfused step.
+template <int NC, bool FIXED>
+__global__ __launch_bounds__(256) void k_step_rows(const StepRowsArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.rows) return;
+  const RunState rs = load_run_state(a.step_counter, a.counter_bias);
+  if constexpr (!FIXED) {
+    if (a.logits_in != nullptr) { step_row<NC, false, true>(a, row, lane, rs); return; }
+  }
+  step_row<NC, FIXED>(a, row, lane, rs);
+}
+template <bool FIXED>
+__global__ void k_step_pos(const StepPosArgs a) {
+  step_pos_elem<FIXED>(a, blockIdx.x * blockDim.x + threadIdx.x, load_run_state(a.step_counter, a.counter_bias));
+}
+
+// The instantiation for a runtime class count and for fixed atoms (instantiations of their own: the others carry none of it).
+// Atom classes: 8 (ligand_atom_mode 'basic'), 13 ('add_aromatic'), 23 ('full') -- utils/transforms.py:15-64,138-151.
+// launch(nc, fixed) takes both as compile-time constants and returns a status.
+template <int NC, class F>
+static int with_fixed(const bool fixed, F&& launch) {
+  return fixed ? launch(std::integral_constant<int, NC>(), std::true_type()) : launch(std::integral_constant<int, NC>(), std::false_type());
+}
+template <class F>
+static int for_atom_classes(const int nc, const bool fixed, F&& launch) {
+  if (nc == 8) return with_fixed<8>(fixed, launch);
+  if (nc == 13) return with_fixed<13>(fixed, launch);
+  if (nc == 23) return with_fixed<23>(fixed, launch);
+  return DD_ERR_UNSUPPORTED_SHAPE;
+}
+
 int launch_step_all(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, hipStream_t st) {
-  if (rb.NC != DD_NUM_B || (rv.NC != 8 && rv.NC != 13 && rv.NC != 23)) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (rb.NC != DD_NUM_B) return DD_ERR_UNSUPPORTED_SHAPE;
   const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
   const dim3 grid(nb_b + nb_v + nb_p);
-  // atom classes: 8 (ligand_atom_mode 'basic'), 13 ('add_aromatic'), 23 ('full') -- utils/transforms.py:15-64,138-151
-  if (p.fx_mask != nullptr) {                              // fixed atoms: instantiations of their own, the others are untouched
-    if (rv.NC == 8) hipLaunchKernelGGL((k_step_all<8, true>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-    else if (rv.NC == 13) hipLaunchKernelGGL((k_step_all<13, true>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-    else hipLaunchKernelGGL((k_step_all<23, true>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-  } else if (rv.NC == 8) hipLaunchKernelGGL((k_step_all<8, false>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-  else if (rv.NC == 13) hipLaunchKernelGGL((k_step_all<13, false>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-  else hipLaunchKernelGGL((k_step_all<23, false>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  return for_atom_classes(rv.NC, p.fx_mask != nullptr, [&](auto nv, auto fixed) -> int {
+    hipLaunchKernelGGL((k_step_all<nv(), fixed()>), grid, dim3(256), 0, st, rb, rv, p, nb_b, nb_v);
+    DD_CHECK_LAUNCH();
+    return DD_OK;
+  });
 }
 
 // Fixed atoms, in front of the first step (dd_fixed_init): one thread per bond row, atom row and coordinate.  Hold: the known
@@ -914,14 +784,14 @@ __global__ __launch_bounds__(256) void k_fixed_init(const StepRowsArgs rb, const
   }
 }
 int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, hipStream_t st) {
-  if (rb.NC != DD_NUM_B || (rv.NC != 8 && rv.NC != 13 && rv.NC != 23) || p.fx_mask == nullptr) return DD_ERR_UNSUPPORTED_SHAPE;
+  if (rb.NC != DD_NUM_B || p.fx_mask == nullptr) return DD_ERR_UNSUPPORTED_SHAPE;
   const long total = (long)rb.rows + rv.rows + (long)p.B * p.NL * 3;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (rv.NC == 8) hipLaunchKernelGGL(k_fixed_init<8>, grid, dim3(256), 0, st, rb, rv, p);
-  else if (rv.NC == 13) hipLaunchKernelGGL(k_fixed_init<13>, grid, dim3(256), 0, st, rb, rv, p);
-  else hipLaunchKernelGGL(k_fixed_init<23>, grid, dim3(256), 0, st, rb, rv, p);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  return for_atom_classes(rv.NC, false, [&](auto nv, auto) -> int {
+    hipLaunchKernelGGL(k_fixed_init<nv()>, grid, dim3(256), 0, st, rb, rv, p);
+    DD_CHECK_LAUNCH();
+    return DD_OK;
+  });
 }
 
 // Resampling (include/decompdiff_hip.h, dd_resample): the forward jump q(x_m | x_l) from the chain's current level
@@ -931,27 +801,18 @@ int launch_fixed_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const Step
 // in class order through v_readlane with the strict > of the serial loops.  Hold mode leaves the held rows alone; replace mode
 // moves every row (a held row at level m is then a valid forward sample of its clean value).  Draws: time word m + 65536 * e with
 // e = the epoch AFTER this jump, streams 3 / 4 / 8, rows and keys addressed as the step addresses them.
-// the first class with the largest score of a row that holds one class per lane: class order, strict > (the serial loops' winner)
+// One class row drawn from the forward process (a jump, the chain init), one class per lane: the draw of (key, row, word, sid),
+// gumbel(u) + log q(v | v0 = from) with lca / l1mca of the level (fixed_q0), or -- from_v0 false -- + the bare log prior; then the
+// first argmax in class order, as the step's.
 template <int NC>
-__device__ __forceinline__ int class_argmax(const float sc) {
-  int best = 0;
-  float bestv = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    const float sk = lane_bcast(sc, k);
-    if (sk > bestv) { bestv = sk; best = k; }
-  }
-  return best;
-}
-template <int NC>
-__device__ __forceinline__ void jump_row(const StepRowsArgs& a, const long row, const int lane, const uint64_t seed, const int word,
-                                         const uint32_t sid, const float lr, const float l1mr) {
-  if (a.fx_mode == DD_FIXED_HOLD && row_held(a, row)) return;      // (wave-uniform)
+__device__ __forceinline__ void forward_row(const StepRowsArgs& a, const long row, const int lane, const uint64_t seed, const int word,
+                                            const uint32_t sid, const float* __restrict__ log_prior, const bool from_v0, const int from,
+                                            const float lca, const float l1mca) {
   const int c = lane < NC ? lane : NC - 1;                         // lanes >= NC shadow the last class (results unused)
-  const int cur = a.state[row];
   const NoiseAddr na = noise_addr(a, row, seed);
   const float u = philox_uniform<NC>(na.key, na.row, word, sid, c);
-  const float sc = gumbel_of(u) + log_add_exp((c == cur ? 0.f : -69.07755278982137f) + lr, l1mr + a.tab[4 * a.T + c]);
+  const float lp = log_prior[c];
+  const float sc = gumbel_of(u) + (from_v0 ? fixed_q0(c == from, lca, l1mca, lp) : lp);
   const int best = class_argmax<NC>(sc);
   if (lane == 0) a.state[row] = best;
 }
@@ -966,10 +827,12 @@ __global__ __launch_bounds__(256) void k_jump(const StepRowsArgs rb, const StepR
   const int word = (int)((uint32_t)m + ((uint32_t)(*rb.epoch + 1) << 16));
   if (blk < nb_b) {
     const long row = (long)blk * 4 + wave;
-    if (row < rb.rows) jump_row<DD_NUM_B>(rb, row, lane, rs.seed, word, 4u, jtab[4 * T + m], jtab[5 * T + m]);
+    if (row >= rb.rows || (rb.fx_mode == DD_FIXED_HOLD && row_held(rb, row))) return;      // (wave-uniform)
+    forward_row<DD_NUM_B>(rb, row, lane, rs.seed, word, 4u, rb.tab + 4 * T, true, rb.state[row], jtab[4 * T + m], jtab[5 * T + m]);
   } else if (blk < nb_b + nb_v) {
     const long row = (long)(blk - nb_b) * 4 + wave;
-    if (row < rv.rows) jump_row<NV>(rv, row, lane, rs.seed, word, 3u, jtab[2 * T + m], jtab[3 * T + m]);
+    if (row >= rv.rows || (rv.fx_mode == DD_FIXED_HOLD && row_held(rv, row))) return;
+    forward_row<NV>(rv, row, lane, rs.seed, word, 3u, rv.tab + 4 * T, true, rv.state[row], jtab[2 * T + m], jtab[3 * T + m]);
   } else {
     const int idx = (blk - nb_b - nb_v) * 256 + threadIdx.x;
     if (idx >= p.B * p.NL * 3) return;
@@ -984,17 +847,16 @@ __global__ void k_reset_epoch(int32_t* epoch) { *epoch = 0; }
 
 int launch_jump(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, const float* jtab, int j, int32_t* epoch,
                 hipStream_t st) {
-  if (rb.NC != DD_NUM_B || (rv.NC != 8 && rv.NC != 13 && rv.NC != 23)) return DD_ERR_UNSUPPORTED_SHAPE;
-  if (p.fx_mask == nullptr || p.fx_cc == nullptr || jtab == nullptr || epoch == nullptr || rb.epoch != epoch || j < 1) return DD_ERR_BAD_ARG;
-  const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
-  const dim3 grid(nb_b + nb_v + nb_p);
-  if (rv.NC == 8) hipLaunchKernelGGL(k_jump<8>, grid, dim3(256), 0, st, rb, rv, p, jtab, j, nb_b, nb_v);
-  else if (rv.NC == 13) hipLaunchKernelGGL(k_jump<13>, grid, dim3(256), 0, st, rb, rv, p, jtab, j, nb_b, nb_v);
-  else hipLaunchKernelGGL(k_jump<23>, grid, dim3(256), 0, st, rb, rv, p, jtab, j, nb_b, nb_v);
-  DD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_jump_tail, dim3(1), dim3(1), 0, st, const_cast<int32_t*>(rb.step_counter), epoch, j);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  if (rb.NC != DD_NUM_B) return DD_ERR_UNSUPPORTED_SHAPE;
+  return for_atom_classes(rv.NC, false, [&](auto nv, auto) -> int {
+    if (p.fx_mask == nullptr || p.fx_cc == nullptr || jtab == nullptr || epoch == nullptr || rb.epoch != epoch || j < 1) return DD_ERR_BAD_ARG;
+    const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
+    hipLaunchKernelGGL(k_jump<nv()>, dim3(nb_b + nb_v + nb_p), dim3(256), 0, st, rb, rv, p, jtab, j, nb_b, nb_v);
+    DD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_jump_tail, dim3(1), dim3(1), 0, st, const_cast<int32_t*>(rb.step_counter), epoch, j);
+    DD_CHECK_LAUNCH();
+    return DD_OK;
+  });
 }
 int launch_reset_epoch(int32_t* epoch, hipStream_t st) {
   hipLaunchKernelGGL(k_reset_epoch, dim3(1), dim3(1), 0, st, epoch);
@@ -1017,18 +879,6 @@ __device__ __forceinline__ bool bond_row_real(const StepRowsArgs& a, const long 
   const int n = a.nl_real[b], dst = r / (a.NL - 1), sp = r - dst * (a.NL - 1);
   return dst < n && sp < n - 1;
 }
-template <int NC>
-__device__ __forceinline__ void chain_init_row(const StepRowsArgs& a, const long row, const int lane, const uint64_t seed, const int word,
-                                               const uint32_t sid, const float* __restrict__ lp, const int32_t* __restrict__ v0,
-                                               const float lca, const float l1mca) {
-  const int c = lane < NC ? lane : NC - 1;                         // lanes >= NC shadow the last class (results unused)
-  const NoiseAddr na = noise_addr(a, row, seed);
-  const float u = philox_uniform<NC>(na.key, na.row, word, sid, c);
-  const float log_prior = lp != nullptr ? lp[c] : a.tab[4 * a.T + c];
-  const float sc = gumbel_of(u) + (v0 != nullptr ? fixed_q0(c == v0[row], lca, l1mca, log_prior) : log_prior);
-  const int best = class_argmax<NC>(sc);
-  if (lane == 0) a.state[row] = best;
-}
 template <int NV>
 __global__ __launch_bounds__(256) void k_chain_init(const StepRowsArgs rb, const StepRowsArgs rv, const StepPosArgs p, const ChainInitArgs ci,
                                                     int nb_b, int nb_v) {
@@ -1041,14 +891,14 @@ __global__ __launch_bounds__(256) void k_chain_init(const StepRowsArgs rb, const
   if (blk < nb_b) {
     const long row = (long)blk * 4 + wave;
     if (row >= rb.rows || !bond_row_real(rb, row)) return;         // (wave-uniform)
-    chain_init_row<DD_NUM_B>(rb, row, lane, rs.seed, l, 6u, ci.lp_b, noised ? ci.b0 : nullptr, noised ? rb.tab[2 * T + l] : 0.f,
-                             noised ? rb.tab[3 * T + l] : 0.f);
+    forward_row<DD_NUM_B>(rb, row, lane, rs.seed, l, 6u, ci.lp_b != nullptr ? ci.lp_b : rb.tab + 4 * T, noised, noised ? ci.b0[row] : 0,
+                          noised ? rb.tab[2 * T + l] : 0.f, noised ? rb.tab[3 * T + l] : 0.f);
   } else if (blk < nb_b + nb_v) {
     const long row = (long)(blk - nb_b) * 4 + wave;
     if (row >= rv.rows) return;
     if (ci.nl_real != nullptr && (int)(row % p.NL) >= ci.nl_real[row / p.NL]) return;
-    chain_init_row<NV>(rv, row, lane, rs.seed, l, 5u, ci.lp_v, noised ? ci.v0 : nullptr, noised ? rv.tab[2 * T + l] : 0.f,
-                       noised ? rv.tab[3 * T + l] : 0.f);
+    forward_row<NV>(rv, row, lane, rs.seed, l, 5u, ci.lp_v != nullptr ? ci.lp_v : rv.tab + 4 * T, noised, noised ? ci.v0[row] : 0,
+                    noised ? rv.tab[2 * T + l] : 0.f, noised ? rv.tab[3 * T + l] : 0.f);
   } else {
     const int idx = (blk - nb_b - nb_v) * 256 + threadIdx.x;
     if (idx >= p.B * p.NL * 3) return;
@@ -1060,39 +910,31 @@ __global__ __launch_bounds__(256) void k_chain_init(const StepRowsArgs rb, const
   }
 }
 int launch_chain_init(const StepRowsArgs& rb, const StepRowsArgs& rv, const StepPosArgs& p, const ChainInitArgs& ci, hipStream_t st) {
-  if (rb.NC != DD_NUM_B || (rv.NC != 8 && rv.NC != 13 && rv.NC != 23)) return DD_ERR_UNSUPPORTED_SHAPE;
-  if ((ci.mode != DD_INIT_PRIOR && ci.mode != DD_INIT_NOISED) || ci.cc == nullptr || ci.std == nullptr) return DD_ERR_BAD_ARG;
-  if (ci.mode == DD_INIT_NOISED && (!ci.x0c || !ci.v0 || !ci.b0 || !ci.tab)) return DD_ERR_BAD_ARG;
-  const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
-  const dim3 grid(nb_b + nb_v + nb_p);
-  if (rv.NC == 8) hipLaunchKernelGGL(k_chain_init<8>, grid, dim3(256), 0, st, rb, rv, p, ci, nb_b, nb_v);
-  else if (rv.NC == 13) hipLaunchKernelGGL(k_chain_init<13>, grid, dim3(256), 0, st, rb, rv, p, ci, nb_b, nb_v);
-  else hipLaunchKernelGGL(k_chain_init<23>, grid, dim3(256), 0, st, rb, rv, p, ci, nb_b, nb_v);
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  if (rb.NC != DD_NUM_B) return DD_ERR_UNSUPPORTED_SHAPE;
+  return for_atom_classes(rv.NC, false, [&](auto nv, auto) -> int {
+    if ((ci.mode != DD_INIT_PRIOR && ci.mode != DD_INIT_NOISED) || ci.cc == nullptr || ci.std == nullptr) return DD_ERR_BAD_ARG;
+    if (ci.mode == DD_INIT_NOISED && (!ci.x0c || !ci.v0 || !ci.b0 || !ci.tab)) return DD_ERR_BAD_ARG;
+    const int nb_b = (rb.rows + 3) / 4, nb_v = (rv.rows + 3) / 4, nb_p = (p.B * p.NL * 3 + 255) / 256;
+    hipLaunchKernelGGL(k_chain_init<nv()>, dim3(nb_b + nb_v + nb_p), dim3(256), 0, st, rb, rv, p, ci, nb_b, nb_v);
+    DD_CHECK_LAUNCH();
+    return DD_OK;
+  });
 }
 
 int launch_step_rows(const StepRowsArgs& a, hipStream_t st) {
   if (a.rows <= 0) return DD_OK;
-  dim3 grid((a.rows + 3) / 4);
-  if (a.fx_mask != nullptr) {                              // fixed atoms
-    if (a.NC == 8) hipLaunchKernelGGL((k_step_rows<8, true>), grid, dim3(256), 0, st, a);
-    else if (a.NC == 13) hipLaunchKernelGGL((k_step_rows<13, true>), grid, dim3(256), 0, st, a);
-    else if (a.NC == 23) hipLaunchKernelGGL((k_step_rows<23, true>), grid, dim3(256), 0, st, a);
-    else if (a.NC == DD_NUM_B) hipLaunchKernelGGL((k_step_rows<DD_NUM_B, true>), grid, dim3(256), 0, st, a);
-    else return DD_ERR_UNSUPPORTED_SHAPE;
-  } else if (a.NC == 8) hipLaunchKernelGGL((k_step_rows<8, false>), grid, dim3(256), 0, st, a);
-  else if (a.NC == 13) hipLaunchKernelGGL((k_step_rows<13, false>), grid, dim3(256), 0, st, a);
-  else if (a.NC == 23) hipLaunchKernelGGL((k_step_rows<23, false>), grid, dim3(256), 0, st, a);
-  else if (a.NC == DD_NUM_B) hipLaunchKernelGGL((k_step_rows<DD_NUM_B, false>), grid, dim3(256), 0, st, a);
-  else return DD_ERR_UNSUPPORTED_SHAPE;
-  DD_CHECK_LAUNCH();
-  return DD_OK;
+  auto launch = [&](auto nc, auto fixed) -> int {
+    hipLaunchKernelGGL((k_step_rows<nc(), fixed()>), dim3((a.rows + 3) / 4), dim3(256), 0, st, a);
+    DD_CHECK_LAUNCH();
+    return DD_OK;
+  };
+  const bool fixed = a.fx_mask != nullptr;
+  return a.NC == DD_NUM_B ? with_fixed<DD_NUM_B>(fixed, launch) : for_atom_classes(a.NC, fixed, launch);
 }
 int launch_step_pos(const StepPosArgs& a, hipStream_t st) {
-  int n = a.B * a.NL * 3;
-  if (a.fx_mask != nullptr) hipLaunchKernelGGL(k_step_pos_fixed, dim3((n + 255) / 256), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_step_pos, dim3((n + 255) / 256), dim3(256), 0, st, a);
+  const dim3 grid((a.B * a.NL * 3 + 255) / 256);
+  if (a.fx_mask != nullptr) hipLaunchKernelGGL(k_step_pos<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_step_pos<false>, grid, dim3(256), 0, st, a);
   DD_CHECK_LAUNCH();
   return DD_OK;
 }
@@ -1176,62 +1018,43 @@ extern "C" int dd_drift_clash(const float* lig_pos, const float* offset, const f
                                 (hipStream_t)stream);
 }
 
-// The caller's dd_restraints as a checked copy (fields beyond its `size` are NULL / 0) laid into the kernel's arguments.  What the
-// host can see is checked here; check_contents adds what only the device arrays say (a synchronous copy of ptr / atom / group on
-// `st`, for the entry points that are called outside a capture).
+// The caller's dd_restraints as a checked copy (fields beyond its `size` are NULL / 0) laid into the kernel's arguments: the point
+// form first, then the trailing fields of the general form; `general` says whether any trailing array or trajectory pointer is set
+// (none: everything behind it stays NULL / 0).  What the host can see is checked here; check_contents adds what only the device
+// arrays say (synchronous copies on `st`, for the entry points that are called outside a capture).
 namespace dd {
-int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, bool check_contents, hipStream_t st, RestraintArgs* out) {
+int read_restraints(const dd_restraints* rs, int B, int NL, bool has_decomp, bool has_v, bool check_contents, hipStream_t st,
+                    RestraintArgs* out) {
   memset(out, 0, sizeof(*out));
-  if (rs == nullptr || rs->size < (int32_t)sizeof(int32_t) || rs->size > 4096) return DD_ERR_BAD_ARG;
   dd_restraints r;
-  memset(&r, 0, sizeof(r));
-  memcpy(&r, rs, (size_t)rs->size < sizeof(r) ? (size_t)rs->size : sizeof(r));
+  if (!read_sized(rs, &r)) return DD_ERR_BAD_ARG;
   if (B <= 0 || NL <= 0 || NL > DD_NL_MAX || r.R < 0 || !r.ptr || r.t_min > r.t_max) return DD_ERR_BAD_ARG;
   if (r.R > 0 && (!r.point || !r.min_d || !r.max_d || !r.weight || !r.atom || !r.group)) return DD_ERR_BAD_ARG;
   out->B = B; out->NL = NL; out->R = r.R; out->ptr = r.ptr; out->point = r.point; out->min_d = r.min_d; out->max_d = r.max_d;
   out->weight = r.weight; out->atom = r.atom; out->group = r.group; out->t_min = r.t_min; out->t_max = r.t_max; out->scale = r.scale != 0;
-  if (!check_contents) return DD_OK;
-  std::vector<int32_t> h((size_t)B + 1 + 2 * (size_t)r.R);
-  auto fetch = [&](int32_t* dst, const int32_t* src, size_t n) {         // (n ints to the host, waited for)
-    return n == 0 || (hipMemcpyAsync(dst, src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                      hipStreamSynchronize(st) == hipSuccess);
-  };
-  if (!fetch(h.data(), r.ptr, (size_t)B + 1)) { (void)hipGetLastError(); return DD_ERR_HIP; }
-  if (h[0] != 0 || h[B] != r.R) return DD_ERR_BAD_ARG;                   // (before anything of length R is read)
-  for (int b = 0; b < B; ++b)
-    if (h[b + 1] < h[b]) return DD_ERR_BAD_ARG;
-  if (!fetch(h.data() + B + 1, r.atom, (size_t)r.R) || !fetch(h.data() + B + 1 + r.R, r.group, (size_t)r.R)) {
-    (void)hipGetLastError();
-    return DD_ERR_HIP;
+  const size_t R = (size_t)r.R;
+  if (check_contents) {
+    std::vector<int32_t> h((size_t)B + 1 + 2 * R);
+    auto fetch = [&](int32_t* dst, const int32_t* src, size_t n) {       // (n ints to the host, waited for)
+      return n == 0 || (hipMemcpyAsync(dst, src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                        hipStreamSynchronize(st) == hipSuccess);
+    };
+    if (!fetch(h.data(), r.ptr, (size_t)B + 1)) { (void)hipGetLastError(); return DD_ERR_HIP; }
+    if (h[0] != 0 || h[B] != r.R) return DD_ERR_BAD_ARG;                 // (before anything of length R is read)
+    for (int b = 0; b < B; ++b)
+      if (h[b + 1] < h[b]) return DD_ERR_BAD_ARG;
+    if (!fetch(h.data() + B + 1, r.atom, R) || !fetch(h.data() + B + 1 + R, r.group, R)) {
+      (void)hipGetLastError();
+      return DD_ERR_HIP;
+    }
+    for (size_t i = 0; i < R; ++i) {
+      const int at = h[B + 1 + i], gp = h[B + 1 + R + i];
+      if (at < -1 || at >= NL) return DD_ERR_BAD_ARG;
+      if (at == -1 && gp != DD_RESTRAINT_ANY && (gp < -1 || !has_decomp)) return DD_ERR_BAD_ARG;
+    }
   }
-  for (int i = 0; i < r.R; ++i) {
-    const int at = h[B + 1 + i], gp = h[B + 1 + r.R + i];
-    if (at < -1 || at >= NL) return DD_ERR_BAD_ARG;
-    if (at == -1 && gp != DD_RESTRAINT_ANY && (gp < -1 || !has_decomp)) return DD_ERR_BAD_ARG;
-  }
-  return DD_OK;
-}
-}  // namespace dd
-
-// The trailing fields of the caller's dd_restraints (NULL / 0 where its `size` ends before them) behind read_restraints' checks.
-namespace dd {
-// does the caller's struct (checked by read_restraints: size >= 4) carry a non-NULL trailing array or trajectory pointer?
-static bool carries_general(const dd_restraints* rs) {
-  dd_restraints r;
-  memset(&r, 0, sizeof(r));
-  memcpy(&r, rs, (size_t)rs->size < sizeof(r) ? (size_t)rs->size : sizeof(r));
-  return r.cls || r.cls2 || r.pair || r.atom2 || r.group2 || r.form || r.dist_traj || r.winner_traj || r.winner2_traj;
-}
-int read_restraints2(const dd_restraints* rs, int B, int NL, bool has_decomp, bool has_v, bool check_contents, hipStream_t st,
-                     Restraint2Args* out) {
-  memset(out, 0, sizeof(*out));
-  const int rc = read_restraints(rs, B, NL, has_decomp, check_contents, st, &out->o);
-  if (rc != DD_OK) return rc;
-  dd_restraints r;
-  memset(&r, 0, sizeof(r));
-  memcpy(&r, rs, (size_t)rs->size < sizeof(r) ? (size_t)rs->size : sizeof(r));
   const bool traj = r.dist_traj || r.winner_traj || r.winner2_traj;
-  out->general = carries_general(rs);
+  out->general = r.cls || r.cls2 || r.pair || r.atom2 || r.group2 || r.form || traj;
   if (!out->general) return DD_OK;
   if ((r.cls || r.cls2) && !has_v) return DD_ERR_BAD_ARG;
   if (r.pair && !r.atom2 && !r.group2) return DD_ERR_BAD_ARG;
@@ -1239,8 +1062,7 @@ int read_restraints2(const dd_restraints* rs, int B, int NL, bool has_decomp, bo
   out->cls = r.cls; out->cls2 = r.cls2; out->pair = r.pair; out->atom2 = r.atom2; out->group2 = r.group2; out->form = r.form;
   out->dist_traj = r.dist_traj; out->winner_traj = r.winner_traj; out->winner2_traj = r.winner2_traj;
   out->traj_positions = traj ? r.traj_positions : 0;
-  if (!check_contents || r.R == 0) return DD_OK;
-  const size_t R = (size_t)r.R;
+  if (!check_contents || R == 0) return DD_OK;
   std::vector<int32_t> h(4 * R, 0);
   int32_t *pr = h.data(), *a2 = pr + R, *g2 = a2 + R, *fm = g2 + R;
   for (size_t i = 0; i < R; ++i) { a2[i] = -1; g2[i] = DD_RESTRAINT_NONE; }
@@ -1265,19 +1087,18 @@ extern "C" int dd_drift_restraint2(const float* lig_pos, const int32_t* lig_v, c
                                    int NL, const dd_restraints* restraints, const int32_t* step_counter, float* grad, int accumulate,
                                    float* dist, int32_t* winner, int32_t* winner2, void* stream) {
   if (!lig_pos || !grad || !restraints) return DD_ERR_BAD_ARG;
-  dd::Restraint2Args a;
-  const int rc = dd::read_restraints2(restraints, B, NL, decomp_index != nullptr, lig_v != nullptr, true, (hipStream_t)stream, &a);
+  dd::RestraintArgs a;
+  const int rc = dd::read_restraints(restraints, B, NL, decomp_index != nullptr, lig_v != nullptr, true, (hipStream_t)stream, &a);
   if (rc != DD_OK) return rc;
-  a.o.pos = lig_pos; a.o.decomp = decomp_index; a.o.nl_real = nl_real; a.o.step_counter = step_counter; a.o.grad = grad;
-  a.o.accumulate = accumulate; a.o.dist = dist; a.o.winner = winner;
+  a.pos = lig_pos; a.decomp = decomp_index; a.nl_real = nl_real; a.step_counter = step_counter; a.grad = grad;
+  a.accumulate = accumulate; a.dist = dist; a.winner = winner;
   a.lig_v = lig_v; a.winner2 = winner2;
-  if (a.general) return dd::launch_drift_restraint2(a, (hipStream_t)stream);
-  if (winner2 != nullptr && a.o.R > 0 &&                                 // (the point kernel knows no second winner: all -1)
-      hipMemsetAsync(winner2, 0xff, sizeof(int32_t) * (size_t)a.o.R, (hipStream_t)stream) != hipSuccess) {
+  if (!a.general && winner2 != nullptr && a.R > 0 &&                    // (the point kernel knows no second winner: all -1)
+      hipMemsetAsync(winner2, 0xff, sizeof(int32_t) * (size_t)a.R, (hipStream_t)stream) != hipSuccess) {
     (void)hipGetLastError();
     return DD_ERR_HIP;
   }
-  return dd::launch_drift_restraint(a.o, (hipStream_t)stream);
+  return dd::launch_drift_restraint(a, (hipStream_t)stream);
 }
 
 extern "C" int dd_drift_restraint(const float* lig_pos, const int32_t* decomp_index, const int32_t* nl_real, int B, int NL,
@@ -1285,9 +1106,9 @@ extern "C" int dd_drift_restraint(const float* lig_pos, const int32_t* decomp_in
                                   int32_t* winner, void* stream) {
   if (!lig_pos || !grad || !restraints) return DD_ERR_BAD_ARG;
   dd::RestraintArgs a;
-  const int rc = dd::read_restraints(restraints, B, NL, decomp_index != nullptr, true, (hipStream_t)stream, &a);
+  const int rc = dd::read_restraints(restraints, B, NL, decomp_index != nullptr, false, true, (hipStream_t)stream, &a);
   if (rc != DD_OK) return rc;
-  if (dd::carries_general(restraints)) return DD_ERR_BAD_ARG;            // (the general form has its own entry point)
+  if (a.general) return DD_ERR_BAD_ARG;                                  // (the general form has its own entry point)
   a.pos = lig_pos; a.decomp = decomp_index; a.nl_real = nl_real; a.step_counter = step_counter; a.grad = grad;
   a.accumulate = accumulate; a.dist = dist; a.winner = winner;
   return dd::launch_drift_restraint(a, (hipStream_t)stream);

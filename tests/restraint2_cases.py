@@ -1,4 +1,4 @@
-"""Deterministic cases for the general distance-restraint kernel (k_drift_restraint2 in csrc/dd_step.hip, dd_drift_restraint2): typed
+"""Deterministic cases for the general distance-restraint kernel (k_drift_restraint<true> in csrc/dd_step.hip, dd_drift_restraint2): typed
 endpoints, ligand-ligand pairs, the harmonic hinge.  The energy of include/decompdiff_hip.h ("the general form") restated in torch,
 its gradient under autograd in float64 (the yardstick) and in fp32; the method, the flat tolerance, the margins and the seed search
 are those of tests/restraint_cases.py.  A plain helper module (no tests): tests/test_restraint2_cases_host.py checks that every case

@@ -418,20 +418,23 @@ def test_cached_graph_serves_other_masks_and_known_values_but_not_the_other_mode
 
 
 def test_separate_step_launches_are_bit_identical_to_the_fused_one(debug_options):
-    """k_step_rows / k_step_pos with fixed atoms (dd_debug_set_option(7, 0), measurement build) against k_step_all: the serial
-    per-row form and the lane-per-class form pick the same classes and write the same bits -- both modes, dense and padded."""
+    """k_step_rows / k_step_pos as launches of their own (dd_debug_set_option(7, 0), measurement build) against k_step_all: the
+    same row and coordinate bodies under the other grid pick the same classes and write the same bits -- without fixed atoms and
+    in both of their modes, dense and padded."""
     if not debug_options:
         return
     lib = hip_lib.load()
     m, b = model(0), pair(85)
     n_l, singles, hb, _ = ragged_case("hold")
-    for mode in ("hold", "replace"):
-        fx = known(b, scaffold(b), 86, mode)
-        fxh = known(hb, torch.cat([scaffold(singles[0]), torch.zeros(6, dtype=torch.bool), torch.ones(9, dtype=torch.bool)]), 87, mode)
+    for mode in (None, "hold", "replace"):
+        kw, kwh = {}, {}
+        if mode is not None:
+            kw = dict(fixed=known(b, scaffold(b), 86, mode))
+            kwh = dict(fixed=known(hb, torch.cat([scaffold(singles[0]), torch.zeros(6, dtype=torch.bool), torch.ones(9, dtype=torch.bool)]), 87, mode))
         try:
-            fused, fused_h = run(m, b, 3, seed=3, fixed=fx), run(m, hb, 3, sample_keys=KEYS[:3], fixed=fxh)
+            fused, fused_h = run(m, b, 3, seed=3, **kw), run(m, hb, 3, sample_keys=KEYS[:3], **kwh)
             assert lib.dd_debug_set_option(7, 0) == 0
-            apart, apart_h = run(m, b, 3, seed=3, fixed=fx), run(m, hb, 3, sample_keys=KEYS[:3], fixed=fxh)
+            apart, apart_h = run(m, b, 3, seed=3, **kw), run(m, hb, 3, sample_keys=KEYS[:3], **kwh)
         finally:
             assert lib.dd_debug_set_option(7, 1) == 0
         assert_same(apart, fused, f"{mode} dense")

@@ -50,6 +50,20 @@ def model(seed=0, priors=None):
     return _MODELS[seed]
 
 
+def model_nc(nc):
+    """The synthetic-weight model with `nc` atom classes (8: the shared one, model(0))."""
+    if nc == 8:
+        return model(0)
+    if ("nc", nc) not in _MODELS:
+        cfg = shipped_config()
+        m = DecompScorePosNet3D(cfg, 29, nc + 2, nc)
+        sd = m.state_dict()
+        sd.update(synth.synthetic_state_dict(cfg, 0, ligand_atom_feature_dim=nc + 2, num_classes=nc))
+        m.load_state_dict(sd, strict=True)
+        _MODELS[("nc", nc)] = m.to(dev())
+    return _MODELS[("nc", nc)]
+
+
 def to_dev(batch):
     return {k: (v.to(dev()) if torch.is_tensor(v) else v) for k, v in batch.items()}
 
@@ -553,22 +567,28 @@ def test_step_fold_bit_identical(debug_options):
             assert torch.equal(torch.stack(ref[k]), torch.stack(o[k])), (key, k)
 
 
-def test_reverse_step_op_equals_the_loop():
+@pytest.mark.parametrize("injected", [True, False], ids=["injected", "philox"])
+@pytest.mark.parametrize("nc", [8, 13, 23])
+def test_reverse_step_op_equals_the_loop(nc, injected):
     """dd_reverse_step (transitions only, fed with network outputs the host holds) after dd_forward reproduces
-    dd_sample_steps bit for bit: same state, same trajectories, with drift and injected noise."""
+    dd_sample_steps bit for bit: same state, same trajectories, with drift; every atom class count, with injected noise and with
+    the device's own Philox draws of an explicit chain seed."""
     lib = hip_lib.load()
-    m = model(0)
+    m = model_nc(nc)
     pocket = synth.make_pocket_small(6)
     torch.manual_seed(8)
-    b = to_dev(synth.build_sampling_batch(pocket, 2))
+    b = to_dev(synth.build_sampling_batch(pocket, 2, num_classes=nc))
     steps = 3
-    noise = synth.draw_step_noise(steps, b["init_ligand_pos"].size(0), b["init_ligand_fc_bond_type"].size(0))
+    noise = None
+    if injected:
+        noise = synth.draw_step_noise(steps, b["init_ligand_pos"].size(0), b["init_ligand_fc_bond_type"].size(0), num_classes=nc)
 
     def chain():
         return m._prepare_chain(b["protein_pos"], b["protein_v"], b["batch_protein"], b["init_ligand_pos"], b["init_ligand_v"],
                                 b["ligand_v_aux"], b["batch_ligand"], b["prior_stds"], b["ligand_decomp_batch"],
                                 b["ligand_decomp_index"], None, b["ligand_fc_bond_index"], b["init_ligand_fc_bond_type"],
-                                b["full_protein_pos"], b["full_batch_protein"], _Call(m.num_timesteps, steps, drift=GU.DRIFT, noise=noise))
+                                b["full_protein_pos"], b["full_batch_protein"],
+                                _Call(m.num_timesteps, steps, drift=GU.DRIFT, noise=noise, seed=0 if injected else 0x5eed0000 + nc))
     st = hip_lib.stream_ptr(dev())
     a = chain()
     hip_lib.check(lib.dd_sample_steps(ctypes.byref(a["s"]), steps, st), "dd_sample_steps")

@@ -11,8 +11,8 @@ import ctypes
 import pytest
 import torch
 
-from decompdiff_amd import DecompScorePosNet3D, hip_lib, sample_keys, shipped_config, synth
-from test_gpu_parity import dev, model, to_dev
+from decompdiff_amd import hip_lib, sample_keys, synth
+from test_gpu_parity import dev, model, model_nc, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -24,21 +24,6 @@ DRIFT = [dict(type="armsca_prox", min_d=1.2, max_d=1.9), dict(type="clash", sigm
 POCKETS = {8: synth.make_pocket_tiny(11, num_protein=48, arm_atoms=(3, 2), scaffold_atoms=3),
            6: synth.make_pocket_tiny(12, num_protein=40, arm_atoms=(2, 2), scaffold_atoms=2),
            9: synth.make_pocket_tiny(13, num_protein=44, arm_atoms=(3, 3), scaffold_atoms=3)}
-_MODELS = {}
-
-
-def model_nc(nc):
-    """The synthetic-weight model with `nc` atom classes (8: the shared one of the parity tests)."""
-    if nc == 8:
-        return model(0)
-    if nc not in _MODELS:
-        cfg = shipped_config()
-        m = DecompScorePosNet3D(cfg, 29, nc + 2, nc)
-        sd = m.state_dict()
-        sd.update(synth.synthetic_state_dict(cfg, 0, ligand_atom_feature_dim=nc + 2, num_classes=nc))
-        m.load_state_dict(sd, strict=True)
-        _MODELS[nc] = m.to(dev())
-    return _MODELS[nc]
 
 
 def single(nl, seed, nc=8):
