@@ -48,7 +48,7 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                                    atom_prior_probs=None, bond_prior_probs=None, pool_batches: int = 1,
                                    sample_key_seed: Optional[int] = None, first_sample_index: int = 0,
                                    fixed_fn=None, fixed_mode: str = "hold", resample=None, init: str = "host",
-                                   restraints_fn=None, restraint_opts=None) -> Dict[str, list]:
+                                   restraints_fn=None, restraint_opts=None, time_levels=None) -> Dict[str, list]:
     """Sample ``num_samples`` ligands for one pocket in batches of ``batch_size``.
 
     ``pool_batches`` > 1 assembles that many consecutive batches exactly as the reference would (same random draws, same
@@ -104,13 +104,19 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
     The dict may carry the general form's keys -- ``classes`` / ``classes2``, ``atom2`` (sample rows) / ``group2``, ``form`` -- and
     ``restraint_opts`` its ``traj``; the output then also has ``restraint_atom2`` (-1 off the pairs) and, with ``traj``,
     ``restraint_dist_traj`` / ``restraint_atom_traj`` / ``restraint_atom2_traj`` [positions, r] per sample.
+
+    ``time_levels`` (not None; only for models that take the extra keywords): strided sampling -- the strictly decreasing list of
+    time levels every model call runs over (``sample_diffusion(time_levels=...)``, `stride_levels`), in every ``init`` mode;
+    ``num_steps`` then counts positions of the list and ``None`` means the whole list.
     """
     out = {k: [] for k in ("pred_pos", "pred_v", "pred_pos_traj", "pred_v_traj", "pred_v0_traj", "pred_vt_traj",
                            "pred_bond_index", "pred_bond_type", "pred_b_traj", "pred_bt_traj", "decomp_mask")}
     time_list = []
     num_batch = int(np.ceil(num_samples / batch_size))
     pool_batches = max(1, int(pool_batches))
-    steps = model.num_timesteps if num_steps is None else num_steps
+    if time_levels is not None and not _accepts_extras(model):
+        raise ValueError("time_levels needs a model whose sample_diffusion takes time_levels=")
+    steps = (model.num_timesteps if time_levels is None else len(time_levels)) if num_steps is None else num_steps
 
     def assemble_alone(g_local):
         """init="device": sample ``g_local`` of this call assembled alone under its own key -> (kwargs, [size], init centers, stds)"""
@@ -199,6 +205,8 @@ def sample_diffusion_ligand_decomp(model, pocket, num_samples: int, batch_size: 
                 extra["fixed"] = fixed
                 if resample is not None:
                     extra["resample"] = resample
+        if time_levels is not None:
+            extra["time_levels"] = time_levels
         drift_opt, rs_entry = energy_drift_opt, None
         if restraints_fn is not None and extra:
             rs_entry = collate_restraints(restraints_fn, int(first_sample_index) + n_done, n_atoms, batch["ligand_decomp_index"],

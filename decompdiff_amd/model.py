@@ -275,6 +275,51 @@ def _as_init(init, batch_ligand, fc_index, ligand_decomp_batch, prior_centers, p
     return out
 
 
+def stride_levels(num_timesteps, n):
+    """``n`` distinct time levels of a schedule of ``num_timesteps``, evenly spaced from ``num_timesteps - 1`` down to 0 (both
+    included) and strictly decreasing: a ``time_levels`` of sample_diffusion.  ``n = num_timesteps``: the full list."""
+    T, n = int(num_timesteps), int(n)
+    if not 2 <= n <= T:
+        raise ValueError(f"stride_levels needs 2 <= n <= num_timesteps, got n = {n}, num_timesteps = {T}")
+    return [((T - 1) * (n - 1 - i) + (n - 1) // 2) // (n - 1) for i in range(n)]     # (rounded; steps of >= 1: distinct)
+
+
+def _as_time_levels(time_levels, num_timesteps):
+    """``time_levels`` of sample_diffusion, validated (ValueError): the int64 tensor [S] of the real level of every VIRTUAL level
+    0 .. S - 1, i.e. the caller's strictly decreasing list reversed."""
+    if torch.is_tensor(time_levels):
+        if time_levels.dim() != 1 or time_levels.dtype.is_floating_point or time_levels.dtype.is_complex or time_levels.dtype == torch.bool:
+            raise ValueError("time_levels must be a one-dimensional integer tensor, array or sequence of ints")
+        vals = time_levels.detach().cpu().tolist()
+    elif isinstance(time_levels, np.ndarray):
+        if time_levels.ndim != 1 or time_levels.dtype.kind not in "iu":
+            raise ValueError("time_levels must be a one-dimensional integer tensor, array or sequence of ints")
+        vals = time_levels.tolist()
+    else:
+        try:
+            vals = list(time_levels)
+        except TypeError:
+            raise ValueError("time_levels must be a one-dimensional integer tensor, array or sequence of ints") from None
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in vals):
+            raise ValueError("time_levels must hold ints")
+        vals = [int(v) for v in vals]
+    if len(vals) < 2:
+        raise ValueError("time_levels needs at least two levels")
+    if any(not 0 <= v <= num_timesteps - 1 for v in vals):
+        raise ValueError(f"time_levels must lie in [0, {num_timesteps - 1}]")
+    if any(a <= b for a, b in zip(vals, vals[1:])):
+        raise ValueError("time_levels must be strictly decreasing (execution order, no level twice)")
+    return torch.tensor(vals[::-1], dtype=torch.int64)
+
+
+def _virtual_window(levels, t_min, t_max):
+    """The virtual levels whose real level (``levels`` int64 [S], ascending) lies in the real window [t_min, t_max], as the
+    inclusive range (lo, hi) -- contiguous, the list is monotonic -- or None: no level does."""
+    lo = int(torch.searchsorted(levels, torch.tensor(int(t_min)), right=False))
+    hi = int(torch.searchsorted(levels, torch.tensor(int(t_max)), right=True)) - 1
+    return (lo, hi) if lo <= hi else None
+
+
 def resample_schedule(t_hi, t_lo, j, r):
     """The resampling ("jump-back") schedule of ``sample_diffusion(resample=dict(jump_length=j, n_resample=r))`` over the reverse
     steps t_hi .. t_lo: a list of ``("step", t)`` and ``("jump", l, l + j)`` in execution order.  Jump points are anchored at the
@@ -548,6 +593,8 @@ class _Call:
     resample: Optional[dict] = None
     chain_init: Optional[dict] = None
     restraints: Optional[dict] = None
+    schedule: Optional[dict] = None     # a strided call's schedule set (`_schedule_set`; num_timesteps is then its length S)
+    levels: Optional[torch.Tensor] = None   # ... and the int64 real level of every virtual level 0 .. S - 1 (ascending)
 
     def __post_init__(self):
         if self.start_step < 0 or self.num_steps + self.start_step > self.num_timesteps:
@@ -560,6 +607,16 @@ class _Call:
     @property
     def n_pos(self):                    # trajectory positions: the reverse steps the chain runs
         return self.num_steps if self.resample is None else self.resample["n_total"]
+
+    @property
+    def t_traj(self):                   # the int64 time of every position, for the calls that report it: resampled, strided (real levels)
+        if self.resample is not None:
+            t = self.resample["t_traj"]
+        elif self.levels is not None:
+            t = torch.arange(self.t_start, self.t_start - int(self.num_steps), -1, dtype=torch.int64)
+        else:
+            return None
+        return t if self.levels is None else self.levels[t]
 
 
 class _Placement:
@@ -813,32 +870,55 @@ class DecompScorePosNet3D(nn.Module):
         self.__dict__["_param_list"] = None                 # (.to() may replace the parameter tensors)
         return r
 
-    def position_step_table(self, model_mean_type=None):
+    def schedule_tables(self, levels=None):
+        """The schedule tables the step tables are composed from, as one dict: the position tables by name, ``atom_type_trans`` /
+        ``bond_type_trans`` -> their categorical tables.  ``levels=None``: this module's own buffers.  Otherwise (ascending time
+        levels, S of them): the respaced schedule of `schedules.position_tables(config, levels)` / `categorical_tables(...,
+        levels=...)`, composed in float64 from the config's schedule -- never from the fp32 buffers, whose small betas cancel --
+        with this module's class priors."""
+        if levels is None:
+            tabs = {k: getattr(self, k).detach() for k in ("alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
+                                                           "posterior_mean_c0_coef", "posterior_mean_ct_coef", "posterior_logvar",
+                                                           "pos_score_coef")}
+            for name in ("atom_type_trans", "bond_type_trans"):
+                tabs[name] = {k: v.detach() for k, v in getattr(self, name)._parameters.items()}
+            return tabs
+        tabs = dict(schedules.position_tables(self.config, levels))
+        for name, ncls in (("atom_type_trans", self.num_classes), ("bond_type_trans", self.num_bond_classes)):
+            tabs[name] = schedules.categorical_tables(self.config.v_beta_schedule, self.num_timesteps, self.config.v_beta_s, ncls,
+                                                      levels=levels)
+            tabs[name]["prior_probs"] = getattr(self, name).prior_probs.detach().float().cpu()
+        return tabs
+
+    def position_step_table(self, model_mean_type=None, tables=None):
         """The [3][T] fp32 table the step kernels read as ``dd_sampler.tab_pos``: for each t, the coefficients of the network's
         coordinate output and of x_t in the posterior mean, then posterior_logvar.  C0: posterior_mean_c0_coef and
         posterior_mean_ct_coef as they are.  'noise': the eps -> x0 map of the reference (_predict_x0_from_eps,
         decompdiff.py:353-356) folded into them -- with eps = pred - x_t the mean c0 * x0 + ct * x_t is
         (-c0 * sqrt_recipm1) * pred + (ct + c0 * (sqrt_recip + sqrt_recipm1)) * x_t, the two rows composed in float64 from
-        this module's schedule tables and rounded once."""
+        this module's schedule tables and rounded once.  ``tables`` (here and in the builders below): the `schedule_tables` dict to
+        compose from; default this module's own."""
         mode = self.model_mean_type if model_mean_type is None else model_mean_type
-        c0, ct = self.posterior_mean_c0_coef.detach(), self.posterior_mean_ct_coef.detach()
+        tb = self.schedule_tables() if tables is None else tables
+        c0, ct = tb["posterior_mean_c0_coef"].detach(), tb["posterior_mean_ct_coef"].detach()
         if mode == "noise":
             c0d, ctd = c0.double(), ct.double()
-            sr = self.sqrt_recip_alphas_cumprod.detach().double()
-            srm1 = self.sqrt_recipm1_alphas_cumprod.detach().double()
+            sr = tb["sqrt_recip_alphas_cumprod"].detach().double()
+            srm1 = tb["sqrt_recipm1_alphas_cumprod"].detach().double()
             c0, ct = -c0d * srm1, ctd + c0d * (sr + srm1)
         elif mode != "C0":
             raise ValueError(mode)
-        return torch.stack([c0.float(), ct.float(), self.posterior_logvar.detach().float()]).contiguous()
+        return torch.stack([c0.float(), ct.float(), tb["posterior_logvar"].detach().float()]).contiguous()
 
-    def fixed_step_table(self):
+    def fixed_step_table(self, tables=None):
         """The [2][T] fp32 table the step kernels read as ``dd_fixed.tab`` (replace mode): sqrt(alphas_cumprod) and
         sqrt(1 - alphas_cumprod) of the forward process (decompdiff.py:436-449), composed in float64 from this module's
         ``alphas_cumprod`` and rounded once."""
-        ac = self.alphas_cumprod.detach().double()
+        tb = self.schedule_tables() if tables is None else tables
+        ac = tb["alphas_cumprod"].detach().double()
         return torch.stack([ac.sqrt(), (1.0 - ac).sqrt()]).float().contiguous()
 
-    def resample_jump_table(self, jump_length):
+    def resample_jump_table(self, jump_length, tables=None):
         """The [6][T] fp32 table ``dd_resample.tab`` of the forward jump from level m - j to level m (j = ``jump_length``), indexed
         by m: A = sqrt(a), S = sqrt(1 - a) with a = alphas_cumprod[m] / alphas_cumprod[m - j] (coordinates), then
         lr = log_cumprod[m] - log_cumprod[m - j] and l1mr = log(1 - exp(lr)) of the atom-type and of the bond-type schedule; level -1
@@ -847,10 +927,11 @@ class DecompScorePosNet3D(nn.Module):
         j = int(jump_length)
         if j < 1:
             raise ValueError("jump_length must be >= 1")
-        T = int(self.betas.numel())
-        ac = torch.cat([torch.ones(1, dtype=torch.float64), self.alphas_cumprod.detach().double().cpu()])        # [level + 1]
-        lv = torch.cat([torch.zeros(1, dtype=torch.float64), self.atom_type_trans.log_alphas_cumprod_v.detach().double().cpu()])
-        lb = torch.cat([torch.zeros(1, dtype=torch.float64), self.bond_type_trans.log_alphas_cumprod_v.detach().double().cpu()])
+        tb = self.schedule_tables() if tables is None else tables
+        T = int(tb["alphas_cumprod"].numel())
+        ac = torch.cat([torch.ones(1, dtype=torch.float64), tb["alphas_cumprod"].detach().double().cpu()])        # [level + 1]
+        lv = torch.cat([torch.zeros(1, dtype=torch.float64), tb["atom_type_trans"]["log_alphas_cumprod_v"].detach().double().cpu()])
+        lb = torch.cat([torch.zeros(1, dtype=torch.float64), tb["bond_type_trans"]["log_alphas_cumprod_v"].detach().double().cpu()])
         tab = torch.zeros(6, T, dtype=torch.float64)
         if j <= T:
             m = torch.arange(j - 1, T)
@@ -888,24 +969,43 @@ class DecompScorePosNet3D(nn.Module):
                 self._evict_chain_cache(0)                                  # cached chains point into the old arena
             sd = {k: v for k, v in self.state_dict().items()}
             arena, offsets, _ = packing.pack_model(sd, self.config, kernel_form=hip_lib.weights_form() == 1)
-            # (an unknown mean type never reaches a step kernel: sample_diffusion refuses it; forward does not read the rows)
-            tab_pos = self.position_step_table("noise" if self.model_mean_type == "noise" else "C0")
-            tv = self.atom_type_trans
-            tb = self.bond_type_trans
-            # [4][T] schedule rows followed by the [K] class log-prior (uniform unless prior_*_types were given)
-            tab_v = torch.cat([tv.log_alphas_v, tv.log_one_minus_alphas_v, tv.log_alphas_cumprod_v,
-                               tv.log_one_minus_alphas_cumprod_v, tv.prior_probs.reshape(-1)]).detach().float().contiguous()
-            tab_b = torch.cat([tb.log_alphas_v, tb.log_one_minus_alphas_v, tb.log_alphas_cumprod_v,
-                               tb.log_one_minus_alphas_cumprod_v, tb.prior_probs.reshape(-1)]).detach().float().contiguous()
+            # (the packed dict IS the schedule set of the module's own tables; a strided call's set: `_schedule_set`)
             self._packed = dict(arena=arena.to(dev), offsets=offsets.numpy().astype(np.int64).copy(),
-                                tab_pos=tab_pos.to(dev), tab_v=tab_v.to(dev), tab_b=tab_b.to(dev),
-                                tab_score=self.pos_score_coef.detach().float().contiguous().to(dev))
+                                **self._step_tables(self.schedule_tables(), dev))
             self._packed["bond_head"] = self._bond_head_descriptor(sd, self._packed)
             self._packed["node_out"] = self._node_out_descriptor(sd, self._packed)
             self._packed["model_opts"] = hip_lib.model_opts(self._packed["bond_head"], self._packed["node_out"], self.config.num_blocks)
             self._packed_key = key
         return self._packed
 
+
+    def _step_tables(self, tables, dev):
+        """The device tables every chain reads, composed from the `schedule_tables` dict ``tables``: tab_pos, tab_v, tab_b, tab_score
+        (dd_sampler), with ``T`` (their length), ``tables`` and ``levels`` (None: the module's own schedule).  tab_fixed and
+        tab_jump join them when a call first needs them (`_bind_call`)."""
+        # (an unknown mean type never reaches a step kernel: sample_diffusion refuses it; forward does not read the rows)
+        tab_pos = self.position_step_table("noise" if self.model_mean_type == "noise" else "C0", tables)
+        # [4][T] schedule rows followed by the [K] class log-prior (uniform unless prior_*_types were given)
+        cat = lambda t: torch.cat([t["log_alphas_v"], t["log_one_minus_alphas_v"], t["log_alphas_cumprod_v"],
+                                   t["log_one_minus_alphas_cumprod_v"], t["prior_probs"].reshape(-1)]).detach().float().contiguous()
+        return dict(tab_pos=tab_pos.to(dev), tab_v=cat(tables["atom_type_trans"]).to(dev), tab_b=cat(tables["bond_type_trans"]).to(dev),
+                    tab_score=tables["pos_score_coef"].detach().float().contiguous().to(dev),
+                    T=int(tables["pos_score_coef"].numel()), tables=tables, levels=None)
+
+    _SCHEDULE_CACHE_MAX = 4
+
+    def _schedule_set(self, pw, levels):
+        """The schedule set (`_step_tables`) of a strided call over ``levels`` (a tuple of ascending ints): kept with the packed
+        weights ``pw`` -- so per device and mean type, dropped when they are --, the least recently used beyond
+        _SCHEDULE_CACHE_MAX forgotten (a cached chain holds its own set)."""
+        sets = pw.setdefault("schedule_sets", {})
+        sch = sets.pop(levels, None)
+        if sch is None:
+            sch = dict(self._step_tables(self.schedule_tables(levels), pw["arena"].device), levels=levels)
+        sets[levels] = sch                                  # (re-inserted: most recently used last)
+        while len(sets) > self._SCHEDULE_CACHE_MAX:
+            sets.pop(next(iter(sets)))
+        return sch
 
     def _bond_head_descriptor(self, sd, pw):
         """The dd_bond_head of the *_ex entry points: None for the lin head (the arena's BH_W1 / BH_b1 slots, the entry points'
@@ -1081,7 +1181,7 @@ class DecompScorePosNet3D(nn.Module):
                            self.num_classes, (kw["full_protein_pos"], kw["full_batch_protein"]))
         s, bufs, ent = self._make_sampler(d, self._packed_weights(), call, rows, offset.contiguous(), masks=pad["masks"])   # (the padded batch keeps the caller's sample order)
         chain = dict(s=s, bufs=bufs, offset=offset, B=d["B"], NL=d["NL"], dev=d["protein_pos"].device, ent=ent,
-                     t_traj=None if call.resample is None else call.resample["t_traj"])
+                     t_traj=call.t_traj)
         self._run_chains([chain], call.n_pos, call.use_graph)
         out = self._collect_chain(chain, call.n_pos, call.keep_traj, rows_atoms=pad["rows_l"], rows_bonds=pad["rows_b"])
         self._restraint_results(call, [chain], out)
@@ -1141,8 +1241,8 @@ class DecompScorePosNet3D(nn.Module):
             out[k] = list(traj[k].unbind(0)) if traj[k] is not None else []
         if all(v is not None for v in traj.values()):
             out["_traj_stacked"] = dict(traj)
-        if call.resample is not None:
-            out["t_traj"] = call.resample["t_traj"].clone()
+        if call.t_traj is not None:
+            out["t_traj"] = call.t_traj.clone()
         self._restraint_results(call, [p[0] for p in prepared], out)
         return out
 
@@ -1278,7 +1378,8 @@ class DecompScorePosNet3D(nn.Module):
         n_pos = call.n_pos
         cacheable = call.noise is None and n_pos > 0 and self._CACHE_MAX > 0 and os.environ.get("DD_CHAIN_CACHE", "1") != "0"
         key, ent = self._chain_entry(d, pw, n_pos, call.keep_traj, cacheable, rows["decomp"] is not None,
-                                     0 if rows["fpp"] is None else int(rows["fpp"].shape[1]), masks is not None, cache_slot)
+                                     0 if rows["fpp"] is None else int(rows["fpp"].shape[1]), masks is not None, cache_slot,
+                                     schedule=call.schedule)
         upload = self._upload_pocket(ent, d, pw, rows["fpp"], cacheable)
         self._upload_state(ent, d, rows["atom_std"], offset, rows["decomp"], masks)
         self._bind_call(ent, d, pw, rows["keys"], rows["fx"], call.resample, rows["ci"], rows["rs"], n_pos)
@@ -1296,9 +1397,12 @@ class DecompScorePosNet3D(nn.Module):
             self._evict_chain_cache(self._CACHE_MAX)
         return sm, ent["bufs"], ent
 
-    def _chain_entry(self, d, pw, n_steps, keep_traj, cacheable, has_decomp=False, NF=0, masked=False, cache_slot=0):
+    def _chain_entry(self, d, pw, n_steps, keep_traj, cacheable, has_decomp=False, NF=0, masked=False, cache_slot=0, schedule=None):
         """(cache key, entry) of a chain of this shape: taken out of the cache (``cacheable``) or allocated, with the dd_sampler
-        fields that never change.  ``n_steps``: trajectory positions of the chain."""
+        fields that never change.  ``n_steps``: trajectory positions of the chain.  ``schedule``: the schedule set whose tables the
+        chain reads (None: ``pw`` itself, the module's own); its levels belong to the key -- a chain's graph carries the table
+        pointers -- and the entry holds the set."""
+        sch = pw if schedule is None else schedule
         lib = hip_lib.load()
         dev = d["protein_pos"].device
         B, NP, NL = d["B"], d["NP"], d["NL"]
@@ -1313,7 +1417,8 @@ class DecompScorePosNet3D(nn.Module):
             hint = int(getattr(self, "traj_capacity_hint", 0) or 0)
             cap = max(32, 1 << (max(int(n_steps), hint) - 1).bit_length())   # trajectory capacity: 5 and 20 steps share buffers
         key = (str(dev), B, NP, NL, K, NF, cap if keep_traj else 0, bool(keep_traj), has_decomp, arena.data_ptr(),
-               masked, int(cache_slot), self.bond_net_type, self.x2h_out_fc, int(self.config.num_blocks))     # cache_slot: chains of ONE call that share a shape need separate buffers
+               masked, int(cache_slot), self.bond_net_type, self.x2h_out_fc, int(self.config.num_blocks),     # cache_slot: chains of ONE call that share a shape need separate buffers
+               sch["levels"])
         ent = DecompScorePosNet3D._chain_cache.pop(key, None) if cacheable else None
         if ent is not None:
             return key, ent
@@ -1344,14 +1449,14 @@ class DecompScorePosNet3D(nn.Module):
             bufs["traj_bt"] = z(cap, B * Eb, 5)
         sm = hip_lib.DDSampler()
         sm.B, sm.NP, sm.NL, sm.K, sm.NF = B, NP, NL, K, NF
-        sm.num_layers, sm.T = int(self.config.num_layers), int(self.betas.numel())
+        sm.num_layers, sm.T = int(self.config.num_layers), sch["T"]
         sm.num_v = int(self.num_classes)
         sm.weights = arena.data_ptr()
         sm.slot_off = offs.ctypes.data
-        sm.tab_pos, sm.tab_v, sm.tab_b = pw["tab_pos"].data_ptr(), pw["tab_v"].data_ptr(), pw["tab_b"].data_ptr()
-        sm.tab_score = pw["tab_score"].data_ptr()
+        sm.tab_pos, sm.tab_v, sm.tab_b = sch["tab_pos"].data_ptr(), sch["tab_v"].data_ptr(), sch["tab_b"].data_ptr()
+        sm.tab_score = sch["tab_score"].data_ptr()
         sm.workspace_floats = ws_floats
-        return key, dict(s=sm, bufs=bufs, graph=None, graph_sig=None, dev=dev, pw=pw)
+        return key, dict(s=sm, bufs=bufs, graph=None, graph_sig=None, dev=dev, pw=pw, sch=sch)
 
     def _upload_pocket(self, ent, d, pw, full_protein_pos, cacheable):
         """The pocket side of a chain's inputs (protein coordinates / embedded features, arm indicators, full protein,
@@ -1405,6 +1510,7 @@ class DecompScorePosNet3D(nn.Module):
         ``rs`` of `_chain_rows`; ``n_pos``: the chain's positions (the rows of the restraint trajectories).  Leaves on the entry ``keyed``, ``fixed`` (the mode), ``resample``, ``restraints``, the host structs,
         and ``launch``: the step-launch arguments of this chain."""
         bufs, dev = ent["bufs"], ent["dev"]
+        sch = ent["sch"]                                    # (tab_fixed / tab_jump: composed from the chain's own schedule set)
         A, E = d["B"] * d["NL"], d["B"] * d["NL"] * (d["NL"] - 1)
         fx, ci = fixed or {}, chain_init or {}
         replace, noised = fx.get("mode") == "replace", ci.get("mode") == "noised"
@@ -1426,25 +1532,25 @@ class DecompScorePosNet3D(nn.Module):
             if wanted and src is not None:
                 bufs[name].copy_(src.reshape(shape))
             bound[name] = bufs[name] if wanted else None
-        if (replace or noised) and pw.get("tab_fixed") is None:
-            pw["tab_fixed"] = self.fixed_step_table().to(dev)
+        if (replace or noised) and sch.get("tab_fixed") is None:
+            sch["tab_fixed"] = self.fixed_step_table(sch["tables"]).to(dev)
         ent["keyed"], ent["fixed"], ent["fixed_struct"] = keys is not None, fx.get("mode"), None
         if fixed is not None:
             ent["fixed_struct"] = hip_lib.fixed_struct(fx["mode"], bound["fx_mask"], bound["fx_v0"], bound["fx_b0"], bound["fx_x0c"],
-                                                       bound["fx_cc"], pw["tab_fixed"] if replace else None)
-        # resampling: the jump table belongs to the packed weights (one per jump length); neither j nor r reaches the captured graph
+                                                       bound["fx_cc"], sch["tab_fixed"] if replace else None)
+        # resampling: the jump table belongs to the schedule set (one per jump length); neither j nor r reaches the captured graph
         ent["resample"], ent["resample_struct"] = None, None
         if resample is not None:
-            tabs = pw.setdefault("tab_jump", {})
+            tabs = sch.setdefault("tab_jump", {})
             if resample["j"] not in tabs:
-                tabs[resample["j"]] = self.resample_jump_table(resample["j"]).to(dev)
+                tabs[resample["j"]] = self.resample_jump_table(resample["j"], sch["tables"]).to(dev)
             ent["resample"] = dict(resample)
             ent["resample_struct"] = hip_lib.resample_struct(resample["j"], tabs[resample["j"]], bound["epoch"])
         # chain init: the launch is part of the chain's preparation (_start_chain), not of its captured graph
         ent["init_struct"] = None
         if chain_init is not None:
             ent["init_struct"] = hip_lib.init_struct(ci["mode"], bound["ci_cc"], bound["ci_std"], bound["ci_lp_v"], bound["ci_lp_b"],
-                                                     bound["ci_x0c"], bound["ci_v0"], bound["ci_b0"], pw["tab_fixed"] if noised else None)
+                                                     bound["ci_x0c"], bound["ci_v0"], bound["ci_b0"], sch["tab_fixed"] if noised else None)
         # distance restraints: the arrays hold a CAPACITY of entries (a power of two, at least 8) that the captured graph's launch
         # carries as R; the call's R entries come first and weight-0 entries of the last sample fill the rest (they add nothing)
         ent["restraints"], ent["restraints_struct"], ent["restraint_sig"] = None, None, None
@@ -1693,7 +1799,7 @@ class DecompScorePosNet3D(nn.Module):
                          energy_drift_opt=None,
                          full_protein_pos=None, full_batch_protein=None,
                          noise=None, seed=None, keep_traj=True, use_graph=True, start_step=0, _drift_norm_batch=0,
-                         sample_keys=None, fixed=None, resample=None, init=None):
+                         sample_keys=None, fixed=None, resample=None, init=None, time_levels=None):
         """Reverse diffusion (reference: models/decompdiff.py:552-703), same arguments and return
         keys.  Extra keyword-only knobs (all optional, reference call sites never pass them):
 
@@ -1777,24 +1883,47 @@ class DecompScorePosNet3D(nn.Module):
           ``restraint_atom2`` [R] (-1 for a point restraint or an empty pair).  Class ids outside ``[0, num_classes)``, an empty
           class set, ``atom2`` of another sample or equal to ``atom``, a pair without a second endpoint, an arm / scaffold
           ``group2`` without ``ligand_decomp_index``, an unknown ``form``, a non-bool ``traj``: ValueError.
+        * ``time_levels`` — strided sampling (EXTENSION): a strictly decreasing sequence, numpy array or 1-D
+          integer tensor of S >= 2 time levels in ``[0, num_timesteps - 1]``, in execution order (:func:`stride_levels` makes an
+          evenly spaced one).  The chain then runs over these levels only, as the chain of a model whose schedule is the respaced
+          one with S timesteps (``alphas_cumprod'[tau] = alphas_cumprod[level tau]``, betas recomputed; the categorical schedules
+          likewise; composed in float64 from the config's schedule): the network takes no time input and the step kernels take time
+          through their tables only, so every kernel serves it unchanged.  ``num_steps`` defaults to S; ``start_step`` and
+          ``num_steps`` count POSITIONS of the list (``start_step + num_steps <= S``), position p runs at level
+          ``time_levels[start_step + p]``, and a split chain equals the unsplit one.  The list's last position lands on the clean
+          sample as the reference's t = 0 step does (no noise), whether or not its level is 0.  The Philox time word of a position
+          is its VIRTUAL level ``tau = S - 1 - position`` (of the whole list), not the real level.  Everything that counts steps
+          counts positions: ``noise`` holds ``[num_steps, ...]`` draws, ``resample``'s ``jump_length`` is in positions.  Real time
+          enters in two places, both mapped on the host: a restraint's ``t_min`` / ``t_max`` stay REAL levels (the term acts at the
+          positions whose real level lies in the window; none: the term never acts, distances are still reported), and
+          ``init=dict(mode="noised")`` noises to the real level ``time_levels[start_step]``.  The result gains ``t_traj``, the int64
+          real levels of the positions (with ``resample``: of the schedule's positions).  Bools, non-ints, a level twice, a list
+          that does not decrease, levels out of range, S < 2, ``start_step + num_steps > S``: ValueError before anything is
+          launched.  ``None``: today's call.
         * ``keep_traj`` — record the six trajectories on the device and copy them once at the end.
         * ``use_graph`` — replay one captured hipGraph per step instead of eager launches.
         """
         if self.model_mean_type not in ("C0", "noise"):          # ('noise': folded into tab_pos, position_step_table)
             raise ValueError(self.model_mean_type)
+        levels, T = None, self.num_timesteps            # T: the timesteps of the schedule the chain runs on
+        if time_levels is not None:
+            levels = _as_time_levels(time_levels, self.num_timesteps)
+            T = int(levels.numel())
+            if num_steps is not None and (int(start_step) < 0 or int(num_steps) + int(start_step) > T):
+                raise ValueError("num_steps (+ start_step) exceeds the positions of time_levels")
         if num_steps is None:
-            num_steps = self.num_timesteps
+            num_steps = T
         if sample_keys is not None:
             if noise is not None or seed is not None:
                 raise ValueError("sample_keys excludes noise= and an explicit seed=: a chain draws from one source")
             sample_keys = _as_sample_keys(sample_keys, batch_ligand)
             seed = 0                                             # (not read by a keyed chain; no draw from torch's generator)
         if resample is not None:
-            resample = _as_resample(resample, fixed, noise, self.num_timesteps, num_steps, start_step)
+            resample = _as_resample(resample, fixed, noise, T, num_steps, start_step)
         if init is not None:
             dev = protein_pos.device
             init = _as_init(init, batch_ligand, ligand_fc_bond_index, ligand_decomp_batch, prior_centers, prior_stds,
-                            (init_ligand_pos, init_ligand_v, init_ligand_fc_bond_type), noise, start_step, self.num_timesteps,
+                            (init_ligand_pos, init_ligand_v, init_ligand_fc_bond_type), noise, start_step, T,
                             self.num_classes, self.num_bond_classes, dev)
             # placeholders of the right shapes: the launch of dd_chain_init overwrites every real row before anything reads it
             init_ligand_pos = torch.zeros(batch_ligand.numel(), 3, device=dev)
@@ -1807,12 +1936,19 @@ class DecompScorePosNet3D(nn.Module):
         energy_drift_opt, restraints = _split_restraints(energy_drift_opt)
         if restraints is not None:
             restraints = _as_restraints(restraints, batch_ligand, ligand_decomp_index, self.num_timesteps, self.num_classes)
+            if levels is not None:                           # (the window: real levels -> the virtual range; none: weights of 0, the
+                window = _virtual_window(levels, restraints["t_min"], restraints["t_max"])     # term adds exact zeros as a closed window does)
+                if window is None:
+                    restraints = dict(restraints, weight=torch.zeros_like(restraints["weight"]), t_min=0, t_max=T - 1)
+                else:
+                    restraints = dict(restraints, t_min=window[0], t_max=window[1])
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         key_t = (protein_pos, batch_protein, batch_ligand, ligand_fc_bond_index, ligand_v_aux)
         static = self._static_memo_get(key_t, center_pos_mode)        # (only dense batches are remembered)
-        call = _Call(self.num_timesteps, num_steps, start_step, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
-                     _drift_norm_batch, sample_keys, fixed, resample, init, restraints)
+        call = _Call(T, num_steps, start_step, center_pos_mode, energy_drift_opt, noise, seed, keep_traj, use_graph,
+                     _drift_norm_batch, sample_keys, fixed, resample, init, restraints,
+                     None if levels is None else self._schedule_set(self._packed_weights(), tuple(levels.tolist())), levels)
         if static is None and self._is_ragged(batch_protein, batch_ligand):
             return self._sample_heterogeneous(
                 dict(protein_pos=protein_pos, protein_v=protein_v, batch_protein=batch_protein, init_ligand_pos=init_ligand_pos,
@@ -1878,7 +2014,7 @@ class DecompScorePosNet3D(nn.Module):
         d["upload_mode"] = call.center_pos_mode
         s, bufs, ent = self._make_sampler(d, pw, call, rows, offset.contiguous(), cache_slot=cache_slot)
         return dict(s=s, bufs=bufs, offset=offset, B=B, NL=NL, dev=dev, ent=ent,
-                    t_traj=None if call.resample is None else call.resample["t_traj"],
+                    t_traj=call.t_traj,
                     static=dict(layout=(B, NP, NL), offset=offset, protein_pos_centered=d["protein_pos_centered"],
                                 aux_onehot=d["aux_onehot"]))
 

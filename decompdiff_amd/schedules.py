@@ -43,7 +43,22 @@ def _t(a):
     return torch.from_numpy(np.asarray(a, dtype=np.float64)).float()
 
 
-def position_tables(config):
+def _as_levels(levels, num_timesteps):
+    """``levels`` of the table builders as an int64 array: ascending, distinct ints in [0, num_timesteps - 1], at least two."""
+    lv = np.asarray(levels)
+    if lv.ndim != 1 or lv.dtype.kind not in "iu" or lv.size < 2:
+        raise ValueError("levels must be a one-dimensional sequence of at least two ints")
+    lv = lv.astype(np.int64)
+    if int(lv[0]) < 0 or int(lv[-1]) > num_timesteps - 1 or bool((np.diff(lv) <= 0).any()):
+        raise ValueError(f"levels must be strictly ascending within [0, {num_timesteps - 1}]")
+    return lv
+
+
+def position_tables(config, levels=None):
+    """``levels`` (ascending time levels, S >= 2 of them): the tables of the respaced schedule with ``num_timesteps = S`` whose
+    level tau is the full schedule's ``levels[tau]`` -- alphas_cumprod selected in float64, alphas / betas recomputed from the
+    selection (alphas'_tau = acp'_tau / acp'_{tau-1}), then every formula below as it stands.  The full list reproduces the
+    tables of ``levels=None`` bit for bit."""
     if config.beta_schedule == "cosine":
         alphas = cosine_beta_schedule(config.num_diffusion_timesteps, config.pos_beta_s) ** 2
         betas = 1.0 - alphas
@@ -53,6 +68,10 @@ def position_tables(config):
                                   num_diffusion_timesteps=config.num_diffusion_timesteps)
         alphas = 1.0 - betas
     acp = np.cumprod(alphas, axis=0)
+    if levels is not None:
+        acp = acp[_as_levels(levels, acp.shape[0])]
+        alphas = acp / np.append(1.0, acp[:-1])
+        betas = 1.0 - alphas
     acp_prev = np.append(1.0, acp[:-1])
     post_var = betas * (1.0 - acp_prev) / (1.0 - acp)
     tabs = {
@@ -74,11 +93,16 @@ def position_tables(config):
     return tabs
 
 
-def categorical_tables(noise_schedule, num_timesteps, s, num_classes, prior_probs=None):
+def categorical_tables(noise_schedule, num_timesteps, s, num_classes, prior_probs=None, levels=None):
+    """``levels``: as in `position_tables` -- log_alphas_cumprod selected in float64, log_alphas'_tau = log_cum'_tau -
+    log_cum'_{tau-1} (log_cum'_0 at tau = 0); the priors do not depend on the schedule."""
     if noise_schedule != "cosine":
         raise NotImplementedError(noise_schedule)
     log_alphas = np.log(cosine_beta_schedule(num_timesteps, s))
     log_cum = np.cumsum(log_alphas)
+    if levels is not None:
+        log_cum = log_cum[_as_levels(levels, log_cum.shape[0])]
+        log_alphas = np.append(log_cum[0], log_cum[1:] - log_cum[:-1])
     l1m = lambda a: np.log(1 - np.exp(a) + 1e-40)
     if prior_probs is None:
         prior = -np.log(num_classes).repeat(num_classes)[None, :]
